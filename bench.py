@@ -14,15 +14,20 @@ The workload is the configuration the metric is quoted on: 1 048 576 PoseWithVel
 reference's own arithmetic type).  Default scaling is STRONG, the metric's "1 M filters on 1/2/4/8 GPUs":
 the filters are sharded over the ranks (131 072 per GPU at N = 8, BASELINE config 3's layout);
 `--scaling weak` gives every rank --filters filters instead.  Filters are independent
-(UnscentedKalmanFilter.hpp:150), so there is no data-path collective; RCCL is used once, after the timed
-region, to gather the means.  Inputs are resident in HBM before the clock starts.
+(UnscentedKalmanFilter.hpp:150), so there is no data-path collective; with --full RCCL is used once, after the
+timed region, to gather the means.  Inputs are resident in HBM before the clock starts.
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line; its extra object:
   roofline     -- HBM roofline of the fused kernel from ALGORITHMIC bytes, the measured
                   PMC traffic of this workload, and a VALU-issue roofline (`valu`) from the committed PMC pass
+`--full` adds everything that takes runs or checks of its own (the --no-* options below switch parts of it off):
   cpu_baseline -- the CPU oracle (a from-scratch port, kind "port") built -O3 -march=native on this host and
                   timed on all hardware threads and on one core
   parity       -- max |GPU - oracle| on a sample of filters after all launches of this run (same inputs)
+  roofline.kernel_ms_per_launch_sustained / _burst, multi_cycle -- extra kernel-time regions after the timed one
+  gather_ms    -- N > 1: the time of the RCCL gather of the means after the timed region
+`--dump-outputs DIR` writes the state the timed steps left (means, covariances, status of a fixed sample of filters) as
+DIR/*.npy, so that two builds can be compared output for output: the inputs depend on the arguments only.
 """
 import argparse
 import json
@@ -49,6 +54,9 @@ RECENT_CYCLES = 16                 # window of the second in-run parity check
 MULTI_CYCLES = 8                   # cycles per launch of the extra multi-cycle region (ukfb_cycle_multi_dev)
 TOL = {"f64": 1e-9, "f32": 1e-4}   # north_star
 F32_HORIZON = {"pose": 450, "orient": 150}   # cycles the fp32 engines stay within 1e-4 of the fp64 oracle (tests/test_gpu_f32_horizon.py)
+DUMP_ALL_MAX = 32768               # --dump-outputs: up to this many filters every filter is written, above it a sample of
+DUMP_BLOCK = 256                   # DUMP_ALL_MAX filters in blocks of DUMP_BLOCK consecutive filters (<= 48 MB in all)
+DUMP_SEED = 20240601
 
 
 class _DevArray:
@@ -74,9 +82,15 @@ def parse():
                     help="with --precision f32: 1 = fp32 arrays in HBM, every instruction of the cycle in fp64 "
                          "(ukfb_config.wide_arithmetic); the line then reports dtype f64 and config.hbm_format f32")
     ap.add_argument("--lanes-per-filter", type=int, default=0, help="16/32/64 (0: engine default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-extra-regions", action="store_true", help="skip the sustained / burst kernel timings")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the in-run parity checks against the oracle, the sustained / burst / multi-cycle "
+                         "kernel regions and (N > 1) the timed gather; a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the state they left (mean, cov, status of every filter up to "
+                         f"{DUMP_ALL_MAX} filters, else of a fixed sample of {DUMP_ALL_MAX}) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity checks")
+    ap.add_argument("--no-extra-regions", action="store_true", help="with --full: skip the sustained / burst kernel timings")
     ap.add_argument("--clock-warmup-seconds", type=float, default=0.4,
                     help="untimed launches before the W warm-up steps (state restored afterwards) so that the GPU clocks have settled")
     ap.add_argument("--clock-warmup-cycles", type=int, default=0,
@@ -117,7 +131,10 @@ def parse():
     ap.add_argument("--bucket-models", type=int, default=1, choices=[0, 1],
                     help="pose-mixed: 1 (engine default) groups the filters by update class on the device before the launch, "
                          "0 launches in filter order (ukfb_config.bucket_models; same-box A/B)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_parity = args.no_extra_regions = True
+    return args
 
 
 # ---------------------------------------------------------------------------------------------- launcher
@@ -379,6 +396,42 @@ def load_profile_entry(name, kernel_name, filters_per_launch, cycles_per_launch=
     return e, exact, src
 
 
+# ---------------------------------------------------------------------------------------------- --dump-outputs
+def dump_blocks(total):
+    """[(first, count)] of the filters --dump-outputs writes: all of them up to DUMP_ALL_MAX filters, else DUMP_ALL_MAX /
+    DUMP_BLOCK blocks of DUMP_BLOCK consecutive filters at seeded positions (the same for every run with the same total)."""
+    import numpy as np
+    if total <= DUMP_ALL_MAX:
+        return [(0, total)]
+    slots = np.random.default_rng(DUMP_SEED).choice(total // DUMP_BLOCK, DUMP_ALL_MAX // DUMP_BLOCK, replace=False)
+    return [(int(s) * DUMP_BLOCK, DUMP_BLOCK) for s in np.sort(slots)]
+
+
+def dump_pieces(fetch, blocks, lo, hi):
+    """[(global first, mean, cov, status)] of the parts of `blocks` inside [lo, hi); fetch(first - lo, count) reads the state"""
+    out = []
+    for b0, n in blocks:
+        a, e = max(b0, lo), min(b0 + n, hi)
+        if a < e:
+            out.append((a,) + tuple(fetch(a - lo, e - a)))
+    return out
+
+
+def write_dump(dirname, pieces, f64):
+    """DIR/{filter_index,mean,cov,status}.npy in filter order: what a caller of the engine reads back (state(), status()),
+    float64 for an fp64 engine, float32 for an fp32 one (its state is fp32 in HBM)"""
+    import numpy as np
+    pieces = sorted(pieces, key=lambda p: p[0])
+    dt = np.float64 if f64 else np.float32
+    arrays = {"filter_index": np.concatenate([np.arange(p[0], p[0] + len(p[1])) for p in pieces]).astype(np.float64),
+              "mean": np.concatenate([p[1] for p in pieces]).astype(dt),
+              "cov": np.concatenate([p[2] for p in pieces]).astype(dt),
+              "status": np.concatenate([p[3] for p in pieces]).astype(np.float64)}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 # ---------------------------------------------------------------------------------------------- one rank
 def run_rank(args):
     import numpy as np
@@ -614,6 +667,14 @@ def run_rank(args):
     rank_lo, rank_hi = rank_stats(elapsed_local / args.steps * 1e3)
     _, barrier_hi = rank_stats(elapsed_barrier / args.steps * 1e3)
     status_or = eng.status_summary()
+    if args.dump_outputs:      # the state the timed steps left, before anything below advances it
+        pieces = dump_pieces(lambda a, n: eng.state(a, n)[:2] + (eng.status(a, n),), dump_blocks(total), first, first + per)
+        if dist is not None:
+            allp = [None] * world
+            dist.all_gather_object(allp, pieces)
+            pieces = [p for ps in allp for p in ps]
+        if rank == 0:
+            write_dump(args.dump_outputs, pieces, prec == spe.F64)
     # which device every rank ran on (the driver's SCALE line verifies itself: N distinct devices, N RCCL ranks)
     rank_devices = None
     try:
@@ -645,7 +706,7 @@ def run_rank(args):
 
     # ---- result gather over RCCL/xGMI (outside the timed region; means only)
     gather_ms = None
-    if dist is not None:
+    if dist is not None and args.full:
         mu_local = mu_view
         if args.backend != "nccl":
             mu_local = mu_local.cpu()
@@ -890,8 +951,11 @@ def run_group(args):
     grp.sync()
     elapsed = time.perf_counter() - t0
     status_or = grp.status_summary()
+    if args.dump_outputs:
+        write_dump(args.dump_outputs, dump_pieces(lambda a, n: grp.state(a, n)[:2] + (grp.status(a, n),), dump_blocks(total), 0, total),
+                   prec == spe.F64)
     gather_ms = None
-    if len(set(devices)) == len(devices):
+    if args.full and len(set(devices)) == len(devices):
         outs = [torch.empty((total, 13), dtype=tdtype, device=torch.device("cuda", d)) for d in devices]
         grp.gather_means(outs)      # first call: communicator + staging
         grp.sync()

@@ -115,3 +115,46 @@ def test_replayed_counters_are_tied_to_the_binary():
     for name in ("traffic_latest.json", "pmc_latest.json"):
         _, _, src = bench.load_profile_entry(name, "ukf_kernel16<f64,pose,cycle>", 1048576, 1.0, "0000")
         assert src["file"] == "profiles/" + name and src["matches_running_lib"] is False
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_sample_is_fixed_bounded_and_shard_independent(tmp_path):
+    """--dump-outputs: every filter of a small batch, a seeded block sample of a large one (the same in every run), at most
+    64 MB for the largest state (OrientationState, fp64), and the same rows whether one rank or several read them."""
+    import numpy as np
+    bench = _bench_module()
+    assert bench.dump_blocks(1000) == [(0, 1000)]
+    for total in (bench.DUMP_ALL_MAX + 1, 1_048_576, 4_194_304):
+        blocks = bench.dump_blocks(total)
+        assert blocks == bench.dump_blocks(total)
+        starts = [b for b, _ in blocks]
+        assert starts == sorted(set(starts)) and all(0 <= b and b + n <= total for b, n in blocks)
+        assert sum(n for _, n in blocks) == bench.DUMP_ALL_MAX
+    S, D = 14, 13
+    assert bench.DUMP_ALL_MAX * (1 + S + D * D + 1) * 8 <= 64 << 20
+
+    def fetch_from(lo):
+        def fetch(a, n):
+            ids = np.arange(lo + a, lo + a + n, dtype=np.float64)
+            return ids[:, None] * np.ones(S), ids[:, None, None] * np.ones((D, D)), np.zeros(n, np.uint32)
+        return fetch
+    total = 1_000_003
+    blocks = bench.dump_blocks(total)
+    one = bench.dump_pieces(fetch_from(0), blocks, 0, total)
+    bounds = [0, 333_333, 333_400, 700_000, total]
+    many = [p for lo, hi in zip(bounds[:-1], bounds[1:]) for p in bench.dump_pieces(fetch_from(lo), blocks, lo, hi)]
+    bench.write_dump(str(tmp_path / "one"), one, True)
+    bench.write_dump(str(tmp_path / "many"), many[::-1], False)
+    for name in ("filter_index", "mean", "cov", "status"):
+        a, b = np.load(tmp_path / "one" / (name + ".npy")), np.load(tmp_path / "many" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b.astype(a.dtype)), name
+    idx = np.load(tmp_path / "one" / "filter_index.npy")
+    assert np.array_equal(np.load(tmp_path / "one" / "mean.npy")[:, 0], idx)
+    assert np.array_equal(idx, np.concatenate([np.arange(b, b + n) for b, n in blocks]))

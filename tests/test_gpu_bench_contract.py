@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +26,7 @@ def run_bench(*args, env=None):
 
 
 def test_bench_line_has_the_contract_fields():
-    d = run_bench("--filters", "16384", "--steps", "5", "--warmup", "2", "--cpu-sample-filters", "256",
+    d = run_bench("--full", "--filters", "16384", "--steps", "5", "--warmup", "2", "--cpu-sample-filters", "256",
                   "--cpu-sample-seconds", "0.5")
     for key, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                      ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str),
@@ -63,26 +64,26 @@ def test_bench_line_has_the_contract_fields():
 
 
 def test_bench_other_workloads_run():
-    d = run_bench("--workload", "orient", "--precision", "f32", "--filters", "8192", "--steps", "3", "--warmup", "1",
+    d = run_bench("--full", "--workload", "orient", "--precision", "f32", "--filters", "8192", "--steps", "3", "--warmup", "1",
                   "--no-cpu-baseline")
     assert d["dtype"] == "f32" and "OrientationState" in d["metric"] and d["status_or"] == 0
     assert d["parity_recent"]["ok"] is True and d["parity_recent"]["tol"] == 1e-4
-    d = run_bench("--workload", "pose-mixed", "--filters", "8192", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    d = run_bench("--full", "--workload", "pose-mixed", "--filters", "8192", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
     assert d["value"] > 0 and d["parity"]["ok"] is True and d["multi_cycle"]["status_or"] == d["status_or"]
     # SURVEY 8(d)'s secondary run: the constant-velocity branch (no acceleration latched)
-    d = run_bench("--workload", "pose-cv", "--filters", "8192", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    d = run_bench("--full", "--workload", "pose-cv", "--filters", "8192", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
     assert "constant-velocity" in d["config"]["workload"] and d["status_or"] == 0 and d["parity"]["ok"] is True
     # position fixes regenerated on the device, step by step, around the filter's own mean (inputs regenerated
     # per cycle, nothing crosses PCIe inside the timed region); the oracle replay regenerates them the same way
     for prec, tol in (("f64", 1e-9), ("f32", 1e-4)):
-        d = run_bench("--inputs", "tracking", "--precision", prec, "--filters", "8192", "--steps", "12", "--warmup", "3", "--no-cpu-baseline")
+        d = run_bench("--full", "--inputs", "tracking", "--precision", prec, "--filters", "8192", "--steps", "12", "--warmup", "3", "--no-cpu-baseline")
         assert "tracking" in d["config"]["workload"] and d["status_or"] == 0 and d["multi_cycle"] is None
         assert d["parity"]["ok"] is True and d["parity"]["tol"] == tol and d["parity_recent"]["ok"] is True
 
 
 def test_bench_cycles_per_launch():
     """K timed cycles as launches of C cycles (ukfb_cycle_multi_dev): exactly K cycles, parity against the oracle replay"""
-    d = run_bench("--filters", "8192", "--steps", "13", "--warmup", "3", "--cycles-per-launch", "4", "--no-cpu-baseline")
+    d = run_bench("--full", "--filters", "8192", "--steps", "13", "--warmup", "3", "--cycles-per-launch", "4", "--no-cpu-baseline")
     r = d["roofline"]
     assert d["steps"] == 13 and "multicycle" in r["kernel"] and abs(r["cycles_per_launch"] - 13 / 4) < 1e-9
     assert d["status_or"] == 0 and d["parity"]["ok"] is True and d["parity_recent"]["ok"] is True
@@ -94,7 +95,7 @@ def test_single_rank_rccl_rehearsal():
     """The N > 1 code path (RCCL process group, barrier, all-reduce MAX, gather) with one rank on the one GPU."""
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    d = run_bench("--gpus", "1", "--filters", "16384", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra-regions",
+    d = run_bench("--full", "--gpus", "1", "--filters", "16384", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra-regions",
                   env={"RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port),
                        "UKFB_BENCH_FORCE_DIST": "1"})
     assert d["rccl_ranks"] == 1 and d["backend"] == "nccl" and d["gather_ms"] is not None and d["status_or"] == 0
@@ -104,7 +105,7 @@ def test_single_rank_rccl_rehearsal():
 def test_two_self_launched_ranks_share_the_gpu_over_gloo():
     """`python bench.py --gpus 2` with no wrapper: two child ranks, strong scaling (8 192 filters each), engine on
     the same device, rank plumbing over gloo (a one-GPU box cannot form a 2-rank RCCL communicator)."""
-    d = run_bench("--gpus", "2", "--backend", "gloo", "--filters", "16384", "--steps", "3", "--warmup", "1",
+    d = run_bench("--full", "--gpus", "2", "--backend", "gloo", "--filters", "16384", "--steps", "3", "--warmup", "1",
                   "--no-cpu-baseline", "--no-extra-regions")
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["filters_per_gpu"] == 8192
     assert d["rccl_ranks"] is None and d["backend"] == "gloo" and d["gather_ms"] is not None and d["status_or"] == 0
@@ -116,10 +117,57 @@ def test_group_launcher_one_process_two_shards():
     box: two shards on device 0 (gather skipped), and a 1-device group whose gather runs through RCCL."""
     for extra, ranks in (["--gpus", "2", "--group-devices", "0,0"], None), (["--gpus", "1"], 1):
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--launcher", "group", "--filters", "32768", "--steps", "8",
-                              "--warmup", "2", "--clock-warmup-seconds", "0.05", "--no-cpu-baseline"] + extra,
+                              "--warmup", "2", "--clock-warmup-seconds", "0.05", "--full", "--no-cpu-baseline"] + extra,
                              capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         d = json.loads(out.stdout.strip().splitlines()[-1])
         assert d["launcher"] == "group" and d["value"] > 0 and d["status_or"] == 0 and d["config"]["filters"] == 32768
         assert d["parity"]["ok"] is True and d["rccl_ranks"] == ranks
         assert (d["gather_ms"] is not None) == (ranks is not None)
+
+
+def test_plain_run_times_only_the_headline():
+    """Without --full the line holds the headline figures and nothing that takes runs or checks of its own."""
+    d = run_bench("--filters", "16384", "--steps", "7", "--warmup", "2")
+    for key, typ in (("metric", str), ("value", float), ("unit", str), ("ms_per_step", float), ("higher_is_better", bool),
+                     ("dtype", str), ("roofline", dict)):
+        assert key in d and isinstance(d[key], typ), key
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["value"] - 16384 * 7 / (d["ms_per_step"] * 7e-3)) / d["value"] < 1e-6 and d["status_or"] == 0
+    assert "cpu_baseline" not in d and d["parity"] is None and d["parity_recent"] is None and d["multi_cycle"] is None
+    r = d["roofline"]
+    assert r["kernel_ms_per_launch"] > 0 and r["kernel_ms_per_launch_sustained"] is None and r["kernel_ms_per_launch_burst"] is None
+
+
+def _load_dump(path):
+    import numpy as np
+    names = sorted(os.listdir(path))
+    assert names == ["cov.npy", "filter_index.npy", "mean.npy", "status.npy"], names
+    return {n[:-4]: np.load(os.path.join(path, n)) for n in names}
+
+
+@pytest.mark.parametrize("filters, prec", [(8192, "f32"), (65536, "f64")])
+def test_dump_outputs_are_the_timed_state_and_repeat(tmp_path, filters, prec):
+    """--dump-outputs writes the state the timed steps left: the same arrays in a second plain run and in a --full run of the
+    same arguments (whose extra regions and checks come after the dump); every filter of a small batch, a fixed sample of a
+    large one."""
+    args = ["--filters", str(filters), "--steps", "5", "--warmup", "2", "--precision", prec]
+    runs = []
+    for i, extra in enumerate(([], [], ["--full", "--no-cpu-baseline"])):
+        d = run_bench(*args, *extra, "--dump-outputs", str(tmp_path / f"run{i}"))
+        assert d["status_or"] == 0
+        runs.append(_load_dump(tmp_path / f"run{i}"))
+    a = runs[0]
+    n = min(filters, 32768)
+    dt = np.float64 if prec == "f64" else np.float32
+    assert a["mean"].shape == (n, 13) and a["cov"].shape == (n, 12, 12) and a["status"].shape == (n,)
+    assert a["mean"].dtype == dt and a["cov"].dtype == dt and a["status"].dtype == np.float64
+    idx = a["filter_index"]
+    assert idx.shape == (n,) and (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < filters
+    if filters <= 32768:
+        assert (idx == np.arange(filters)).all()
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert np.isfinite(a["mean"]).all() and np.isfinite(a["cov"]).all() and (a["status"] == 0).all()
+    for b in runs[1:]:
+        for k in a:
+            assert np.array_equal(a[k], b[k]), k

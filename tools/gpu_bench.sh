@@ -2,7 +2,7 @@
 # Runs ON THE GPU BOX: the reference bench lines of a build (short, default and fp32), compact summary on stdout.
 out=gpurun_out/${UKFB_ROUND:-r04}_$1; mkdir -p $out; shift
 export TMPDIR=/tmp
-run() { name=$1; shift; timeout -k 10 400 python3 bench.py "$@" > $out/$name.json 2> $out/$name.err || tail -3 $out/$name.err;
+run() { name=$1; shift; timeout -k 10 400 python3 bench.py --full "$@" > $out/$name.json 2> $out/$name.err || tail -3 $out/$name.err;
   python3 - $out/$name.json $name <<'PY'
 import json,sys
 try:

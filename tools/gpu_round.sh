@@ -14,9 +14,9 @@ for what in "$@"; do
       done
       cat $out/stamps_pose_f64.txt ;;
     bench)
-      timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_20.json 2> $out/bench_20.err
-      timeout -k 10 300 python3 bench.py --no-cpu-baseline > $out/bench_default.json 2> $out/bench_default.err
-      timeout -k 10 300 python3 bench.py --no-cpu-baseline --precision f32 > $out/bench_f32.json 2> $out/bench_f32.err
+      timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_20.json 2> $out/bench_20.err
+      timeout -k 10 300 python3 bench.py --full --no-cpu-baseline > $out/bench_default.json 2> $out/bench_default.err
+      timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --precision f32 > $out/bench_f32.json 2> $out/bench_f32.err
       cat $out/bench_20.json $out/bench_default.json $out/bench_f32.json ;;
   esac
 done

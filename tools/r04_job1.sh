@@ -10,6 +10,6 @@ for w in "pose f64" "pose f32" "orient f32" "orient f64"; do
   UKFB_LIB=$PWD/slam-pose_estimation_amd/lib/ab/counts.so timeout -k 10 300 python3 tools/phase_stamps.py $1 $2 262144 --counts > $out/counts_$1_$2.txt 2>&1 || tail -5 $out/counts_$1_$2.txt
   UKFB_LIB=$PWD/slam-pose_estimation_amd/lib/ab/stamps.so timeout -k 10 300 python3 tools/phase_stamps.py $1 $2 262144 > $out/stamps_$1_$2.txt 2>&1 || tail -5 $out/stamps_$1_$2.txt
 done
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_20.json 2> $out/bench_20.err
-timeout -k 10 300 python3 bench.py --no-cpu-baseline > $out/bench_default.json 2> $out/bench_default.err
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_20.json 2> $out/bench_20.err
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline > $out/bench_default.json 2> $out/bench_default.err
 cat $out/counts_pose_f64.txt $out/stamps_pose_f64.txt $out/bench_20.json

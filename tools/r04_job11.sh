@@ -5,7 +5,7 @@ set -o pipefail
 out=gpurun_out/r04_job11; mkdir -p $out
 export TMPDIR=/tmp
 L=slam-pose_estimation_amd/lib
-UKFB_LIB=$PWD/$L/ab/persist.so timeout -k 10 300 python3 bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-extra-regions > $out/bench_persist.json 2> $out/bench_persist.err || { tail -5 $out/bench_persist.err; exit 1; }
+UKFB_LIB=$PWD/$L/ab/persist.so timeout -k 10 300 python3 bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --no-extra-regions > $out/bench_persist.json 2> $out/bench_persist.err || { tail -5 $out/bench_persist.err; exit 1; }
 python3 - $out/bench_persist.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

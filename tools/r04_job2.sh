@@ -7,11 +7,11 @@ timeout -k 10 600 python -m pytest tests/test_gpu_wide_arithmetic.py -x -q -s > 
 tail -30 $out/pytest_wide.log
 timeout -k 10 900 python -m pytest tests -m gpu -x -q --deselect tests/test_gpu_wide_arithmetic.py > $out/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $out/pytest.log
 tail -4 $out/pytest.log
-timeout -k 10 400 python3 bench.py --precision f32 --wide-arithmetic 1 --no-cpu-baseline > $out/bench_cfg3_wide.json 2> $out/bench_cfg3_wide.err
-timeout -k 10 400 python3 bench.py --precision f32 --no-cpu-baseline > $out/bench_cfg3_f32.json 2> $out/bench_cfg3_f32.err
-timeout -k 10 500 python3 bench.py --workload orient --precision f32 --filters 4194304 --wide-arithmetic 1 --no-cpu-baseline > $out/bench_cfg4_wide.json 2> $out/bench_cfg4_wide.err
-timeout -k 10 500 python3 bench.py --workload orient --precision f32 --filters 4194304 --no-cpu-baseline > $out/bench_cfg4_f32.json 2> $out/bench_cfg4_f32.err
-timeout -k 10 300 python3 bench.py --workload orient --filters 4194304 --no-cpu-baseline --steps 100 > $out/bench_orient_f64.json 2> $out/bench_orient_f64.err
+timeout -k 10 400 python3 bench.py --full --precision f32 --wide-arithmetic 1 --no-cpu-baseline > $out/bench_cfg3_wide.json 2> $out/bench_cfg3_wide.err
+timeout -k 10 400 python3 bench.py --full --precision f32 --no-cpu-baseline > $out/bench_cfg3_f32.json 2> $out/bench_cfg3_f32.err
+timeout -k 10 500 python3 bench.py --full --workload orient --precision f32 --filters 4194304 --wide-arithmetic 1 --no-cpu-baseline > $out/bench_cfg4_wide.json 2> $out/bench_cfg4_wide.err
+timeout -k 10 500 python3 bench.py --full --workload orient --precision f32 --filters 4194304 --no-cpu-baseline > $out/bench_cfg4_f32.json 2> $out/bench_cfg4_f32.err
+timeout -k 10 300 python3 bench.py --full --workload orient --filters 4194304 --no-cpu-baseline --steps 100 > $out/bench_orient_f64.json 2> $out/bench_orient_f64.err
 for f in cfg3_wide cfg3_f32 cfg4_wide cfg4_f32 orient_f64; do python3 - $out/bench_$f.json <<'PY'
 import json,sys
 try:
