@@ -132,7 +132,8 @@ typedef struct ukfb_config {
                              * factorises only the columns of the downdated covariance that applyDelta reads (RT + 3 of them) when
                              * positive definiteness of that covariance is already established: the filter's prediction was committed
                              * in the same launch (its input covariance factorised, the predicted one is a Gram matrix + noise), the
-                             * batch-uniform process noise is positive semidefinite (checked on the host when it is set) and the
+                             * batch-uniform process noise is positive semidefinite with its rotated blocks [0:3] and [3:6] coupled to
+                             * no other entry, so that the prediction's rotation keeps it so (checked on the host when it is set) and the
                              * sample's measurement covariance is positive definite (checked per filter in the kernel).  Results are
                              * bit-identical with the complete factorisation; what differs: a covariance that is indefinite through
                              * ROUNDING alone is reported by the next prediction's factorisation (UKFB_ST_ERR_CHOLESKY there), not by

@@ -368,14 +368,25 @@ bool is_psd(const double* A, int D) {
 }
 
 // ukfb_config::full_update_check: the host-side condition of the short update factorisation -- the batch-uniform process noise as the
-// prediction adds it (rotation of its diagonal blocks and scaling by dt / dt^2 keep semidefiniteness; Pose acceleration branch: the
-// velocity block replaced by 2 acc.cov, PoseUKF.cpp:190-191) is positive semidefinite
+// prediction adds it is positive semidefinite.  The prediction rotates the diagonal blocks [0:3] and [3:6] and leaves every other
+// entry raw (PoseUKF.cpp:184-185, OrientationUKF.cpp:84-85); that is the congruence blockdiag(rot, rot, I) R blockdiag(rot, rot, I)^T,
+// which keeps R semidefinite for any rot (non-unit quaternions included), only when rows / columns 0..5 are zero outside their own
+// 3x3 diagonal block.  A semidefinite R with such cross terms can turn indefinite, so it keeps the complete factorisation.  Scaling
+// by dt / dt^2 keeps semidefiniteness; Pose acceleration branch: the unrotated R with the velocity block replaced by 2 acc.cov
+// (PoseUKF.cpp:190-191) must be semidefinite as well.
+bool rotated_blocks_uncoupled(const double* A, int D) {
+    for (int r = 0; r < D; ++r)
+        for (int c = 0; c < 6; ++c)
+            if (r / 3 != c / 3 && (A[size_t(r) * D + c] != 0.0 || A[size_t(c) * D + r] != 0.0)) return false;
+    return true;
+}
+
 void refresh_noise_psd(ukfb_engine* e) {
     if (e->Rn_per_filter || e->Rn_host.size() != size_t(e->D) * e->D) {
         e->noise_psd = false;
         return;
     }
-    bool ok = is_psd(e->Rn_host.data(), e->D);
+    bool ok = rotated_blocks_uncoupled(e->Rn_host.data(), e->D) && is_psd(e->Rn_host.data(), e->D);
     if (ok && e->model == UKFB_MODEL_POSE) {
         std::vector<double> Ra(e->Rn_host);
         for (int r = 0; r < 3; ++r)

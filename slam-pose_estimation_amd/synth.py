@@ -164,3 +164,73 @@ def orient_cycle_inputs(n: int, cycle: int, mu_q=None, seed: int = SEED_BASE + 4
     z = uniform(s, ids, [6, 7, 8], -0.05, 0.05)
     Q = np.broadcast_to(0.05 ** 2 * np.eye(3), (n, 3, 3)).copy()
     return gyro, acc, z, Q
+
+
+# ------------------------------------------------------------------------------- dense process noise (tests)
+# Process noise whose every lower-triangle entry is nonzero and distinct: a kernel that reads one entry of the noise from the
+# wrong place (a swapped pair, a cross block read as zero) changes the predicted covariance.  Standard deviations per state
+# dimension: the noise moves the predicted covariance by ~1e-3 .. 1e-2 at dt = 0.01 .. 0.05 (Pose, constant-velocity branch:
+# dt R; OrientationState: dt^2 R), far above the fp32 tolerance, while the orientation blocks stay small enough for ordinary
+# sigma-point spreads.  The Pose velocity block stays below 2 dense_acc_cov(), so the acceleration branch's noise (velocity
+# block replaced by 2 acc.cov, PoseUKF.cpp:190-191) stays positive definite as well.
+DENSE_NOISE_STD = {
+    "pose": np.array([1.0] * 3 + [0.03] * 3 + [0.3] * 3 + [0.3] * 3),
+    "orient": np.array([1.0] * 3 + [3.0] * 3 + [0.3] * 3 + [3.0] * 3 + [3.0]),
+}
+ROTATION_INDEFINITE_Q = np.array([0.5, 0.5, 0.5, 0.5])   # (x, y, z, w): a rotation by 120 degrees that moves every axis
+
+
+def _dense_spd(seed, ids, std):
+    """S^1/2 C S^1/2: C the correlation matrix of I / 8 + G G^T / dof, G ~ U(-1, 1)^(dof x dof) (correlations of both signs, no
+    entry zero), S = std^2 times U(1, 2) per entry of the diagonal (no two variances equal)."""
+    n, dof = len(ids), len(std)
+    G = uniform(seed, ids, np.arange(dof * dof), -1.0, 1.0).reshape(n, dof, dof)
+    A = 0.125 * np.eye(dof)[None] + (G @ np.swapaxes(G, 1, 2)) / float(dof)
+    d = 1.0 / np.sqrt(np.einsum("nii->ni", A))
+    sd = std[None, :] * np.sqrt(uniform(seed, ids, np.arange(dof * dof, dof * dof + dof), 1.0, 2.0))
+    C = (d[:, :, None] * A * d[:, None, :]) * (sd[:, :, None] * sd[:, None, :])
+    C = 0.5 * (C + np.swapaxes(C, 1, 2))
+    # The prediction rotates the diagonal blocks [0:3] and [3:6] and keeps everything else (not a congruence): scale the entries
+    # coupling the three groups [0:3], [3:6], [6:] so that the noise stays positive definite for ANY rotation.  With the groups'
+    # smallest eigenvalues l (invariant under the rotation) and X the coupling entries, ||diag(l)^-1/2 X diag(l)^-1/2|| <= 1/2.
+    grp = np.minimum(np.arange(dof) // 3, 2)
+    cross = grp[:, None] != grp[None, :]
+    lam = np.empty((n, dof))
+    for g in range(3):
+        lam[:, grp == g] = np.linalg.eigvalsh(C[:, grp == g][:, :, grp == g]).min(axis=1)[:, None]
+    X = np.where(cross[None], C, 0.0)
+    K = X / np.sqrt(lam[:, :, None] * lam[:, None, :])
+    t = np.minimum(1.0, 0.5 / np.linalg.norm(K, ord=2, axis=(1, 2)))
+    return np.where(cross[None], C * t[:, None, None], C)
+
+
+def dense_process_noise_per_filter(model: str, n: int, seed: int = SEED_BASE + 7):
+    """[n, D, D]: a different dense positive definite process noise per filter (model "pose" or "orient")."""
+    return _dense_spd(seed, np.arange(n), DENSE_NOISE_STD[model])
+
+
+def dense_process_noise(model: str, seed: int = SEED_BASE + 7):
+    """[D, D]: one dense positive definite process noise (model "pose" or "orient"); = filter 0 of the per-filter stack."""
+    return dense_process_noise_per_filter(model, 1, seed)[0]
+
+
+def dense_acc_cov(seed: int = SEED_BASE + 8):
+    """A full SPD 3x3 acceleration covariance, eigenvalues >= 0.3 (see DENSE_NOISE_STD)."""
+    G = uniform(seed, [0], np.arange(9), -1.0, 1.0).reshape(3, 3)
+    A = 0.3 * np.eye(3) + 0.05 * (G @ G.T)
+    return 0.5 * (A + A.T)
+
+
+def rotation_indefinite_noise(model: str):
+    """A positive semidefinite process noise that the prediction makes INDEFINITE at the orientation ROTATION_INDEFINITE_Q: the
+    prediction rotates the diagonal blocks [0:3] and [3:6] but leaves their cross blocks raw (PoseUKF.cpp:184-185,
+    OrientationUKF.cpp:84-85), which is not a congruence.  An anisotropic rotated block (variance along x only) is coupled almost
+    perfectly to a block that is not rotated: Pose position x <-> velocity x, OrientationState velocity x <-> acceleration bias x.
+    Orientations that keep the x axis (rotations about x) keep the noise semidefinite."""
+    if model == "pose":
+        R = np.diag(np.r_[1e-2 * np.array([1.0, 1e-6, 1e-6]), [1e-3] * 3, [1e-2] * 3, [1e-5] * 3])
+        R[0, 6] = R[6, 0] = 0.99e-2
+    else:
+        R = np.diag(np.r_[[1e-3] * 3, [1.0, 1e-6, 1e-6], [1e-4] * 3, [1.0] * 3, [1e-4]])
+        R[3, 9] = R[9, 3] = 0.99
+    return R
