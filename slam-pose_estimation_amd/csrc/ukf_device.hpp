@@ -178,6 +178,9 @@ UKFB_DEV double m_rint(double x) { return __builtin_rint(x); }
 UKFB_DEV float m_rint(float x) { return __builtin_rintf(x); }
 UKFB_DEV double m_abs(double x) { return __builtin_fabs(x); }
 UKFB_DEV float m_abs(float x) { return __builtin_fabsf(x); }
+// the sign bit, -0.0 included: MTK's atan(|vec| / -0.0) is -pi/2, so a log at w = -0.0 is -pi vec/|vec| (w < 0 would say +)
+UKFB_DEV bool m_signbit(double x) { return __builtin_signbit(x); }
+UKFB_DEV bool m_signbit(float x) { return __builtin_signbitf(x); }
 
 // (cos(sqrt(y)), sin(sqrt(y))/sqrt(y)) for y >= 0 with no sqrt / sincos / division on the common path:
 // Taylor polynomial in y up to (pi/4)^2; one angle doubling up to (pi/2)^2; beyond that the angle is
@@ -228,7 +231,7 @@ template <class T> UKFB_DEV void so3_exp_fast(const T (&v)[3], T scale, T (&q)[4
 // 2 atan(|vec|/w)/|vec| * vec = (2/w) * [atan(t)/t] * vec with t^2 = |vec|^2 / w^2.  Beyond ~30 degrees
 // (wave-uniform branch) the half angle phi = atan(|vec|/|w|) is halved three times with
 // tan(phi/2) = t / (1 + sqrt(1 + t^2)), which brings it below atan(0.2); sign of w restores MTK's
-// plus/minus periodicity.  No ocml calls.
+// plus/minus periodicity (the sign bit of w, so that w = -0.0 is negative as in MTK).  No ocml calls.
 template <class T> UKFB_DEV void so3_log_fast(const T (&q)[4], T (&r)[3]) {
     const T v2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2];
     const T w = q[3];
@@ -251,7 +254,7 @@ template <class T> UKFB_DEV void so3_log_fast(const T (&q)[4], T (&r)[3]) {
         const T r3 = fast_rcp(T(1) + q3 * fast_rsqrt(q3));
         const T t3 = t2 * r3 * r3;                       // tan^2(phi/8) <= 0.0396
         const T sb = T(16) * (r1 * r2) * r3 * poly_atan_ratio(t3);
-        s = big ? ((w < T(0)) ? -sb : sb) : s;
+        s = big ? (m_signbit(w) ? -sb : sb) : s;
     }
     r[0] = s * q[0]; r[1] = s * q[1]; r[2] = s * q[2];
 }
@@ -283,7 +286,7 @@ template <class T> UKFB_DEV void so3_log_fast_n(const T (&q)[4], T nrm, T (&r)[3
         const T r3 = fast_rcp(T(1) + q3 * fast_rsqrt(q3));
         const T t3 = t2 * r3 * r3;                       // tan^2(phi/8) <= 0.0396
         const T sb = T(16) * (r1b * r2) * r3 * poly_atan_ratio(t3);
-        s = big ? ((w < T(0)) ? -sb : sb) : s;
+        s = big ? (m_signbit(w) ? -sb : sb) : s;
     }
     r[0] = s * q[0]; r[1] = s * q[1]; r[2] = s * q[2];
 }
@@ -315,7 +318,7 @@ template <class T> UKFB_DEV void so3_log_fast_n2(const T (&qa)[4], const T (&qb)
             const T r3 = fast_rcp(T(1) + q3 * fast_rsqrt(q3));
             const T t3 = t2 * r3 * r3;
             const T sw = T(16) * (r1w * r2) * r3 * poly_atan_ratio(t3);
-            return (w < T(0)) ? -sw : sw;
+            return m_signbit(w) ? -sw : sw;
         };
         const T wa = wide(v2a, qa[3]), wb = wide(v2b, qb[3]);
         sa = lane_of(biga) ? wa : sa;
