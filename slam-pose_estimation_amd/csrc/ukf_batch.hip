@@ -202,13 +202,6 @@ int launch(ukfb_engine* e, const ukfb::LaunchReq& r) {
 // behind the kernel of the previous call: copy and kernel alternate (1 M Pose filters fp64: 2.0 ms of PCIe + 1.1 ms of
 // kernel per cycle).  Here the upload of call k + 1 runs on a separate stream into the staging set call k is not reading;
 // the call returns when ITS copies have been consumed (the caller's buffers are free), not when the kernel is done.
-struct Staged {
-    void* z = nullptr;
-    void* Q = nullptr;
-    hipEvent_t ready = nullptr, done = nullptr;
-    int slot = 0;
-};
-
 int ensure_copy_path(ukfb_engine* e) {
     if (e->copy_stream) return UKFB_OK;
     const size_t n = size_t(e->cap), ts = e->tsize;
@@ -263,7 +256,16 @@ int upload_on_copy_stream(ukfb_engine* e, void* dst_dev, const double* src, size
 
 hipError_t wait_stream_polling(hipStream_t s);
 
-int stage_cycle_inputs(ukfb_engine* e, const double* z, const double* Q, size_t nq, Staged* out) {
+// a bounded wait gave up (its text is written): work of unknown state is still queued, the engine is poisoned (see ENGINE_SYNC)
+bool gave_up(ukfb_engine* e, hipError_t w) {
+    if (w != hipErrorNotReady || !g_wait_timed_out) return false;
+    e->poisoned = true;
+    g_wait_timed_out = false;
+    return true;
+}
+
+// host-fed launch: z and Q are uploaded into a staging set on the copy stream, the kernel waits for them and frees the set behind it
+int launch_staged(ukfb_engine* e, ukfb::LaunchReq r, const double* z, const double* Q, size_t nq) {
     if (!z || !Q) return fail(UKFB_ERR_INVALID_ARG, "z and Q must not be NULL");
     if (e->poisoned) return fail(UKFB_ERR_HIP, "engine poisoned by an earlier wait that timed out (UKFB_WAIT_TIMEOUT_S)");
     int rc = ensure_copy_path(e);
@@ -288,26 +290,21 @@ int stage_cycle_inputs(ukfb_engine* e, const double* z, const double* Q, size_t 
     if (rc) return rc;
     HIP_TRY(hipEventRecord(e->ev_copy[s], e->copy_stream));
     // the caller's buffers are free again once the copies have been consumed: wait for the COPY stream only (bounded)
-    {
-        const hipError_t w = wait_stream_polling(e->copy_stream);
-        if (w == hipErrorNotReady && g_wait_timed_out) {
-            e->poisoned = true;
-            g_wait_timed_out = false;
-            return UKFB_ERR_HIP;
-        }
-        HIP_TRY(w);
-    }
-    out->z = e->zc_stage[s];
-    out->Q = e->Qc_stage[s];
-    out->ready = e->ev_copy[s];
-    out->done = e->ev_used[s];
-    out->slot = s;
-    return UKFB_OK;
+    const hipError_t w = wait_stream_polling(e->copy_stream);
+    if (gave_up(e, w)) return UKFB_ERR_HIP;
+    HIP_TRY(w);
+    r.z_dev = e->zc_stage[s];
+    r.Q_dev = e->Qc_stage[s];
+    r.wait_event = e->ev_copy[s];
+    r.done_event = e->ev_used[s];
+    r.no_split = true;   // one kernel on the engine's stream: the done event covers all of it
+    rc = launch(e, r);
+    if (!rc) e->stage_busy[s] = true;
+    return rc;
 }
 
-bool meas_model_ok(const ukfb_engine* e, int m) {
-    if (e->model == UKFB_MODEL_POSE) return m >= UKFB_MEAS_POS3 && m <= UKFB_MEAS_ANGVEL3;
-    return m == UKFB_MEAS_ORIENT_BODYVEL3;
+int check_meas_model(const ukfb_engine* e, int m) {
+    return ukfb::meas_model_ok(e->model, m) ? UKFB_OK : fail(UKFB_ERR_WRONG_MODEL, "measurement model id not valid for this engine");
 }
 
 // stage host measurement arrays into the engine's device buffers
@@ -337,67 +334,10 @@ template <class T> __global__ void build_racc_kernel(const T* Rn, T* Racc, int64
     Racc[i] = vel ? T(2) * acc_cov9[(r - 6) * 3 + (c - 6)] : Rn[i];
 }
 
-// Positive semidefinite? -- of the symmetric matrix the kernels use (they read the lower triangle).  Cholesky with a tolerance: a pivot
-// below -tol fails; a pivot within tol must head a column of zeros (a zero direction, e.g. the all-zero default noise).
-bool is_psd(const double* A, int D) {
-    std::vector<double> L(size_t(D) * D, 0.0);
-    double dmax = 0.0;
-    for (int i = 0; i < D; ++i) dmax = std::max(dmax, std::fabs(A[size_t(i) * D + i]));
-    const double tol = 1e-12 * dmax;
-    for (int k = 0; k < D; ++k) {
-        double x = A[size_t(k) * D + k];
-        if (!std::isfinite(x)) return false;
-        for (int j = 0; j < k; ++j) x -= L[size_t(k) * D + j] * L[size_t(k) * D + j];
-        if (x < -tol) return false;
-        const bool zero = x <= tol;
-        const double d = zero ? 0.0 : std::sqrt(x);
-        L[size_t(k) * D + k] = d;
-        for (int i = k + 1; i < D; ++i) {
-            double v = A[size_t(i) * D + k];
-            if (!std::isfinite(v)) return false;
-            for (int j = 0; j < k; ++j) v -= L[size_t(i) * D + j] * L[size_t(k) * D + j];
-            if (zero) {
-                if (std::fabs(v) > std::sqrt(tol * std::max(dmax, 1e-300)) + 1e-300) return false;
-                L[size_t(i) * D + k] = 0.0;
-            } else {
-                L[size_t(i) * D + k] = v / d;
-            }
-        }
-    }
-    return true;
-}
-
-// ukfb_config::full_update_check: the host-side condition of the short update factorisation -- the batch-uniform process noise as the
-// prediction adds it is positive semidefinite.  The prediction rotates the diagonal blocks [0:3] and [3:6] and leaves every other
-// entry raw (PoseUKF.cpp:184-185, OrientationUKF.cpp:84-85); that is the congruence blockdiag(rot, rot, I) R blockdiag(rot, rot, I)^T,
-// which keeps R semidefinite for any rot (non-unit quaternions included), only when rows / columns 0..5 are zero outside their own
-// 3x3 diagonal block.  A semidefinite R with such cross terms can turn indefinite, so it keeps the complete factorisation.  Scaling
-// by dt / dt^2 keeps semidefiniteness; Pose acceleration branch: the unrotated R with the velocity block replaced by 2 acc.cov
-// (PoseUKF.cpp:190-191) must be semidefinite as well.
-bool rotated_blocks_uncoupled(const double* A, int D) {
-    for (int r = 0; r < D; ++r)
-        for (int c = 0; c < 6; ++c)
-            if (r / 3 != c / 3 && (A[size_t(r) * D + c] != 0.0 || A[size_t(c) * D + r] != 0.0)) return false;
-    return true;
-}
-
-void refresh_noise_psd(ukfb_engine* e) {
-    if (e->Rn_per_filter || e->Rn_host.size() != size_t(e->D) * e->D) {
-        e->noise_psd = false;
-        return;
-    }
-    bool ok = rotated_blocks_uncoupled(e->Rn_host.data(), e->D) && is_psd(e->Rn_host.data(), e->D);
-    if (ok && e->model == UKFB_MODEL_POSE) {
-        std::vector<double> Ra(e->Rn_host);
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) Ra[size_t(6 + r) * e->D + (6 + c)] = 2.0 * e->acc_cov[r * 3 + c];
-        ok = is_psd(Ra.data(), e->D);
-    }
-    e->noise_psd = ok;
-}
-
 int rebuild_racc(ukfb_engine* e) {
-    refresh_noise_psd(e);
+    // the short update factorisation's host-side condition (ukfb::short_update_ok) for the batch-uniform noise
+    e->noise_psd = !e->Rn_per_filter && e->Rn_host.size() == size_t(e->D) * e->D &&
+                   ukfb::short_update_ok(e->model, e->D, e->Rn_host.data(), e->acc_cov);
     if (e->model != UKFB_MODEL_POSE) return UKFB_OK;
     const int64_t nmat = e->Rn_per_filter ? e->cap : 1;
     const size_t dd = size_t(e->D) * e->D;
@@ -507,13 +447,6 @@ template <class T> int import_body_states(ukfb_engine* e, int64_t first, int64_t
     return UKFB_OK;
 }
 
-// Class of a filter's update in a call: 0 = none (negative / invalid model id: prediction only), 1 = closed form (the eight
-// linear sub-state selections of PoseUKF), 2 = sigma-point path (PoseUKF OrientationMeasurement, OrientationUKF body velocity)
-__device__ __forceinline__ int update_class(int engine_model, int mid) {
-    if (engine_model == UKFB_MODEL_POSE) return (mid < 0 || mid > 8) ? 0 : ((mid == 3) ? 2 : 1);
-    return (mid == 9) ? 2 : 0;
-}
-
 // ---- device-side ordering of an event stream ------------------------------------------------------------
 __global__ void events_init_kernel(const int64_t* filt, const int64_t* ts, int64_t n, int64_t cap, uint32_t* idx,
                                    int64_t* key_t, uint32_t* flags) {
@@ -543,7 +476,7 @@ __global__ void events_rank_kernel(const uint32_t* start, const uint32_t* idx, c
     if (k >= n) return;
     const uint32_t r = uint32_t(k) - start[k];
     if (r >= (1u << 30)) atomicOr(&flags[0], 2u);   // a billion samples of one filter in one call: not representable in the key
-    key[k] = (r << 2) | uint32_t(2 - update_class(engine_model, meas[idx[k]]));
+    key[k] = (r << 2) | uint32_t(2 - ukfb::update_class(engine_model, meas[idx[k]]));
     atomicMax(&flags[1], r);
 }
 // first position of every round in the (rank, filter)-ordered event list; off[rounds] = n
@@ -578,7 +511,7 @@ __global__ void events_gather_kernel(const int64_t* filt, const int64_t* ts, con
 // block scatters from its offsets.  The
 // classes follow each other from the most expensive to the cheapest, each
 // starts at a multiple of 4 (one wavefront = 4 filters); the gaps behind the classes are filled with -1 (padding) by the scatter kernel.
-constexpr int BK_THREADS = 256, BK_PER_THREAD = 4, BK_BLOCK = BK_THREADS * BK_PER_THREAD;
+using ukfb::BK_THREADS, ukfb::BK_PER_THREAD, ukfb::BK_BLOCK;
 __global__ void __launch_bounds__(BK_THREADS) bucket_count_kernel(const int32_t* meas, int64_t n, int engine_model, uint32_t* counts,
                                                                   int nblocks) {
     using Reduce = hipcub::BlockReduce<uint32_t, BK_THREADS>;
@@ -588,7 +521,7 @@ __global__ void __launch_bounds__(BK_THREADS) bucket_count_kernel(const int32_t*
 #pragma unroll
     for (int j = 0; j < BK_PER_THREAD; ++j)
         if (base + j < n) {
-            const int c = update_class(engine_model, meas[base + j]);
+            const int c = ukfb::update_class(engine_model, meas[base + j]);
             c1 += c == 1;
             c2 += c == 2;
             ++valid;
@@ -688,7 +621,7 @@ __global__ void __launch_bounds__(BK_THREADS) bucket_scatter_kernel(const int32_
     const int64_t base = int64_t(blockIdx.x) * BK_BLOCK + int64_t(threadIdx.x) * BK_PER_THREAD;
     int cls[BK_PER_THREAD];
 #pragma unroll
-    for (int j = 0; j < BK_PER_THREAD; ++j) cls[j] = (base + j < n) ? update_class(engine_model, meas[base + j]) : -1;
+    for (int j = 0; j < BK_PER_THREAD; ++j) cls[j] = (base + j < n) ? ukfb::update_class(engine_model, meas[base + j]) : -1;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         uint32_t mine = 0;
@@ -703,22 +636,19 @@ __global__ void __launch_bounds__(BK_THREADS) bucket_scatter_kernel(const int32_
             if (cls[j] == c) order[rank++] = int32_t(base + j);
     }
 }
-constexpr int BUCKET_INLINE_BLOCKS = 2048;   // up to 2 M filters: every scatter block sums 3 x 2048 counts at most
-constexpr int64_t BUCKET_MIN_FILTERS = 16384;
-
 // fills e->bucket_idx for the model ids in meas_dev; *items = entries of the list that a launch must cover (an upper bound
 // known without reading anything back: every class is padded to a multiple of 4)
 int build_model_buckets(ukfb_engine* e, const int32_t* meas_dev, int64_t* items) {
     const int64_t n = e->cap;
-    const int nblocks = int((n + BK_BLOCK - 1) / BK_BLOCK);
-    const size_t list = size_t(n) + 16;
+    const ukfb::BucketGeometry geo = ukfb::bucket_geometry(n);
+    const int nblocks = geo.blocks;
     if (!e->bucket_idx || !e->bucket_counts) {
         // both or neither: the engine sees the pair only when every allocation succeeded (a half-published pair would let the
         // next call skip the allocation and launch through a null pointer)
         int32_t* idx = nullptr;
-        uint32_t* cnt = nullptr;   // [3][blocks] counts, [3][blocks] exclusive prefix sums, [3] totals (+ 1 pad)
-        if (hipMalloc(reinterpret_cast<void**>(&idx), list * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&cnt), (size_t(6) * nblocks + 4) * sizeof(uint32_t)) != hipSuccess) {
+        uint32_t* cnt = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(&idx), geo.list * sizeof(int32_t)) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&cnt), geo.count_words * sizeof(uint32_t)) != hipSuccess) {
             if (idx) (void)hipFree(idx);
             return fail(UKFB_ERR_HIP, "model buckets: device allocation failed");
         }
@@ -729,11 +659,11 @@ int build_model_buckets(ukfb_engine* e, const int32_t* meas_dev, int64_t* items)
     }
     uint32_t* const before = e->bucket_counts + size_t(3) * nblocks;
     uint32_t* const total = e->bucket_counts + size_t(6) * nblocks;
-    *items = (n + 3 + 3 + 3) / 4 * 4;   // sum of three counts each rounded up to 4 <= n + 9, itself rounded up to whole wavefronts
+    *items = geo.items;
     // (the gaps of the list -- behind each class, up to *items -- are written by the scatter kernel: no memset)
     hipLaunchKernelGGL(bucket_count_kernel, dim3(nblocks), dim3(BK_THREADS), 0, ukfb::main_stream(e), meas_dev, n, e->model, e->bucket_counts,
                        nblocks);
-    if (nblocks <= BUCKET_INLINE_BLOCKS) {
+    if (geo.inline_scan) {
         hipLaunchKernelGGL(bucket_scatter_kernel<true>, dim3(nblocks), dim3(BK_THREADS), 0, ukfb::main_stream(e), meas_dev, n, e->model,
                            static_cast<const uint32_t*>(e->bucket_counts), static_cast<const uint32_t*>(before),
                            static_cast<const uint32_t*>(total), nblocks, e->bucket_idx, uint32_t(*items));
@@ -803,13 +733,68 @@ int engine_wait(ukfb_engine* e) {
     if (e->poisoned) return fail(UKFB_ERR_HIP, "engine poisoned by an earlier wait that timed out (UKFB_WAIT_TIMEOUT_S)");
     const hipError_t r = wait_stream_polling(ukfb::main_stream(e));
     if (r == hipSuccess) return UKFB_OK;
-    if (r == hipErrorNotReady && g_wait_timed_out) {
-        e->poisoned = true;
-        g_wait_timed_out = false;
-    } else {
-        ukfb::set_error("waiting for the engine's stream", r);
-    }
+    if (!gave_up(e, r)) ukfb::set_error("waiting for the engine's stream", r);
     return UKFB_ERR_HIP;
+}
+
+// The launches of a multi-cycle call (ukfb::CyclePlan) over device rings [slots][capacity][...]: z, Q, the latched inputs
+// (optional) and per-filter model ids (meas_dev, optional).  sched_dt / sched_model: a host schedule [cycles], or NULL and the
+// uniform dt / meas_model.  A per-cycle launch reads its ring slot through the engine's bound inputs, restored afterwards.
+int run_cycle_plan(ukfb_engine* e, const ukfb::CyclePlan& plan, double dt, int meas_model, const double* sched_dt,
+                   const int32_t* sched_model, const int32_t* meas_dev, const void* in_a_dev, const void* in_b_dev,
+                   const void* z_dev, const void* Q_dev) {
+    const size_t w = e->tsize;
+    const void* keep_a = e->in_a_bound;
+    const void* keep_b = e->in_b_bound;
+    int rc = UKFB_OK;
+    for (int k = 0; k < plan.launches() && rc == UKFB_OK; ++k) {
+        const ukfb::CycleLaunch c = plan[k];
+        ukfb::LaunchReq r;
+        r.do_predict = true;
+        r.do_update = true;
+        r.status_accumulate = c.status_accumulate;
+        if (plan.multi) {
+            r.dt_uniform = dt;
+            r.meas_uniform = meas_model;
+            r.meas_dev = meas_dev;
+            r.z_dev = z_dev;
+            r.Q_dev = Q_dev;
+            r.cycles = c.cycles;
+            r.slots = plan.slots;
+            r.first_slot = c.slot;
+            r.in_a_slots = in_a_dev;
+            r.in_b_slots = in_b_dev;
+            if (sched_dt) {
+                r.sched_dt = sched_dt + c.first_cycle;
+                r.sched_model = sched_model + c.first_cycle;
+            }
+        } else {
+            const size_t s = size_t(c.slot) * size_t(e->cap);
+            if (in_a_dev) e->in_a_bound = static_cast<const char*>(in_a_dev) + s * 3 * w;
+            if (in_b_dev) e->in_b_bound = static_cast<const char*>(in_b_dev) + s * 3 * w;
+            r.do_update = !sched_model || sched_model[c.first_cycle] >= 0;
+            r.dt_uniform = sched_dt ? sched_dt[c.first_cycle] : dt;
+            r.meas_uniform = sched_model ? sched_model[c.first_cycle] : meas_model;
+            r.meas_dev = meas_dev ? meas_dev + s : nullptr;
+            r.z_dev = static_cast<const char*>(z_dev) + s * 3 * w;
+            r.Q_dev = static_cast<const char*>(Q_dev) + s * 9 * w;
+        }
+        rc = launch(e, r);
+    }
+    e->in_a_bound = keep_a;
+    e->in_b_bound = keep_b;
+    return rc;
+}
+
+// meas_dev != NULL: per-filter model ids, a ring [slots][capacity] like z and Q (meas_model is then ignored)
+int cycle_multi_impl(ukfb_engine* e, int cycles, double dt, int meas_model, const int32_t* meas_dev, int slots, int first_slot,
+                     const void* in_a_dev, const void* in_b_dev, const void* z_dev, const void* Q_dev) {
+    if (!e || !z_dev || !Q_dev) return UKFB_ERR_INVALID_ARG;
+    const ukfb::Verdict v = ukfb::check_cycle_args(cycles, slots, first_slot);
+    if (v.rc) return fail(v.rc, v.msg);
+    if (const int rc = meas_dev ? UKFB_OK : check_meas_model(e, meas_model)) return rc;
+    const ukfb::CyclePlan plan(cycles, slots, first_slot, e->cfg.lanes_per_filter == 16, false);
+    return run_cycle_plan(e, plan, dt, meas_model, nullptr, nullptr, meas_dev, in_a_dev, in_b_dev, z_dev, Q_dev);
 }
 }  // namespace
 
@@ -925,10 +910,7 @@ int ukfb_create_on_stream(ukfb_engine** out, int model, int precision, int64_t c
 }
 
 int ukfb_layout_supported(int precision, int lanes_per_filter) {
-    if (precision != UKFB_F64 && precision != UKFB_F32) return 0;
-    if (lanes_per_filter == 0 || lanes_per_filter == 16) return 1;
-    if (lanes_per_filter != 32 && lanes_per_filter != 64) return 0;
-    return (precision == UKFB_F32 || UKFB_GENERIC_F64 != 0) ? 1 : 0;
+    return ukfb::layout_supported(precision, lanes_per_filter, UKFB_GENERIC_F64 != 0) ? 1 : 0;
 }
 
 int ukfb_destroy(ukfb_engine* e) {
@@ -968,16 +950,8 @@ int ukfb_destroy(ukfb_engine* e) {
 int ukfb_set_config(ukfb_engine* e, const ukfb_config* cfg) {
     if (!e || !cfg) return UKFB_ERR_INVALID_ARG;
     ukfb_config c = *cfg;
-    if (c.lanes_per_filter == 0) c.lanes_per_filter = 16;
-    if (c.lanes_per_filter != 16 && c.lanes_per_filter != 32 && c.lanes_per_filter != 64)
-        return fail(UKFB_ERR_INVALID_ARG, "lanes_per_filter must be 16, 32 or 64");
-    if (!ukfb_layout_supported(e->prec, c.lanes_per_filter))
-        return fail(UKFB_ERR_INVALID_ARG, "lanes_per_filter 32 / 64 in fp64 is a diagnostic build option (make GENERIC_F64=1)");
-    if (c.mean_max_iter < 1) return fail(UKFB_ERR_INVALID_ARG, "mean_max_iter must be >= 1");
-    if (c.wide_arithmetic != 0 && c.wide_arithmetic != 1) return fail(UKFB_ERR_INVALID_ARG, "wide_arithmetic must be 0 or 1");
-    if (c.full_update_check != 0 && c.full_update_check != 1) return fail(UKFB_ERR_INVALID_ARG, "full_update_check must be 0 or 1");
-    if (c.wide_arithmetic && e->prec == UKFB_F32 && c.lanes_per_filter != 16)
-        return fail(UKFB_ERR_INVALID_ARG, "wide_arithmetic runs on the tuned layout only (lanes_per_filter 16)");
+    const ukfb::Verdict v = ukfb::check_config(e->prec, UKFB_GENERIC_F64 != 0, c);
+    if (v.rc) return fail(v.rc, v.msg);
     e->cfg = c;
     return UKFB_OK;
 }
@@ -1108,16 +1082,7 @@ int ukfb_set_process_noise(ukfb_engine* e, const double* R) {
     ON_DEVICE(e->device);
     const size_t dd = size_t(e->D) * e->D;
     e->Rn_host.assign(R, R + dd);
-    {   // blocks [0:3,0:3] and [3:6,3:6] are the ones predictionStepImpl rotates (PoseUKF.cpp:184-185, OrientationUKF.cpp:84-85)
-        bool iso = true;
-        for (int b = 0; b < 6; b += 3)
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 3; ++c) {
-                    const double v = R[size_t(b + r) * e->D + (b + c)];
-                    iso = iso && (r == c ? v == R[size_t(b) * e->D + b] : v == 0.0);
-                }
-        e->noise_iso = iso;
-    }
+    e->noise_iso = ukfb::rotated_blocks_isotropic(R, e->D);
     if (e->Rn_per_filter) {
         std::vector<double> all(size_t(e->cap) * dd);
         for (int64_t i = 0; i < e->cap; ++i) std::memcpy(all.data() + size_t(i) * dd, R, dd * sizeof(double));
@@ -1323,8 +1288,7 @@ int ukfb_predict_timestamps(ukfb_engine* e, const int64_t* ts_us) {
 int ukfb_update_dev(ukfb_engine* e, int meas_model_uniform, const int32_t* meas_model_dev, const void* z_dev,
                     const void* Q_dev) {
     if (!e || !z_dev || !Q_dev) return UKFB_ERR_INVALID_ARG;
-    if (!meas_model_dev && !meas_model_ok(e, meas_model_uniform))
-        return fail(UKFB_ERR_WRONG_MODEL, "measurement model id not valid for this engine");
+    if (const int rc = meas_model_dev ? UKFB_OK : check_meas_model(e, meas_model_uniform)) return rc;
     ukfb::LaunchReq r;
     r.do_update = true;
     r.meas_uniform = meas_model_uniform;
@@ -1336,29 +1300,15 @@ int ukfb_update_dev(ukfb_engine* e, int meas_model_uniform, const int32_t* meas_
 
 int ukfb_update(ukfb_engine* e, int meas_model, const double* z, const double* Q, const uint8_t* active) {
     if (!e) return UKFB_ERR_INVALID_ARG;
-    if (!meas_model_ok(e, meas_model)) return fail(UKFB_ERR_WRONG_MODEL, "measurement model id not valid for this engine");
+    if (const int rc = check_meas_model(e, meas_model)) return rc;
     ON_DEVICE(e->device);
-    if (!active) {   // the common form: samples uploaded on the copy stream while the previous kernel runs (see stage_cycle_inputs)
-        Staged sg;
-        const int src = stage_cycle_inputs(e, z, Q, size_t(e->cap) * 9, &sg);
-        if (src) return src;
-        ukfb::LaunchReq r;
-        r.do_update = true;
-        r.meas_uniform = meas_model;
-        r.z_dev = sg.z;
-        r.Q_dev = sg.Q;
-        r.wait_event = sg.ready;
-        r.done_event = sg.done;
-        r.no_split = true;
-        const int lrc = launch(e, r);
-        if (!lrc) e->stage_busy[sg.slot] = true;
-        return lrc;
-    }
-    int rc = stage_measurements(e, z, Q, nullptr, active);
-    if (rc) return rc;
     ukfb::LaunchReq r;
     r.do_update = true;
     r.meas_uniform = meas_model;
+    // the common form: samples uploaded on the copy stream while the previous kernel runs (see launch_staged)
+    if (!active) return launch_staged(e, r, z, Q, size_t(e->cap) * 9);
+    const int rc = stage_measurements(e, z, Q, nullptr, active);
+    if (rc) return rc;
     r.z_dev = e->z_stage;
     r.Q_dev = e->Q_stage;
     r.active_dev = active ? e->active_stage : nullptr;
@@ -1382,8 +1332,7 @@ int ukfb_update_mixed(ukfb_engine* e, const int32_t* meas_model, const double* z
 int ukfb_cycle_dev(ukfb_engine* e, double dt, int meas_model_uniform, const int32_t* meas_model_dev, const void* z_dev,
                    const void* Q_dev) {
     if (!e || !z_dev || !Q_dev) return UKFB_ERR_INVALID_ARG;
-    if (!meas_model_dev && !meas_model_ok(e, meas_model_uniform))
-        return fail(UKFB_ERR_WRONG_MODEL, "measurement model id not valid for this engine");
+    if (const int rc = meas_model_dev ? UKFB_OK : check_meas_model(e, meas_model_uniform)) return rc;
     ukfb::LaunchReq r;
     r.do_predict = true;
     r.do_update = true;
@@ -1392,8 +1341,7 @@ int ukfb_cycle_dev(ukfb_engine* e, double dt, int meas_model_uniform, const int3
     r.meas_dev = meas_model_dev;
     r.z_dev = z_dev;
     r.Q_dev = Q_dev;
-    if (meas_model_dev && e->cfg.bucket_models && e->cfg.lanes_per_filter == 16 && e->cap >= BUCKET_MIN_FILTERS &&
-        e->cap <= 0x7fffffff - 16) {
+    if (ukfb::buckets_apply(meas_model_dev != nullptr, e->cfg, e->cap)) {
         // Mixed stream: wavefronts of four neighbouring filters would each run the most expensive path any of the four
         // needs.  Group the filters by the class of their update first (device side, nothing read back), then ONE indirect
         // launch over the grouped list: every wavefront is class-uniform, the sigma-point branch of the update is taken by
@@ -1407,57 +1355,6 @@ int ukfb_cycle_dev(ukfb_engine* e, double dt, int meas_model_uniform, const int3
         r.inputs_by_filter = true;
         r.n_items = items;
     }
-    return launch(e, r);
-}
-
-// meas_dev != NULL: per-filter model ids, a ring [slots][capacity] like z and Q (meas_model is then ignored)
-static int cycle_multi_impl(ukfb_engine* e, int cycles, double dt, int meas_model, const int32_t* meas_dev, int slots,
-                            int first_slot, const void* in_a_dev, const void* in_b_dev, const void* z_dev, const void* Q_dev) {
-    if (!e || !z_dev || !Q_dev) return UKFB_ERR_INVALID_ARG;
-    if (cycles < 0 || slots < 1 || first_slot < 0 || first_slot >= slots)
-        return fail(UKFB_ERR_INVALID_ARG, "cycles >= 0, slots >= 1, 0 <= first_slot < slots");
-    if (!meas_dev && !meas_model_ok(e, meas_model))
-        return fail(UKFB_ERR_WRONG_MODEL, "measurement model id not valid for this engine");
-    if (cycles == 0) return UKFB_OK;
-    if (e->cfg.lanes_per_filter != 16) {
-        // the one-wavefront-per-filter layouts have no multi-cycle kernel: one launch per cycle, same results.  The
-        // status word must still be the OR over the cycles.
-        const size_t w = e->tsize;
-        const void* keep_a = e->in_a_bound;
-        const void* keep_b = e->in_b_bound;
-        int rc = UKFB_OK;
-        for (int c = 0; c < cycles && rc == UKFB_OK; ++c) {
-            const size_t s = size_t((first_slot + c) % slots) * size_t(e->cap);
-            if (in_a_dev) e->in_a_bound = static_cast<const char*>(in_a_dev) + s * 3 * w;
-            if (in_b_dev) e->in_b_bound = static_cast<const char*>(in_b_dev) + s * 3 * w;
-            ukfb::LaunchReq r;
-            r.do_predict = true;
-            r.do_update = true;
-            r.dt_uniform = dt;
-            r.meas_uniform = meas_model;
-            r.meas_dev = meas_dev ? meas_dev + s : nullptr;
-            r.z_dev = static_cast<const char*>(z_dev) + s * 3 * w;
-            r.Q_dev = static_cast<const char*>(Q_dev) + s * 9 * w;
-            r.status_accumulate = c > 0;
-            rc = launch(e, r);
-        }
-        e->in_a_bound = keep_a;
-        e->in_b_bound = keep_b;
-        return rc;
-    }
-    ukfb::LaunchReq r;
-    r.do_predict = true;
-    r.do_update = true;
-    r.dt_uniform = dt;
-    r.meas_uniform = meas_model;
-    r.meas_dev = meas_dev;
-    r.z_dev = z_dev;
-    r.Q_dev = Q_dev;
-    r.cycles = cycles;
-    r.slots = slots;
-    r.first_slot = first_slot;
-    r.in_a_slots = in_a_dev;
-    r.in_b_slots = in_b_dev;
     return launch(e, r);
 }
 
@@ -1475,57 +1372,19 @@ int ukfb_cycle_multi_mixed_dev(ukfb_engine* e, int cycles, double dt, int slots,
 int ukfb_cycle_schedule_dev(ukfb_engine* e, int cycles, const double* dt, const int32_t* meas_model, int slots, int first_slot,
                             const void* in_a_dev, const void* in_b_dev, const void* z_dev, const void* Q_dev) {
     if (!e || !dt || !meas_model || !z_dev || !Q_dev) return UKFB_ERR_INVALID_ARG;
-    if (cycles < 0 || slots < 1 || first_slot < 0 || first_slot >= slots)
-        return fail(UKFB_ERR_INVALID_ARG, "cycles >= 0, slots >= 1, 0 <= first_slot < slots");
+    const ukfb::Verdict v = ukfb::check_cycle_args(cycles, slots, first_slot);
+    if (v.rc) return fail(v.rc, v.msg);
     for (int c = 0; c < cycles; ++c)
-        if (meas_model[c] >= 0 && !meas_model_ok(e, meas_model[c]))
-            return fail(UKFB_ERR_WRONG_MODEL, "measurement model id not valid for this engine");
-    const bool tuned = e->cfg.lanes_per_filter == 16;
-    const size_t w = e->tsize;
-    const void* keep_a = e->in_a_bound;
-    const void* keep_b = e->in_b_bound;
-    int rc = UKFB_OK;
-    // the tuned layout: launches of up to UKFB_MAX_MULTI_CYCLES cycles, the schedule travels in the kernel arguments;
-    // the one-wavefront-per-filter layouts: one launch per cycle
-    const int chunk = tuned ? UKFB_MAX_MULTI_CYCLES : 1;
-    for (int c0 = 0; c0 < cycles && rc == UKFB_OK; c0 += chunk) {
-        const int nc = (cycles - c0 < chunk) ? (cycles - c0) : chunk;
-        ukfb::LaunchReq r;
-        r.do_predict = true;
-        r.status_accumulate = c0 > 0;         // the status word is the OR over ALL cycles of the call
-        if (tuned) {
-            r.do_update = true;
-            r.z_dev = z_dev;
-            r.Q_dev = Q_dev;
-            r.cycles = nc;
-            r.slots = slots;
-            r.first_slot = (first_slot + c0) % slots;
-            r.in_a_slots = in_a_dev;
-            r.in_b_slots = in_b_dev;
-            r.sched_dt = dt + c0;
-            r.sched_model = meas_model + c0;
-        } else {
-            const size_t s = size_t((first_slot + c0) % slots) * size_t(e->cap);
-            if (in_a_dev) e->in_a_bound = static_cast<const char*>(in_a_dev) + s * 3 * w;
-            if (in_b_dev) e->in_b_bound = static_cast<const char*>(in_b_dev) + s * 3 * w;
-            r.do_update = meas_model[c0] >= 0;
-            r.dt_uniform = dt[c0];
-            r.meas_uniform = meas_model[c0];
-            r.z_dev = static_cast<const char*>(z_dev) + s * 3 * w;
-            r.Q_dev = static_cast<const char*>(Q_dev) + s * 9 * w;
-        }
-        rc = launch(e, r);
-    }
-    e->in_a_bound = keep_a;
-    e->in_b_bound = keep_b;
-    return rc;
+        if (const int rc = meas_model[c] >= 0 ? check_meas_model(e, meas_model[c]) : UKFB_OK) return rc;
+    const ukfb::CyclePlan plan(cycles, slots, first_slot, e->cfg.lanes_per_filter == 16, true);
+    return run_cycle_plan(e, plan, 0.0, -1, dt, meas_model, nullptr, in_a_dev, in_b_dev, z_dev, Q_dev);
 }
 
 int ukfb_cycle_multi(ukfb_engine* e, int cycles, double dt, int meas_model, const double* in_a, const double* in_b,
                      const double* z, const double* Q) {
     if (!e || !z || !Q) return UKFB_ERR_INVALID_ARG;
     if (cycles < 0) return fail(UKFB_ERR_INVALID_ARG, "cycles >= 0");
-    if (!meas_model_ok(e, meas_model)) return fail(UKFB_ERR_WRONG_MODEL, "measurement model id not valid for this engine");
+    if (const int rc = check_meas_model(e, meas_model)) return rc;
     if (cycles == 0) return UKFB_OK;
     ON_DEVICE(e->device);
     // device rings of this call's samples, one slot per cycle: [z | Q | in_a | in_b]
@@ -1556,7 +1415,7 @@ int ukfb_cycle_multi(ukfb_engine* e, int cycles, double dt, int meas_model, cons
 // ---- batch-uniform measurement covariance -------------------------------------------------------
 int ukfb_cycle_uniform_q_dev(ukfb_engine* e, double dt, int meas_model, const void* z_dev, const void* Q9_dev) {
     if (!e || !z_dev || !Q9_dev) return UKFB_ERR_INVALID_ARG;
-    if (!meas_model_ok(e, meas_model)) return fail(UKFB_ERR_WRONG_MODEL, "measurement model id not valid for this engine");
+    if (const int rc = check_meas_model(e, meas_model)) return rc;
     ukfb::LaunchReq r;
     r.do_predict = true;
     r.do_update = true;
@@ -1570,30 +1429,20 @@ int ukfb_cycle_uniform_q_dev(ukfb_engine* e, double dt, int meas_model, const vo
 
 int ukfb_cycle_uniform_q(ukfb_engine* e, double dt, int meas_model, const double* z, const double* Q9) {
     if (!e || !z || !Q9) return UKFB_ERR_INVALID_ARG;
-    if (!meas_model_ok(e, meas_model)) return fail(UKFB_ERR_WRONG_MODEL, "measurement model id not valid for this engine");
+    if (const int rc = check_meas_model(e, meas_model)) return rc;
     ON_DEVICE(e->device);
-    Staged sg;
-    const int rc = stage_cycle_inputs(e, z, Q9, 9, &sg);
-    if (rc) return rc;
     ukfb::LaunchReq r;
     r.do_predict = true;
     r.do_update = true;
     r.dt_uniform = dt;
     r.meas_uniform = meas_model;
-    r.z_dev = sg.z;
-    r.Q_dev = sg.Q;
     r.q_uniform = true;
-    r.wait_event = sg.ready;
-    r.done_event = sg.done;
-    r.no_split = true;
-    const int lrc = launch(e, r);
-    if (!lrc) e->stage_busy[sg.slot] = true;
-    return lrc;
+    return launch_staged(e, r, z, Q9, 9);
 }
 
 int ukfb_update_uniform_q(ukfb_engine* e, int meas_model, const double* z, const double* Q9, const uint8_t* active) {
     if (!e || !z || !Q9) return UKFB_ERR_INVALID_ARG;
-    if (!meas_model_ok(e, meas_model)) return fail(UKFB_ERR_WRONG_MODEL, "measurement model id not valid for this engine");
+    if (const int rc = check_meas_model(e, meas_model)) return rc;
     ON_DEVICE(e->device);
     int rc = upload(e, e->z_stage, 0, z, size_t(e->cap) * 3);
     if (!rc) rc = upload(e, e->Q_stage, 0, Q9, 9);
@@ -1611,24 +1460,14 @@ int ukfb_update_uniform_q(ukfb_engine* e, int meas_model, const double* z, const
 
 int ukfb_cycle(ukfb_engine* e, double dt, int meas_model, const double* z, const double* Q) {
     if (!e) return UKFB_ERR_INVALID_ARG;
-    if (!meas_model_ok(e, meas_model)) return fail(UKFB_ERR_WRONG_MODEL, "measurement model id not valid for this engine");
+    if (const int rc = check_meas_model(e, meas_model)) return rc;
     ON_DEVICE(e->device);
-    Staged sg;
-    const int rc = stage_cycle_inputs(e, z, Q, size_t(e->cap) * 9, &sg);
-    if (rc) return rc;
     ukfb::LaunchReq r;
     r.do_predict = true;
     r.do_update = true;
     r.dt_uniform = dt;
     r.meas_uniform = meas_model;
-    r.z_dev = sg.z;
-    r.Q_dev = sg.Q;
-    r.wait_event = sg.ready;
-    r.done_event = sg.done;
-    r.no_split = true;
-    const int lrc = launch(e, r);
-    if (!lrc) e->stage_busy[sg.slot] = true;
-    return lrc;
+    return launch_staged(e, r, z, Q, size_t(e->cap) * 9);
 }
 
 int ukfb_cycle_timestamps_dev(ukfb_engine* e, const int64_t* ts_us_dev, const int32_t* meas_model_dev, const void* z_dev,
@@ -1662,17 +1501,6 @@ int ukfb_cycle_timestamps(ukfb_engine* e, const int64_t* ts_us, const int32_t* m
 // sort by filter index (hipCUB) = per-filter time order with arrival order for equal stamps; the rank of a sample
 // inside its filter's run is its round.
 namespace {
-struct Carver {   // bump allocator over the workspace (256-byte aligned pieces)
-    char* base;
-    size_t used = 0;
-    explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-    template <class P> P* take(size_t count) {
-        P* p = base ? reinterpret_cast<P*>(base + used) : nullptr;
-        used += (count * sizeof(P) + 255) / 256 * 256;
-        return p;
-    }
-};
-
 template <class S>
 int process_events_device(ukfb_engine* e, int64_t n, const int64_t* d_f, const int64_t* d_t, const int32_t* d_m, const S* d_z,
                           const S* d_q, size_t ws_offset, uint32_t* status_or, int64_t* rounds) {
@@ -1688,7 +1516,7 @@ int process_events_device(ukfb_engine* e, int64_t n, const int64_t* d_f, const i
     HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, tmp_scan, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr),
                                               hipcub::Max(), int(n), ukfb::main_stream(e)));
     const size_t tmp_bytes = std::max(tmp_sort_t, std::max(tmp_sort_f, tmp_scan));
-    Carver c(static_cast<char*>(e->ev_dev) + ws_offset);
+    ukfb::Carver c(static_cast<char*>(e->ev_dev) + ws_offset);
     const size_t ne = size_t(n);
     uint32_t* idx_a = c.take<uint32_t>(ne);
     uint32_t* idx_b = c.take<uint32_t>(ne);
@@ -1772,15 +1600,6 @@ int process_events_device(ukfb_engine* e, int64_t n, const int64_t* d_f, const i
     return UKFB_OK;
 }
 
-// bytes of workspace process_events_device needs for n events (an upper bound that does not depend on hipCUB's
-// temporary-storage query: 4x the key/value arrays covers rocPRIM's double buffers)
-size_t events_workspace_bytes(int64_t n) {
-    const size_t ne = size_t(n);
-    // 4 index + 2 time-key + 2 filter-key + head/start/rank/rank_sorted/off + compact events (int32, int64, int32,
-    // 12 scalars of <= 8 bytes) + alignment slack + radix-sort temporaries
-    return (4 * 4 + 2 * 8 + 2 * 4 + 5 * 4 + 4 + 8 + 4 + 12 * 8) * ne + 32 * 256 + (size_t(64) << 20) / 4 + 24 * ne;
-}
-
 int ensure_events_arena(ukfb_engine* e, size_t bytes) {
     if (bytes <= e->ev_bytes) return UKFB_OK;
     if (e->ev_dev) HIP_TRY(hipFree(e->ev_dev));
@@ -1805,11 +1624,11 @@ int ukfb_process_events(ukfb_engine* e, int64_t n_events, const int64_t* filter,
     // raw events go to the device as they are (one copy per array); ordering, conversion to the engine's
     // precision and the per-round scatter all happen there
     const size_t ne = size_t(n_events);
-    Carver raw(nullptr);
+    ukfb::Carver raw(nullptr);
     raw.take<int64_t>(ne); raw.take<int64_t>(ne); raw.take<int32_t>(ne); raw.take<double>(3 * ne); raw.take<double>(9 * ne);
-    int rc = ensure_events_arena(e, raw.used + events_workspace_bytes(n_events));
+    int rc = ensure_events_arena(e, raw.used + ukfb::events_workspace_bytes(n_events));
     if (rc) return rc;
-    Carver c(e->ev_dev);
+    ukfb::Carver c(e->ev_dev);
     int64_t* d_f = c.take<int64_t>(ne);
     int64_t* d_t = c.take<int64_t>(ne);
     int32_t* d_m = c.take<int32_t>(ne);
@@ -1835,7 +1654,7 @@ int ukfb_process_events_dev(ukfb_engine* e, int64_t n_events, const int64_t* fil
     if (status_or) *status_or = 0;
     if (rounds) *rounds = 0;
     if (n_events == 0) return UKFB_OK;
-    int rc = ensure_events_arena(e, events_workspace_bytes(n_events));
+    int rc = ensure_events_arena(e, ukfb::events_workspace_bytes(n_events));
     if (rc) return rc;
     if (e->prec == UKFB_F64)
         return process_events_device<double>(e, n_events, filter_dev, ts_us_dev, meas_model_dev, static_cast<const double*>(z_dev),
@@ -1882,15 +1701,9 @@ int ukfb_timer_end(ukfb_engine* e, float* elapsed_ms) {
     ON_DEVICE(e->device);
     if (e->poisoned) return fail(UKFB_ERR_HIP, "engine poisoned by an earlier wait that timed out (UKFB_WAIT_TIMEOUT_S)");
     HIP_TRY(hipEventRecord(e->ev1, ukfb::main_stream(e)));
-    {
-        const hipError_t w = wait_event_polling(e->ev1);
-        if (w == hipErrorNotReady && g_wait_timed_out) {
-            e->poisoned = true;
-            g_wait_timed_out = false;
-            return UKFB_ERR_HIP;
-        }
-        HIP_TRY(w);
-    }
+    const hipError_t w = wait_event_polling(e->ev1);
+    if (gave_up(e, w)) return UKFB_ERR_HIP;
+    HIP_TRY(w);
     HIP_TRY(hipEventElapsedTime(elapsed_ms, e->ev0, e->ev1));
     return UKFB_OK;
 }

@@ -9,10 +9,7 @@
 #include <vector>
 
 #include "../../include/ukf_batch.h"
-
-#ifndef UKFB_MAX_MULTI_CYCLES
-#define UKFB_MAX_MULTI_CYCLES 32   // cycles of one multi-cycle launch with a schedule (the host splits longer ones)
-#endif
+#include "ukf_host.hpp"
 
 #ifndef UKFB_GENERIC_F64
 #define UKFB_GENERIC_F64 0   // 1: also build the fp64 one-wavefront-per-filter kernels (AGPR-backed, diagnostics only)

@@ -82,19 +82,17 @@ int gfail(int code, const std::string& msg) {
     return code;
 }
 
-// rc of an engine call: the engine has left its text in ukfb_last_error() already
-int efail(int rc) { return rc; }
+// call(shard) -> rc on every shard in turn; the first failure ends it (the engine has left its text in ukfb_last_error())
+template <class F> int each_shard(ukfb_group* g, F&& call) {
+    for (size_t r = 0; r < g->engines.size(); ++r)
+        if (const int rc = call(r)) return rc;
+    return UKFB_OK;
+}
 
 bool shard_ok(const ukfb_group* g, int r) { return g && r >= 0 && r < int(g->engines.size()); }
 
-// [first, first + count) of the batch cut by shard r: (offset inside the caller's arrays, offset inside the shard, length)
-struct Cut {
-    int64_t src, dst, len;
-};
-Cut cut(const ukfb_group* g, int r, int64_t first, int64_t count) {
-    const int64_t lo = std::max(first, g->first[r]), hi = std::min(first + count, g->first[r] + g->count[r]);
-    return {lo - first, lo - g->first[r], std::max<int64_t>(0, hi - lo)};
-}
+using ukfb::Cut;
+Cut cut(const ukfb_group* g, int r, int64_t first, int64_t count) { return ukfb::cut(g->first[r], g->count[r], first, count); }
 
 void release_gather(ukfb_group* g) {
     for (size_t r = 0; r < g->comms.size(); ++r)
@@ -119,13 +117,7 @@ void release_gather(ukfb_group* g) {
 constexpr int64_t THREAD_MIN_FILTERS = 32768;
 template <class F> int fan_out(ukfb_group* g, int64_t filters_touched, F&& call) {   // call(shard) -> rc, text in ukfb_last_error()
     const size_t n = g->engines.size();
-    if (n == 1 || filters_touched < THREAD_MIN_FILTERS) {
-        for (size_t r = 0; r < n; ++r) {
-            const int rc = call(r);
-            if (rc) return rc;
-        }
-        return UKFB_OK;
-    }
+    if (n == 1 || filters_touched < THREAD_MIN_FILTERS) return each_shard(g, call);
     std::vector<int> rcs(n, UKFB_OK);
     std::vector<std::string> errs(n);
     const auto run = [&](size_t r) {
@@ -156,11 +148,7 @@ void release_routing(ukfb_group* g) {
 extern "C" {
 
 int ukfb_group_shard_range(int64_t total, int n_shards, int shard, int64_t* first, int64_t* count) {
-    if (total < 0 || n_shards <= 0 || shard < 0 || shard >= n_shards) return UKFB_ERR_INVALID_ARG;
-    const int64_t base = total / n_shards, extra = total % n_shards;
-    if (count) *count = base + (shard < extra ? 1 : 0);
-    if (first) *first = shard * base + std::min<int64_t>(shard, extra);
-    return UKFB_OK;
+    return ukfb::shard_range(total, n_shards, shard, first, count);
 }
 
 int ukfb_group_create(ukfb_group** out, int model, int precision, int64_t total_filters, const int* devices, int n_devices) {
@@ -223,11 +211,7 @@ int ukfb_group_shard(ukfb_group* g, int shard, ukfb_engine** engine, int* device
 
 int ukfb_group_set_config(ukfb_group* g, const ukfb_config* cfg) {
     if (!g || !cfg) return UKFB_ERR_INVALID_ARG;
-    for (ukfb_engine* e : g->engines) {
-        const int rc = ukfb_set_config(e, cfg);
-        if (rc) return efail(rc);
-    }
-    return UKFB_OK;
+    return each_shard(g, [&](size_t r) { return ukfb_set_config(g->engines[r], cfg); });
 }
 
 int ukfb_group_initialize(ukfb_group* g, int64_t first, int64_t count, const double* mu, const double* cov) {
@@ -255,111 +239,84 @@ int ukfb_group_get_state(ukfb_group* g, int64_t first, int64_t count, double* mu
 int ukfb_group_get_status(ukfb_group* g, int64_t first, int64_t count, uint32_t* status) {
     if (!g || !status || first < 0 || count < 0 || first + count > g->total)
         return gfail(UKFB_ERR_OUT_OF_RANGE, "ukfb_group_get_status: bad range");
-    for (size_t r = 0; r < g->engines.size(); ++r) {
+    return each_shard(g, [&](size_t r) {
         const Cut c = cut(g, int(r), first, count);
-        if (!c.len) continue;
-        const int rc = ukfb_get_status(g->engines[r], c.dst, c.len, status + c.src);
-        if (rc) return efail(rc);
-    }
-    return UKFB_OK;
+        return c.len ? ukfb_get_status(g->engines[r], c.dst, c.len, status + c.src) : int(UKFB_OK);
+    });
 }
 
 int ukfb_group_get_status_summary(ukfb_group* g, uint32_t* or_of_all) {
     if (!g || !or_of_all) return UKFB_ERR_INVALID_ARG;
     uint32_t all = 0;
-    for (ukfb_engine* e : g->engines) {
+    const int rc = each_shard(g, [&](size_t r) {
         uint32_t v = 0;
-        const int rc = ukfb_get_status_summary(e, &v);
-        if (rc) return efail(rc);
+        const int src = ukfb_get_status_summary(g->engines[r], &v);
         all |= v;
-    }
-    *or_of_all = all;
-    return UKFB_OK;
+        return src;
+    });
+    if (!rc) *or_of_all = all;
+    return rc;
 }
 
 int ukfb_group_set_process_noise(ukfb_group* g, const double* R) {
     if (!g || !R) return UKFB_ERR_INVALID_ARG;
-    for (ukfb_engine* e : g->engines) {
-        const int rc = ukfb_set_process_noise(e, R);
-        if (rc) return efail(rc);
-    }
-    return UKFB_OK;
+    return each_shard(g, [&](size_t r) { return ukfb_set_process_noise(g->engines[r], R); });
 }
 
 int ukfb_group_pose_set_acceleration(ukfb_group* g, int64_t first, int64_t count, const double* acc_mu, const double* acc_cov) {
     if (!g || first < 0 || count < 0 || first + count > g->total)
         return gfail(UKFB_ERR_OUT_OF_RANGE, "ukfb_group_pose_set_acceleration: bad range");
-    for (size_t r = 0; r < g->engines.size(); ++r) {
+    return each_shard(g, [&](size_t r) {
         const Cut c = cut(g, int(r), first, count);
         // (the batch-uniform covariance goes to every shard, also to one the range does not touch)
-        const int rc = ukfb_pose_set_acceleration(g->engines[r], c.len ? c.dst : 0, c.len, (acc_mu && c.len) ? acc_mu + size_t(c.src) * 3 : nullptr,
-                                                  acc_cov);
-        if (rc) return efail(rc);
-    }
-    return UKFB_OK;
+        return ukfb_pose_set_acceleration(g->engines[r], c.len ? c.dst : 0, c.len, (acc_mu && c.len) ? acc_mu + size_t(c.src) * 3 : nullptr,
+                                          acc_cov);
+    });
 }
 
 int ukfb_group_orient_set_params(ukfb_group* g, double gyro_bias_tau, double acc_bias_tau, const double earth_rotation[3]) {
     if (!g) return UKFB_ERR_INVALID_ARG;
-    for (ukfb_engine* e : g->engines) {
-        const int rc = ukfb_orient_set_params(e, gyro_bias_tau, acc_bias_tau, earth_rotation);
-        if (rc) return efail(rc);
-    }
-    return UKFB_OK;
+    return each_shard(g, [&](size_t r) { return ukfb_orient_set_params(g->engines[r], gyro_bias_tau, acc_bias_tau, earth_rotation); });
 }
 
 int ukfb_group_orient_set_inputs(ukfb_group* g, int64_t first, int64_t count, const double* gyro, const double* acc) {
     if (!g || first < 0 || count < 0 || first + count > g->total)
         return gfail(UKFB_ERR_OUT_OF_RANGE, "ukfb_group_orient_set_inputs: bad range");
-    for (size_t r = 0; r < g->engines.size(); ++r) {
+    return each_shard(g, [&](size_t r) {
         const Cut c = cut(g, int(r), first, count);
-        if (!c.len) continue;
-        const int rc = ukfb_orient_set_inputs(g->engines[r], c.dst, c.len, gyro ? gyro + size_t(c.src) * 3 : nullptr,
-                                              acc ? acc + size_t(c.src) * 3 : nullptr);
-        if (rc) return efail(rc);
-    }
-    return UKFB_OK;
+        return c.len ? ukfb_orient_set_inputs(g->engines[r], c.dst, c.len, gyro ? gyro + size_t(c.src) * 3 : nullptr,
+                                              acc ? acc + size_t(c.src) * 3 : nullptr)
+                     : int(UKFB_OK);
+    });
 }
 
 // ---- the hot path, fanned out: every call below only ENQUEUES on the shards' streams (one after the other from this
 // thread, the devices then run concurrently) and returns; ukfb_group_sync waits for all of them
 int ukfb_group_cycle_dev(ukfb_group* g, double dt, int meas_model, const void* const* z_dev, const void* const* Q_dev) {
     if (!g || !z_dev || !Q_dev) return UKFB_ERR_INVALID_ARG;
-    for (size_t r = 0; r < g->engines.size(); ++r) {
-        const int rc = ukfb_cycle_dev(g->engines[r], dt, meas_model, nullptr, z_dev[r], Q_dev[r]);
-        if (rc) return efail(rc);
-    }
-    return UKFB_OK;
+    return each_shard(g, [&](size_t r) { return ukfb_cycle_dev(g->engines[r], dt, meas_model, nullptr, z_dev[r], Q_dev[r]); });
 }
 
 int ukfb_group_cycle_multi_dev(ukfb_group* g, int cycles, double dt, int meas_model, int slots, int first_slot,
                                const void* const* in_a_dev, const void* const* in_b_dev, const void* const* z_dev,
                                const void* const* Q_dev) {
     if (!g || !z_dev || !Q_dev) return UKFB_ERR_INVALID_ARG;
-    for (size_t r = 0; r < g->engines.size(); ++r) {
-        const int rc = ukfb_cycle_multi_dev(g->engines[r], cycles, dt, meas_model, slots, first_slot, in_a_dev ? in_a_dev[r] : nullptr,
-                                            in_b_dev ? in_b_dev[r] : nullptr, z_dev[r], Q_dev[r]);
-        if (rc) return efail(rc);
-    }
-    return UKFB_OK;
+    return each_shard(g, [&](size_t r) {
+        return ukfb_cycle_multi_dev(g->engines[r], cycles, dt, meas_model, slots, first_slot, in_a_dev ? in_a_dev[r] : nullptr,
+                                    in_b_dev ? in_b_dev[r] : nullptr, z_dev[r], Q_dev[r]);
+    });
 }
 
 int ukfb_group_pose_bind_acceleration_dev(ukfb_group* g, const void* const* acc_mu_dev) {
     if (!g) return UKFB_ERR_INVALID_ARG;
-    for (size_t r = 0; r < g->engines.size(); ++r) {
-        const int rc = ukfb_pose_bind_acceleration_dev(g->engines[r], acc_mu_dev ? acc_mu_dev[r] : nullptr);
-        if (rc) return efail(rc);
-    }
-    return UKFB_OK;
+    return each_shard(g, [&](size_t r) { return ukfb_pose_bind_acceleration_dev(g->engines[r], acc_mu_dev ? acc_mu_dev[r] : nullptr); });
 }
 
 int ukfb_group_orient_bind_inputs_dev(ukfb_group* g, const void* const* gyro_dev, const void* const* acc_dev) {
     if (!g) return UKFB_ERR_INVALID_ARG;
-    for (size_t r = 0; r < g->engines.size(); ++r) {
-        const int rc = ukfb_orient_bind_inputs_dev(g->engines[r], gyro_dev ? gyro_dev[r] : nullptr, acc_dev ? acc_dev[r] : nullptr);
-        if (rc) return efail(rc);
-    }
-    return UKFB_OK;
+    return each_shard(g, [&](size_t r) {
+        return ukfb_orient_bind_inputs_dev(g->engines[r], gyro_dev ? gyro_dev[r] : nullptr, acc_dev ? acc_dev[r] : nullptr);
+    });
 }
 
 // host arrays over the whole batch (z [total][3], Q [total][3][3]): every shard uploads and launches its range
@@ -372,11 +329,7 @@ int ukfb_group_cycle(ukfb_group* g, double dt, int meas_model, const double* z, 
 
 int ukfb_group_predict(ukfb_group* g, double dt) {
     if (!g) return UKFB_ERR_INVALID_ARG;
-    for (ukfb_engine* e : g->engines) {
-        const int rc = ukfb_predict(e, dt);
-        if (rc) return efail(rc);
-    }
-    return UKFB_OK;
+    return each_shard(g, [&](size_t r) { return ukfb_predict(g->engines[r], dt); });
 }
 
 int ukfb_group_update(ukfb_group* g, int meas_model, const double* z, const double* Q) {
@@ -390,11 +343,7 @@ int ukfb_group_update(ukfb_group* g, int meas_model, const double* z, const doub
 int ukfb_group_cycle_mixed_dev(ukfb_group* g, double dt, const int32_t* const* meas_model_dev, const void* const* z_dev,
                                const void* const* Q_dev) {
     if (!g || !meas_model_dev || !z_dev || !Q_dev) return UKFB_ERR_INVALID_ARG;
-    for (size_t r = 0; r < g->engines.size(); ++r) {
-        const int rc = ukfb_cycle_dev(g->engines[r], dt, 0, meas_model_dev[r], z_dev[r], Q_dev[r]);
-        if (rc) return efail(rc);
-    }
-    return UKFB_OK;
+    return each_shard(g, [&](size_t r) { return ukfb_cycle_dev(g->engines[r], dt, 0, meas_model_dev[r], z_dev[r], Q_dev[r]); });
 }
 
 // fused predictionStepFromSampleTime + integrateMeasurement per filter, host arrays over the whole batch
@@ -430,18 +379,8 @@ int ukfb_group_process_events(ukfb_group* g, int64_t n_events, const int64_t* fi
     // its own events, in arrival order, into its pinned routing buffer and hands them to its engine
     std::vector<uint8_t> owner(static_cast<size_t>(n_events));
     std::vector<size_t> counts(n, 0);
-    {
-        const double per_filter = double(n) / double(g->total);   // (a multiply, not a 64-bit division per event)
-        for (int64_t i = 0; i < n_events; ++i) {
-            const int64_t f = filter[i];
-            if (f < 0 || f >= g->total) return gfail(UKFB_ERR_OUT_OF_RANGE, "ukfb_group_process_events: filter index outside the batch");
-            size_t r = std::min(n - 1, size_t(double(f) * per_filter));   // shards differ by one filter at most: the guess is off by one at most
-            while (f < g->first[r]) --r;
-            while (f >= g->first[r] + g->count[r]) ++r;
-            owner[size_t(i)] = uint8_t(r);
-            ++counts[r];
-        }
-    }
+    if (ukfb::route_events(filter, n_events, g->total, g->first.data(), g->count.data(), n, owner.data(), counts.data()))
+        return gfail(UKFB_ERR_OUT_OF_RANGE, "ukfb_group_process_events: filter index outside the batch");
     if (g->route_buf.empty()) {
         g->route_buf.assign(n, nullptr);
         g->route_cap.assign(n, 0);
@@ -535,7 +474,7 @@ int ukfb_group_sync(ukfb_group* g) {
     int rc = UKFB_OK;
     for (ukfb_engine* e : g->engines) {
         const int r = ukfb_sync(e);
-        if (r && !rc) rc = efail(r);
+        if (r && !rc) rc = r;
     }
     return rc;
 }
@@ -543,25 +482,22 @@ int ukfb_group_sync(ukfb_group* g) {
 // HIP-event timing over all shards: begin / end bracket a region on every shard's stream, elapsed = the slowest shard
 int ukfb_group_timer_begin(ukfb_group* g) {
     if (!g) return UKFB_ERR_INVALID_ARG;
-    for (ukfb_engine* e : g->engines) {
-        const int rc = ukfb_timer_begin(e);
-        if (rc) return efail(rc);
-    }
-    return UKFB_OK;
+    return each_shard(g, [&](size_t r) { return ukfb_timer_begin(g->engines[r]); });
 }
 
 int ukfb_group_timer_end(ukfb_group* g, float* elapsed_ms_max, float* elapsed_ms_per_shard) {
     if (!g || !elapsed_ms_max) return UKFB_ERR_INVALID_ARG;
     float mx = 0.f;
-    for (size_t r = 0; r < g->engines.size(); ++r) {
+    const int rc = each_shard(g, [&](size_t r) {
         float ms = 0.f;
-        const int rc = ukfb_timer_end(g->engines[r], &ms);
-        if (rc) return efail(rc);
+        const int src = ukfb_timer_end(g->engines[r], &ms);
+        if (src) return src;
         if (elapsed_ms_per_shard) elapsed_ms_per_shard[r] = ms;
         mx = std::max(mx, ms);
-    }
-    *elapsed_ms_max = mx;
-    return UKFB_OK;
+        return int(UKFB_OK);
+    });
+    if (!rc) *elapsed_ms_max = mx;
+    return rc;
 }
 
 // ---- result gather.  out_dev[r] (device r, engine precision, [total][S]) receives the means of ALL filters in batch order.

@@ -1,0 +1,273 @@
+// ukf_host.hpp -- the engine's host decisions as pure functions of plain values: configuration checks, process-noise
+// classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, workspace sizing and the
+// kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "../../include/ukf_batch.h"
+
+#if defined(__HIP__)
+#define UKFB_HD __host__ __device__ __forceinline__
+#else
+#define UKFB_HD inline
+#endif
+
+#ifndef UKFB_MAX_MULTI_CYCLES
+#define UKFB_MAX_MULTI_CYCLES 32   // cycles of one multi-cycle launch with a schedule (the host splits longer ones)
+#endif
+
+namespace ukfb {
+
+struct Verdict {   // a return code and, unless UKFB_OK, the text ukfb_last_error() reports
+    int rc = UKFB_OK;
+    const char* msg = nullptr;
+};
+
+// ---- configuration ------------------------------------------------------------------------------------------------------
+// generic_f64: the fp64 one-wavefront-per-filter layouts are built (make GENERIC_F64=1)
+inline bool layout_supported(int precision, int lanes_per_filter, bool generic_f64) {
+    if (precision != UKFB_F64 && precision != UKFB_F32) return false;
+    if (lanes_per_filter == 0 || lanes_per_filter == 16) return true;
+    if (lanes_per_filter != 32 && lanes_per_filter != 64) return false;
+    return precision == UKFB_F32 || generic_f64;
+}
+
+// ukfb_set_config's checks, in their order; c is normalised in place (lanes_per_filter 0 = 16)
+inline Verdict check_config(int precision, bool generic_f64, ukfb_config& c) {
+    if (c.lanes_per_filter == 0) c.lanes_per_filter = 16;
+    if (c.lanes_per_filter != 16 && c.lanes_per_filter != 32 && c.lanes_per_filter != 64)
+        return {UKFB_ERR_INVALID_ARG, "lanes_per_filter must be 16, 32 or 64"};
+    if (!layout_supported(precision, c.lanes_per_filter, generic_f64))
+        return {UKFB_ERR_INVALID_ARG, "lanes_per_filter 32 / 64 in fp64 is a diagnostic build option (make GENERIC_F64=1)"};
+    if (c.mean_max_iter < 1) return {UKFB_ERR_INVALID_ARG, "mean_max_iter must be >= 1"};
+    if (c.wide_arithmetic != 0 && c.wide_arithmetic != 1) return {UKFB_ERR_INVALID_ARG, "wide_arithmetic must be 0 or 1"};
+    if (c.full_update_check != 0 && c.full_update_check != 1) return {UKFB_ERR_INVALID_ARG, "full_update_check must be 0 or 1"};
+    if (c.wide_arithmetic && precision == UKFB_F32 && c.lanes_per_filter != 16)
+        return {UKFB_ERR_INVALID_ARG, "wide_arithmetic runs on the tuned layout only (lanes_per_filter 16)"};
+    return {};
+}
+
+// ---- process noise (D x D, row-major) -----------------------------------------------------------------------------------
+// Positive semidefinite? -- of the symmetric matrix the kernels use (they read the lower triangle).  Cholesky with a tolerance: a pivot
+// below -tol fails; a pivot within tol must head a column of zeros (a zero direction, e.g. the all-zero default noise).
+inline bool is_psd(const double* A, int D) {
+    std::vector<double> L(size_t(D) * D, 0.0);
+    double dmax = 0.0;
+    for (int i = 0; i < D; ++i) dmax = std::max(dmax, std::fabs(A[size_t(i) * D + i]));
+    const double tol = 1e-12 * dmax;
+    for (int k = 0; k < D; ++k) {
+        double x = A[size_t(k) * D + k];
+        if (!std::isfinite(x)) return false;
+        for (int j = 0; j < k; ++j) x -= L[size_t(k) * D + j] * L[size_t(k) * D + j];
+        if (x < -tol) return false;
+        const bool zero = x <= tol;
+        const double d = zero ? 0.0 : std::sqrt(x);
+        L[size_t(k) * D + k] = d;
+        for (int i = k + 1; i < D; ++i) {
+            double v = A[size_t(i) * D + k];
+            if (!std::isfinite(v)) return false;
+            for (int j = 0; j < k; ++j) v -= L[size_t(i) * D + j] * L[size_t(k) * D + j];
+            if (zero) {
+                if (std::fabs(v) > std::sqrt(tol * std::max(dmax, 1e-300)) + 1e-300) return false;
+                L[size_t(i) * D + k] = 0.0;
+            } else {
+                L[size_t(i) * D + k] = v / d;
+            }
+        }
+    }
+    return true;
+}
+
+// rows / columns 0..5 are zero outside their own 3x3 diagonal block (the blocks the prediction rotates)
+inline bool rotated_blocks_uncoupled(const double* A, int D) {
+    for (int r = 0; r < D; ++r)
+        for (int c = 0; c < 6; ++c)
+            if (r / 3 != c / 3 && (A[size_t(r) * D + c] != 0.0 || A[size_t(c) * D + r] != 0.0)) return false;
+    return true;
+}
+
+// blocks [0:3,0:3] and [3:6,3:6], the ones predictionStepImpl rotates (PoseUKF.cpp:184-185, OrientationUKF.cpp:84-85), are s * I
+inline bool rotated_blocks_isotropic(const double* A, int D) {
+    bool iso = true;
+    for (int b = 0; b < 6; b += 3)
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) {
+                const double v = A[size_t(b + r) * D + (b + c)];
+                iso = iso && (r == c ? v == A[size_t(b) * D + b] : v == 0.0);
+            }
+    return iso;
+}
+
+// ukfb_config::full_update_check: the host-side condition of the short update factorisation -- the batch-uniform process noise as the
+// prediction adds it is positive semidefinite.  The prediction rotates the diagonal blocks [0:3] and [3:6] and leaves every other
+// entry raw (PoseUKF.cpp:184-185, OrientationUKF.cpp:84-85); that is the congruence blockdiag(rot, rot, I) R blockdiag(rot, rot, I)^T,
+// which keeps R semidefinite for any rot (non-unit quaternions included), only when rows / columns 0..5 are zero outside their own
+// 3x3 diagonal block.  A semidefinite R with such cross terms can turn indefinite, so it keeps the complete factorisation.  Scaling
+// by dt / dt^2 keeps semidefiniteness; Pose acceleration branch: the unrotated R with the velocity block replaced by 2 acc.cov
+// (PoseUKF.cpp:190-191) must be semidefinite as well.
+inline bool short_update_ok(int model, int D, const double* R, const double* acc_cov) {
+    if (!rotated_blocks_uncoupled(R, D) || !is_psd(R, D)) return false;
+    if (model != UKFB_MODEL_POSE) return true;
+    std::vector<double> Ra(R, R + size_t(D) * D);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Ra[size_t(6 + r) * D + (6 + c)] = 2.0 * acc_cov[r * 3 + c];
+    return is_psd(Ra.data(), D);
+}
+
+// ---- measurement models -------------------------------------------------------------------------------------------------
+inline bool meas_model_ok(int engine_model, int m) {
+    if (engine_model == UKFB_MODEL_POSE) return m >= UKFB_MEAS_POS3 && m <= UKFB_MEAS_ANGVEL3;
+    return m == UKFB_MEAS_ORIENT_BODYVEL3;
+}
+
+// Class of a filter's update in a call: 0 = none (negative / invalid model id: prediction only), 1 = closed form (the eight
+// linear sub-state selections of PoseUKF), 2 = sigma-point path (PoseUKF OrientationMeasurement, OrientationUKF body velocity)
+UKFB_HD int update_class(int engine_model, int mid) {
+    if (engine_model == UKFB_MODEL_POSE) return (mid < 0 || mid > 8) ? 0 : ((mid == 3) ? 2 : 1);
+    return (mid == 9) ? 2 : 0;
+}
+
+// ---- shards of a device group -------------------------------------------------------------------------------------------
+inline int shard_range(int64_t total, int n_shards, int shard, int64_t* first, int64_t* count) {
+    if (total < 0 || n_shards <= 0 || shard < 0 || shard >= n_shards) return UKFB_ERR_INVALID_ARG;
+    const int64_t base = total / n_shards, extra = total % n_shards;
+    if (count) *count = base + (shard < extra ? 1 : 0);
+    if (first) *first = shard * base + std::min<int64_t>(shard, extra);
+    return UKFB_OK;
+}
+
+// [first, first + count) of the batch cut by the shard [shard_first, shard_first + shard_count): (offset inside the caller's
+// arrays, offset inside the shard, length)
+struct Cut { int64_t src, dst, len; };
+inline Cut cut(int64_t shard_first, int64_t shard_count, int64_t first, int64_t count) {
+    const int64_t lo = std::max(first, shard_first), hi = std::min(first + count, shard_first + shard_count);
+    return {lo - first, lo - shard_first, std::max<int64_t>(0, hi - lo)};
+}
+
+// The owner pass of ukfb_group_process_events: owner[i] = the shard of filter[i], counts[r] = the events of shard r (shards as
+// shard_range cuts them, at most 255).  UKFB_ERR_OUT_OF_RANGE for an index outside [0, total).
+inline int route_events(const int64_t* filter, int64_t n_events, int64_t total, const int64_t* first, const int64_t* count,
+                        size_t n_shards, uint8_t* owner, size_t* counts) {
+    std::fill(counts, counts + n_shards, size_t(0));
+    const double per_filter = double(n_shards) / double(total);   // (a multiply, not a 64-bit division per event)
+    for (int64_t i = 0; i < n_events; ++i) {
+        const int64_t f = filter[i];
+        if (f < 0 || f >= total) return UKFB_ERR_OUT_OF_RANGE;
+        size_t r = std::min(n_shards - 1, size_t(double(f) * per_filter));   // shards differ by one filter at most: off by one at most
+        while (f < first[r]) --r;
+        while (f >= first[r] + count[r]) ++r;
+        owner[size_t(i)] = uint8_t(r);
+        ++counts[r];
+    }
+    return UKFB_OK;
+}
+
+// ---- multi-cycle calls --------------------------------------------------------------------------------------------------
+inline Verdict check_cycle_args(int cycles, int slots, int first_slot) {
+    if (cycles < 0 || slots < 1 || first_slot < 0 || first_slot >= slots)
+        return {UKFB_ERR_INVALID_ARG, "cycles >= 0, slots >= 1, 0 <= first_slot < slots"};
+    return {};
+}
+
+struct CycleLaunch {
+    int first_cycle, cycles, slot;   // slot: the ring slot of first_cycle
+    bool status_accumulate;          // the status word is the OR over ALL cycles of the call
+};
+// The launches of a call: the tuned layout runs multi-cycle launches (with a schedule: up to UKFB_MAX_MULTI_CYCLES each, the
+// schedule travels in the kernel arguments); the one-wavefront-per-filter layouts have no multi-cycle kernel, one launch per cycle.
+struct CyclePlan {
+    int cycles, slots, first_slot;
+    bool multi;       // multi-cycle launches (the tuned layout), else one single-cycle launch per cycle
+    int per_launch;   // cycles of a launch, the last one's excepted
+    CyclePlan(int cycles_, int slots_, int first_slot_, bool tuned, bool schedule)
+        : cycles(cycles_), slots(slots_), first_slot(first_slot_), multi(tuned),
+          per_launch(!tuned ? 1 : (schedule ? UKFB_MAX_MULTI_CYCLES : std::max(cycles_, 1))) {}
+    int launches() const { return int((int64_t(cycles) + per_launch - 1) / per_launch); }
+    CycleLaunch operator[](int k) const {
+        const int c0 = k * per_launch;
+        return {c0, std::min(per_launch, cycles - c0), int((int64_t(first_slot) + c0) % slots), k > 0};
+    }
+};
+
+// ---- workspace sizing ---------------------------------------------------------------------------------------------------
+// model-class buckets (ukf_batch.hip): blocks of BK_BLOCK filters for the count and scatter kernels
+constexpr int BK_THREADS = 256, BK_PER_THREAD = 4, BK_BLOCK = BK_THREADS * BK_PER_THREAD;
+constexpr int BUCKET_INLINE_BLOCKS = 2048;   // up to 2 M filters: every scatter block sums 3 x 2048 counts at most
+constexpr int64_t BUCKET_MIN_FILTERS = 16384;
+
+inline bool buckets_apply(bool per_filter_models, const ukfb_config& cfg, int64_t cap) {
+    return per_filter_models && cfg.bucket_models && cfg.lanes_per_filter == 16 && cap >= BUCKET_MIN_FILTERS && cap <= 0x7fffffff - 16;
+}
+
+struct BucketGeometry {
+    int blocks;
+    int64_t items;        // entries of the list a launch covers: every class padded to a multiple of 4 (an upper bound)
+    size_t list;          // entries of the filter list
+    size_t count_words;   // [3][blocks] counts, [3][blocks] exclusive prefix sums, [3] totals (+ 1 pad)
+    bool inline_scan;     // the scatter blocks sum the counts themselves (no scan launch)
+};
+inline BucketGeometry bucket_geometry(int64_t n) {
+    const int blocks = int((n + BK_BLOCK - 1) / BK_BLOCK);
+    // sum of three counts each rounded up to 4 <= n + 9, itself rounded up to whole wavefronts
+    return {blocks, (n + 3 + 3 + 3) / 4 * 4, size_t(n) + 16, size_t(6) * blocks + 4, blocks <= BUCKET_INLINE_BLOCKS};
+}
+
+struct Carver {   // bump allocator over a workspace (256-byte aligned pieces); a NULL base only measures
+    char* base;
+    size_t used = 0;
+    explicit Carver(void* b) : base(static_cast<char*>(b)) {}
+    template <class P> P* take(size_t count) {
+        P* p = base ? reinterpret_cast<P*>(base + used) : nullptr;
+        used += (count * sizeof(P) + 255) / 256 * 256;
+        return p;
+    }
+};
+
+// bytes of workspace process_events_device needs for n events (an upper bound that does not depend on hipCUB's
+// temporary-storage query: 4x the key/value arrays covers rocPRIM's double buffers)
+inline size_t events_workspace_bytes(int64_t n) {
+    const size_t ne = size_t(n);
+    // 4 index + 2 time-key + 2 filter-key + head/start/rank/rank_sorted/off + compact events (int32, int64, int32,
+    // 12 scalars of <= 8 bytes) + alignment slack + radix-sort temporaries
+    return (4 * 4 + 2 * 8 + 2 * 4 + 5 * 4 + 4 + 8 + 4 + 12 * 8) * ne + 32 * 256 + (size_t(64) << 20) / 4 + 24 * ne;
+}
+
+// Split launches (ukf_launch.inc.hpp): direct launches of SPLIT_MIN_FILTERS <= n < split_max filters on an engine with a second
+// stream run as two halves; the first covers whole wavefronts of 4 filters
+constexpr int64_t SPLIT_MIN_FILTERS = 16384;
+inline bool split_launch(bool indirect, bool no_split, bool has_stream_b, bool split_streams, int64_t n, int64_t split_max) {
+    return !indirect && !no_split && has_stream_b && split_streams && n >= SPLIT_MIN_FILTERS && n < split_max;
+}
+inline int64_t split_first_half(int64_t n) { return (n / 2 + 3) / 4 * 4; }
+
+// ---- kernel level of a tuned launch (ukf_kernel16<..., PLAIN>): what the kernel may take as compile-time facts -----------
+//   streams only (level 1)  no per-filter timestamps / time steps / activity flags, the accept-any gate, a fresh status word
+//   plain        (level 2)  ... and ONE full-3-vector measurement model for the launch (prediction-only launches: level 1 = 2)
+// Indirect launches qualify for level 1 when their list is a bucketed filter list (event rounds carry timestamps); multi-cycle
+// launches for level 2 when they have no schedule.
+struct LaunchFacts {
+    bool timestamps = false, dt_array = false, active = false, status_accumulate = false, gate = false;
+    bool indirect = false, bucketed = false, multi = false, schedule = false, update = false, meas_per_filter = false;
+    int meas_uniform = -1;
+};
+inline int kernel_level(int engine_model, const LaunchFacts& f) {
+    const bool streams_only = !f.timestamps && !f.dt_array && !f.active && !f.status_accumulate && !f.gate &&
+                              (!f.multi || !f.schedule) && (!f.indirect || f.bucketed);
+    if (!streams_only) return 0;
+    const bool full3 = !f.meas_per_filter && (engine_model != UKFB_MODEL_POSE ? f.meas_uniform == UKFB_MEAS_ORIENT_BODYVEL3
+                                                                              : (f.meas_uniform == UKFB_MEAS_POS3 ||
+                                                                                 f.meas_uniform == UKFB_MEAS_VEL3 ||
+                                                                                 f.meas_uniform == UKFB_MEAS_ANGVEL3));
+    if (f.indirect) return 1;
+    if (f.multi) return full3 ? 2 : 0;
+    if (!f.update) return 2;
+    return full3 ? 2 : 1;
+}
+
+}  // namespace ukfb

@@ -11,6 +11,14 @@
 
 namespace ukfb {
 
+// UKFB_OK, or UKFB_ERR_HIP with the error of the launches just enqueued
+static int launch_status(const char* what) {
+    const hipError_t err = hipGetLastError();
+    if (err == hipSuccess) return UKFB_OK;
+    set_error(what, err);
+    return UKFB_ERR_HIP;
+}
+
 template <class T, class M, int G> static int launch_g(ukfb_engine* e, const LaunchReq& r, const KArgs<T>& args) {
     constexpr int FPW = 64 / G;
     const int64_t grid = (args.n + FPW - 1) / FPW;
@@ -29,12 +37,7 @@ template <class T, class M, int G> static int launch_g(ukfb_engine* e, const Lau
         hipLaunchKernelGGL((ukf_kernel<T, M, G, true, false>), gd, bd, lds, main_stream(e), args);
     else
         hipLaunchKernelGGL((ukf_kernel<T, M, G, false, true>), gd, bd, lds, main_stream(e), args);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("kernel launch", err);
-        return UKFB_ERR_HIP;
-    }
-    return UKFB_OK;
+    return launch_status("kernel launch");
 }
 
 // The instantiation of the tuned kernel for a launch shape: go(kernel) is called with the matching ukf_kernel16<...> (one of
@@ -145,7 +148,6 @@ template <class T, class M, class TC = T> static int launch_row16_stamped(ukfb_e
 }
 #endif
 
-constexpr int64_t SPLIT_MIN_FILTERS = 16384;
 // (UKFB_SPLIT_MAX in the environment moves the upper bound: measurements only)
 static int64_t split_max_filters() {
     static const int64_t v = [] {
@@ -167,24 +169,12 @@ template <class T, class M, class TC = T> static int launch_row16(ukfb_engine* e
     static const int lds_pad = [] { const char* s = std::getenv("UKFB_LDS_PAD_BYTES"); return s ? std::atoi(s) : 0; }();
     const int lds = FPW * lds_bytes_per_filter16<TC, MC>() + lds_pad;
     const bool multi = r.cycles > 0;   // ukfb_cycle_multi_dev: fused cycles only (checked by the caller)
-    // What the kernel may take as compile-time facts about this launch (ukf_kernel16<..., PLAIN>):
-    //   streams only (level 1)  no per-filter timestamps / time steps / activity flags, the accept-any gate, a fresh status word
-    //   plain        (level 2)  ... and ONE full-3-vector measurement model for the launch (prediction-only launches: level 1 = 2)
-    // Indirect launches qualify for level 1 when their list is a bucketed filter list (event rounds carry timestamps); multi-cycle
-    // launches for level 2 when they have no schedule.
     const char* const plain_env = std::getenv("UKFB_NO_PLAIN_KERNEL");   // (A/B and tests: =1 keeps the general kernel; read per launch)
-    const bool plain_off = plain_env && plain_env[0] == '1';
-    const bool streams_only = !plain_off && !args.ts && !args.dt && !args.active && !args.status_accumulate && args.gate_chi2 < T(0) &&
-                              (!multi || !args.cyc_sched) && (!args.fidx || args.fidx_inputs);
-    const bool full3 = !args.meas && (M::MODEL != 0 ? args.meas_uniform == 9
-                                                    : (args.meas_uniform == 0 || args.meas_uniform == 4 || args.meas_uniform == 8));
-    int level = 0;
-    if (streams_only) {
-        if (args.fidx) level = 1;
-        else if (multi) level = full3 ? 2 : 0;
-        else if (!r.do_update) level = 2;
-        else level = full3 ? 2 : 1;
-    }
+    LaunchFacts f;   // what the kernel may take as compile-time facts about this launch (kernel_level, ukf_host.hpp)
+    f.timestamps = args.ts; f.dt_array = args.dt; f.active = args.active; f.status_accumulate = args.status_accumulate;
+    f.gate = !(args.gate_chi2 < T(0)); f.indirect = args.fidx; f.bucketed = args.fidx_inputs; f.multi = multi;
+    f.schedule = args.cyc_sched; f.update = r.do_update; f.meas_per_filter = args.meas; f.meas_uniform = args.meas_uniform;
+    const int level = (plain_env && plain_env[0] == '1') ? 0 : kernel_level(M::MODEL == 0 ? UKFB_MODEL_POSE : UKFB_MODEL_ORIENT, f);
     const char* const suffix = level == 2 ? "-plain" : (level == 1 ? "-streams" : "");
     const std::string mode = std::string(multi ? "multicycle" : (r.do_predict ? (r.do_update ? (args.fidx_inputs ? "cycle-bucketed" : "cycle") : "predict") : "update")) + suffix;
     e->last_kernel = std::string("ukf_kernel16<") + (sizeof(T) == 8 ? "f64" : (sizeof(TC) == 8 ? "f32-wide" : "f32")) + "," +
@@ -201,9 +191,9 @@ template <class T, class M, class TC = T> static int launch_row16(ukfb_engine* e
     // launch k + 1's first half follows launch k's first half on `stream`, its second half follows launch k's second half on
     // stream_b -- the tail of one half (a partly empty last round of workgroups) overlaps the head of the other stream's next
     // kernel.  Filters are independent, the halves touch disjoint filters: results are bit-identical.
-    if (!args.fidx && !r.no_split && e->stream_b && e->cfg.split_streams && args.n >= SPLIT_MIN_FILTERS && args.n < split_max_filters()) {
+    if (split_launch(args.fidx, r.no_split, e->stream_b, e->cfg.split_streams, args.n, split_max_filters())) {
         KArgs<T> h1 = args, h2 = args;
-        h1.n = (args.n / 2 + FPW - 1) / FPW * FPW;
+        h1.n = split_first_half(args.n);
         h2.item0 = h1.n;
         const dim3 g1((unsigned)(h1.n / FPW)), g2((unsigned)((args.n - h1.n + FPW - 1) / FPW));
         hipStream_t sa = e->stream, sb = e->stream_b;    // (raw: a pending second half is NOT joined, that is the point)
@@ -215,12 +205,7 @@ template <class T, class M, class TC = T> static int launch_row16(ukfb_engine* e
         };
         with_kernel16<T, M, TC>(false, multi, r.do_predict, r.do_update, level, go);
         e->split_pending = true;
-        const hipError_t serr = hipGetLastError();
-        if (serr != hipSuccess) {
-            set_error("kernel launch (split)", serr);
-            return UKFB_ERR_HIP;
-        }
-        return UKFB_OK;
+        return launch_status("kernel launch (split)");
     }
     if (args.fidx) {   // indirect launch (event rounds): the fused cycle over a list of filters
         if (multi || !(r.do_predict && r.do_update)) {
@@ -230,12 +215,7 @@ template <class T, class M, class TC = T> static int launch_row16(ukfb_engine* e
     }
     with_kernel16<T, M, TC>(args.fidx != nullptr, multi, r.do_predict, r.do_update, level,
                             [&](auto kern) { hipLaunchKernelGGL(kern, gd, bd, lds, main_stream(e), args); });
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        set_error("kernel launch", err);
-        return UKFB_ERR_HIP;
-    }
-    return UKFB_OK;
+    return launch_status("kernel launch");
 }
 
 template <class T, class M> static int launch_typed(ukfb_engine* e, const LaunchReq& r) {
@@ -294,7 +274,9 @@ template <class T, class M> static int launch_typed(ukfb_engine* e, const Launch
     // instantiations need more than 256 VGPRs and the compiler parks the excess in AGPRs -- live-range-split copies of the
     // kind DESIGN.md 4.5 distrusts with this toolchain.  -DUKFB_GENERIC_F64=1 (make GENERIC_F64=1) builds them for
     // diagnostics; ukfb_set_config refuses the setting otherwise (ukfb_layout_supported tells).
-#if !defined(UKFB_LAUNCH_WIDE)
+#if defined(UKFB_LAUNCH_WIDE)
+    return launch_row16<T, M, double>(e, r, a);
+#else
     if constexpr (sizeof(T) == 4 || UKFB_GENERIC_F64 != 0) {
         switch (e->cfg.lanes_per_filter) {
             case 64: return launch_g<T, M, 64>(e, r, a);
@@ -302,10 +284,6 @@ template <class T, class M> static int launch_typed(ukfb_engine* e, const Launch
             default: break;
         }
     }
-#endif
-#if defined(UKFB_LAUNCH_WIDE)
-    return launch_row16<T, M, double>(e, r, a);
-#else
     return launch_row16<T, M>(e, r, a);
 #endif
 }

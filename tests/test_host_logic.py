@@ -1,0 +1,33 @@
+"""The engine's host decisions on the CPU: slam-pose_estimation_amd/csrc/ukf_host.hpp (configuration checks, process-noise
+classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, workspace sizing, the
+kernel level of a launch) compiled with g++ under ASan / UBSan and driven by tests/cpp/host_logic.cpp."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CPP = os.path.join(ROOT, "tests", "cpp")
+
+
+def noise_cases(synth):
+    """(name, model, R, short update allowed): synth.py's dense noise couples position / velocity (Pose) and the rotated blocks
+    to the rest, so the prediction can make it indefinite -- the short update factorisation must be refused (the gate that
+    69f2198 fixed); the diagonal defaults keep it."""
+    return [("pose_dense", 0, synth.dense_process_noise("pose"), 0),
+            ("orient_dense", 1, synth.dense_process_noise("orient"), 0),
+            ("pose_rotation_indefinite", 0, synth.rotation_indefinite_noise("pose"), 0),
+            ("orient_rotation_indefinite", 1, synth.rotation_indefinite_noise("orient"), 0),
+            ("pose_default", 0, synth.pose_default_process_noise(), 1),
+            ("orient_config4", 1, synth.orient_process_noise(), 1)]
+
+
+def test_host_logic_under_sanitizers(spe, tmp_path):
+    subprocess.run(["make", "-s", "-C", CPP, "host_asan"], check=True, timeout=300)
+    cases = tmp_path / "noise.txt"
+    with open(cases, "w") as f:
+        for name, model, R, ok in noise_cases(spe.synth):
+            f.write(f"{name} {model} {R.shape[0]} {ok} " + " ".join(repr(float(v)) for v in R.ravel()) + "\n")
+    out = subprocess.run([os.path.join(CPP, "build", "host_logic_asan"), str(cases)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "OK: 0 failure(s)" in out.stdout
+    for marker in ("AddressSanitizer", "LeakSanitizer", "runtime error", "UndefinedBehaviorSanitizer"):
+        assert marker not in out.stderr + out.stdout, out.stderr
