@@ -68,6 +68,44 @@ public:
         check(ukfb_process_events(engine, n_events, filter, ts_us, model, z, Q, NULL, &rounds));
         return rounds;
     }
+    /** Innovation statistics WITHOUT an update (ukfb_innovation): `candidates` samples per filter, z [candidates][N][3],
+     *  Q [N][3][3].  The filters are not changed.  With maha a caller evaluates any acceptance predicate ukfom allows;
+     *  best is the nearest candidate inside ukfb_config.gate_chi2 (-1: none). */
+    struct Innovation
+    {
+        std::vector<double> z_pred;    // [N][4]
+        std::vector<double> S;         // [N][3][3]
+        std::vector<double> innov;     // [candidates][N][3]
+        std::vector<double> maha;      // [candidates][N]
+        std::vector<double> loglik;    // [candidates][N]
+        std::vector<int32_t> best;     // [N]
+        std::vector<uint32_t> status;  // [N]  UKFB_ST_* of the call
+    };
+    Innovation innovation(int model, int candidates, const double* z, const double* Q)
+    {
+        const size_t n = static_cast<size_t>(cap), k = static_cast<size_t>(candidates > 0 ? candidates : 0);
+        Innovation r;
+        r.z_pred.resize(n * 4); r.S.resize(n * 9); r.innov.resize(k * n * 3); r.maha.resize(k * n); r.loglik.resize(k * n);
+        r.best.resize(n); r.status.resize(n);
+        check(ukfb_innovation(engine, model, candidates, z, Q, r.z_pred.data(), r.S.data(), r.innov.data(), r.maha.data(),
+                              r.loglik.data(), r.best.data(), r.status.data()));
+        return r;
+    }
+    /** nearest-neighbour association from host arrays: z_sel [N][3] = the chosen candidate of every filter, model_sel [N] = model
+     *  or -1 where best < 0 -- the arguments of integrateMixedMeasurements(model_sel, z_sel, Q) */
+    void selectCandidates(int model, int candidates, const std::vector<int32_t>& best, const double* z, std::vector<double>& z_sel,
+                          std::vector<int32_t>& model_sel) const
+    {
+        const size_t n = static_cast<size_t>(cap);
+        if (best.size() != n) throw std::runtime_error("pose_estimation engine: selectCandidates needs one choice per filter");
+        z_sel.assign(n * 3, 0.0);
+        model_sel.assign(n, -1);
+        for (size_t i = 0; i < n; ++i) {
+            if (best[i] < 0 || best[i] >= candidates) continue;
+            for (int c = 0; c < 3; ++c) z_sel[i * 3 + c] = z[(static_cast<size_t>(best[i]) * n + i) * 3 + c];
+            model_sel[i] = model;
+        }
+    }
     std::vector<uint32_t> status()
     {
         std::vector<uint32_t> st(static_cast<size_t>(cap), 0u);

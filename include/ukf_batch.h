@@ -330,6 +330,51 @@ int ukfb_process_events_dev(ukfb_engine* e, int64_t n_events, const int64_t* fil
                             int64_t* rounds);
 
 
+/* ---- innovation statistics and measurement association, WITHOUT an update ------------------------------------------------ */
+/* The first half of ukf::update -- predicted measurement z-bar, innovation covariance S, innovation nu = z (-) z-bar, squared
+ * Mahalanobis distance d^2 = nu^T S^-1 nu (the normalised innovation squared) and the measurement log-likelihood -- for up to
+ * 32 CANDIDATE samples per filter, and the candidate nearest to the filter inside the chi-square gate.  ukfom makes the
+ * acceptance test a predicate at every call site (accept_any_mahalanobis_distance, PoseUKF.cpp:116); with these numbers a
+ * caller evaluates any predicate, associates detections with filters, monitors consistency or weights a bank of filters.
+ * The call is READ-ONLY: mean, covariance, last measurement time, latched inputs and the engine's own status array are bit
+ * for bit what they were.  It is stream-ordered like every "_dev" call.
+ *  - z_dev [candidates][capacity][3] -- the slot layout of ukfb_cycle_multi_dev's sample ring, so a buffered ring is scored
+ *    as it lies; Q_dev [capacity][9], or ONE 3x3 when q_is_uniform (as ukfb_update_uniform_q); candidates 1 ... 32; model ids
+ *    and the axis-angle input of UKFB_MEAS_ORIENT_SO3 exactly as ukfb_update_dev.
+ *  - status (of THIS call): UNINITIALISED; INACTIVE (model id negative or not one of the engine's); ERR_CHOLESKY (the
+ *    covariance is not factorisable in the columns the measurement reads, or S is not positive definite -- the sub-state
+ *    selections of PoseWithVelocity read S = Sigma[sel][sel] + Q in closed form, as the update kernels do, so for them it is S
+ *    that is judged); WARN_MEAN_NOCONV.  A filter with one of the first three writes NaN to its float outputs and -1 to best.
+ *    A candidate with a non-finite entry among its first m gets NaN innov / maha / loglik and is never best;
+ *    ERR_NONFINITE_MEAS is set when EVERY candidate of the filter is non-finite.
+ *  - the arithmetic is the update kernels' (same device functions, same order), so maha[k] is the number ukfb_update_dev
+ *    compares with ukfb_config.gate_chi2 for candidate k.  The kernel is the tuned one-row-per-filter layout for every
+ *    lanes_per_filter setting; fp32 engines with wide_arithmetic compute in fp64 and store fp32.
+ *  - device groups: ukfb_group_shard hands out each shard's engine, on which these per-engine calls work. */
+typedef struct ukfb_innovation_out {   /* device pointers, engine precision; any may be NULL */
+    void*     z_pred;   /* [capacity][4]  z-bar: first m entries (rest 0); ORIENT_SO3: quaternion x,y,z,w */
+    void*     S;        /* [capacity][9]  row-major 3x3, leading m x m block = S, rest 0                    */
+    void*     innov;    /* [candidates][capacity][3]  nu = z (-) z-bar, first m entries (rest 0)             */
+    void*     maha;     /* [candidates][capacity]     d^2 = nu^T S^-1 nu                                     */
+    void*     loglik;   /* [candidates][capacity]     -0.5 (d^2 + ln det S + m ln 2 pi)                      */
+    int32_t*  best;     /* [capacity]  candidate with the smallest d^2 among those that are finite and, if
+                           cfg.gate_chi2 >= 0, have d^2 <= gate_chi2 (the update's own comparison); -1: none;
+                           equal d^2: the lower candidate index                                              */
+    uint32_t* status;   /* [capacity]  UKFB_ST_* of THIS call (the engine's own status array is not written) */
+} ukfb_innovation_out;
+
+int ukfb_innovation_dev(ukfb_engine* e, int meas_model_uniform, const int32_t* meas_model_dev, int candidates,
+                        const void* z_dev, const void* Q_dev, int q_is_uniform, const ukfb_innovation_out* out);
+/* z_sel[i] = z[best[i]][i] (zeros where best[i] < 0) and meas_model_sel[i] = best[i] < 0 ? -1 : model(i) (may be NULL), so
+ * that ukfb_update_dev(e, 0, meas_model_sel, z_sel, Q) -- or ukfb_cycle_dev -- finishes nearest-neighbour association with
+ * no host round trip: filters without an accepted candidate are left untouched (status INACTIVE). */
+int ukfb_select_candidates_dev(ukfb_engine* e, int candidates, const int32_t* best_dev, int meas_model_uniform,
+                               const int32_t* meas_model_dev, const void* z_dev, void* z_sel_dev, int32_t* meas_model_sel_dev);
+/* host arrays of doubles (z [candidates][capacity][3], Q [capacity][3][3]), any output NULL; synchronises */
+int ukfb_innovation(ukfb_engine* e, int meas_model, int candidates, const double* z, const double* Q, double* z_pred,
+                    double* S, double* innov, double* maha, double* loglik, int32_t* best, uint32_t* status);
+
+
 /* ---- device groups: one host process, several MI355X ------------------------------------------------------------------ */
 /* north_star's multi-GPU shape for a C++ host.  The filters of a batch are independent -- every filter of the reference owns
  * its own `ukf` object (src/UnscentedKalmanFilter.hpp:150) -- so `total_filters` split into contiguous shards (the first

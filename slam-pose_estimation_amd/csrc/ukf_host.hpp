@@ -175,6 +175,30 @@ inline Verdict check_cycle_args(int cycles, int slots, int first_slot) {
     return {};
 }
 
+// ---- innovation statistics (ukfb_innovation_dev, ukfb_select_candidates_dev) ---------------------------------------------
+constexpr int MAX_CANDIDATES = 32;   // two passes of the sixteen lanes of a filter's row (ukf_innovation.hpp)
+// per_filter_models: the model ids come from a device array (checked per filter by the kernel: an id the engine's model does
+// not have marks the filter INACTIVE, as in ukfb_update_dev); otherwise the one id must be the engine model's.
+inline Verdict check_innovation_args(int engine_model, bool per_filter_models, int meas_model_uniform, int candidates, bool has_z,
+                                     bool has_Q, const ukfb_innovation_out* out) {
+    if (candidates < 1 || candidates > MAX_CANDIDATES) return {UKFB_ERR_INVALID_ARG, "candidates must be 1 ... 32"};
+    if (!has_z || !has_Q) return {UKFB_ERR_INVALID_ARG, "z and Q must not be NULL"};
+    if (!out) return {UKFB_ERR_INVALID_ARG, "out must not be NULL"};
+    if (!out->z_pred && !out->S && !out->innov && !out->maha && !out->loglik && !out->best && !out->status)
+        return {UKFB_ERR_INVALID_ARG, "every output of ukfb_innovation_out is NULL: nothing to compute"};
+    if (!per_filter_models && !meas_model_ok(engine_model, meas_model_uniform))
+        return {UKFB_ERR_WRONG_MODEL, "measurement model id not valid for this engine"};
+    return {};
+}
+inline Verdict check_select_args(int engine_model, bool per_filter_models, int meas_model_uniform, int candidates, bool has_best,
+                                 bool has_z, bool has_z_sel) {
+    if (candidates < 1 || candidates > MAX_CANDIDATES) return {UKFB_ERR_INVALID_ARG, "candidates must be 1 ... 32"};
+    if (!has_best || !has_z || !has_z_sel) return {UKFB_ERR_INVALID_ARG, "best, z and z_sel must not be NULL"};
+    if (!per_filter_models && !meas_model_ok(engine_model, meas_model_uniform))
+        return {UKFB_ERR_WRONG_MODEL, "measurement model id not valid for this engine"};
+    return {};
+}
+
 struct CycleLaunch {
     int first_cycle, cycles, slot;   // slot: the ring slot of first_cycle
     bool status_accumulate;          // the status word is the OR over ALL cycles of the call

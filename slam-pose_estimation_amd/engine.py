@@ -49,6 +49,8 @@ EXPORTS = [
     "ukfb_last_model_groups",
     "ukfb_timer_begin", "ukfb_timer_end", "ukfb_pose_export_body_states", "ukfb_pose_import_body_states",
     "ukfb_cycle_timestamps", "ukfb_cycle_timestamps_dev", "ukfb_process_events", "ukfb_process_events_dev",
+    # innovation statistics / measurement association (read-only)
+    "ukfb_innovation_dev", "ukfb_select_candidates_dev", "ukfb_innovation",
     # device groups (one process, several GPUs)
     "ukfb_group_shard_range", "ukfb_group_create", "ukfb_group_destroy", "ukfb_group_size", "ukfb_group_shard",
     "ukfb_group_set_config", "ukfb_group_initialize", "ukfb_group_get_state", "ukfb_group_get_status",
@@ -67,6 +69,12 @@ class Config(C.Structure):
                 ("min_time_delta", C.c_double), ("max_time_delta", C.c_double), ("lanes_per_filter", C.c_int32),
                 ("bucket_models", C.c_int32), ("split_streams", C.c_int32), ("wide_arithmetic", C.c_int32),
                 ("full_update_check", C.c_int32)]
+
+
+class InnovationOut(C.Structure):
+    """ukfb_innovation_out: device pointers in engine precision, any may be NULL"""
+    _fields_ = [("z_pred", C.c_void_p), ("S", C.c_void_p), ("innov", C.c_void_p), ("maha", C.c_void_p),
+                ("loglik", C.c_void_p), ("best", C.c_void_p), ("status", C.c_void_p)]
 
 
 class UkfbError(RuntimeError):
@@ -338,6 +346,39 @@ class BatchUKF:
     def update_dev(self, meas_model_uniform: int, z_dev, Q_dev, meas_model_dev=None):
         _chk(self._lib.ukfb_update_dev(self._h, C.c_int(meas_model_uniform), _devptr(meas_model_dev), _devptr(z_dev),
                                        _devptr(Q_dev)), "ukfb_update_dev")
+
+    # ---- innovation statistics and association (read-only: the engine's state and status are not touched)
+    def innovation_dev(self, meas_model_uniform: int, candidates: int, z_dev, Q_dev, q_is_uniform: bool = False,
+                       meas_model_dev=None, z_pred=None, S=None, innov=None, maha=None, loglik=None, best=None, status=None):
+        """z_dev [candidates][capacity][3], Q_dev [capacity][9] (or 9 scalars with q_is_uniform); the keyword outputs are
+        device buffers in engine precision (best int32, status uint32), None = not wanted.  Stream-ordered."""
+        ptr = lambda x: None if x is None else _devptr(x).value
+        out = InnovationOut(ptr(z_pred), ptr(S), ptr(innov), ptr(maha), ptr(loglik), ptr(best), ptr(status))
+        _chk(self._lib.ukfb_innovation_dev(self._h, C.c_int(meas_model_uniform), _devptr(meas_model_dev), C.c_int(candidates),
+                                           _devptr(z_dev), _devptr(Q_dev), C.c_int(1 if q_is_uniform else 0), C.byref(out)),
+             "ukfb_innovation_dev")
+
+    def select_candidates_dev(self, candidates: int, best_dev, meas_model_uniform: int, z_dev, z_sel_dev, meas_model_sel_dev=None,
+                              meas_model_dev=None):
+        """z_sel[i] = z[best[i]][i], meas_model_sel[i] = -1 where best[i] < 0: update_dev(0, z_sel, Q, meas_model_sel) then
+        applies the nearest gated candidate of every filter and leaves the others untouched."""
+        _chk(self._lib.ukfb_select_candidates_dev(self._h, C.c_int(candidates), _devptr(best_dev), C.c_int(meas_model_uniform),
+                                                  _devptr(meas_model_dev), _devptr(z_dev), _devptr(z_sel_dev),
+                                                  _devptr(meas_model_sel_dev)), "ukfb_select_candidates_dev")
+
+    def innovation(self, meas_model: int, z, Q):
+        """Host arrays: z [candidates, capacity, 3] (or [capacity, 3] for one candidate), Q [capacity, 3, 3].  Returns a dict of
+        NumPy arrays: z_pred [n, 4], S [n, 3, 3], innov [K, n, 3], maha [K, n], loglik [K, n], best [n], status [n]."""
+        n = self.capacity
+        z = _f64(z, (-1, n, 3)); Q = _f64(Q, (n, 3, 3))
+        K = z.shape[0]
+        o = {"z_pred": np.empty((n, 4)), "S": np.empty((n, 3, 3)), "innov": np.empty((K, n, 3)), "maha": np.empty((K, n)),
+             "loglik": np.empty((K, n)), "best": np.empty(n, dtype=np.int32), "status": np.empty(n, dtype=np.uint32)}
+        _chk(self._lib.ukfb_innovation(self._h, C.c_int(int(meas_model)), C.c_int(K), _pd(z), _pd(Q), _pd(o["z_pred"]), _pd(o["S"]),
+                                       _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]),
+                                       o["best"].ctypes.data_as(C.POINTER(C.c_int32)),
+                                       o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_innovation")
+        return o
 
     # ---- fused cycle
     def cycle(self, dt: float, meas_model: int, z, Q):
