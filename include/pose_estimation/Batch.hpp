@@ -106,6 +106,38 @@ public:
             model_sel[i] = model;
         }
     }
+    /** Filter banks (ukf_batch.h, "filter banks"): the batch read as capacity / hypotheses tracks of `hypotheses` filters each,
+     *  track-major.  bankCombine: the mixture moments of every track under the weights w [N] (the filters are not changed). */
+    struct BankEstimate
+    {
+        std::vector<double> mu;        // [T][S]
+        std::vector<double> cov;       // [T][D][D]
+        std::vector<uint32_t> status;  // [T]  UKFB_ST_* of the call
+    };
+    BankEstimate bankCombine(int hypotheses, const double* w)
+    {
+        const size_t t = hypotheses > 0 ? static_cast<size_t>(cap) / static_cast<size_t>(hypotheses) : 0;
+        BankEstimate r;
+        r.mu.resize(t * S); r.cov.resize(t * D * D); r.status.resize(t);
+        check(ukfb_bank_combine(engine, hypotheses, w, r.mu.data(), r.cov.data(), r.status.data()));
+        return r;
+    }
+    /** IMM interaction: every hypothesis re-seeded from all of its track under the row-stochastic transition [M][M]; returns the
+     *  predicted model probabilities [N]; status [T] (may be NULL) receives the per-track status of the call */
+    std::vector<double> bankMix(int hypotheses, const double* w, const double* transition, std::vector<uint32_t>* status = NULL)
+    {
+        const size_t t = hypotheses > 0 ? static_cast<size_t>(cap) / static_cast<size_t>(hypotheses) : 0;
+        std::vector<double> w_pred(static_cast<size_t>(cap));
+        if (status) status->assign(t, 0u);
+        check(ukfb_bank_mix(engine, hypotheses, w, transition, w_pred.data(), status ? status->data() : NULL));
+        return w_pred;
+    }
+    /** posterior weights on the device (engine precision arrays [N]): logw_out = logw_in + loglik - logsumexp per track */
+    void bankWeights(int hypotheses, const void* logw_in_dev, const void* loglik_dev, void* logw_out_dev, void* w_out_dev = NULL,
+                     uint32_t* status_dev = NULL)
+    {
+        check(ukfb_bank_weights_dev(engine, hypotheses, logw_in_dev, loglik_dev, logw_out_dev, w_out_dev, status_dev));
+    }
     std::vector<uint32_t> status()
     {
         std::vector<uint32_t> st(static_cast<size_t>(cap), 0u);

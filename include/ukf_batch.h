@@ -95,7 +95,8 @@ enum {
     UKFB_ST_WARN_MEAN_NOCONV = 1u << 6,   /* ukfom: meanSigmaPoints() did not converge       */
     UKFB_ST_UNINITIALISED = 1u << 7,      /* UnscentedKalmanFilter.hpp:53,59                 */
     UKFB_ST_INACTIVE = 1u << 8,           /* filter masked out of this call                  */
-    UKFB_ST_REJECTED_GATE = 1u << 9       /* mahalanobis gate rejected the update            */
+    UKFB_ST_REJECTED_GATE = 1u << 9,      /* mahalanobis gate rejected the update            */
+    UKFB_ST_ERR_WEIGHTS = 1u << 10        /* filter banks: the weights of a track are not a distribution */
 };
 
 /* ---- configuration ---------------------------------------------------------------------- */
@@ -373,6 +374,56 @@ int ukfb_select_candidates_dev(ukfb_engine* e, int candidates, const int32_t* be
 /* host arrays of doubles (z [candidates][capacity][3], Q [capacity][3][3]), any output NULL; synchronises */
 int ukfb_innovation(ukfb_engine* e, int meas_model, int candidates, const double* z, const double* Q, double* z_pred,
                     double* S, double* innov, double* maha, double* loglik, int32_t* best, uint32_t* status);
+
+
+/* ---- filter banks: IMM mixing, weights and mixture moments ---------------------------------------------------------------- */
+/* An engine of `capacity` filters read as T = capacity / M TRACKS of M = `hypotheses` HYPOTHESES, track-major: hypothesis j of
+ * track t is filter t * M + j (e.g. a quiet and a manoeuvring process noise set per filter, or PoseUKF's constant-velocity and
+ * acceleration branches through per-filter NaN acceleration rows).  2 <= M <= 8; capacity % M != 0 is UKFB_ERR_INVALID_ARG.
+ * All device arrays in engine precision; stream-ordered like every "_dev" call: no host synchronisation, no allocation at
+ * call time.  The same kernels serve every lanes_per_filter setting; fp32 engines compute in fp32, with wide_arithmetic in
+ * fp64 (stored fp32).  The engine's own status array, last measurement times, latched inputs and noise are never written.
+ *
+ * MIXTURE MOMENTS of a track under weights w_j >= 0, sum_j w_j = 1 ((+) / (-): the engine's, right multiplication on SO(3)):
+ *   1. ref = mu_j*, j* the hypothesis of the largest weight (ties: the lowest index);
+ *   2. d = sum_j w_j (mu_j (-) ref), ref <- ref (+) d, ukfom's stopping rule as for the sigma-point means
+ *      (do ... while (|d| > mean_tol && ++it < mean_max_iter)); mean = ref; the cap sets UKFB_ST_WARN_MEAN_NOCONV;
+ *   3. delta_j = mu_j (-) mean; J_j = the D x D identity with its SO(3) block replaced by
+ *      Jr^-1(phi) = I + [phi]x / 2 + c(theta) [phi]x^2, phi = the rotation part of delta_j, theta = |phi|,
+ *      c = 1/theta^2 - (1 + cos theta) / (2 theta sin theta): the first-order transport of a covariance from the tangent
+ *      space at mu_j to the one at the mean, (mu_j (+) eps) (-) mean = delta_j + J_j eps + O(eps^2);
+ *   4. cov = sum_j w_j (J_j Sigma_j J_j^T + delta_j delta_j^T);
+ *   5. a hypothesis of weight exactly 0 is skipped (selected out, not multiplied by 0): whatever its state holds, NaN
+ *      included, never reaches the result.  One-hot weights return that hypothesis bit for bit.
+ * Per-TRACK status, written to the caller's array ([T], may be NULL):
+ *   UNINITIALISED     any hypothesis of the track is uninitialised;
+ *   ERR_WEIGHTS       a weight is negative or non-finite, or |sum_j w_j - 1| > 16 M eps, eps the machine epsilon of the
+ *                     engine's storage precision (2^-52 / 2^-23); the w_out of ukfb_bank_weights_dev meets this bound by
+ *                     construction (w_out = e_j / sum e_j with e_j = exp(a_j - max a));
+ *   WARN_MEAN_NOCONV  the mean iteration hit its cap (mean_max_iter); the mean is the last iterate.
+ * A track with either of the first two writes NaN to its outputs (combine) or is left bit for bit untouched (mix). */
+
+/* logw_out[t][j] = logw_in[t][j] + loglik[t][j] - logsumexp_j(logw_in + loglik), w_out = exp(logw_out) (may be NULL).
+ * logw_in = NULL: uniform prior; loglik = NULL: normalise only.  A NaN loglik (what ukfb_innovation_dev writes for a filter it
+ * could not score) kills that hypothesis: weight 0, logw_out = -inf.  Every hypothesis of a track dead: ERR_WEIGHTS, and
+ * logw_out is logw_in normalised on its own (uniform if that is not a distribution either). */
+int ukfb_bank_weights_dev(ukfb_engine* e, int hypotheses, const void* logw_in_dev, const void* loglik_dev,
+                          void* logw_out_dev, void* w_out_dev, uint32_t* status_dev);
+/* One estimate per track: w_dev [capacity], mu_out_dev [T][S], cov_packed_out_dev [T][PK] (lower triangle as
+ * ukfb_device_views; may be NULL).  READ-ONLY on the engine. */
+int ukfb_bank_combine_dev(ukfb_engine* e, int hypotheses, const void* w_dev, void* mu_out_dev, void* cov_packed_out_dev,
+                          uint32_t* status_dev);
+/* IMM interaction: with the row-stochastic `transition` (HOST, [M][M], transition[j][i] = P(model i now | model j before);
+ * checked on the host: finite, non-negative, rows sum to 1 within 1e-12; passed to the kernel by value),
+ *   c_i = sum_j transition[j][i] w_j,  w_{j|i} = transition[j][i] w_j / c_i,
+ * hypothesis i of every track is REPLACED (mean and covariance) by the mixture moments of all M hypotheses -- as they were
+ * before the call -- under w_{.|i}, and w_pred_out_dev [capacity] receives c_i.  c_i = 0 exactly: hypothesis i keeps its
+ * state, w_pred = 0.  A failing track (above) keeps every bit and gets w_pred = w. */
+int ukfb_bank_mix_dev(ukfb_engine* e, int hypotheses, const void* w_dev, const double* transition, void* w_pred_out_dev,
+                      uint32_t* status_dev);
+/* host arrays of doubles: w [capacity], mu [T][S], cov [T][D][D] (may be NULL), status [T] (may be NULL); synchronise */
+int ukfb_bank_combine(ukfb_engine* e, int hypotheses, const double* w, double* mu, double* cov, uint32_t* status);
+int ukfb_bank_mix(ukfb_engine* e, int hypotheses, const double* w, const double* transition, double* w_pred, uint32_t* status);
 
 
 /* ---- device groups: one host process, several MI355X ------------------------------------------------------------------ */

@@ -199,6 +199,51 @@ inline Verdict check_select_args(int engine_model, bool per_filter_models, int m
     return {};
 }
 
+// ---- filter banks (ukfb_bank_weights_dev, ukfb_bank_combine_dev, ukfb_bank_mix_dev) ---------------------------------------
+// An engine of `capacity` filters read as capacity / M tracks of M hypotheses, track-major (hypothesis j of track t = filter
+// t * M + j).  One track per 16-lane row, four per wavefront, one wavefront per workgroup (ukf_bank.hpp).
+constexpr int BANK_MIN_HYPOTHESES = 2, BANK_MAX_HYPOTHESES = 8, BANK_TRACKS_PER_GROUP = 4;
+constexpr double BANK_TRANSITION_ROW_TOL = 1e-12;
+inline Verdict check_bank_args(int hypotheses, int64_t capacity) {
+    if (hypotheses < BANK_MIN_HYPOTHESES || hypotheses > BANK_MAX_HYPOTHESES)
+        return {UKFB_ERR_INVALID_ARG, "hypotheses per track must be 2 ... 8"};
+    if (capacity < 0 || capacity % hypotheses != 0)
+        return {UKFB_ERR_INVALID_ARG, "the engine's capacity is not a multiple of the hypotheses per track"};
+    return {};
+}
+// row-stochastic [M][M]: finite, non-negative, every row sums to 1 within BANK_TRANSITION_ROW_TOL
+inline Verdict check_bank_transition(const double* P, int hypotheses) {
+    if (!P) return {UKFB_ERR_INVALID_ARG, "transition must not be NULL"};
+    for (int j = 0; j < hypotheses; ++j) {
+        double sum = 0.0;
+        for (int i = 0; i < hypotheses; ++i) {
+            const double v = P[size_t(j) * hypotheses + i];
+            if (!std::isfinite(v) || v < 0.0) return {UKFB_ERR_INVALID_ARG, "transition entries must be finite and non-negative"};
+            sum += v;
+        }
+        if (!(std::fabs(sum - 1.0) <= BANK_TRANSITION_ROW_TOL))
+            return {UKFB_ERR_INVALID_ARG, "every row of transition must sum to 1 (within 1e-12)"};
+    }
+    return {};
+}
+// LDS of one track, in scalars of the compute type: the M records (mean, packed covariance), the M deltas to the mixture's
+// mean with their weights, and one output record.  Every scalar a kernel reads is one it wrote.
+UKFB_HD int bank_track_scalars(int S, int D, int hypotheses) {
+    const int PK = D * (D + 1) / 2;
+    return (hypotheses * (S + PK + D + 1) + S + PK + 1) / 2 * 2;
+}
+constexpr int BANK_GROUP_SCALARS = 64;   // per workgroup, in front of the tracks: the transition matrix
+struct BankGeometry {
+    int64_t tracks, grid;   // grid: workgroups of BANK_TRACKS_PER_GROUP tracks
+    int lds_bytes;          // dynamic LDS of a workgroup
+};
+// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
+inline BankGeometry bank_geometry(int S, int D, int hypotheses, int64_t capacity, size_t compute_size) {
+    const int64_t tracks = capacity / hypotheses;
+    return {tracks, (tracks + BANK_TRACKS_PER_GROUP - 1) / BANK_TRACKS_PER_GROUP,
+            int((size_t(BANK_GROUP_SCALARS) + size_t(BANK_TRACKS_PER_GROUP) * bank_track_scalars(S, D, hypotheses)) * compute_size)};
+}
+
 struct CycleLaunch {
     int first_cycle, cycles, slot;   // slot: the ring slot of first_cycle
     bool status_accumulate;          // the status word is the OR over ALL cycles of the call

@@ -32,6 +32,7 @@ ST_WARN_MEAN_NOCONV = 1 << 6
 ST_UNINITIALISED = 1 << 7
 ST_INACTIVE = 1 << 8
 ST_REJECTED_GATE = 1 << 9
+ST_ERR_WEIGHTS = 1 << 10   # filter banks: the weights of a track are not a distribution
 
 # every symbol include/ukf_batch.h declares (tests check the library exports all of them)
 EXPORTS = [
@@ -51,6 +52,8 @@ EXPORTS = [
     "ukfb_cycle_timestamps", "ukfb_cycle_timestamps_dev", "ukfb_process_events", "ukfb_process_events_dev",
     # innovation statistics / measurement association (read-only)
     "ukfb_innovation_dev", "ukfb_select_candidates_dev", "ukfb_innovation",
+    # filter banks: IMM mixing, weights, mixture moments
+    "ukfb_bank_weights_dev", "ukfb_bank_combine_dev", "ukfb_bank_mix_dev", "ukfb_bank_combine", "ukfb_bank_mix",
     # device groups (one process, several GPUs)
     "ukfb_group_shard_range", "ukfb_group_create", "ukfb_group_destroy", "ukfb_group_size", "ukfb_group_shard",
     "ukfb_group_set_config", "ukfb_group_initialize", "ukfb_group_get_state", "ukfb_group_get_status",
@@ -379,6 +382,52 @@ class BatchUKF:
                                        o["best"].ctypes.data_as(C.POINTER(C.c_int32)),
                                        o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_innovation")
         return o
+
+    # ---- filter banks: capacity / M tracks of M hypotheses, track-major (hypothesis j of track t = filter t * M + j)
+    def bank_weights_dev(self, hypotheses: int, logw_in, loglik, logw_out, w_out=None, status=None):
+        """logw_out = logw_in + loglik - logsumexp over a track's hypotheses, w_out = exp(logw_out).  Torch tensors (or device
+        addresses) of [capacity] in engine precision; logw_in None = uniform, loglik None = normalise only; status uint32 [T]."""
+        _chk(self._lib.ukfb_bank_weights_dev(self._h, C.c_int(hypotheses), _devptr(logw_in), _devptr(loglik), _devptr(logw_out),
+                                             _devptr(w_out), _devptr(status)), "ukfb_bank_weights_dev")
+
+    def bank_combine_dev(self, hypotheses: int, w, mu_out, cov_packed_out=None, status=None):
+        """Mixture moments of every track: w [capacity], mu_out [T, S], cov_packed_out [T, PK] (lower triangle).  Read-only."""
+        _chk(self._lib.ukfb_bank_combine_dev(self._h, C.c_int(hypotheses), _devptr(w), _devptr(mu_out), _devptr(cov_packed_out),
+                                             _devptr(status)), "ukfb_bank_combine_dev")
+
+    def bank_mix_dev(self, hypotheses: int, w, transition, w_pred=None, status=None):
+        """IMM interaction: every hypothesis replaced by the mixture of its track under the mixing weights; transition is a HOST
+        [M, M] row-stochastic matrix, w a device tensor [capacity].  Returns (w_pred, status): the caller's buffers ([capacity]
+        in engine precision, int32 [T]) where given -- the call then allocates nothing -- else torch tensors created here."""
+        P = _f64(transition, (hypotheses, hypotheses))
+        if w_pred is None or status is None:
+            import torch
+            if w_pred is None:
+                w_pred = torch.empty_like(w)
+            if status is None:
+                status = torch.empty(self.capacity // max(int(hypotheses), 1), dtype=torch.int32, device=w.device)
+        _chk(self._lib.ukfb_bank_mix_dev(self._h, C.c_int(hypotheses), _devptr(w), _pd(P), _devptr(w_pred), _devptr(status)),
+             "ukfb_bank_mix_dev")
+        return w_pred, status
+
+    def bank_combine(self, hypotheses: int, w):
+        """Host arrays: w [capacity] -> (mu [T, S], cov [T, D, D], status [T])"""
+        w = _f64(w, (self.capacity,))
+        T = self.capacity // max(int(hypotheses), 1)
+        mu, cov, st = np.empty((T, self.S)), np.empty((T, self.D, self.D)), np.empty(T, dtype=np.uint32)
+        _chk(self._lib.ukfb_bank_combine(self._h, C.c_int(hypotheses), _pd(w), _pd(mu), _pd(cov),
+                                         st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_bank_combine")
+        return mu, cov, st
+
+    def bank_mix(self, hypotheses: int, w, transition):
+        """Host arrays: w [capacity], transition [M, M] -> (w_pred [capacity], status [T]); replaces mean and covariance"""
+        w = _f64(w, (self.capacity,))
+        P = _f64(transition, (hypotheses, hypotheses))
+        T = self.capacity // max(int(hypotheses), 1)
+        wp, st = np.empty(self.capacity), np.empty(T, dtype=np.uint32)
+        _chk(self._lib.ukfb_bank_mix(self._h, C.c_int(hypotheses), _pd(w), _pd(P), _pd(wp),
+                                     st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_bank_mix")
+        return wp, st
 
     # ---- fused cycle
     def cycle(self, dt: float, meas_model: int, z, Q):

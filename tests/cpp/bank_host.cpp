@@ -1,0 +1,73 @@
+// bank_host.cpp -- the filter-bank host decisions of ukf_host.hpp on the CPU (g++ under ASan / UBSan, compiled by
+// tests/test_bank_host.py): hypotheses per track, divisibility, the transition matrix, launch sizing.
+#include <cmath>
+#include <cstdio>
+#include <limits>
+#include <vector>
+
+#include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
+
+static int failures = 0;
+#define EXPECT(cond)                                                        \
+    do {                                                                    \
+        if (!(cond)) {                                                      \
+            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
+            ++failures;                                                     \
+        }                                                                   \
+    } while (0)
+
+int main() {
+    using namespace ukfb;
+    // hypotheses per track: 2 ... 8
+    for (int m : {-1, 0, 1, 2, 3, 8, 9, 16}) {
+        const Verdict v = check_bank_args(m, int64_t(m > 0 ? m : 1) * 6);
+        EXPECT((v.rc == UKFB_OK) == (m >= 2 && m <= 8));
+        EXPECT(v.rc == UKFB_OK || (v.rc == UKFB_ERR_INVALID_ARG && v.msg != nullptr));
+    }
+    // ragged capacity
+    EXPECT(check_bank_args(2, 7).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_bank_args(3, 1048576).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_bank_args(8, 1048576).rc == UKFB_OK);
+    EXPECT(check_bank_args(4, 0).rc == UKFB_OK);
+    // transition: row-stochastic
+    for (int m : {2, 3, 8}) {
+        std::vector<double> P(size_t(m) * m, 1.0 / m);
+        EXPECT(check_bank_transition(P.data(), m).rc == UKFB_OK);
+        std::vector<double> I(size_t(m) * m, 0.0);
+        for (int j = 0; j < m; ++j) I[size_t(j) * m + j] = 1.0;
+        EXPECT(check_bank_transition(I.data(), m).rc == UKFB_OK);
+        for (int k = 0; k < m * m; k += m + 1) {
+            std::vector<double> B = P;
+            B[k] = -B[k];
+            EXPECT(check_bank_transition(B.data(), m).rc == UKFB_ERR_INVALID_ARG);
+            B = P;
+            B[k] = std::numeric_limits<double>::quiet_NaN();
+            EXPECT(check_bank_transition(B.data(), m).rc == UKFB_ERR_INVALID_ARG);
+            B[k] = std::numeric_limits<double>::infinity();
+            EXPECT(check_bank_transition(B.data(), m).rc == UKFB_ERR_INVALID_ARG);
+            B = P;
+            B[k] += 1e-9;   // the row no longer sums to 1
+            EXPECT(check_bank_transition(B.data(), m).rc == UKFB_ERR_INVALID_ARG);
+            B = P;
+            B[k] += 1e-14;  // inside the tolerance
+            EXPECT(check_bank_transition(B.data(), m).rc == UKFB_OK);
+        }
+        // columns need not sum to 1
+        std::vector<double> C(size_t(m) * m, 0.0);
+        for (int j = 0; j < m; ++j) C[size_t(j) * m] = 1.0;
+        EXPECT(check_bank_transition(C.data(), m).rc == UKFB_OK);
+    }
+    EXPECT(check_bank_transition(nullptr, 2).rc == UKFB_ERR_INVALID_ARG);
+    // launch sizing: every track in a workgroup of four, the LDS of the largest bank inside the 64 KiB a workgroup may take
+    for (int m = 2; m <= 8; ++m)
+        for (int64_t tracks : {int64_t(0), int64_t(1), int64_t(4), int64_t(5), int64_t(262144)}) {
+            const BankGeometry g = bank_geometry(14, 13, m, tracks * m, 8);
+            EXPECT(g.tracks == tracks && g.grid == (tracks + 3) / 4);
+            EXPECT(g.lds_bytes == int((BANK_GROUP_SCALARS + 4 * bank_track_scalars(14, 13, m)) * 8));
+            EXPECT(g.lds_bytes <= 65536 && g.lds_bytes % 16 == 0);
+            EXPECT(bank_track_scalars(14, 13, m) >= m * (14 + 91 + 13 + 1) + 14 + 91);
+            EXPECT(bank_geometry(13, 12, m, tracks * m, 4).lds_bytes * 2 <= g.lds_bytes);
+        }
+    std::printf("OK: %d failure(s)\n", failures);
+    return failures ? 1 : 0;
+}
