@@ -138,6 +138,29 @@ public:
     {
         check(ukfb_bank_weights_dev(engine, hypotheses, logw_in_dev, loglik_dev, logw_out_dev, w_out_dev, status_dev));
     }
+    /** Fixed-interval smoothing (ukf_batch.h, "fixed-interval smoothing").  historyPush: stream-ordered copy of the current
+     *  mean and packed covariance into slot `slot` of the caller's device rings [slots][N][S] / [slots][N][PK]. */
+    void historyPush(int slots, int slot, void* mu_hist_dev, void* cov_hist_dev)
+    {
+        check(ukfb_history_push_dev(engine, slots, slot, mu_hist_dev, cov_hist_dev));
+    }
+    /** the RTS backward pass over `steps` slots from first_slot on; dt: host, steps - 1 entries; outputs: rings like the history
+     *  (they may be the history itself; cov_out_dev may be NULL); in_a_dev / in_b_dev: input rings or NULL (the latched inputs) */
+    void smoothDev(int steps, const double* dt, int slots, int first_slot, const void* mu_hist_dev, const void* cov_hist_dev,
+                   void* mu_out_dev, void* cov_out_dev = NULL, uint32_t* status_dev = NULL, const void* in_a_dev = NULL,
+                   const void* in_b_dev = NULL)
+    {
+        check(ukfb_smooth_dev(engine, steps, dt, slots, first_slot, mu_hist_dev, cov_hist_dev, in_a_dev, in_b_dev, mu_out_dev,
+                              cov_out_dev, status_dev));
+    }
+    /** host arrays in window order, smoothed in place: mu [steps][N][S], cov [steps][N][D][D]; returns the per-filter status */
+    std::vector<uint32_t> smooth(int steps, const double* dt, double* mu, double* cov, const double* in_a = NULL,
+                                 const double* in_b = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_smooth(engine, steps, dt, mu, cov, in_a, in_b, st.data()));
+        return st;
+    }
     std::vector<uint32_t> status()
     {
         std::vector<uint32_t> st(static_cast<size_t>(cap), 0u);

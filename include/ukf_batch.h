@@ -425,6 +425,64 @@ int ukfb_bank_mix_dev(ukfb_engine* e, int hypotheses, const void* w_dev, const d
 int ukfb_bank_combine(ukfb_engine* e, int hypotheses, const double* w, double* mu, double* cov, uint32_t* status);
 int ukfb_bank_mix(ukfb_engine* e, int hypotheses, const double* w, const double* transition, double* w_pred, uint32_t* status);
 
+/* ---- fixed-interval smoothing: a manifold Rauch-Tung-Striebel backward pass -------------------------------------------- */
+/* The estimate of step k given the WHOLE window (a track's past after an association is confirmed, an offline trajectory,
+ * fixed-lag output a few cycles behind real time), without a round trip through the host.
+ * A HISTORY is a ring of `slots` copies of the engine's state in the engine's own device format: mu_hist [slots][capacity][S],
+ * cov_hist [slots][capacity][PK] (packed lower triangle, as ukfb_device_views), engine precision.  A WINDOW is `steps`
+ * consecutive slots, oldest first: step c (0 ... steps - 1) lives in slot (first_slot + c) % slots -- the convention of the
+ * sample rings of ukfb_cycle_multi_dev.  Step c holds the FILTERED state at time c (after that time's update, before the
+ * prediction to c + 1); dt[c] (HOST, steps - 1 entries, passed to the kernels by value) is the time step of the prediction
+ * c -> c + 1.  in_a_dev / in_b_dev: optional input rings [slots][capacity][3] indexed like the history (slot of step c = the
+ * inputs of the prediction c -> c + 1), with the meaning they have in ukfb_cycle_multi_dev, the per-filter NaN acceleration row
+ * that selects PoseUKF's constant-velocity branch included; NULL: the engine's latched inputs serve every step.  Process noise
+ * (batch-uniform or per filter), acc.cov, the taus, the earth rotation, mean_tol, mean_max_iter and min / max_time_delta are
+ * the engine's at the time of the call.
+ *
+ * Per filter ((+) / (-): the engine's, right multiplication on SO(3)): (mu^s, Sigma^s) at step steps - 1 is the filtered state
+ * of that step, bit for bit; then for c = steps - 2 ... 0, with (mu, Sigma) the history's step c:
+ *   1. the prediction from (mu, Sigma) by dt[c] with step c's inputs is REDONE exactly as ukfb_predict makes it (noise shaping
+ *      and the acceleration-branch rule of PoseUKF.cpp:188-193 included): L = chol(Sigma), sigma points X_i, Y_i = g(X_i), the
+ *      iterated mean mu^-, delta_i = Y_i (-) mu^-, Sigma^- = 1/2 sum_i delta_i delta_i^T + R;
+ *   2. C = 1/2 sum_i (X_i (-) mu) delta_i^T  (D x D, not symmetric; X_j+- (-) mu = +-L col j, which the kernel uses);
+ *   3. G = C (Sigma^-)^-1 through a Cholesky factorisation of Sigma^- and two triangular solves per row;
+ *   4. e = mu^s_(c+1) (-) mu^-; Sigma^t = J Sigma^s_(c+1) J^T, J the identity but for the SO(3) block Jr^-1(phi), phi the
+ *      rotation part of e (the transport of the filter banks above);
+ *   5. Sigma~ = Sigma + G (Sigma^t - Sigma^-) G^T (the lower triangle is computed);
+ *   6. (mu^s_c, Sigma^s_c) = applyDelta(mu, Sigma~, G e), the update's own commit: Sigma~ is factorised and re-sampled around
+ *      mu (+) G e.
+ * Status of the call, written to the caller's array ([capacity], may be NULL) as the OR over the steps:
+ *   SKIPPED_SMALL_DT / ERR_NEG_DT / ERR_DT_TOO_LARGE  dt[c] is gated (<= min_time_delta, < 0, > max_time_delta): the forward
+ *                     pass made no prediction there, step c receives the bits of step c + 1's smoothed state;
+ *   ERR_CHOLESKY      Sigma, Sigma^- or Sigma~ of a step is not positive definite: that step's smoothed state is its filtered
+ *                     state, bit for bit, and the chain continues from it;
+ *   WARN_MEAN_NOCONV  the mean iteration hit its cap (mean_max_iter); the last iterate is used;
+ *   UNINITIALISED     nothing is written for that filter.
+ * A filter that fails, is gated or is uninitialised never changes the bits of another filter.  The calls are READ-ONLY on the
+ * engine: mean, covariance, last measurement times, latches, noise and the engine's own status array keep every bit.
+ * Device groups: per shard through ukfb_group_shard. */
+
+/* Stream-ordered copy of the engine's current mean and packed covariance into slot `slot` of the caller's rings.  Needed, not
+ * a convenience: an engine that owns its stream may run a launch as two halves on two internal streams (split_streams), so a
+ * caller cannot order a copy of ukfb_device_views behind a launch without ukfb_sync; this call joins the streams as every
+ * other call does.  No host synchronisation; the first push of an engine creates the one-record workspace that
+ * ukfb_smooth_dev needs for windows without a covariance output, no later push allocates. */
+int ukfb_history_push_dev(ukfb_engine* e, int slots, int slot, void* mu_hist_dev, void* cov_hist_dev);
+/* 2 <= steps <= slots.  mu_out_dev / cov_out_dev: rings of the history's shape and indexing; they may be the history itself
+ * (in place), and cov_out_dev may be NULL.  Between the steps of a launch the smoothed state stays in LDS; a launch covers at
+ * most 32 backward steps, longer windows are chained by the host and the next launch starts from the smoothed state the
+ * previous one stored (with cov_out_dev = NULL the chain's covariance crosses that boundary through the engine's one-record
+ * workspace, which ukfb_history_push_dev created; only an engine that never pushed creates it here, once).  Stream-ordered, no
+ * host synchronisation, no allocation at call time.  The same
+ * kernel serves every lanes_per_filter setting; fp32 engines compute in fp32, with wide_arithmetic in fp64 (stored fp32). */
+int ukfb_smooth_dev(ukfb_engine* e, int steps, const double* dt, int slots, int first_slot, const void* mu_hist_dev,
+                    const void* cov_hist_dev, const void* in_a_dev, const void* in_b_dev, void* mu_out_dev, void* cov_out_dev,
+                    uint32_t* status_dev);
+/* host arrays of doubles in window order, smoothed IN PLACE: mu [steps][capacity][S], cov [steps][capacity][D][D];
+ * in_a / in_b [steps][capacity][3] or NULL (the latched inputs); status [capacity] (may be NULL); synchronises */
+int ukfb_smooth(ukfb_engine* e, int steps, const double* dt, double* mu, double* cov, const double* in_a, const double* in_b,
+                uint32_t* status);
+
 
 /* ---- device groups: one host process, several MI355X ------------------------------------------------------------------ */
 /* north_star's multi-GPU shape for a C++ host.  The filters of a batch are independent -- every filter of the reference owns

@@ -81,6 +81,8 @@ struct ukfb_engine {
     // ukfb_cycle_multi: device rings of the host samples of one call (grow-only)
     void* multi_dev = nullptr;
     size_t multi_bytes = 0;
+    // ukfb_smooth_dev without a covariance output over more than one launch: the chain's covariance between launches [cap][PK] (grow-only)
+    void* smooth_chain = nullptr;
     // model-class buckets of ukfb_cycle_dev with per-filter model ids: filter list ordered by class, padded to whole
     // wavefronts [cap + 16], and the per-block class counts [3][blocks]
     int32_t* bucket_idx = nullptr;

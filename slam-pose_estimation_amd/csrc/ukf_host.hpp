@@ -244,6 +244,55 @@ inline BankGeometry bank_geometry(int S, int D, int hypotheses, int64_t capacity
             int((size_t(BANK_GROUP_SCALARS) + size_t(BANK_TRACKS_PER_GROUP) * bank_track_scalars(S, D, hypotheses)) * compute_size)};
 }
 
+// ---- fixed-interval smoothing (ukfb_history_push_dev, ukfb_smooth_dev) ---------------------------------------------------
+// A window of `steps` consecutive slots of a ring of `slots`, oldest first: step c lives in slot (first_slot + c) % slots.  The
+// backward pass has steps - 1 steps; a launch covers at most SMOOTH_MAX_BACK of them (their dt travel in the kernel arguments)
+// and the next launch starts from the smoothed record the previous one stored.
+constexpr int SMOOTH_MAX_BACK = 32, SMOOTH_LS = 14, SMOOTH_FILTERS_PER_GROUP = 4;
+inline Verdict check_history_args(int slots, int slot, bool has_mu_hist, bool has_cov_hist) {
+    if (slots < 1 || slot < 0 || slot >= slots) return {UKFB_ERR_INVALID_ARG, "slots >= 1, 0 <= slot < slots"};
+    if (!has_mu_hist || !has_cov_hist) return {UKFB_ERR_INVALID_ARG, "mu_hist and cov_hist must not be NULL"};
+    return {};
+}
+inline Verdict check_smooth_args(int steps, int slots, int first_slot, bool has_dt, bool has_mu_hist, bool has_cov_hist, bool has_mu_out) {
+    if (slots < 1 || steps < 2 || steps > slots) return {UKFB_ERR_INVALID_ARG, "2 <= steps <= slots"};
+    if (first_slot < 0 || first_slot >= slots) return {UKFB_ERR_INVALID_ARG, "0 <= first_slot < slots"};
+    if (!has_dt) return {UKFB_ERR_INVALID_ARG, "dt must not be NULL"};
+    if (!has_mu_hist || !has_cov_hist || !has_mu_out) return {UKFB_ERR_INVALID_ARG, "mu_hist, cov_hist and mu_out must not be NULL"};
+    return {};
+}
+struct SmoothLaunch {
+    int top_step, top_slot;   // the step whose smoothed record the launch starts from, and its slot
+    int back;                 // backward steps: the launch writes steps top_step - 1 ... top_step - back
+    int dt_first;             // backward step k of the launch redoes the prediction of dt[dt_first - k]
+    bool first;               // the call's first launch: starts from the filtered record of the last step
+};
+struct SmoothPlan {
+    int steps, slots, first_slot;
+    SmoothPlan(int steps_, int slots_, int first_slot_) : steps(steps_), slots(slots_), first_slot(first_slot_) {}
+    int launches() const { return (steps - 1 + SMOOTH_MAX_BACK - 1) / SMOOTH_MAX_BACK; }
+    SmoothLaunch operator[](int k) const {
+        const int top = steps - 1 - k * SMOOTH_MAX_BACK;
+        return {top, int((int64_t(first_slot) + top) % slots), std::min(SMOOTH_MAX_BACK, top), top - 1, k == 0};
+    }
+};
+// LDS of one filter, in scalars of the compute type (ukf_smooth.hpp, SmoothLayout): the factor region with its reciprocal
+// pivots, the delta table of 2 D + 1 rows (G and M alias it), the chain record and the filtered record (mean padded to 16,
+// packed covariance padded to even), the rotation matrix (9 + 1 pad), the sink of
+// lane-predicated stores (16), and what is parked across the solves (the rows of Sigma^-, mu^- padded to 16).  Every scalar the kernel reads is one it wrote: the pads are never read.
+constexpr int smooth_filter_scalars(int S, int D) {
+    return S > 16 ? -1 : 2 * D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 2 * (16 + (D * (D + 1) / 2 + 1) / 2 * 2) + 10 + 16 + 16;
+}
+struct SmoothGeometry {
+    int64_t grid;    // workgroups of four filters
+    int lds_bytes;   // dynamic LDS of a workgroup
+};
+// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
+inline SmoothGeometry smooth_geometry(int S, int D, int64_t capacity, size_t compute_size) {
+    return {(capacity + SMOOTH_FILTERS_PER_GROUP - 1) / SMOOTH_FILTERS_PER_GROUP,
+            int(size_t(SMOOTH_FILTERS_PER_GROUP) * smooth_filter_scalars(S, D) * compute_size)};
+}
+
 struct CycleLaunch {
     int first_cycle, cycles, slot;   // slot: the ring slot of first_cycle
     bool status_accumulate;          // the status word is the OR over ALL cycles of the call

@@ -54,6 +54,8 @@ EXPORTS = [
     "ukfb_innovation_dev", "ukfb_select_candidates_dev", "ukfb_innovation",
     # filter banks: IMM mixing, weights, mixture moments
     "ukfb_bank_weights_dev", "ukfb_bank_combine_dev", "ukfb_bank_mix_dev", "ukfb_bank_combine", "ukfb_bank_mix",
+    # fixed-interval smoothing: history rings and the RTS backward pass (read-only)
+    "ukfb_history_push_dev", "ukfb_smooth_dev", "ukfb_smooth",
     # device groups (one process, several GPUs)
     "ukfb_group_shard_range", "ukfb_group_create", "ukfb_group_destroy", "ukfb_group_size", "ukfb_group_shard",
     "ukfb_group_set_config", "ukfb_group_initialize", "ukfb_group_get_state", "ukfb_group_get_status",
@@ -428,6 +430,41 @@ class BatchUKF:
         _chk(self._lib.ukfb_bank_mix(self._h, C.c_int(hypotheses), _pd(w), _pd(P), _pd(wp),
                                      st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_bank_mix")
         return wp, st
+
+    # ---- fixed-interval smoothing: history rings [slots, capacity, S] / [slots, capacity, PK] in engine precision
+    def history_push_dev(self, slots: int, slot: int, mu_hist, cov_hist):
+        """Stream-ordered copy of the engine's current mean and packed covariance into slot `slot` of the caller's rings (torch
+        tensors or device addresses); ordered behind every launch enqueued so far, split launches included.  No allocation."""
+        _chk(self._lib.ukfb_history_push_dev(self._h, C.c_int(slots), C.c_int(slot), _devptr(mu_hist), _devptr(cov_hist)),
+             "ukfb_history_push_dev")
+
+    def smooth_dev(self, dt, slots: int, first_slot: int, mu_hist, cov_hist, mu_out=None, cov_out=None, status=None,
+                   in_a_dev=None, in_b_dev=None):
+        """RTS backward pass over the window of len(dt) + 1 steps that starts at slot first_slot (step c in slot (first_slot + c)
+        % slots); dt[c] (host) is the time step of the prediction c -> c + 1.  mu_out / cov_out: rings like the history, None =
+        in place (pass cov_out=False for no covariance output); status uint32 / int32 [capacity] or None; in_a_dev / in_b_dev:
+        input rings [slots, capacity, 3] or None (the latched inputs).  Caller-supplied buffers: nothing is allocated.
+        Read-only on the engine.  Returns (mu_out, cov_out)."""
+        d = np.ascontiguousarray(dt, dtype=np.float64).reshape(-1)
+        mu_out = mu_hist if mu_out is None else mu_out
+        cov_out = cov_hist if cov_out is None else (None if cov_out is False else cov_out)
+        _chk(self._lib.ukfb_smooth_dev(self._h, C.c_int(d.size + 1), _pd(d), C.c_int(slots), C.c_int(first_slot), _devptr(mu_hist),
+                                       _devptr(cov_hist), _devptr(in_a_dev), _devptr(in_b_dev), _devptr(mu_out), _devptr(cov_out),
+                                       _devptr(status)), "ukfb_smooth_dev")
+        return mu_out, cov_out
+
+    def smooth(self, dt, mu, cov, in_a=None, in_b=None):
+        """Host arrays in window order: mu [steps, capacity, S], cov [steps, capacity, D, D], dt [steps - 1], in_a / in_b
+        [steps, capacity, 3] or None -> (mu_s, cov_s, status [capacity]); synchronises"""
+        d = np.ascontiguousarray(dt, dtype=np.float64).reshape(-1)
+        steps, n = d.size + 1, self.capacity
+        mu = _f64(mu, (steps, n, self.S)).copy(); cov = _f64(cov, (steps, n, self.D, self.D)).copy()
+        a = _f64(in_a, (steps, n, 3)) if in_a is not None else None
+        b = _f64(in_b, (steps, n, 3)) if in_b is not None else None
+        st = np.zeros(n, dtype=np.uint32)
+        _chk(self._lib.ukfb_smooth(self._h, C.c_int(steps), _pd(d), _pd(mu), _pd(cov), _pd(a), _pd(b),
+                                   st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_smooth")
+        return mu, cov, st
 
     # ---- fused cycle
     def cycle(self, dt: float, meas_model: int, z, Q):
