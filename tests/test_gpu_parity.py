@@ -1,7 +1,8 @@
 """GPU parity: the HIP engine (through the C-ABI, via ctypes) against the CPU oracle on identical
 seeded inputs.  Tolerances are BASELINE.json's north_star: 1e-9 for fp64, 1e-4 for fp32 (absolute,
 max over every state and covariance entry).  PARITY UNPINNED w.r.t. real MTK: the oracle is a
-restatement (see oracle/ukf_oracle.hpp)."""
+restatement (see oracle/ukf_oracle.hpp).  One absolute bound says little about the small blocks of the state
+(gyro bias: variance 1e-6): tests/test_gpu_scaled_parity.py holds every block to its own sigma."""
 import numpy as np
 import pytest
 
