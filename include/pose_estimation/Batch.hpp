@@ -153,6 +153,29 @@ public:
         check(ukfb_smooth_dev(engine, steps, dt, slots, first_slot, mu_hist_dev, cov_hist_dev, in_a_dev, in_b_dev, mu_out_dev,
                               cov_out_dev, status_dev));
     }
+    /** Joint state-block measurements (ukf_batch.h, "joint state-block measurements"): ukf->update(z, h, Q) with z the compound
+     *  of the blocks `block_mask` selects (UKFB_BLOCK_*) and h their selection.  Device form: z_dev [N][S] in the state's own
+     *  layout, Qz_packed_dev [N][PK] (a record of deviceViews, a history slot or bankCombineDev as it lies); block_mask_dev
+     *  int32 [N] or NULL; the update runs on state_inflation * Sigma and meas_inflation * Qz (1 / w, 1 / (1 - w): covariance
+     *  intersection); commit = false is read-only (only `out` is written).  Stream-ordered. */
+    void integrateStateMeasurementsDev(uint32_t block_mask, const void* z_dev, const void* Qz_packed_dev,
+                                       const int32_t* block_mask_dev = NULL, double state_inflation = 1.0,
+                                       double meas_inflation = 1.0, bool commit = true, const ukfb_state_meas_out* out = NULL)
+    {
+        check(ukfb_update_state_dev(engine, block_mask, block_mask_dev, z_dev, Qz_packed_dev, state_inflation, meas_inflation,
+                                    commit ? 1 : 0, out));
+    }
+    /** host arrays: z [N][S], Qz [N][D][D], block_mask_per_filter [N] or NULL; maha / loglik [N] or NULL; returns the status */
+    std::vector<uint32_t> integrateStateMeasurements(uint32_t block_mask, const double* z, const double* Qz,
+                                                     const int32_t* block_mask_per_filter = NULL, double state_inflation = 1.0,
+                                                     double meas_inflation = 1.0, bool commit = true, double* maha = NULL,
+                                                     double* loglik = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_update_state(engine, block_mask, block_mask_per_filter, z, Qz, state_inflation, meas_inflation, commit ? 1 : 0,
+                                maha, loglik, st.data()));
+        return st;
+    }
     /** host arrays in window order, smoothed in place: mu [steps][N][S], cov [steps][N][D][D]; returns the per-filter status */
     std::vector<uint32_t> smooth(int steps, const double* dt, double* mu, double* cov, const double* in_a = NULL,
                                  const double* in_b = NULL)
@@ -191,6 +214,9 @@ public:
     }
     /** integrateMeasurement(AccelerationMeasurement) per filter; NaN row = none (PoseUKF.cpp:109,175-178) */
     void setAccelerations(int64_t first, int64_t count, const double* acc_mu, const double* acc_cov3x3) { check(ukfb_pose_set_acceleration(engine, first, count, acc_mu, acc_cov3x3)); }
+    /** base::samples::RigidBodyState records [N][49] (the layout of ukfb_pose_export_body_states) integrated as measurements of
+     *  the blocks `block_mask` selects: the fields as they are, the four 3 x 3 covariances on the diagonal; active [N] or NULL */
+    void integrateBodyStates(uint32_t block_mask, const double* records, const uint8_t* active = NULL) { check(ukfb_pose_update_body_states(engine, block_mask, records, active)); }
 };
 
 class BatchOrientationUKF : public BatchUKF

@@ -483,6 +483,83 @@ int ukfb_smooth_dev(ukfb_engine* e, int steps, const double* dt, int slots, int 
 int ukfb_smooth(ukfb_engine* e, int steps, const double* dt, double* mu, double* cov, const double* in_a, const double* in_b,
                 uint32_t* status);
 
+/* ---- joint state-block measurements: update and fuse with full covariance ------------------------------------------------ */
+/* ukf->update(z, h, Q) with z a SUB-MANIFOLD of the state and h the selection of blocks: a 6-DOF pose with its joint
+ * covariance as ONE measurement, another estimate of the same state (a second engine's ukfb_device_views, a history slot, a
+ * record of ukfb_bank_combine_dev) fused as information, with covariance intersection where the two are correlated to an
+ * unknown degree, and the D-dimensional Mahalanobis distance / likelihood between a filter and a full estimate.
+ * BLOCKS in host-layout order, one bit each:
+ *   Pose              bit 0 position, bit 1 orientation, bit 2 velocity, bit 3 angular velocity;
+ *   OrientationState  bit 0 orientation, bit 1 velocity, bit 2 bias_gyro, bit 3 bias_acc, bit 4 gravity.
+ * A mask selects m = sum of the block dimensions tangent dimensions; the measurement manifold is the compound of the selected
+ * blocks in state order.  z_dev [capacity][S] is a measurement in the STATE'S OWN LAYOUT: entries of unselected blocks are never
+ * read and may be NaN; a selected quaternion is taken as given, as the state's is.  Qz_packed_dev [capacity][PK] is the packed
+ * lower triangle of a D x D matrix in the state's tangent order (the format of ukfb_device_views); only rows and columns of
+ * selected dimensions are read.  So a record of ukfb_device_views, a history slot or ukfb_bank_combine_dev is a valid
+ * measurement as it lies.  block_mask_dev: int32 [capacity], or NULL so that block_mask_uniform serves every filter.  A
+ * per-filter mask <= 0 or with bits beyond the model's blocks: no measurement for that filter (untouched, INACTIVE); such a
+ * uniform mask is UKFB_ERR_INVALID_ARG.
+ * state_inflation = a >= 1 and meas_inflation = b >= 1 (HOST, by value; below 1 or non-finite: UKFB_ERR_INVALID_ARG): the update
+ * runs on a Sigma and b Qz.  1, 1 is the Kalman update (the multiplication by 1.0 is exact); a = 1 / w, b = 1 / (1 - w) is
+ * covariance intersection with weight w.
+ * Per filter with a valid mask ((+) / (-): the engine's; sel = the selected tangent dimensions):
+ *   1. L = chol(a Sigma), sigma points X_i, Z_i = the selected blocks of X_i;
+ *   2. z-bar = the iterated mean of the Z_i on the measurement manifold (start Z_0, mean_tol / mean_max_iter);
+ *   3. S = 1/2 sum dz_i dz_i^T + b Qz[sel][sel], C = 1/2 sum (X_i (-) mu) dz_i^T (D x m; X_j+- (-) mu = +-L col j, which the
+ *      kernel uses);
+ *   4. S = Ls Ls^T; Y = C Ls^-T (one triangular solve per row), so that K = Y Ls^-1 and K S K^T = Y Y^T;
+ *   5. nu = z (-) z-bar, y = Ls^-1 nu, d^2 = nu^T S^-1 nu = |y|^2, ln det S = sum ln of the pivots;
+ *   6. the gate of ukfb_update_dev (gate_chi2 < 0: accept; else d^2 <= gate_chi2): REJECTED_GATE keeps the state, maha and
+ *      loglik are still written;
+ *   7. Sigma~ = a Sigma - Y Y^T;
+ *   8. (mu, Sigma) = applyDelta(mu, Sigma~, Y y), the update's own commit.
+ * commit = 1: an update like ukfb_update_dev, mean, covariance and the engine's own status array are written.  commit = 0:
+ * READ-ONLY like ukfb_innovation_dev -- mean, covariance, times, latches, noise and the engine's status keep every bit, only
+ * `out` is written (the same numbers: every step above still runs).
+ * Status of THIS call (out->status, and with commit = 1 the engine's status array):
+ *   UNINITIALISED       the filter is uninitialised;
+ *   INACTIVE            no valid mask for this filter;
+ *   ERR_NONFINITE_MEAS  a SELECTED entry of z or Qz is non-finite;
+ *   ERR_CHOLESKY        a Sigma, S or (an accepted update's) Sigma~ is not positive definite;
+ *   WARN_MEAN_NOCONV    the mean iteration hit its cap;
+ *   REJECTED_GATE       the gate rejected the update.
+ * A filter with one of the first four keeps its state bit for bit and writes NaN to maha / loglik; it never changes a bit of
+ * another filter.  Stream-ordered, no host synchronisation, no allocation at call time.  The same kernel serves every
+ * lanes_per_filter setting; fp32 engines compute in fp32, with wide_arithmetic in fp64 (stored fp32).  Device groups: per shard
+ * through ukfb_group_shard. */
+#define UKFB_BLOCK_POSE_POSITION 1u
+#define UKFB_BLOCK_POSE_ORIENTATION 2u
+#define UKFB_BLOCK_POSE_VELOCITY 4u
+#define UKFB_BLOCK_POSE_ANGULAR_VELOCITY 8u
+#define UKFB_BLOCK_POSE_ALL 15u
+#define UKFB_BLOCK_ORIENT_ORIENTATION 1u
+#define UKFB_BLOCK_ORIENT_VELOCITY 2u
+#define UKFB_BLOCK_ORIENT_BIAS_GYRO 4u
+#define UKFB_BLOCK_ORIENT_BIAS_ACC 8u
+#define UKFB_BLOCK_ORIENT_GRAVITY 16u
+#define UKFB_BLOCK_ORIENT_ALL 31u
+typedef struct ukfb_state_meas_out {   /* device pointers, engine precision; any may be NULL */
+    void*     maha;     /* [capacity]  d^2 = nu^T S^-1 nu over the m selected dimensions          */
+    void*     loglik;   /* [capacity]  -0.5 (d^2 + ln det S + m ln 2 pi)                          */
+    uint32_t* status;   /* [capacity]  UKFB_ST_* of THIS call                                     */
+} ukfb_state_meas_out;
+/* out may be NULL with commit = 1 */
+int ukfb_update_state_dev(ukfb_engine* e, uint32_t block_mask_uniform, const int32_t* block_mask_dev,
+                          const void* z_dev, const void* Qz_packed_dev,
+                          double state_inflation, double meas_inflation, int commit,
+                          const ukfb_state_meas_out* out);
+/* host arrays of doubles: z [capacity][S], Qz [capacity][D][D] (the lower triangle is read), block_mask_per_filter [capacity]
+ * or NULL; maha / loglik / status [capacity], any may be NULL; synchronises */
+int ukfb_update_state(ukfb_engine* e, uint32_t block_mask, const int32_t* block_mask_per_filter /* or NULL */,
+                      const double* z, const double* Qz, double state_inflation, double meas_inflation, int commit,
+                      double* maha, double* loglik, uint32_t* status);
+/* Pose engines only (else UKFB_ERR_WRONG_MODEL): base::samples::RigidBodyState records (the 49 scalars of
+ * ukfb_pose_export_body_states) integrated as measurements.  z = the record's fields AS THEY ARE (no inverse rotation of the
+ * velocity, as fromRigidBodyState and ukfb_pose_import_body_states), Qz = the four 3 x 3 blocks on the diagonal; inflation 1, 1,
+ * commit = 1.  active [capacity] or NULL: a filter with active == 0 gets no measurement (INACTIVE).  Synchronises. */
+int ukfb_pose_update_body_states(ukfb_engine* e, uint32_t block_mask, const double* records /* [capacity][49] */,
+                                 const uint8_t* active /* or NULL */);
+
 
 /* ---- device groups: one host process, several MI355X ------------------------------------------------------------------ */
 /* north_star's multi-GPU shape for a C++ host.  The filters of a batch are independent -- every filter of the reference owns

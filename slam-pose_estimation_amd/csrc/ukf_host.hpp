@@ -293,6 +293,60 @@ inline SmoothGeometry smooth_geometry(int S, int D, int64_t capacity, size_t com
             int(size_t(SMOOTH_FILTERS_PER_GROUP) * smooth_filter_scalars(S, D) * compute_size)};
 }
 
+// ---- joint state-block measurements (ukfb_update_state_dev) --------------------------------------------------------------
+// A measurement is a sub-manifold of the state: the compound of the blocks a mask selects, in state order.  Every block but the
+// OrientationState's gravity has three tangent dimensions, so tangent dimension t belongs to block t / 3 in both models.
+constexpr int STATE_MEAS_FILTERS_PER_GROUP = 4;
+constexpr int state_meas_blocks(int engine_model) { return engine_model == UKFB_MODEL_POSE ? 4 : 5; }
+constexpr bool state_meas_mask_ok(int blocks, int64_t mask) { return mask > 0 && (mask >> blocks) == 0; }
+// tangent dimensions of a mask (D: 12 / 13; the last block of OrientationState has one)
+inline int state_meas_dim(int D, uint32_t mask) {
+    int m = 0;
+    for (int t = 0; t < D; ++t) m += int((mask >> (t / 3)) & 1u);
+    return m;
+}
+// per_filter_masks: the masks come from a device array (checked per filter by the kernel: INACTIVE); otherwise the one mask must
+// select at least one block and none the model does not have
+inline Verdict check_state_meas_args(int engine_model, bool per_filter_masks, uint32_t mask_uniform, bool has_z, bool has_Qz,
+                                     double state_inflation, double meas_inflation, int commit, const ukfb_state_meas_out* out) {
+    if (!has_z || !has_Qz) return {UKFB_ERR_INVALID_ARG, "z and Qz must not be NULL"};
+    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    if (!(std::isfinite(state_inflation) && state_inflation >= 1.0) || !(std::isfinite(meas_inflation) && meas_inflation >= 1.0))
+        return {UKFB_ERR_INVALID_ARG, "state_inflation and meas_inflation must be finite and >= 1"};
+    if (!per_filter_masks && !state_meas_mask_ok(state_meas_blocks(engine_model), int64_t(mask_uniform)))
+        return {UKFB_ERR_INVALID_ARG, "block_mask must select at least one block and none beyond the model's (Pose: 4, OrientationState: 5)"};
+    if (commit == 0 && (!out || (!out->maha && !out->loglik && !out->status)))
+        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
+    return {};
+}
+// LDS of one filter, in scalars of the compute type (ukf_state_meas.hpp, StateMeasLayout): the factor region with its reciprocal
+// pivots, the delta table of 2 D + 1 rows (the solved cross-covariance aliases it), the state's and the measurement's record
+// (mean padded to 16, packed covariance padded to even) and the sink of lane-predicated stores (16); rounded up to a multiple
+// of four so that every filter's slice starts 16-byte aligned in either precision.  Every scalar the kernel reads is one it
+// wrote: the pads are never read.
+constexpr int state_meas_filter_scalars(int S, int D) {
+    return S > 16 ? -1 : (D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 2 * (16 + (D * (D + 1) / 2 + 1) / 2 * 2) + 16 + 3) / 4 * 4;
+}
+struct StateMeasGeometry {
+    int64_t grid;    // workgroups of four filters
+    int lds_bytes;   // dynamic LDS of a workgroup
+};
+// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
+inline StateMeasGeometry state_meas_geometry(int S, int D, int64_t capacity, size_t compute_size) {
+    return {(capacity + STATE_MEAS_FILTERS_PER_GROUP - 1) / STATE_MEAS_FILTERS_PER_GROUP,
+            int(size_t(STATE_MEAS_FILTERS_PER_GROUP) * state_meas_filter_scalars(S, D) * compute_size)};
+}
+// A base::samples::RigidBodyState record (49 scalars: position, orientation x y z w, velocity, angular velocity, then the four
+// 3 x 3 covariances in that order) as a Pose measurement: z = the record's first 13 scalars as they are, Qz = the four blocks
+// on the diagonal of a 12 x 12 matrix (row-major), zero elsewhere
+inline void body_state_to_measurement(const double* rec, double* z, double* Qz) {
+    for (int s = 0; s < 13; ++s) z[s] = rec[s];
+    std::fill(Qz, Qz + 144, 0.0);
+    for (int b = 0; b < 4; ++b)
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) Qz[(3 * b + r) * 12 + 3 * b + c] = rec[13 + 9 * b + 3 * r + c];
+}
+
 struct CycleLaunch {
     int first_cycle, cycles, slot;   // slot: the ring slot of first_cycle
     bool status_accumulate;          // the status word is the OR over ALL cycles of the call

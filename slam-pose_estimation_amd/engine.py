@@ -56,6 +56,8 @@ EXPORTS = [
     "ukfb_bank_weights_dev", "ukfb_bank_combine_dev", "ukfb_bank_mix_dev", "ukfb_bank_combine", "ukfb_bank_mix",
     # fixed-interval smoothing: history rings and the RTS backward pass (read-only)
     "ukfb_history_push_dev", "ukfb_smooth_dev", "ukfb_smooth",
+    # joint state-block measurements: update / fuse with full covariance, covariance intersection, track-to-track distance
+    "ukfb_update_state_dev", "ukfb_update_state", "ukfb_pose_update_body_states",
     # device groups (one process, several GPUs)
     "ukfb_group_shard_range", "ukfb_group_create", "ukfb_group_destroy", "ukfb_group_size", "ukfb_group_shard",
     "ukfb_group_set_config", "ukfb_group_initialize", "ukfb_group_get_state", "ukfb_group_get_status",
@@ -67,6 +69,12 @@ EXPORTS = [
     "ukfb_group_timer_end", "ukfb_group_gather_means", "ukfb_group_last_gather_exchange",
 ]
 BODY_STATE_SCALARS = 49
+
+# state blocks of ukfb_update_state_dev, one bit each, in host-layout order
+BLOCK_POSE_POSITION, BLOCK_POSE_ORIENTATION, BLOCK_POSE_VELOCITY, BLOCK_POSE_ANGULAR_VELOCITY = 1, 2, 4, 8
+BLOCK_POSE_ALL = 15
+BLOCK_ORIENT_ORIENTATION, BLOCK_ORIENT_VELOCITY, BLOCK_ORIENT_BIAS_GYRO, BLOCK_ORIENT_BIAS_ACC, BLOCK_ORIENT_GRAVITY = 1, 2, 4, 8, 16
+BLOCK_ORIENT_ALL = 31
 
 
 class Config(C.Structure):
@@ -80,6 +88,11 @@ class InnovationOut(C.Structure):
     """ukfb_innovation_out: device pointers in engine precision, any may be NULL"""
     _fields_ = [("z_pred", C.c_void_p), ("S", C.c_void_p), ("innov", C.c_void_p), ("maha", C.c_void_p),
                 ("loglik", C.c_void_p), ("best", C.c_void_p), ("status", C.c_void_p)]
+
+
+class StateMeasOut(C.Structure):
+    """ukfb_state_meas_out: device pointers in engine precision (status uint32), any may be NULL"""
+    _fields_ = [("maha", C.c_void_p), ("loglik", C.c_void_p), ("status", C.c_void_p)]
 
 
 class UkfbError(RuntimeError):
@@ -465,6 +478,42 @@ class BatchUKF:
         _chk(self._lib.ukfb_smooth(self._h, C.c_int(steps), _pd(d), _pd(mu), _pd(cov), _pd(a), _pd(b),
                                    st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_smooth")
         return mu, cov, st
+
+    # ---- joint state-block measurements: z in the state's own layout [capacity, S], Qz the packed lower triangle [capacity, PK]
+    def update_state_dev(self, block_mask: int, z_dev, Qz_packed_dev, block_mask_dev=None, state_inflation: float = 1.0,
+                         meas_inflation: float = 1.0, commit: bool = True, maha=None, loglik=None, status=None):
+        """ukfom's update with the blocks `block_mask` selects as ONE measurement with its full covariance (BLOCK_* constants;
+        block_mask_dev int32 [capacity] = a mask per filter, <= 0: none).  A record of device_views, a history slot or
+        bank_combine_dev is a valid (z_dev, Qz_packed_dev) as it lies.  The update runs on state_inflation * Sigma and
+        meas_inflation * Qz (1 / w, 1 / (1 - w): covariance intersection).  commit=False is read-only: only the keyword
+        outputs (device buffers [capacity] in engine precision, status uint32 / int32) are written.  Stream-ordered."""
+        ptr = lambda x: None if x is None else _devptr(x).value
+        out = StateMeasOut(ptr(maha), ptr(loglik), ptr(status))
+        _chk(self._lib.ukfb_update_state_dev(self._h, C.c_uint32(int(block_mask)), _devptr(block_mask_dev), _devptr(z_dev),
+                                             _devptr(Qz_packed_dev), C.c_double(state_inflation), C.c_double(meas_inflation),
+                                             C.c_int(1 if commit else 0), C.byref(out)), "ukfb_update_state_dev")
+
+    def update_state(self, block_mask, z, Qz, state_inflation: float = 1.0, meas_inflation: float = 1.0, commit: bool = True):
+        """Host arrays: z [capacity, S], Qz [capacity, D, D]; block_mask an int or an int32 array [capacity].  Returns
+        (maha [capacity], loglik [capacity], status [capacity]); synchronises"""
+        n = self.capacity
+        z = _f64(z, (n, self.S)); Qz = _f64(Qz, (n, self.D, self.D))
+        per = None if np.isscalar(block_mask) else np.ascontiguousarray(block_mask, dtype=np.int32).reshape(n)
+        maha, ll, st = np.empty(n), np.empty(n), np.empty(n, dtype=np.uint32)
+        _chk(self._lib.ukfb_update_state(self._h, C.c_uint32(0 if per is not None else int(block_mask)),
+                                         per.ctypes.data_as(C.POINTER(C.c_int32)) if per is not None else None, _pd(z), _pd(Qz),
+                                         C.c_double(state_inflation), C.c_double(meas_inflation), C.c_int(1 if commit else 0),
+                                         _pd(maha), _pd(ll), st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_update_state")
+        return maha, ll, st
+
+    def update_body_states(self, block_mask: int, records, active=None):
+        """Pose engines: [capacity, 49] RigidBodyState records (the shape of export_body_states) integrated as measurements
+        of the blocks `block_mask` selects; active uint8 [capacity] or None.  Synchronises."""
+        rec = _f64(records, (self.capacity, BODY_STATE_SCALARS))
+        act = np.ascontiguousarray(active, dtype=np.uint8).reshape(self.capacity) if active is not None else None
+        _chk(self._lib.ukfb_pose_update_body_states(self._h, C.c_uint32(int(block_mask)), _pd(rec),
+                                                    act.ctypes.data_as(C.POINTER(C.c_uint8)) if act is not None else None),
+             "ukfb_pose_update_body_states")
 
     # ---- fused cycle
     def cycle(self, dt: float, meas_model: int, z, Q):

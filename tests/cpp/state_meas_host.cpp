@@ -1,0 +1,97 @@
+// state_meas_host.cpp -- the host decisions of the joint state-block measurements (ukf_host.hpp) on the CPU (g++ under ASan /
+// UBSan, compiled by tests/test_state_meas_host.py): mask range per model, inflations, NULL pointers, commit, the launch
+// geometry and the RigidBodyState record as a measurement.
+#include <cmath>
+#include <cstdio>
+#include <limits>
+#include <vector>
+
+#include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
+
+static int failures = 0;
+#define EXPECT(cond)                                                        \
+    do {                                                                    \
+        if (!(cond)) {                                                      \
+            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
+            ++failures;                                                     \
+        }                                                                   \
+    } while (0)
+
+int main() {
+    using namespace ukfb;
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::nan("");
+    ukfb_state_meas_out none{nullptr, nullptr, nullptr};
+    uint32_t word = 0;
+    ukfb_state_meas_out st_only{nullptr, nullptr, &word};
+    // blocks and masks per model
+    EXPECT(state_meas_blocks(UKFB_MODEL_POSE) == 4 && state_meas_blocks(UKFB_MODEL_ORIENT) == 5);
+    EXPECT(UKFB_BLOCK_POSE_ALL == 15u && UKFB_BLOCK_ORIENT_ALL == 31u);
+    EXPECT((UKFB_BLOCK_POSE_POSITION | UKFB_BLOCK_POSE_ORIENTATION | UKFB_BLOCK_POSE_VELOCITY | UKFB_BLOCK_POSE_ANGULAR_VELOCITY) == UKFB_BLOCK_POSE_ALL);
+    EXPECT((UKFB_BLOCK_ORIENT_ORIENTATION | UKFB_BLOCK_ORIENT_VELOCITY | UKFB_BLOCK_ORIENT_BIAS_GYRO | UKFB_BLOCK_ORIENT_BIAS_ACC | UKFB_BLOCK_ORIENT_GRAVITY) == UKFB_BLOCK_ORIENT_ALL);
+    for (int64_t m = 1; m <= 15; ++m) EXPECT(state_meas_mask_ok(4, m) && state_meas_mask_ok(5, m));
+    EXPECT(!state_meas_mask_ok(4, 0) && !state_meas_mask_ok(4, -1) && !state_meas_mask_ok(4, 16) && !state_meas_mask_ok(4, 31));
+    EXPECT(state_meas_mask_ok(5, 16) && state_meas_mask_ok(5, 31) && !state_meas_mask_ok(5, 32) && !state_meas_mask_ok(5, 63));
+    EXPECT(!state_meas_mask_ok(5, int64_t(0x80000000u)) && !state_meas_mask_ok(5, int64_t(int32_t(0x80000001u))));
+    EXPECT(state_meas_dim(12, 15) == 12 && state_meas_dim(12, 3) == 6 && state_meas_dim(12, 8) == 3);
+    EXPECT(state_meas_dim(13, 31) == 13 && state_meas_dim(13, 16) == 1 && state_meas_dim(13, 17) == 4 && state_meas_dim(13, 0) == 0);
+    // the uniform mask is checked on the host, per-filter masks by the kernel
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 15, true, true, 1.0, 1.0, 1, nullptr).rc == UKFB_OK);
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 16, true, true, 1.0, 1.0, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 0, true, true, 1.0, 1.0, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_state_meas_args(UKFB_MODEL_ORIENT, false, 16, true, true, 1.0, 1.0, 1, nullptr).rc == UKFB_OK);
+    EXPECT(check_state_meas_args(UKFB_MODEL_ORIENT, false, 32, true, true, 1.0, 1.0, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_state_meas_args(UKFB_MODEL_ORIENT, false, 0xffffffffu, true, true, 1.0, 1.0, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, true, 0, true, true, 1.0, 1.0, 1, nullptr).rc == UKFB_OK);
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, true, 0xffffu, true, true, 1.0, 1.0, 1, nullptr).rc == UKFB_OK);
+    // NULL pointers
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 3, false, true, 1.0, 1.0, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 3, true, false, 1.0, 1.0, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    // inflations: finite and >= 1
+    for (double v : {0.0, 0.5, 1.0 - 1e-16, -1.0, inf, -inf, nan}) {
+        EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 3, true, true, v, 1.0, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+        const Verdict w = check_state_meas_args(UKFB_MODEL_POSE, false, 3, true, true, 1.0, v, 1, nullptr);
+        EXPECT(w.rc == UKFB_ERR_INVALID_ARG && w.msg != nullptr);
+    }
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 3, true, true, 1.0 / 0.3, 1.0 / 0.7, 1, nullptr).rc == UKFB_OK);
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 3, true, true, 1e300, 1.0, 1, nullptr).rc == UKFB_OK);
+    // commit is 0 or 1; a read-only call needs somewhere to write
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 3, true, true, 1.0, 1.0, 2, &st_only).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 3, true, true, 1.0, 1.0, -1, &st_only).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 3, true, true, 1.0, 1.0, 0, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 3, true, true, 1.0, 1.0, 0, &none).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 3, true, true, 1.0, 1.0, 0, &st_only).rc == UKFB_OK);
+    EXPECT(check_state_meas_args(UKFB_MODEL_POSE, false, 3, true, true, 1.0, 1.0, 1, &none).rc == UKFB_OK);
+    // LDS per model and precision: four filters per workgroup
+    struct { int S, D; } models[2] = {{13, 12}, {14, 13}};
+    for (const auto& m : models) {
+        const int PK = m.D * (m.D + 1) / 2;
+        const int sc = state_meas_filter_scalars(m.S, m.D);
+        // one D x 14 matrix, the delta table, two records, and no more than 15 % on top
+        const int floor_sc = m.D * SMOOTH_LS + (2 * m.D + 1) * SMOOTH_LS + 2 * (m.S + PK);
+        EXPECT(sc >= floor_sc && sc <= floor_sc * 115 / 100 && sc % 4 == 0);
+        EXPECT(sc < smooth_filter_scalars(m.S, m.D));
+        for (size_t bytes : {size_t(4), size_t(8)}) {
+            const StateMeasGeometry g = state_meas_geometry(m.S, m.D, 1022, bytes);
+            EXPECT(g.grid == 256 && g.lds_bytes == int(4 * sc * bytes));
+            EXPECT(g.lds_bytes <= 65536 && g.lds_bytes % 16 == 0 && (sc * int(bytes)) % 16 == 0);
+            EXPECT((sc * int(bytes) / 4) % 32 != 0);   // the four slices start on different banks
+        }
+        EXPECT(state_meas_geometry(m.S, m.D, 0, 8).grid == 0 && state_meas_geometry(m.S, m.D, 5, 8).grid == 2);
+    }
+    EXPECT(state_meas_filter_scalars(13, 12) == 740 && state_meas_filter_scalars(14, 13) == 808);
+    EXPECT(state_meas_filter_scalars(17, 16) == -1);
+    // a RigidBodyState record as a measurement: the fields as they are, the four blocks on the diagonal
+    {
+        std::vector<double> rec(UKFB_BODY_STATE_SCALARS), z(13, -1.0), Qz(144, -1.0);
+        for (size_t i = 0; i < rec.size(); ++i) rec[i] = 100.0 + double(i);
+        body_state_to_measurement(rec.data(), z.data(), Qz.data());
+        for (int s = 0; s < 13; ++s) EXPECT(z[size_t(s)] == rec[size_t(s)]);
+        for (int r = 0; r < 12; ++r)
+            for (int c = 0; c < 12; ++c) {
+                const double want = (r / 3 == c / 3) ? rec[size_t(13 + 9 * (r / 3) + 3 * (r % 3) + c % 3)] : 0.0;
+                EXPECT(Qz[size_t(r * 12 + c)] == want);
+            }
+    }
+    std::printf("OK: %d failure(s)\n", failures);
+    return failures ? 1 : 0;
+}
