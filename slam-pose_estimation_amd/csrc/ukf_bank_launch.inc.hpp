@@ -9,13 +9,6 @@
 
 namespace ukfb {
 
-inline int bank_launched(const char* what) {
-    const hipError_t err = hipGetLastError();
-    if (err == hipSuccess) return UKFB_OK;
-    set_error(what, err);
-    return UKFB_ERR_HIP;
-}
-
 template <class TS, class M, class TC> static int launch_bank_typed(ukfb_engine* e, const BankReq& r) {
     using MC = typename M::template rebind<TC>;
     const BankGeometry geo = bank_geometry(MC::S, MC::D, r.hypotheses, e->cap, sizeof(TC));
@@ -38,12 +31,12 @@ template <class TS, class M, class TC> static int launch_bank_typed(ukfb_engine*
         a.w_pred = static_cast<TS*>(r.w_pred_dev);
         for (int k = 0; k < r.hypotheses * r.hypotheses; ++k) a.Pi[k] = TC(r.transition[k]);
         hipLaunchKernelGGL((ukf_bank_mix_kernel<TC, MC, TS>), grid, block, size_t(geo.lds_bytes), main_stream(e), a);
-        return bank_launched("bank mix kernel launch");
+        return launch_status("bank mix kernel launch");
     }
     a.mu_out = static_cast<TS*>(r.mu_out_dev);
     a.cov_out = static_cast<TS*>(r.cov_out_dev);
     hipLaunchKernelGGL((ukf_bank_combine_kernel<TC, MC, TS>), grid, block, size_t(geo.lds_bytes), main_stream(e), a);
-    return bank_launched("bank combine kernel launch");
+    return launch_status("bank combine kernel launch");
 }
 
 template <class M64, class M32> static int launch_bank_model(ukfb_engine* e, const BankReq& r) {
@@ -63,7 +56,7 @@ template <class TS, class TC> static int launch_bank_weights_typed(ukfb_engine* 
     a.status = r.status_dev;
     if (a.tracks == 0) return UKFB_OK;
     hipLaunchKernelGGL((ukf_bank_weights_kernel<TC, TS>), dim3((unsigned)((a.tracks + 255) / 256)), dim3(256), 0, main_stream(e), a);
-    return bank_launched("bank weights kernel launch");
+    return launch_status("bank weights kernel launch");
 }
 
 }  // namespace ukfb

@@ -140,6 +140,14 @@ int launch_orient_f32w(ukfb_engine* e, const LaunchReq& r);
 void set_error(const char* what, hipError_t err);
 void set_error_text(const std::string& text);   // what ukfb_last_error() returns on this thread
 
+// UKFB_OK, or UKFB_ERR_HIP with the error of the launches just enqueued
+inline int launch_status(const char* what) {
+    const hipError_t err = hipGetLastError();
+    if (err == hipSuccess) return UKFB_OK;
+    set_error(what, err);
+    return UKFB_ERR_HIP;
+}
+
 // Every entry point works on its engine's device and hands the calling thread back on the device it came with: a host that
 // drives several engines from one thread (ukfb_group_*), or shares the thread with another HIP user, keeps its own notion of
 // "current device".  Nothing is switched (one thread-local read) when the caller already is on the engine's device.

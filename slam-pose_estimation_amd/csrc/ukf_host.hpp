@@ -1,6 +1,6 @@
 // ukf_host.hpp -- the engine's host decisions as pure functions of plain values: configuration checks, process-noise
-// classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, workspace sizing and the
-// kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
+// classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, packed covariances, workspace sizing and
+// the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
 #pragma once
 
 #include <stddef.h>
@@ -345,6 +345,26 @@ inline void body_state_to_measurement(const double* rec, double* z, double* Qz) 
     for (int b = 0; b < 4; ++b)
         for (int r = 0; r < 3; ++r)
             for (int c = 0; c < 3; ++c) Qz[(3 * b + r) * 12 + 3 * b + c] = rec[13 + 9 * b + 3 * r + c];
+}
+
+// ---- packed covariances of the host-array forms ---------------------------------------------------------------------------
+// `count` row-major D x D matrices <-> their lower triangles, row by row (entry (r, c), c <= r, at r (r + 1) / 2 + c of D (D + 1) / 2).
+// pack_lower reads the lower triangle only; unpack_symmetric writes both triangles.
+inline void pack_lower(const double* full, size_t count, int D, double* packed) {
+    const size_t d = size_t(D), PK = d * (d + 1) / 2;
+    for (size_t i = 0; i < count; ++i)
+        for (size_t r = 0; r < d; ++r)
+            for (size_t c = 0; c <= r; ++c) packed[i * PK + r * (r + 1) / 2 + c] = full[(i * d + r) * d + c];
+}
+inline void unpack_symmetric(const double* packed, size_t count, int D, double* full) {
+    const size_t d = size_t(D), PK = d * (d + 1) / 2;
+    for (size_t i = 0; i < count; ++i)
+        for (size_t r = 0; r < d; ++r)
+            for (size_t c = 0; c <= r; ++c) {
+                const double v = packed[i * PK + r * (r + 1) / 2 + c];
+                full[(i * d + r) * d + c] = v;
+                full[(i * d + c) * d + r] = v;
+            }
 }
 
 struct CycleLaunch {

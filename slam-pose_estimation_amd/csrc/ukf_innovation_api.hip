@@ -3,74 +3,21 @@
 #include <cmath>
 #include <vector>
 
+#include "ukf_api_common.hpp"
 #include "ukf_innovation.hpp"
 #include "ukf_innovation_req.hpp"
-
-namespace {
-
-int fail(const ukfb::Verdict& v) {
-    if (v.rc != UKFB_OK) ukfb::set_error_text(v.msg ? v.msg : "invalid argument");
-    return v.rc;
-}
-
-#define INNOV_HIP_TRY(expr)                        \
-    do {                                           \
-        const hipError_t _e = (expr);              \
-        if (_e != hipSuccess) {                    \
-            ukfb::set_error(#expr, _e);            \
-            return UKFB_ERR_HIP;                   \
-        }                                          \
-    } while (0)
-
-struct DeviceBuffers {   // temporaries of the host-array form, freed on every path
-    std::vector<void*> ptrs;
-    ~DeviceBuffers() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    hipError_t take(void** p, size_t bytes) {
-        const hipError_t err = hipMalloc(p, bytes ? bytes : 1);
-        if (err == hipSuccess) ptrs.push_back(*p);
-        return err;
-    }
-};
-
-// host doubles -> engine precision on the device (through a host copy: this form is a convenience, not a hot path)
-int upload_scalars(ukfb_engine* e, void* dst, const double* src, size_t n) {
-    if (e->prec == UKFB_F64) {
-        INNOV_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, ukfb::main_stream(e)));
-        return ukfb_sync(e);
-    }
-    std::vector<float> tmp(n);
-    for (size_t i = 0; i < n; ++i) tmp[i] = float(src[i]);
-    INNOV_HIP_TRY(hipMemcpyAsync(dst, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice, ukfb::main_stream(e)));
-    return ukfb_sync(e);
-}
-
-int download_scalars(ukfb_engine* e, const void* src, double* dst, size_t n) {
-    if (e->prec == UKFB_F64) {
-        INNOV_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-        return ukfb_sync(e);
-    }
-    std::vector<float> tmp(n);
-    INNOV_HIP_TRY(hipMemcpyAsync(tmp.data(), src, n * sizeof(float), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    if (const int rc = ukfb_sync(e)) return rc;
-    for (size_t i = 0; i < n; ++i) dst[i] = double(tmp[i]);
-    return UKFB_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
 int ukfb_innovation_dev(ukfb_engine* e, int meas_model_uniform, const int32_t* meas_model_dev, int candidates, const void* z_dev,
                         const void* Q_dev, int q_is_uniform, const ukfb_innovation_out* out) {
     if (!e) return UKFB_ERR_INVALID_ARG;
-    if (const int rc = fail(ukfb::check_innovation_args(e->model, meas_model_dev != nullptr, meas_model_uniform, candidates,
-                                                        z_dev != nullptr, Q_dev != nullptr, out)))
+    if (const int rc = ukfb::fail(ukfb::check_innovation_args(e->model, meas_model_dev != nullptr, meas_model_uniform, candidates,
+                                                              z_dev != nullptr, Q_dev != nullptr, out)))
         return rc;
-    if (e->poisoned) return fail({UKFB_ERR_HIP, "engine poisoned by an earlier wait that timed out (UKFB_WAIT_TIMEOUT_S)"});
+    if (const int rc = ukfb::refuse_poisoned(e)) return rc;
     ukfb::DeviceScope scope(e->device);
-    INNOV_HIP_TRY(scope.err);
+    UKFB_HIP_TRY(scope.err);
     ukfb::InnovReq r;
     r.meas_uniform = meas_model_uniform;
     r.meas_dev = meas_model_dev;
@@ -85,12 +32,12 @@ int ukfb_innovation_dev(ukfb_engine* e, int meas_model_uniform, const int32_t* m
 int ukfb_select_candidates_dev(ukfb_engine* e, int candidates, const int32_t* best_dev, int meas_model_uniform,
                                const int32_t* meas_model_dev, const void* z_dev, void* z_sel_dev, int32_t* meas_model_sel_dev) {
     if (!e) return UKFB_ERR_INVALID_ARG;
-    if (const int rc = fail(ukfb::check_select_args(e->model, meas_model_dev != nullptr, meas_model_uniform, candidates,
-                                                    best_dev != nullptr, z_dev != nullptr, z_sel_dev != nullptr)))
+    if (const int rc = ukfb::fail(ukfb::check_select_args(e->model, meas_model_dev != nullptr, meas_model_uniform, candidates,
+                                                          best_dev != nullptr, z_dev != nullptr, z_sel_dev != nullptr)))
         return rc;
-    if (e->poisoned) return fail({UKFB_ERR_HIP, "engine poisoned by an earlier wait that timed out (UKFB_WAIT_TIMEOUT_S)"});
+    if (const int rc = ukfb::refuse_poisoned(e)) return rc;
     ukfb::DeviceScope scope(e->device);
-    INNOV_HIP_TRY(scope.err);
+    UKFB_HIP_TRY(scope.err);
     if (e->cap == 0) return UKFB_OK;
     const dim3 gd((unsigned)((e->cap + 255) / 256)), bd(256);
     if (e->prec == UKFB_F64)
@@ -101,7 +48,7 @@ int ukfb_select_candidates_dev(ukfb_engine* e, int candidates, const int32_t* be
         hipLaunchKernelGGL(ukfb::select_candidates_kernel<float>, gd, bd, 0, ukfb::main_stream(e), e->cap, candidates, best_dev,
                            meas_model_uniform, meas_model_dev, static_cast<const float*>(z_dev), static_cast<float*>(z_sel_dev),
                            meas_model_sel_dev);
-    INNOV_HIP_TRY(hipGetLastError());
+    UKFB_HIP_TRY(hipGetLastError());
     return UKFB_OK;
 }
 
@@ -111,33 +58,33 @@ int ukfb_innovation(ukfb_engine* e, int meas_model, int candidates, const double
     ukfb_innovation_out asked{};   // non-NULL where the caller wants the output (checked before anything is allocated)
     asked.z_pred = z_pred; asked.S = S; asked.innov = innov; asked.maha = maha; asked.loglik = loglik;
     asked.best = best; asked.status = status;
-    if (const int rc = fail(ukfb::check_innovation_args(e->model, false, meas_model, candidates, z != nullptr, Q != nullptr, &asked)))
+    if (const int rc = ukfb::fail(ukfb::check_innovation_args(e->model, false, meas_model, candidates, z != nullptr, Q != nullptr, &asked)))
         return rc;
     ukfb::DeviceScope scope(e->device);
-    INNOV_HIP_TRY(scope.err);
+    UKFB_HIP_TRY(scope.err);
     const size_t n = size_t(e->cap), K = size_t(candidates), ts = e->tsize;
-    DeviceBuffers buf;
+    ukfb::DeviceBuffers buf;
     void *z_d = nullptr, *Q_d = nullptr;
     ukfb_innovation_out o{};
-    INNOV_HIP_TRY(buf.take(&z_d, K * n * 3 * ts));
-    INNOV_HIP_TRY(buf.take(&Q_d, n * 9 * ts));
-    if (z_pred) INNOV_HIP_TRY(buf.take(&o.z_pred, n * 4 * ts));
-    if (S) INNOV_HIP_TRY(buf.take(&o.S, n * 9 * ts));
-    if (innov) INNOV_HIP_TRY(buf.take(&o.innov, K * n * 3 * ts));
-    if (maha) INNOV_HIP_TRY(buf.take(&o.maha, K * n * ts));
-    if (loglik) INNOV_HIP_TRY(buf.take(&o.loglik, K * n * ts));
-    if (best) INNOV_HIP_TRY(buf.take(reinterpret_cast<void**>(&o.best), n * sizeof(int32_t)));
-    if (status) INNOV_HIP_TRY(buf.take(reinterpret_cast<void**>(&o.status), n * sizeof(uint32_t)));
-    if (const int rc = upload_scalars(e, z_d, z, K * n * 3)) return rc;
-    if (const int rc = upload_scalars(e, Q_d, Q, n * 9)) return rc;
+    UKFB_HIP_TRY(buf.take(&z_d, K * n * 3 * ts));
+    UKFB_HIP_TRY(buf.take(&Q_d, n * 9 * ts));
+    if (z_pred) UKFB_HIP_TRY(buf.take(&o.z_pred, n * 4 * ts));
+    if (S) UKFB_HIP_TRY(buf.take(&o.S, n * 9 * ts));
+    if (innov) UKFB_HIP_TRY(buf.take(&o.innov, K * n * 3 * ts));
+    if (maha) UKFB_HIP_TRY(buf.take(&o.maha, K * n * ts));
+    if (loglik) UKFB_HIP_TRY(buf.take(&o.loglik, K * n * ts));
+    if (best) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&o.best), n * sizeof(int32_t)));
+    if (status) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&o.status), n * sizeof(uint32_t)));
+    if (const int rc = ukfb::upload_scalars(e, z_d, z, K * n * 3)) return rc;
+    if (const int rc = ukfb::upload_scalars(e, Q_d, Q, n * 9)) return rc;
     if (const int rc = ukfb_innovation_dev(e, meas_model, nullptr, candidates, z_d, Q_d, 0, &o)) return rc;
-    if (z_pred) if (const int rc = download_scalars(e, o.z_pred, z_pred, n * 4)) return rc;
-    if (S) if (const int rc = download_scalars(e, o.S, S, n * 9)) return rc;
-    if (innov) if (const int rc = download_scalars(e, o.innov, innov, K * n * 3)) return rc;
-    if (maha) if (const int rc = download_scalars(e, o.maha, maha, K * n)) return rc;
-    if (loglik) if (const int rc = download_scalars(e, o.loglik, loglik, K * n)) return rc;
-    if (best) INNOV_HIP_TRY(hipMemcpyAsync(best, o.best, n * sizeof(int32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    if (status) INNOV_HIP_TRY(hipMemcpyAsync(status, o.status, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
+    if (z_pred) if (const int rc = ukfb::download_scalars(e, o.z_pred, z_pred, n * 4)) return rc;
+    if (S) if (const int rc = ukfb::download_scalars(e, o.S, S, n * 9)) return rc;
+    if (innov) if (const int rc = ukfb::download_scalars(e, o.innov, innov, K * n * 3)) return rc;
+    if (maha) if (const int rc = ukfb::download_scalars(e, o.maha, maha, K * n)) return rc;
+    if (loglik) if (const int rc = ukfb::download_scalars(e, o.loglik, loglik, K * n)) return rc;
+    if (best) UKFB_HIP_TRY(hipMemcpyAsync(best, o.best, n * sizeof(int32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
+    if (status) UKFB_HIP_TRY(hipMemcpyAsync(status, o.status, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
     return ukfb_sync(e);   // (the temporaries are freed after the stream has drained)
 }
 

@@ -33,10 +33,7 @@ template <class TS, class M, class TC> static int launch_innovation_typed(ukfb_e
     const int64_t grid = (a.n + 3) / 4;
     if (grid == 0) return UKFB_OK;
     hipLaunchKernelGGL((ukf_innovation_kernel<TC, MC, TS>), dim3((unsigned)grid), dim3(64), 0, main_stream(e), a);
-    const hipError_t err = hipGetLastError();
-    if (err == hipSuccess) return UKFB_OK;
-    set_error("innovation kernel launch", err);
-    return UKFB_ERR_HIP;
+    return launch_status("innovation kernel launch");
 }
 
 template <class M64, class M32> static int launch_innovation_model(ukfb_engine* e, const InnovReq& r) {

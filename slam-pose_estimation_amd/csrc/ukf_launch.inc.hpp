@@ -11,14 +11,6 @@
 
 namespace ukfb {
 
-// UKFB_OK, or UKFB_ERR_HIP with the error of the launches just enqueued
-static int launch_status(const char* what) {
-    const hipError_t err = hipGetLastError();
-    if (err == hipSuccess) return UKFB_OK;
-    set_error(what, err);
-    return UKFB_ERR_HIP;
-}
-
 template <class T, class M, int G> static int launch_g(ukfb_engine* e, const LaunchReq& r, const KArgs<T>& args) {
     constexpr int FPW = 64 / G;
     const int64_t grid = (args.n + FPW - 1) / FPW;

@@ -46,10 +46,7 @@ template <class TS, class M, class TC> static int launch_smooth_typed(ukfb_engin
     a.status = r.status_dev;
     a.status_accumulate = p.first ? 0 : 1;
     hipLaunchKernelGGL((ukf_smooth_kernel<TC, MC, TS>), dim3((unsigned)geo.grid), dim3(64), size_t(geo.lds_bytes), main_stream(e), a);
-    const hipError_t err = hipGetLastError();
-    if (err == hipSuccess) return UKFB_OK;
-    set_error("smoother kernel launch", err);
-    return UKFB_ERR_HIP;
+    return launch_status("smoother kernel launch");
 }
 
 template <class M64, class M32> static int launch_smooth_model(ukfb_engine* e, const SmoothReq& r) {

@@ -2,64 +2,14 @@
 // measurements"): argument checks (ukf_host.hpp), the device form, the host-array form and the RigidBodyState adapter.
 #include <vector>
 
+#include "ukf_api_common.hpp"
 #include "ukf_state_meas_req.hpp"
 
 namespace {
 
-int fail(const ukfb::Verdict& v) {
-    if (v.rc != UKFB_OK) ukfb::set_error_text(v.msg ? v.msg : "invalid argument");
-    return v.rc;
-}
-
-#define STM_HIP_TRY(expr)                          \
-    do {                                           \
-        const hipError_t _e = (expr);              \
-        if (_e != hipSuccess) {                    \
-            ukfb::set_error(#expr, _e);            \
-            return UKFB_ERR_HIP;                   \
-        }                                          \
-    } while (0)
-
-struct DeviceBuffers {   // temporaries of the host-array form, freed on every path
-    std::vector<void*> ptrs;
-    ~DeviceBuffers() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    hipError_t take(void** p, size_t bytes) {
-        const hipError_t err = hipMalloc(p, bytes ? bytes : 1);
-        if (err == hipSuccess) ptrs.push_back(*p);
-        return err;
-    }
-};
-
 int entry(ukfb_engine* e) {
     if (!e) return UKFB_ERR_INVALID_ARG;
-    if (e->poisoned) return fail({UKFB_ERR_HIP, "engine poisoned by an earlier wait that timed out (UKFB_WAIT_TIMEOUT_S)"});
-    return UKFB_OK;
-}
-
-// host doubles <-> engine precision on the device (through a host copy: the host-array form is a convenience, not a hot path)
-int upload_scalars(ukfb_engine* e, void* dst, const double* src, size_t n) {
-    if (e->prec == UKFB_F64) {
-        STM_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, ukfb::main_stream(e)));
-        return ukfb_sync(e);
-    }
-    std::vector<float> tmp(n);
-    for (size_t i = 0; i < n; ++i) tmp[i] = float(src[i]);
-    STM_HIP_TRY(hipMemcpyAsync(dst, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice, ukfb::main_stream(e)));
-    return ukfb_sync(e);
-}
-
-int download_scalars(ukfb_engine* e, const void* src, double* dst, size_t n) {
-    if (e->prec == UKFB_F64) {
-        STM_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-        return ukfb_sync(e);
-    }
-    std::vector<float> tmp(n);
-    STM_HIP_TRY(hipMemcpyAsync(tmp.data(), src, n * sizeof(float), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    if (const int rc = ukfb_sync(e)) return rc;
-    for (size_t i = 0; i < n; ++i) dst[i] = double(tmp[i]);
-    return UKFB_OK;
+    return ukfb::refuse_poisoned(e);
 }
 
 }  // namespace
@@ -70,11 +20,11 @@ int ukfb_update_state_dev(ukfb_engine* e, uint32_t block_mask_uniform, const int
                           const void* Qz_packed_dev, double state_inflation, double meas_inflation, int commit,
                           const ukfb_state_meas_out* out) {
     if (const int rc = entry(e)) return rc;
-    if (const int rc = fail(ukfb::check_state_meas_args(e->model, block_mask_dev != nullptr, block_mask_uniform, z_dev != nullptr,
-                                                        Qz_packed_dev != nullptr, state_inflation, meas_inflation, commit, out)))
+    if (const int rc = ukfb::fail(ukfb::check_state_meas_args(e->model, block_mask_dev != nullptr, block_mask_uniform, z_dev != nullptr,
+                                                              Qz_packed_dev != nullptr, state_inflation, meas_inflation, commit, out)))
         return rc;
     ukfb::DeviceScope scope(e->device);
-    STM_HIP_TRY(scope.err);
+    UKFB_HIP_TRY(scope.err);
     ukfb::StateMeasReq r;
     r.mask_uniform = block_mask_uniform;
     r.mask_dev = block_mask_dev;
@@ -92,45 +42,43 @@ int ukfb_update_state(ukfb_engine* e, uint32_t block_mask, const int32_t* block_
     if (const int rc = entry(e)) return rc;
     // (the outputs the device call will see: a buffer for each one the caller wants)
     ukfb_state_meas_out wanted{maha, loglik, status};
-    if (const int rc = fail(ukfb::check_state_meas_args(e->model, block_mask_per_filter != nullptr, block_mask, z != nullptr,
-                                                        Qz != nullptr, state_inflation, meas_inflation, commit, &wanted)))
+    if (const int rc = ukfb::fail(ukfb::check_state_meas_args(e->model, block_mask_per_filter != nullptr, block_mask, z != nullptr,
+                                                              Qz != nullptr, state_inflation, meas_inflation, commit, &wanted)))
         return rc;
     ukfb::DeviceScope scope(e->device);
-    STM_HIP_TRY(scope.err);
-    const size_t n = size_t(e->cap), ts = e->tsize, S = size_t(e->S), D = size_t(e->D), PK = size_t(e->PK);
-    DeviceBuffers buf;
+    UKFB_HIP_TRY(scope.err);
+    const size_t n = size_t(e->cap), ts = e->tsize, S = size_t(e->S), PK = size_t(e->PK);
+    ukfb::DeviceBuffers buf;
     void *z_d = nullptr, *q_d = nullptr, *maha_d = nullptr, *ll_d = nullptr;
     int32_t* mask_d = nullptr;
     uint32_t* st_d = nullptr;
-    STM_HIP_TRY(buf.take(&z_d, n * S * ts));
-    STM_HIP_TRY(buf.take(&q_d, n * PK * ts));
-    if (block_mask_per_filter) STM_HIP_TRY(buf.take(reinterpret_cast<void**>(&mask_d), n * sizeof(int32_t)));
-    if (maha) STM_HIP_TRY(buf.take(&maha_d, n * ts));
-    if (loglik) STM_HIP_TRY(buf.take(&ll_d, n * ts));
-    if (status) STM_HIP_TRY(buf.take(reinterpret_cast<void**>(&st_d), n * sizeof(uint32_t)));
+    UKFB_HIP_TRY(buf.take(&z_d, n * S * ts));
+    UKFB_HIP_TRY(buf.take(&q_d, n * PK * ts));
+    if (block_mask_per_filter) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&mask_d), n * sizeof(int32_t)));
+    if (maha) UKFB_HIP_TRY(buf.take(&maha_d, n * ts));
+    if (loglik) UKFB_HIP_TRY(buf.take(&ll_d, n * ts));
+    if (status) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&st_d), n * sizeof(uint32_t)));
     std::vector<double> packed(n * PK);
-    for (size_t i = 0; i < n; ++i)
-        for (size_t r = 0; r < D; ++r)
-            for (size_t c = 0; c <= r; ++c) packed[i * PK + r * (r + 1) / 2 + c] = Qz[(i * D + r) * D + c];
-    if (const int rc = upload_scalars(e, z_d, z, n * S)) return rc;
-    if (const int rc = upload_scalars(e, q_d, packed.data(), n * PK)) return rc;
-    if (mask_d) STM_HIP_TRY(hipMemcpyAsync(mask_d, block_mask_per_filter, n * sizeof(int32_t), hipMemcpyHostToDevice, ukfb::main_stream(e)));
+    ukfb::pack_lower(Qz, n, e->D, packed.data());
+    if (const int rc = ukfb::upload_scalars(e, z_d, z, n * S)) return rc;
+    if (const int rc = ukfb::upload_scalars(e, q_d, packed.data(), n * PK)) return rc;
+    if (mask_d) UKFB_HIP_TRY(hipMemcpyAsync(mask_d, block_mask_per_filter, n * sizeof(int32_t), hipMemcpyHostToDevice, ukfb::main_stream(e)));
     const ukfb_state_meas_out out{maha_d, ll_d, st_d};
     if (const int rc = ukfb_update_state_dev(e, block_mask, mask_d, z_d, q_d, state_inflation, meas_inflation, commit, &out)) return rc;
     if (maha)
-        if (const int rc = download_scalars(e, maha_d, maha, n)) return rc;
+        if (const int rc = ukfb::download_scalars(e, maha_d, maha, n)) return rc;
     if (loglik)
-        if (const int rc = download_scalars(e, ll_d, loglik, n)) return rc;
-    if (status) STM_HIP_TRY(hipMemcpyAsync(status, st_d, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
+        if (const int rc = ukfb::download_scalars(e, ll_d, loglik, n)) return rc;
+    if (status) UKFB_HIP_TRY(hipMemcpyAsync(status, st_d, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
     return ukfb_sync(e);   // (the temporaries are freed after the stream has drained)
 }
 
 int ukfb_pose_update_body_states(ukfb_engine* e, uint32_t block_mask, const double* records, const uint8_t* active) {
     if (const int rc = entry(e)) return rc;
-    if (e->model != UKFB_MODEL_POSE) return fail({UKFB_ERR_WRONG_MODEL, "Pose engines only"});
-    if (!records) return fail({UKFB_ERR_INVALID_ARG, "records must not be NULL"});
+    if (e->model != UKFB_MODEL_POSE) return ukfb::fail({UKFB_ERR_WRONG_MODEL, "Pose engines only"});
+    if (!records) return ukfb::fail({UKFB_ERR_INVALID_ARG, "records must not be NULL"});
     if (!ukfb::state_meas_mask_ok(ukfb::state_meas_blocks(e->model), int64_t(block_mask)))
-        return fail({UKFB_ERR_INVALID_ARG, "block_mask must select at least one block and none beyond the model's (Pose: 4, OrientationState: 5)"});
+        return ukfb::fail({UKFB_ERR_INVALID_ARG, "block_mask must select at least one block and none beyond the model's (Pose: 4, OrientationState: 5)"});
     const size_t n = size_t(e->cap);
     std::vector<double> z(n * 13), Qz(n * 144);
     for (size_t i = 0; i < n; ++i) ukfb::body_state_to_measurement(records + i * UKFB_BODY_STATE_SCALARS, z.data() + i * 13, Qz.data() + i * 144);

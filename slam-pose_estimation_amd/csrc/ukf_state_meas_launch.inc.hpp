@@ -33,10 +33,7 @@ template <class TS, class M, class TC> static int launch_state_meas_typed(ukfb_e
     a.loglik = static_cast<TS*>(r.out.loglik);
     a.status = r.out.status;
     hipLaunchKernelGGL((ukf_state_meas_kernel<TC, MC, TS>), dim3((unsigned)geo.grid), dim3(64), size_t(geo.lds_bytes), main_stream(e), a);
-    const hipError_t err = hipGetLastError();
-    if (err == hipSuccess) return UKFB_OK;
-    set_error("state-measurement kernel launch", err);
-    return UKFB_ERR_HIP;
+    return launch_status("state-measurement kernel launch");
 }
 
 template <class M64, class M32> static int launch_state_meas_model(ukfb_engine* e, const StateMeasReq& r) {

@@ -401,6 +401,39 @@ void models() {
     }
 }
 
+// ---- packed covariances -------------------------------------------------------------------------------------------------------
+// D = 12, 13: the two models; 15: the largest the 16-lane kernels admit (S = D + 1 <= 16).  The strict upper triangle of every input is NaN:
+// pack_lower must not read it.  count = 0 works on zero-length vectors, so that ASan sees any access.
+void packing() {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int D : {12, 13, 15})
+        for (size_t count : {size_t(0), size_t(3)}) {
+            const size_t d = size_t(D), PK = d * (d + 1) / 2;
+            std::vector<double> A(count * d * d), packed(count * PK, nan), back(count * d * d, nan);
+            for (size_t i = 0; i < count; ++i)
+                for (size_t r = 0; r < d; ++r)
+                    for (size_t c = 0; c < d; ++c) A[(i * d + r) * d + c] = c <= r ? 1.0 / double(1 + i * d * d + r * d + c) : nan;
+            ukfb::pack_lower(A.data(), count, D, packed.data());
+            size_t k = 0;   // the packed order: matrix by matrix, row by row, columns 0 ... r
+            for (size_t i = 0; i < count; ++i)
+                for (size_t r = 0; r < d; ++r)
+                    for (size_t c = 0; c <= r; ++c, ++k)
+                        CHECK(std::isfinite(packed[k]) && std::memcmp(&packed[k], &A[(i * d + r) * d + c], sizeof(double)) == 0,
+                              "D %d matrix %zu (%zu, %zu): packed %g", D, i, r, c, packed[k]);
+            CHECK(k == packed.size(), "D %d count %zu: %zu packed entries of %zu", D, count, k, packed.size());
+            ukfb::unpack_symmetric(packed.data(), count, D, back.data());
+            for (size_t i = 0; i < count; ++i)
+                for (size_t r = 0; r < d; ++r)
+                    for (size_t c = 0; c < d; ++c) {
+                        const double& lower = A[(i * d + std::max(r, c)) * d + std::min(r, c)];   // A's lower triangle mirrored
+                        CHECK(std::memcmp(&back[(i * d + r) * d + c], &lower, sizeof(double)) == 0, "D %d matrix %zu (%zu, %zu): unpacked %g",
+                              D, i, r, c, back[(i * d + r) * d + c]);
+                        CHECK(std::memcmp(&back[(i * d + r) * d + c], &back[(i * d + c) * d + r], sizeof(double)) == 0,
+                              "D %d matrix %zu (%zu, %zu): not symmetric", D, i, r, c);
+                    }
+        }
+}
+
 // ---- kernel level -------------------------------------------------------------------------------------------------------------
 // The table as launch_row16 (ukf_launch.inc.hpp) wrote it before the logic moved to ukf_host.hpp, restated literally.
 int level_before(int model, const ukfb::LaunchFacts& f) {
@@ -473,6 +506,7 @@ int main(int argc, char** argv) {
     plans();
     sizing();
     models();
+    packing();
     kernel_levels();
     std::printf("%s: %d failure(s)\n", failures ? "FAILED" : "OK", failures);
     return failures ? 1 : 0;

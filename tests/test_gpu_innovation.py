@@ -396,6 +396,24 @@ def test_statuses_and_argument_errors(spe, onp):
     eo.close()
 
 
+@pytest.mark.parametrize("name,prec,wide,tol", PRECS[1:], ids=["f32", "f32w"])
+@pytest.mark.parametrize("kind,mid", [("pose", 0), ("orient", 9)])
+def test_host_array_form_fp32(spe, onp, kind, mid, name, prec, wide, tol):
+    """fp32 engines: ukfb_innovation narrows the host doubles itself; every output is the bits of the device form fed the same
+    values rounded to float32.  Five filters (one full wavefront and a one-row tail), two candidates."""
+    n = 5
+    e, Q = make_engine(spe, kind, n, prec, wide, gate_chi2=7.81)
+    mu, _, _ = e.state()
+    z = clutter(onp, spe, kind, mid, mu)[:2]
+    assert not np.array_equal(z, stored(e, z)) and not np.array_equal(Q, stored(e, Q))   # doubles that are NOT fp32 values
+    ho = e.innovation(mid, z, Q)
+    out = run_innovation(e, mid, stored(e, z), stored(e, Q))
+    assert (ho["status"] == 0).all() and np.isfinite(ho["maha"]).all()
+    for key in ("z_pred", "S", "innov", "maha", "loglik", "best", "status"):
+        assert np.array_equal(ho[key], out[key]), key
+    e.close()
+
+
 def test_thirty_two_candidates_and_ties(spe, onp):
     """two passes of the sixteen lanes; equal distances keep the lower index"""
     n, k = 70, 32

@@ -306,6 +306,32 @@ def test_bit_level_properties(spe, model):
 
 
 @pytest.mark.parametrize("model", ["pose", "orient"])
+@pytest.mark.parametrize("pname", ["f32", "f32w"])
+def test_host_array_form_fp32(spe, model, pname):
+    """fp32 engines: ukfb_update_state narrows the host doubles and packs Qz itself; its outputs and the committed state are the
+    bits of the device form fed the same values rounded to float32.  Five filters: one full wavefront and a one-row tail."""
+    n = 5
+    c = case(spe, model, pname, n)
+    z, Qz = make_inputs(model, c.mu, c.cov, np.float64)   # doubles that are NOT fp32 values
+    z32, Qz32 = z.astype(np.float32).astype(np.float64), Qz.astype(np.float32).astype(np.float64)
+    assert not np.array_equal(z, z32) and not np.array_equal(Qz, Qz32)
+    full = full_mask(model)
+    per = np.array([full, 0, 1, 0b0110, 0b0101], dtype=np.int32)
+    for masks in (0b0110, per):
+        e, twin = engine_of(spe, c), engine_of(spe, c)
+        d2, ll, st = e.update_state(masks, z, Qz)
+        mu, cov, _ = e.state()
+        dev = run(twin, masks, z32, Qz32)
+        assert np.array_equal(st, dev[4]) and np.array_equal(e.status(), twin.status())
+        assert np.array_equal(d2, dev[2], equal_nan=True) and np.array_equal(ll, dev[3], equal_nan=True)
+        assert np.array_equal(mu, dev[0]) and np.array_equal(cov, dev[1])
+        idle = np.broadcast_to(np.asarray(masks) == 0, (n,))
+        assert np.array_equal(st, np.where(idle, ST_INACTIVE, 0)), st
+        assert np.isfinite(d2[~idle]).all() and not np.array_equal(mu[~idle], c.mu[~idle])
+        e.close(); twin.close()
+
+
+@pytest.mark.parametrize("model", ["pose", "orient"])
 def test_failures_stay_inside_their_filter(spe, model):
     n, dead, nan_sel, nan_unsel, neg, idle = 64, 22, 13, 14, 15, 16   # 13 ... 16 share a wavefront
     man = man_of(model)
