@@ -176,6 +176,29 @@ public:
                                 maha, loglik, st.data()));
         return st;
     }
+    /** Sensor-frame measurements (ukf_batch.h, "sensor-frame measurements"): ukf->update(z, h, Q) with h one of the
+     *  UKFB_SENSOR_* models -- a lever arm, a range, a point seen in the sensor frame, a velocity at the sensor, a nav-frame
+     *  vector -- so that the sigma points carry the coupling to the orientation and angular-velocity uncertainty that shifting
+     *  the sample into the body frame with the current mean discards.  Device form: the arrays of ukfb_sensor_in; commit =
+     *  false is read-only (only `out` is written).  Stream-ordered. */
+    void integrateSensorMeasurementDev(int model_uniform, const ukfb_sensor_in& in, bool commit = true, const ukfb_sensor_out* out = NULL)
+    {
+        check(ukfb_update_sensor_dev(engine, model_uniform, &in, commit ? 1 : 0, out));
+    }
+    /** host arrays: z [N][3], Q [N][3][3]; mount_uniform [7] = r, then qs (x, y, z, w) (NULL: r = 0, qs the identity) and
+     *  point_uniform [3] (NULL: 0) serve every filter unless mount [N][7] / point [N][3] are given; model_per_filter [N] or
+     *  NULL; z_pred [N][3], S [N][3][3], innov [N][3], maha / loglik [N] or NULL; returns the status */
+    std::vector<uint32_t> integrateSensorMeasurement(int model, const double* z, const double* Q, const double* mount_uniform = NULL,
+                                                     const double* point_uniform = NULL, const double* mount = NULL,
+                                                     const double* point = NULL, const int32_t* model_per_filter = NULL,
+                                                     bool commit = true, double* z_pred = NULL, double* S = NULL, double* innov = NULL,
+                                                     double* maha = NULL, double* loglik = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_update_sensor(engine, model, model_per_filter, z, Q, mount, mount_uniform, point, point_uniform, commit ? 1 : 0,
+                                 z_pred, S, innov, maha, loglik, st.data()));
+        return st;
+    }
     /** host arrays in window order, smoothed in place: mu [steps][N][S], cov [steps][N][D][D]; returns the per-filter status */
     std::vector<uint32_t> smooth(int steps, const double* dt, double* mu, double* cov, const double* in_a = NULL,
                                  const double* in_b = NULL)

@@ -560,6 +560,92 @@ int ukfb_update_state(ukfb_engine* e, uint32_t block_mask, const int32_t* block_
 int ukfb_pose_update_body_states(ukfb_engine* e, uint32_t block_mask, const double* records /* [capacity][49] */,
                                  const uint8_t* active /* or NULL */);
 
+/* ---- sensor-frame measurements: lever arms, ranges and landmark fixes ---------------------------------------------------- */
+/* ukf->update(z, h, Q) for sensors that are NOT at the body origin or not aligned with the body: h is nonlinear in the
+ * orientation (and, with a lever arm, couples the sample to the angular velocity), and the sigma points carry that coupling
+ * into the update -- which rotating and shifting the sample into the body frame with the current mean, before an update with
+ * a state-selecting model, discards.  The measurement space is R^m, m = 1 or 3.  q = the state's orientation (body -> nav),
+ * R(q) x = the rotation of x by q (Eigen's _transformVector), R(q)^T x = the rotation by q^-1 = conj(q) / |q|^2.
+ * MOUNT = r[3], the sensor's origin in the body frame, then qs[4] (x, y, z, w), the sensor -> body rotation; POINT = b[3], a
+ * nav-frame vector.  qs is taken as given, as the state's quaternion is.
+ *   id  engine  m  h(X)
+ *   0   Pose    3  p + R(q) r                                  antenna with a lever arm
+ *   1   Pose    1  | (p - b) + R(q) r |                        range to a beacon at b
+ *   2   Pose    3  R(qs)^T (R(q)^T (b - p) - r)                a known point seen in the sensor frame (USBL, landmark)
+ *   3   Pose    3  R(qs)^T (v + omega x r)                     velocity at the sensor, sensor frame (v, omega: body frame)
+ *   4   Pose    3  R(q) v                                      nav-frame velocity
+ *   5   Orient  3  R(qs)^T (R(q)^T v + (w_gyro - b_g) x r)     the same for OrientationState; w_gyro = the latched gyro input
+ *   6   Orient  3  R(qs)^T R(q)^T b                            a nav-frame direction seen from the sensor (magnetometer, sun)
+ *   7   Orient  3  R(q)^T (0, 0, g) + b_a                      accelerometer at rest (g, b_a from the state)
+ * A model reads only what its h names: POSITION / RANGE r; POINT r, qs; the VELOCITY models r, qs; NAV_VECTOR qs; and b where
+ * it appears.  Entries a model does not read -- z[m ...], Q outside the leading m x m, the rest of mount / point -- are never
+ * used and may be NaN.  A negative per-filter id: no measurement for that filter (untouched, INACTIVE); so is an id of the
+ * other engine's models or beyond 7.  Such a UNIFORM id is UKFB_ERR_WRONG_MODEL.
+ * Per filter the steps are those of ukf::update:
+ *   1. L = chol(Sigma), sigma points X_i, Z_i = h(X_i);
+ *   2. z-bar = the iterated mean from Z_0 (mean_tol / mean_max_iter; on a vector space it moves once and confirms);
+ *   3. S = 1/2 sum dz_i dz_i^T + Q;  C = 1/2 sum (X_i (-) mu) dz_i^T  (D x m; X_j+- (-) mu = +-L col j, which the kernel uses);
+ *   4. S = Ls Ls^T; Y = C Ls^-T, so that K = Y Ls^-1 and K S K^T = Y Y^T;
+ *   5. nu = z - z-bar, y = Ls^-1 nu, d^2 = nu^T S^-1 nu = |y|^2, ln det S = sum ln of the pivots;
+ *   6. the gate of ukfb_update_dev (gate_chi2 < 0: accept; else d^2 <= gate_chi2): REJECTED_GATE keeps the state, the outputs
+ *      are still written;
+ *   7. Sigma~ = Sigma - Y Y^T; (mu, Sigma) = applyDelta(mu, Sigma~, Y y), the update's own commit.
+ * commit = 1: mean, covariance and the engine's own status array are written.  commit = 0: READ-ONLY like
+ * ukfb_innovation_dev -- mean, covariance, times, latches, noise and the engine's status keep every bit, only `out` is written
+ * (the same numbers: every step above still runs).
+ * Status of THIS call (out->status, and with commit = 1 the engine's status array):
+ *   UNINITIALISED       the filter is uninitialised;
+ *   INACTIVE            no valid model id for this filter;
+ *   ERR_NONFINITE_MEAS  a non-finite value among the first m of z, the leading m x m of Q or the mount / point entries the
+ *                       filter's model reads;
+ *   ERR_CHOLESKY        Sigma, S or (an accepted update's) Sigma~ is not positive definite;
+ *   WARN_MEAN_NOCONV    the mean iteration hit its cap;
+ *   REJECTED_GATE       the gate rejected the update.
+ * A filter with one of the first four keeps its state bit for bit and writes NaN to its float outputs (padding entries: 0); it
+ * never changes a bit of another filter.  Stream-ordered, no host synchronisation, no allocation at call time.  The same kernel
+ * serves every lanes_per_filter setting; fp32 engines compute in fp32, with wide_arithmetic in fp64 (stored fp32).  Device
+ * groups: per shard through ukfb_group_shard. */
+enum ukfb_sensor_model {
+    UKFB_SENSOR_NONE = -1,
+    UKFB_SENSOR_POSE_POSITION = 0,
+    UKFB_SENSOR_POSE_RANGE = 1,
+    UKFB_SENSOR_POSE_POINT = 2,
+    UKFB_SENSOR_POSE_VELOCITY = 3,
+    UKFB_SENSOR_POSE_NAV_VELOCITY = 4,
+    UKFB_SENSOR_ORIENT_VELOCITY = 5,
+    UKFB_SENSOR_ORIENT_NAV_VECTOR = 6,
+    UKFB_SENSOR_ORIENT_SPECIFIC_FORCE = 7
+};
+typedef struct ukfb_sensor_in {   /* device pointers in engine precision; the *_uniform values are host doubles, by value */
+    const int32_t* model_dev;     /* [capacity] model id per filter, or NULL: the call's model_uniform serves every filter */
+    const void*    z_dev;         /* [capacity][3]  the first m entries are read                                          */
+    const void*    Q_dev;         /* [capacity][9] row-major 3x3, or ONE 3x3 with q_is_uniform; the lower triangle of the
+                                     leading m x m block is what the factorisation reads (as ukfb_update_dev)             */
+    int            q_is_uniform;
+    const void*    mount_dev;     /* [capacity][7] r, then qs (x, y, z, w); NULL: mount_uniform serves every filter       */
+    double         mount_uniform[7];
+    const void*    point_dev;     /* [capacity][3]; NULL: point_uniform serves every filter                               */
+    double         point_uniform[3];
+} ukfb_sensor_in;
+typedef struct ukfb_sensor_out {  /* device pointers, engine precision; any may be NULL                                  */
+    void*     z_pred;   /* [capacity][3]  z-bar: first m entries (rest 0)                                                */
+    void*     S;        /* [capacity][9]  row-major 3x3, leading m x m block = S, rest 0                                 */
+    void*     innov;    /* [capacity][3]  nu = z - z-bar, first m entries (rest 0)                                       */
+    void*     maha;     /* [capacity]     d^2 = nu^T S^-1 nu                                                             */
+    void*     loglik;   /* [capacity]     -0.5 (d^2 + ln det S + m ln 2 pi)                                              */
+    uint32_t* status;   /* [capacity]     UKFB_ST_* of THIS call                                                         */
+} ukfb_sensor_out;
+/* out may be NULL with commit = 1 */
+int ukfb_update_sensor_dev(ukfb_engine* e, int model_uniform, const ukfb_sensor_in* in, int commit, const ukfb_sensor_out* out);
+/* host arrays of doubles: z [capacity][3], Q [capacity][3][3]; model_per_filter [capacity] or NULL (then `model`); mount
+ * [capacity][7] or NULL, then mount_uniform [7] (NULL: r = 0, qs the identity); point [capacity][3] or NULL, then point_uniform
+ * [3] (NULL: 0).  z_pred [capacity][3], S [capacity][3][3], innov [capacity][3], maha / loglik / status [capacity]: any may be
+ * NULL.  Synchronises. */
+int ukfb_update_sensor(ukfb_engine* e, int model, const int32_t* model_per_filter /* or NULL */, const double* z, const double* Q,
+                       const double* mount /* or NULL */, const double* mount_uniform /* or NULL */,
+                       const double* point /* or NULL */, const double* point_uniform /* or NULL */, int commit,
+                       double* z_pred, double* S, double* innov, double* maha, double* loglik, uint32_t* status);
+
 
 /* ---- device groups: one host process, several MI355X ------------------------------------------------------------------ */
 /* north_star's multi-GPU shape for a C++ host.  The filters of a batch are independent -- every filter of the reference owns

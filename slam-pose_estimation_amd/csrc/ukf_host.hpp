@@ -347,6 +347,68 @@ inline void body_state_to_measurement(const double* rec, double* z, double* Qz) 
             for (int c = 0; c < 3; ++c) Qz[(3 * b + r) * 12 + 3 * b + c] = rec[13 + 9 * b + 3 * r + c];
 }
 
+// ---- sensor-frame measurements (ukfb_update_sensor_dev) -------------------------------------------------------------------
+// Measurement models with a mount (lever arm r, sensor -> body rotation qs) and / or a nav-frame point b: ids 0 ... 4 are the
+// Pose engine's, 5 ... 7 the OrientationState engine's (UKFB_SENSOR_*).  Bit id of each set: the model reads that input.
+constexpr int SENSOR_MODELS = 8, SENSOR_FILTERS_PER_GROUP = 4;
+constexpr unsigned SENSOR_READS_LEVER = 0x2fu;      // POSE_POSITION, POSE_RANGE, POSE_POINT, POSE_VELOCITY, ORIENT_VELOCITY
+constexpr unsigned SENSOR_READS_ROTATION = 0x6cu;   // POSE_POINT, POSE_VELOCITY, ORIENT_VELOCITY, ORIENT_NAV_VECTOR
+constexpr unsigned SENSOR_READS_POINT = 0x46u;      // POSE_RANGE, POSE_POINT, ORIENT_NAV_VECTOR
+constexpr bool sensor_model_ok(int engine_model, int64_t id) {
+    return engine_model == UKFB_MODEL_POSE ? (id >= UKFB_SENSOR_POSE_POSITION && id <= UKFB_SENSOR_POSE_NAV_VELOCITY)
+                                           : (id >= UKFB_SENSOR_ORIENT_VELOCITY && id <= UKFB_SENSOR_ORIENT_SPECIFIC_FORCE);
+}
+// dimension of the measurement space (0: no such model)
+constexpr int sensor_meas_dim(int64_t id) { return (id < 0 || id >= SENSOR_MODELS) ? 0 : (id == UKFB_SENSOR_POSE_RANGE ? 1 : 3); }
+constexpr bool sensor_reads_lever(int64_t id) { return id >= 0 && id < SENSOR_MODELS && ((SENSOR_READS_LEVER >> id) & 1u) != 0; }
+constexpr bool sensor_reads_rotation(int64_t id) { return id >= 0 && id < SENSOR_MODELS && ((SENSOR_READS_ROTATION >> id) & 1u) != 0; }
+constexpr bool sensor_reads_point(int64_t id) { return id >= 0 && id < SENSOR_MODELS && ((SENSOR_READS_POINT >> id) & 1u) != 0; }
+// The record of one filter's inputs as the kernel stages it: z (3), Q row-major (9), mount r then qs (7), point (3); entry i is
+// read by model id iff sensor_input_used(id, i).  An entry that is not read is replaced by its neutral value (0; the w of qs: 1)
+// before anything computes with it, so that it may hold anything, NaN included.
+constexpr int SENSOR_INPUT_Z = 0, SENSOR_INPUT_Q = 3, SENSOR_INPUT_MOUNT = 12, SENSOR_INPUT_POINT = 19, SENSOR_INPUT_SCALARS = 22;
+constexpr bool sensor_input_used(int64_t id, int i) {
+    const int m = sensor_meas_dim(id);
+    return i < 0 ? false
+         : i < SENSOR_INPUT_Q ? i < m
+         : i < SENSOR_INPUT_MOUNT ? ((i - SENSOR_INPUT_Q) / 3 < m && (i - SENSOR_INPUT_Q) % 3 < m)
+         : i < SENSOR_INPUT_MOUNT + 3 ? sensor_reads_lever(id)
+         : i < SENSOR_INPUT_POINT ? sensor_reads_rotation(id)
+         : i < SENSOR_INPUT_SCALARS ? sensor_reads_point(id) : false;
+}
+constexpr double sensor_input_neutral(int i) { return i == SENSOR_INPUT_MOUNT + 6 ? 1.0 : 0.0; }
+// per_filter_models: the ids come from a device array (checked per filter by the kernel: an id the engine's model does not have
+// marks the filter INACTIVE); otherwise the one id must be the engine model's
+inline Verdict check_sensor_args(int engine_model, bool per_filter_models, int model_uniform, const ukfb_sensor_in* in, int commit,
+                                 const ukfb_sensor_out* out) {
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    if (!in->z_dev || !in->Q_dev) return {UKFB_ERR_INVALID_ARG, "z_dev and Q_dev must not be NULL"};
+    if (in->q_is_uniform != 0 && in->q_is_uniform != 1) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
+    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    if (!per_filter_models && !sensor_model_ok(engine_model, model_uniform))
+        return {UKFB_ERR_WRONG_MODEL, "sensor model id not valid for this engine (Pose: 0 ... 4, OrientationState: 5 ... 7)"};
+    if (commit == 0 && (!out || (!out->z_pred && !out->S && !out->innov && !out->maha && !out->loglik && !out->status)))
+        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
+    return {};
+}
+// LDS of one filter, in scalars of the compute type (ukf_sensor_meas.hpp, SensorLayout): the factor region with its reciprocal
+// pivots, the delta table of the commit (2 D + 1 rows; the D x 3 half differences W and the D x 3 solved cross-covariance Y
+// alias it, four scalars a row), the state's record (mean padded to 16, packed covariance padded to even), the input record
+// (32) and the sink of lane-predicated stores (16); rounded up to a multiple of four so that every filter's slice starts
+// 16-byte aligned in either precision.  Every scalar the kernel reads is one it wrote: the pads are never read.
+constexpr int sensor_filter_scalars(int S, int D) {
+    return S > 16 ? -1 : (D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 32 + 16 + 3) / 4 * 4;
+}
+struct SensorGeometry {
+    int64_t grid;    // workgroups of four filters
+    int lds_bytes;   // dynamic LDS of a workgroup
+};
+// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
+inline SensorGeometry sensor_geometry(int S, int D, int64_t capacity, size_t compute_size) {
+    return {(capacity + SENSOR_FILTERS_PER_GROUP - 1) / SENSOR_FILTERS_PER_GROUP,
+            int(size_t(SENSOR_FILTERS_PER_GROUP) * sensor_filter_scalars(S, D) * compute_size)};
+}
+
 // ---- packed covariances of the host-array forms ---------------------------------------------------------------------------
 // `count` row-major D x D matrices <-> their lower triangles, row by row (entry (r, c), c <= r, at r (r + 1) / 2 + c of D (D + 1) / 2).
 // pack_lower reads the lower triangle only; unpack_symmetric writes both triangles.

@@ -58,6 +58,8 @@ EXPORTS = [
     "ukfb_history_push_dev", "ukfb_smooth_dev", "ukfb_smooth",
     # joint state-block measurements: update / fuse with full covariance, covariance intersection, track-to-track distance
     "ukfb_update_state_dev", "ukfb_update_state", "ukfb_pose_update_body_states",
+    # sensor-frame measurements: lever arms, ranges, landmark fixes, nav-frame vectors
+    "ukfb_update_sensor_dev", "ukfb_update_sensor",
     # device groups (one process, several GPUs)
     "ukfb_group_shard_range", "ukfb_group_create", "ukfb_group_destroy", "ukfb_group_size", "ukfb_group_shard",
     "ukfb_group_set_config", "ukfb_group_initialize", "ukfb_group_get_state", "ukfb_group_get_status",
@@ -76,6 +78,12 @@ BLOCK_POSE_ALL = 15
 BLOCK_ORIENT_ORIENTATION, BLOCK_ORIENT_VELOCITY, BLOCK_ORIENT_BIAS_GYRO, BLOCK_ORIENT_BIAS_ACC, BLOCK_ORIENT_GRAVITY = 1, 2, 4, 8, 16
 BLOCK_ORIENT_ALL = 31
 
+# models of ukfb_update_sensor_dev: 0 ... 4 the Pose engine's, 5 ... 7 the OrientationState engine's
+SENSOR_NONE = -1
+SENSOR_POSE_POSITION, SENSOR_POSE_RANGE, SENSOR_POSE_POINT, SENSOR_POSE_VELOCITY, SENSOR_POSE_NAV_VELOCITY = 0, 1, 2, 3, 4
+SENSOR_ORIENT_VELOCITY, SENSOR_ORIENT_NAV_VECTOR, SENSOR_ORIENT_SPECIFIC_FORCE = 5, 6, 7
+SENSOR_MOUNT_IDENTITY = (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0)   # r = 0, qs = (0, 0, 0, 1)
+
 
 class Config(C.Structure):
     _fields_ = [("mean_tol", C.c_double), ("mean_max_iter", C.c_int32), ("gate_chi2", C.c_double),
@@ -93,6 +101,19 @@ class InnovationOut(C.Structure):
 class StateMeasOut(C.Structure):
     """ukfb_state_meas_out: device pointers in engine precision (status uint32), any may be NULL"""
     _fields_ = [("maha", C.c_void_p), ("loglik", C.c_void_p), ("status", C.c_void_p)]
+
+
+class SensorIn(C.Structure):
+    """ukfb_sensor_in: device pointers in engine precision (model_dev int32); the *_uniform values are host doubles"""
+    _fields_ = [("model_dev", C.c_void_p), ("z_dev", C.c_void_p), ("Q_dev", C.c_void_p), ("q_is_uniform", C.c_int),
+                ("mount_dev", C.c_void_p), ("mount_uniform", C.c_double * 7), ("point_dev", C.c_void_p),
+                ("point_uniform", C.c_double * 3)]
+
+
+class SensorOut(C.Structure):
+    """ukfb_sensor_out: device pointers in engine precision (status uint32), any may be NULL"""
+    _fields_ = [("z_pred", C.c_void_p), ("S", C.c_void_p), ("innov", C.c_void_p), ("maha", C.c_void_p),
+                ("loglik", C.c_void_p), ("status", C.c_void_p)]
 
 
 class UkfbError(RuntimeError):
@@ -514,6 +535,40 @@ class BatchUKF:
         _chk(self._lib.ukfb_pose_update_body_states(self._h, C.c_uint32(int(block_mask)), _pd(rec),
                                                     act.ctypes.data_as(C.POINTER(C.c_uint8)) if act is not None else None),
              "ukfb_pose_update_body_states")
+
+    # ---- sensor-frame measurements: z [capacity, 3], Q [capacity, 9] (or 9 scalars), mount [capacity, 7], point [capacity, 3]
+    def update_sensor_dev(self, model: int, z_dev, Q_dev, q_is_uniform: bool = False, model_dev=None, mount_dev=None,
+                          mount=SENSOR_MOUNT_IDENTITY, point_dev=None, point=(0.0, 0.0, 0.0), commit: bool = True, z_pred=None,
+                          S=None, innov=None, maha=None, loglik=None, status=None):
+        """ukfom's update through a sensor-frame model (SENSOR_* constants; model_dev int32 [capacity] = an id per filter,
+        negative: none).  mount = r[3] then qs[4] (x, y, z, w), point = b[3]: host values for the whole batch, or device
+        arrays per filter (mount_dev / point_dev).  commit=False is read-only: only the keyword outputs (device buffers in
+        engine precision, status uint32 / int32) are written.  Stream-ordered."""
+        ptr = lambda x: None if x is None else _devptr(x).value
+        sin = SensorIn(ptr(model_dev), ptr(z_dev), ptr(Q_dev), 1 if q_is_uniform else 0, ptr(mount_dev),
+                       (C.c_double * 7)(*[float(v) for v in mount]), ptr(point_dev), (C.c_double * 3)(*[float(v) for v in point]))
+        out = SensorOut(ptr(z_pred), ptr(S), ptr(innov), ptr(maha), ptr(loglik), ptr(status))
+        _chk(self._lib.ukfb_update_sensor_dev(self._h, C.c_int(int(model)), C.byref(sin), C.c_int(1 if commit else 0), C.byref(out)),
+             "ukfb_update_sensor_dev")
+
+    def update_sensor(self, model, z, Q, mount=SENSOR_MOUNT_IDENTITY, point=(0.0, 0.0, 0.0), commit: bool = True):
+        """Host arrays: z [capacity, 3], Q [capacity, 3, 3]; model an int or an int32 array [capacity]; mount [7] or
+        [capacity, 7], point [3] or [capacity, 3].  Returns a dict of NumPy arrays: z_pred [n, 3], S [n, 3, 3], innov [n, 3],
+        maha [n], loglik [n], status [n]; synchronises"""
+        n = self.capacity
+        z = _f64(z, (n, 3)); Q = _f64(Q, (n, 3, 3))
+        per = None if np.isscalar(model) else np.ascontiguousarray(model, dtype=np.int32).reshape(n)
+        mount = _f64(mount); point = _f64(point)
+        mp, mu_ = (mount.reshape(n, 7), None) if mount.ndim == 2 else (None, mount.reshape(7))
+        pp, pu = (point.reshape(n, 3), None) if point.ndim == 2 else (None, point.reshape(3))
+        o = {"z_pred": np.empty((n, 3)), "S": np.empty((n, 3, 3)), "innov": np.empty((n, 3)), "maha": np.empty(n),
+             "loglik": np.empty(n), "status": np.empty(n, dtype=np.uint32)}
+        _chk(self._lib.ukfb_update_sensor(self._h, C.c_int(0 if per is not None else int(model)),
+                                          per.ctypes.data_as(C.POINTER(C.c_int32)) if per is not None else None, _pd(z), _pd(Q),
+                                          _pd(mp), _pd(mu_), _pd(pp), _pd(pu), C.c_int(1 if commit else 0), _pd(o["z_pred"]),
+                                          _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]),
+                                          o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_update_sensor")
+        return o
 
     # ---- fused cycle
     def cycle(self, dt: float, meas_model: int, z, Q):
