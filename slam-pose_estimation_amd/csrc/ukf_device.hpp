@@ -71,6 +71,20 @@ UKFB_DEV unsigned long long lanes_gt(float x, float bound) {
     asm("v_cmp_lt_f32_e64 %0, %1, %2" : "=s"(m) : "s"(bound), "v"(x));
     return m;
 }
+// x > 0 and finite: the classes +subnormal | +normal (v_cmp_class bits 7, 8).  For every finite x this is lanes_gt(x, 0); +Inf and
+// NaN are both false.  One compare, like lanes_gt (the class mask travels in an SGPR).
+UKFB_DEV unsigned long long lanes_pos_finite(double x) {
+    unsigned long long m;
+    asm("v_cmp_class_f64_e64 %0, %1, %2" : "=s"(m) : "v"(x), "s"(0x180));
+    return m;
+}
+UKFB_DEV unsigned long long lanes_pos_finite(float x) {
+    unsigned long long m;
+    asm("v_cmp_class_f32_e64 %0, %1, %2" : "=s"(m) : "v"(x), "s"(0x180));
+    return m;
+}
+UKFB_DEV bool pos_finite(double x) { return __builtin_amdgcn_class(x, 0x180); }
+UKFB_DEV bool pos_finite(float x) { return __builtin_amdgcn_classf(x, 0x180); }
 UKFB_DEV bool lane_of(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 
 // ---------------------------------------------------------------------------------------------

@@ -135,13 +135,13 @@ template <int G> UKFB_DEV float gshfl(float v, int src) { return __shfl(v, src, 
 // Row-per-lane right-looking Cholesky.  Lane l < D holds row l (entries 0..l) in a[]; column k of
 // the factor is published to Lc (column-major, stride LS, zeros above the diagonal) as soon as it
 // is final and read back (LDS broadcast) for the trailing update.  false: a pivot was <= 0
-// (Eigen LLT: NumericalIssue).
+// (Eigen LLT: NumericalIssue) or not finite (+Inf has rsqrt 0: the diagonal would come out as Inf * 0).
 template <class T, int D, int LS, int G> UKFB_DEV bool chol_rows_to_lds(T (&a)[D], T* Lc, int l, int dum) {
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < D; ++k) {
         const T akk = gshfl<G>(a[k], k);
-        ok = ok && (akk > T(0));
+        ok = ok && pos_finite(akk);
         const T inv = fast_rsqrt(akk);
         const T d = akk * inv;
         const T lk = (l > k) ? a[k] * inv : ((l == k) ? d : T(0));

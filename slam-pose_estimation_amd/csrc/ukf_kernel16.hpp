@@ -457,7 +457,8 @@ template <class T, class M> struct AsmTab {
 // broadcasts (lane c's A[c][k] for the trailing update, lane k's pivot); column k is published UNSCALED
 // (v_l = a_l[k], pivot included) with one LDS write for the consumers.  L[c][k] = Lc[k*LS+c]*rs_k
 // for c >= k (entries above the diagonal are garbage and must be masked by the consumer).
-// Returns this lane's rs_l (lane l < D); ok = all pivots > 0.
+// Returns this lane's rs_l (lane l < D); ok = all pivots > 0 and finite (a +Inf pivot has rsqrt 0: the column would come out as
+// Inf * 0; tests/test_gpu_chol_primitive.py).
 // ---------------------------------------------------------------------------------------------
 // scheduling fence: keeps the machine scheduler from hoisting the next phase's loads / ALU work
 // across this point (it otherwise trades ~2x the registers for ILP and ends up spilling)
@@ -516,7 +517,7 @@ template <class T, int D, int LS, int KS = D, int PUB = KS> UKFB_DEV T chol16(T 
         dpp_hazard_fence(a[k]);   // written by the previous step's fused FMA, read through DPP from here on
         if constexpr (k >= PUB) {   // not published: checked as it comes (the published pivots are checked once, below)
             const T akk = row_bcast<k>(a[k]);
-            good = good && (akk > T(0));
+            good = good && pos_finite(akk);
         }
         const T nt = -(a[k] * rcp_bcast<k>(a[k]));   // trailing update needs 1/pivot only; 1/sqrt is taken once, at the end
         if constexpr (k + 1 < KS) {
@@ -535,7 +536,7 @@ template <class T, int D, int LS, int KS = D, int PUB = KS> UKFB_DEV T chol16(T 
     // pivot k is final once step k - 1 has run and is what column k publishes on its diagonal: lane l < PUB checks its own,
     // one compare for all of them instead of one broadcast + compare per step (lanes >= PUB of every row: a constant mask)
     constexpr unsigned long long NO_PIVOT = ((0xFFFFull << PUB) & 0xFFFFull) * 0x0001000100010001ull;
-    ok = good && row_all(NO_PIVOT | lanes_gt(pv, T(0)));
+    ok = good && row_all(NO_PIVOT | lanes_pos_finite(pv));
     return fast_rsqrt(pv);   // this lane's column scale 1/sqrt(pivot_l) (lanes >= PUB: the last published one)
 }
 

@@ -1,0 +1,432 @@
+"""Reference, error bounds and input families for the device Cholesky (tests/test_gpu_chol_primitive.py,
+tests/test_chol_reference.py).  Nothing here needs a GPU.
+
+The reference of a matrix is the plain Cholesky factor of the T-rounded input: mpmath at 40 digits for fp64, float64 for
+fp32 (unit roundoff 2^29 times smaller).
+
+The bound B(T, D, j)
+--------------------
+chol16 (slam-pose_estimation_amd/csrc/ukf_kernel16.hpp) runs, for k = 0 .. KS-1 and every row i,
+
+    r_k  = rcp(p_k)(1 + dr),  |dr| <= rho        p_k = a_kk^(k), the pivot
+    t_ik = -fl(a_ik^(k) r_k)                     one rounding, u
+    a_ic^(k+1) = fma(v_ck, t_ik, a_ic^(k))       one rounding per step, c > k;  v_ck = a_ck^(k) is lane c's entry
+
+keeps the columns unscaled (v_ik = a_ik^(k)) and returns rs_k = rsqrt(p_k)(1 + ds), |ds| <= sigma.  The consumer's factor is
+L_ik = v_ik rs_k, formed here without rounding.  rho = sigma = 24 eps (fp64), 2 eps (fp32) are the bounds that
+tests/test_gpu_so3_primitives.py pins for fast_rcp and fast_rsqrt (eps = 2u = 2^-52, 2^-23).
+
+Unrolling the recurrence for i >= j (Higham, Accuracy and Stability of Numerical Algorithms, 2nd ed., proof of Thm 10.3
+through Lemma 8.4): entry (i, j) sees at most j + 1 roundings of size u and one reciprocal error per column term, so
+
+    a_ij = v_ij (1 + th_j) + sum_{k<j} v_ik v_jk / p_k (1 + th_k),      |th| <= theta_j := 1 / ((1-u)^(j+1) (1-rho)) - 1,
+
+while (L L^T)_ij = v_ij (1 + ds_j)^2 + sum_{k<j} v_ik v_jk / p_k (1 + ds_k)^2: the update divides by the pivot through rcp,
+the consumer multiplies by rs^2 -- one reciprocal and two rsqrt errors per column term.  With v_ik v_jk / p_k =
+L_ik L_jk / (1 + ds_k)^2:
+
+    |A - L L^T|_ij <= eps_j (|L||L^T|)_ij,    eps_j := (theta_j + 2 sigma + sigma^2) / (1 - sigma)^2      [Thm 10.3 with
+                                                                        gamma_{D+1} replaced; j + 1 <= D < D + 1]
+    (|L||L^T|)_ij <= sqrt((L L^T)_ii (L L^T)_jj) <= sqrt(a_ii a_jj) / (1 - eps_{D-1})                    [Cauchy-Schwarz]
+
+    B(T, D, j) = eps_j / (1 - eps_{D-1})        |A - L L^T|_ij <= B(T, D, min(i, j)) sqrt(a_ii a_jj).
+
+B(fp64, 13, 12) = 78.5 eps = 1.7e-14, B(fp32, 13, 12) = 12.5 eps = 1.5e-6.  The bound is invariant under the two-sided
+diagonal scaling S A S, as the recurrence is up to over- and underflow.
+
+Verdict margin: with H = diag(A)^-1/2 A diag(A)^-1/2 the bound says |dH|_ij <= B, so ||dH||_2 <= D B; a run whose pivots are
+all positive exhibits a positive semi-definite H + dH, hence lambda_min(H) >= -D B, and the induction of Higham Thm 10.7
+(Demmel's condition) gives success for lambda_min(H) > D B.  m(T, D) = D B(T, D, D-1): 1.0e3 eps (fp64), 1.6e2 eps (fp32) at
+D = 13.  Inputs with lambda_min(H) >= m are "clearly PD", with lambda_min(H) <= -m "clearly indefinite"; no family generates
+a matrix in between (tests/test_chol_reference.py asserts it), so no input is ever excluded from a verdict assertion.
+Because the clearly-PD inputs must clear m, the graded-condition family runs in decades of kappa(H) from 1e1 to the last
+decade below 0.1 / u at which lambda_min(H) >= 2 m is certain (cond_decades: 1e12 in fp64, 1e4 in fp32; beyond it a matrix is
+neither clearly PD nor clearly indefinite and no verdict could be asserted) and then, in finer steps, down to
+lambda_min(H) = 1.5 m.  Where a diagonal entry is not positive (the indefinite family at pivot 0, by necessity) H scales by
+|a_ii|.
+
+Forward error (Higham Thm 10.8, Sun's perturbation bound for the Cholesky factor): if A = L L^T, A + dA = (L + dL)(L + dL)^T
+and kappa_2(A) e < 1 with e = ||dA||_F / ||A||_F, then
+
+    ||dL||_F / ||L||_F <= 2^-1/2 kappa_2(A) e / (1 - kappa_2(A) e).
+
+Applied to H, whose factor is the row-scaled factor of A: |dH|_ij <= B gives ||dH||_F <= D B, a unit diagonal gives
+||H||_F >= sqrt D, so e <= sqrt(D) B and
+
+    ||L_H - Lref_H||_F / ||Lref_H||_F <= c kappa_2(H) B,    c = sqrt(D / 2) / (1 - kappa_2(H) sqrt(D) B)
+
+(forward_bound; no statement where kappa_2(H) sqrt(D) B >= 1, which the decades of the family stay clear of).
+"""
+import functools
+import glob
+import math
+import os
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F64, F32 = 0, 1
+DT = {F64: np.float64, F32: np.float32}
+EPS = {F64: 2.0 ** -52, F32: 2.0 ** -23}
+U = {F64: 2.0 ** -53, F32: 2.0 ** -24}
+# relative error bounds of fast_rcp / fast_rsqrt in eps(T): tests/test_gpu_so3_primitives.py, test_primitive_against_40_digits
+PRIM_EPS = {F64: 24.0, F32: 2.0}
+SEED = 20241018
+# two-sided row scales of a state (standard deviations): bias sigmas of 1e-6 beside UTM-sized positions
+SCALE_RANGE = {F64: (-12.0, 6.0), F32: (-6.0, 3.0)}
+FINITE_PD = ("well", "cond", "scale", "block")
+
+
+# ----------------------------------------------------------------------------------------------------------- the bounds
+def eps_term(prec, j):
+    u, rho = U[prec], PRIM_EPS[prec] * EPS[prec]
+    theta = math.expm1(-(j + 1) * math.log1p(-u) - math.log1p(-rho))
+    return (theta + 2 * rho + rho * rho) / (1 - rho) ** 2
+
+
+def B(prec, D, j):
+    """|A - L L^T|_ij <= B(prec, D, min(i, j)) sqrt(a_ii a_jj)  (module docstring)"""
+    return eps_term(prec, j) / (1 - eps_term(prec, D - 1))
+
+
+def margin(prec, D):
+    return D * B(prec, D, D - 1)
+
+
+def B_matrix(prec, D):
+    j = np.minimum.outer(np.arange(D), np.arange(D))
+    return np.vectorize(lambda q: B(prec, D, int(q)))(j)
+
+
+# ----------------------------------------------------------------------------------------------------- reference algebra
+def _mp():
+    import mpmath
+    return mpmath
+
+
+def _mp_chol(a, D, shift=0.0):
+    """lower factor of a - shift I (lists of mpf), None if a pivot is not positive"""
+    mp = _mp()
+    L = [[mp.mpf(0)] * D for _ in range(D)]
+    for j in range(D):
+        s = a[j][j] - shift - sum(L[j][k] * L[j][k] for k in range(j))
+        if not s > 0:
+            return None
+        L[j][j] = mp.sqrt(s)
+        for i in range(j + 1, D):
+            L[i][j] = (a[i][j] - sum(L[i][k] * L[j][k] for k in range(j))) / L[j][j]
+    return L
+
+
+def _mp_rows(A):
+    mp = _mp()
+    return [[mp.mpf(float(x)) for x in r] for r in A]
+
+
+def ref_chol(A, prec):
+    """lower Cholesky factor of one T-rounded matrix, to float64 (fp64: rounded from 40 digits); None if not PD"""
+    D = A.shape[0]
+    if prec == F32:
+        try:
+            return np.linalg.cholesky(A)
+        except np.linalg.LinAlgError:
+            return None
+    mp = _mp()
+    with mp.workdps(40):
+        L = _mp_chol(_mp_rows(A), D)
+        return None if L is None else np.array([[float(x) for x in r] for r in L])
+
+
+def scaled(A):
+    d = 1.0 / np.sqrt(np.abs(np.diagonal(A, axis1=-2, axis2=-1)))
+    return A * d[..., :, None] * d[..., None, :]
+
+
+def lambda_min_H(A, prec):
+    """lambda_min of H = diag(A)^-1/2 A diag(A)^-1/2 of one T-rounded matrix in the reference precision.  fp32: float64
+    eigenvalues.  fp64: the float64 estimate, certified at 40 digits to a relative 1e-2 + an absolute 1e-3 m by two
+    factorisations (H - lo I is positive definite, H - hi I is not); returns the bracket end nearer to zero, the side that
+    makes a classification harder."""
+    D = A.shape[0]
+    if prec == F32:
+        return float(np.linalg.eigvalsh(scaled(A))[0])
+    mp = _mp()
+    est = float(np.linalg.eigvalsh(scaled(A))[0])
+    tol = 1e-2 * abs(est) + 1e-3 * margin(prec, D)
+    with mp.workdps(40):
+        a = _mp_rows(A)
+        d = [1 / mp.sqrt(abs(a[i][i])) for i in range(D)]
+        h = [[a[i][j] * d[i] * d[j] for j in range(D)] for i in range(D)]
+        lo, hi = est - tol, est + tol
+        if _mp_chol(h, D, lo) is None or _mp_chol(h, D, hi) is not None:   # the estimate was off: the eigenvalues themselves
+            return float(min(mp.eigsy(mp.matrix(h), eigvals_only=True)))
+    return hi if est < 0 else lo
+
+
+def classify(A, prec):
+    """+1: lambda_min(H) >= m (clearly PD), -1: lambda_min(H) <= -m (clearly indefinite), 0: in between -- decided in the
+    reference precision: fp32 from float64 eigenvalues, fp64 by factorising H - m I and H + m I at 40 digits"""
+    D = A.shape[0]
+    m = margin(prec, D)
+    if prec == F32:
+        lam = float(np.linalg.eigvalsh(scaled(A))[0])
+        return 1 if lam >= m else (-1 if lam <= -m else 0)
+    mp = _mp()
+    with mp.workdps(40):
+        a = _mp_rows(A)
+        d = [1 / mp.sqrt(abs(a[i][i])) for i in range(D)]
+        h = [[a[i][j] * d[i] * d[j] for j in range(D)] for i in range(D)]
+        if _mp_chol(h, D, mp.mpf(m)) is not None:
+            return 1
+        return -1 if _mp_chol(h, D, -mp.mpf(m)) is None else 0     # H + m I is not positive definite
+
+
+def forward_bound(prec, D, kappa):
+    x = kappa * math.sqrt(D) * B(prec, D, D - 1)
+    return math.inf if x >= 1 else math.sqrt(D / 2.0) / (1 - x) * kappa * B(prec, D, D - 1)
+
+
+def residual(A, L, prec):
+    """A - L L^T of one matrix with L as given (float64 entries), in the reference precision; float64 result"""
+    if prec == F32:
+        return A - L @ L.T
+    mp = _mp()
+    D, K = L.shape
+    with mp.workdps(40):
+        l = _mp_rows(L)
+        R = np.zeros((D, D))
+        for i in range(D):
+            for j in range(i + 1):
+                R[i, j] = R[j, i] = float(mp.mpf(float(A[i, j])) - sum(l[i][k] * l[j][k] for k in range(K)))
+    return R
+
+
+def residual_from_device(A, Lc, rs, prec):
+    """A - L L^T with L[c][k] = Lc[k][c] rs[k] (rows c >= k of the first K = len(rs) columns), everything in the reference
+    precision (fp64: 40 digits, products unrounded); float64 result, lower triangle mirrored"""
+    K, D = Lc.shape
+    if prec == F32:
+        L = np.tril((Lc * rs[:, None]).T)
+        return A - L @ L.T
+    mp = _mp()
+    with mp.workdps(40):
+        l = [[mp.mpf(float(Lc[k, c])) * mp.mpf(float(rs[k])) if c >= k else mp.mpf(0) for k in range(K)] for c in range(D)]
+        R = np.zeros((D, D))
+        for i in range(D):
+            for j in range(i + 1):
+                R[i, j] = R[j, i] = float(mp.mpf(float(A[i, j])) - sum(l[i][k] * l[j][k] for k in range(min(j + 1, K))))
+    return R
+
+
+# ---------------------------------------------------------------------------------------------------- the input families
+def _round(A, prec):
+    A = 0.5 * (A + np.swapaxes(A, -1, -2))
+    return A.astype(DT[prec]).astype(np.float64)
+
+
+def _orth(rng, D):
+    q, r = np.linalg.qr(rng.normal(size=(D, D)))
+    return q * np.sign(np.diag(r))
+
+
+def _unit_diag_with_lmin(rng, D, kappa, target=None):
+    """unit-diagonal H with condition about kappa; with target: its smallest eigenvalue moved to about target"""
+    lam = 10.0 ** (-np.log10(kappa) * np.sort(rng.uniform(0, 1, D)))
+    lam[0], lam[-1] = 1.0, 1.0 / kappa
+    q = _orth(rng, D)
+    H = scaled((q * lam) @ q.T)
+    if target is not None:
+        for _ in range(3):
+            w, v = np.linalg.eigh(H)
+            H = scaled(H + (target - w[0]) * np.outer(v[:, 0], v[:, 0]))
+    return H
+
+
+def _golden(D):
+    out = []
+    for f in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "*.npz"))):
+        z = np.load(f)
+        for k in z.files:
+            a = z[k]
+            if a.ndim == 3 and a.shape[1:] == (D, D) and k != "Q":
+                out.append(a)
+    return np.concatenate(out)
+
+
+def _synth_like(rng, D, n):
+    """Sigma = S (I + 0.1 G G^T / D) S as slam-pose_estimation_amd/synth.py draws its initial covariances"""
+    std = np.array([0.1] * 3 + [0.05] * 3 + [0.1] * 3 + [0.02] * 3 + [0.5] * (D - 12))
+    G = rng.uniform(-1, 1, (n, D, D))
+    return std[:, None] * (np.eye(D) + 0.1 * G @ np.swapaxes(G, 1, 2) / D) * std[None, :]
+
+
+def cond_decades(prec, D):
+    """decades of kappa(H) of the graded-condition family: 1e1 .. the last one below 0.1 / u whose draws all clear the margin"""
+    top = int(math.floor(math.log10(0.1 / U[prec])))
+    # H = S C S with the eigenvalues of C in [1 / kappa, 1] and S = diag(C)^-1/2 >= I: lambda_min(H) >= 1 / kappa
+    safe = int(math.floor(math.log10(1.0 / (2.0 * margin(prec, D)))))
+    return list(range(1, min(top, safe) + 1))
+
+
+@functools.lru_cache(maxsize=None)
+def family(name, prec, D):
+    """(m, D, D) float64 matrices, symmetric and exact in T.  Deterministic."""
+    rng = np.random.default_rng([SEED, prec, D, sum(map(ord, name))])
+    m = margin(prec, D)
+    if name == "well":
+        g = _golden(D)
+        return _round(np.concatenate([_synth_like(rng, D, 200), g[np.isfinite(g).all(axis=(1, 2))]]), prec)
+    if name == "cond":
+        Hs = [_unit_diag_with_lmin(rng, D, 10.0 ** e) for e in cond_decades(prec, D) for _ in range(16)]
+        Hs += [_unit_diag_with_lmin(rng, D, 10.0 ** rng.uniform(2, 4), t * m) for t in (1.5, 2, 3, 5, 10, 30, 100) for _ in range(8)]
+        return _round(np.array(Hs), prec)
+    if name == "scale":
+        lo, hi = SCALE_RANGE[prec]
+        out = []
+        for i in range(200):
+            H = _unit_diag_with_lmin(rng, D, 10.0 ** rng.uniform(1, 3))
+            s = 10.0 ** rng.uniform(lo, hi, D)
+            if i % 4 == 0:
+                s[rng.permutation(D)[:2]] = 10.0 ** np.array([lo, hi])    # both ends of the range in one matrix
+            out.append(s[:, None] * H * s[None, :])
+        return _round(np.array(out), prec)
+    if name == "block":
+        out = []
+        for i in range(70):     # block diagonal, as after import_body_states: 3 x 3 blocks (and the gravity scalar) of their own scales
+            A = np.zeros((D, D))
+            for b in range(0, D, 3):
+                k = min(3, D - b)
+                g = rng.normal(size=(k, k + 2))
+                A[b:b + k, b:b + k] = (g @ g.T) * 10.0 ** rng.uniform(-4, 1)
+            out.append(A)
+        nz = {F64: (-9.0, -2.0), F32: (-2.5, -1.0)}[prec]
+        for i in range(70):     # Gram matrix of fewer vectors than rows, plus noise
+            g = rng.normal(size=(D, D - 1 - i % 4))
+            out.append(g @ g.T / D + np.diag(10.0 ** rng.uniform(*nz, D)))
+        for i in range(70):     # downdated Sigma - Y Y^T, one direction almost removed
+            H = _unit_diag_with_lmin(rng, D, 10.0 ** rng.uniform(1, 2))
+            L = np.linalg.cholesky(H)
+            w = rng.normal(size=D)
+            w *= math.sqrt(1.0 - 10.0 ** rng.uniform(*nz)) / np.linalg.norm(w)
+            out.append(H - np.outer(L @ w, L @ w))
+        return _round(np.array(out), prec)
+    if name == "indef":
+        # L diag(1 .. 1, -s, 1 .. 1) L^T: the pivot at position p is the first that fails, every leading block before it is PD
+        out = []
+        for p in range(D):
+            for i in range(16):
+                H = _unit_diag_with_lmin(rng, D, 10.0 ** rng.uniform(1, 2))
+                L = np.linalg.cholesky(H)
+                d = np.ones(D)
+                x = np.linalg.solve(L.T, np.eye(D)[p])
+                # x^T A x = -s: lambda_min(A) <= -s / |x|^2 ; half of the draws close to the margin, half far from it
+                d[p] = -(10.0 ** rng.uniform(0.5, 1.5) * m * float(x @ x) if i % 2 else 10.0 ** rng.uniform(-3, 0))
+                out.append((L * d) @ L.T)
+        return _round(np.array(out), prec)
+    raise KeyError(name)
+
+
+def indef_position(D):
+    """position of the first failing pivot of every record of the indefinite family"""
+    return np.repeat(np.arange(D), 16)
+
+
+def tri_positions(D):
+    return [(r, c) for r in range(D) for c in range(r + 1)]
+
+
+@functools.lru_cache(maxsize=None)
+def special(name, prec, D):
+    """non-finite and exactly singular inputs: (matrices, positions (r, c) per record)"""
+    base = family("well", prec, D)[3].copy()
+    out, pos = [], []
+    if name in ("nan", "inf"):
+        v = np.nan if name == "nan" else np.inf
+        for r, c in tri_positions(D):
+            A = base.copy()
+            A[r, c] = A[c, r] = v
+            out.append(A)
+            pos.append((r, c))
+    elif name == "zero_row":
+        for p in range(D):
+            A = base.copy()
+            A[p, :] = 0.0
+            A[:, p] = 0.0
+            out.append(A)
+            pos.append((p, p))
+    elif name == "dup_row":
+        for p in range(D - 1):
+            for q in (p + 1, D - 1):
+                A = base.copy()
+                A[q, :] = A[p, :]
+                A[:, q] = A[:, p]
+                A[q, q] = A[p, p]
+                A[p, q] = A[q, p] = A[p, p]
+                out.append(A)
+                pos.append((q, p))
+    else:
+        raise KeyError(name)
+    return np.array(out), np.array(pos)
+
+
+@functools.lru_cache(maxsize=None)
+def classes(name, prec, D, lead=None):
+    """classify() of every record of a family (of its leading lead x lead block)"""
+    A = family(name, prec, D)
+    k = D if lead is None else lead
+    return np.array([classify(a[:k, :k], prec) for a in A])
+
+
+# ----------------------------------------------------------------------------------- the published recurrence, emulated in T
+def emulate(A, prec, rng, KS=None, PUB=None):
+    """The recurrence chol16 publishes, in NumPy arithmetic of T over a batch: trailing update by a rcp(pivot), columns kept
+    unscaled, rs = rsqrt(pivot) at the end; rcp and rsqrt carry random relative errors up to the pinned primitive bounds (drawn
+    before the rounding to T, which is part of the bound).  Returns (v: (n, K, D) unscaled columns with zeros above the diagonal,
+    rs: (n, K), ok: (n,)) for K = PUB columns; ok looks at the first KS pivots."""
+    T = DT[prec]
+    n, D, _ = A.shape
+    KS = D if KS is None else KS
+    PUB = KS if PUB is None else PUB
+    amp = PRIM_EPS[prec] * EPS[prec] - U[prec]
+
+    def prim(x):
+        with np.errstate(all="ignore"):
+            return (x.astype(np.float64) * (1.0 + amp * rng.uniform(-1, 1, x.shape))).astype(T)
+    a = A.astype(T).copy()
+    ok = np.ones(n, dtype=bool)
+    with np.errstate(all="ignore"):
+        for k in range(KS):
+            p = a[:, k, k].copy()
+            ok &= p > 0
+            r = prim(1.0 / p.astype(np.float64))
+            t = -(a[:, :, k] * r[:, None])                       # (n, D): every row's multiplier, rounded to T
+            col = a[:, :, k].copy()                               # v_ck
+            for c in range(k + 1, KS):
+                # fused multiply-add: the product is exact in float64 for fp32; for fp64 the separate rounding of the product
+                # stays inside the same u per step that the bound charges twice (t and the update)
+                if prec == F32:
+                    a[:, :, c] = (a[:, :, c].astype(np.float64) + col[:, c, None].astype(np.float64) * t.astype(np.float64)).astype(T)
+                else:
+                    a[:, :, c] = _fma64(col[:, c, None], t, a[:, :, c])
+        piv = np.stack([a[:, k, k] for k in range(PUB)], axis=1)
+        rs = prim(1.0 / np.sqrt(piv.astype(np.float64)))
+    v = np.stack([np.where(np.arange(D)[None, :] >= k, a[:, :, k], T(0)) for k in range(PUB)], axis=1)
+    return v.astype(np.float64), rs.astype(np.float64), ok
+
+
+def _split(x):
+    c = 134217729.0 * x
+    hi = c - (c - x)
+    return hi, x - hi
+
+
+def _fma64(x, y, z):
+    """round(x y + z) in float64 up to a relative 2^-100: the product by Dekker's error-free split, the sum compensated"""
+    p = x * y
+    xh, xl = _split(x)
+    yh, yl = _split(y)
+    e = ((xh * yh - p) + xh * yl + xl * yh) + xl * yl          # x y = p + e exactly
+    s = p + z
+    bb = s - p
+    err = (p - (s - bb)) + (z - bb)                              # p + z = s + err exactly
+    return s + (err + e)
