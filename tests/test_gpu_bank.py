@@ -6,6 +6,14 @@ engine and on the weights as the device arrays hold them, so that fp32 storage r
 Parity bound: |x - ref| <= tol (1 + |ref|), tol = the README's parity gates 1e-9 (fp64) / 1e-4 (fp32); fp32 engines with
 wide_arithmetic compute in fp64 and store fp32: 1e-9 + 2^-23.  The maxima measured on an MI355X are in profiles/bank_parity.txt.
 
+Every parity comparison also makes the SCALED one (tests/feature_scaled_parity.py): the combined moments and every mixed hypothesis whitened by the
+reference's own sigmas and held block by block -- fp64 1e-9; wide_arithmetic 2 u v + 1e-9 against the float64 reference on the
+inputs as stored (the kernel narrows each stored output once); plain fp32 max(M_feat d_32, 20 u v), d_32 the distance of the
+all-float32 evaluation of the same call (tests/feature_f32.py) from its float64 evaluation on the same batch.  It prints one
+SCALED line: the largest fraction of a bound and the block it belongs to.  The weights are dimensionless
+and stay on the bound above.  The IMM run is a chain of 120 launches, not one call: its fp64 run is held to 1e-9 in the
+whitened metric at its first and last cycle, its fp32 runs stay on the run-length rule below.
+
 The end-to-end IMM run compares a 20-cycle chain (mix, predict, innovation, update, weights, combine) against the same chain in
 NumPy float64, started from the state as downloaded.  All 20 cycles run and are printed in every precision.  fp64 and fp32 engines
 are held to their gates for all 20 (measured worst: 3.7e-15 and 1.9e-6).  An fp32 engine with wide_arithmetic stores fp32 after every
@@ -19,6 +27,8 @@ import pytest
 import torch
 
 import bank_reference as br
+import feature_f32 as ff
+import feature_scaled_parity as fsp
 from test_bank_reference import make_tracks
 
 pytestmark = pytest.mark.gpu
@@ -117,6 +127,16 @@ def scaled_err(x, ref):
     return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref)))) if x.size else 0.0
 
 
+def scaled_combine(name, model, pname, m_g, C_g, m_r, C_r, mu, cov, w, **kw):
+    """the scaled check (tests/feature_scaled_parity.py) of combined moments against the reference's, block by block"""
+    fsp.judge_state(name, model, pname, m_g, C_g, m_r, C_r, f32=lambda: tuple(ff.mixture(model, mu, cov, w, p, **kw) for p in ("f32", "f64")))
+
+
+def scaled_mix(name, model, pname, mu_g, cov_g, mu_r, cov_r, mu, cov, w, Pk, **kw):
+    """the same for every mixed hypothesis"""
+    fsp.judge_state(name, model, pname, mu_g, cov_g, mu_r, cov_r, f32=lambda: tuple(ff.mix(model, mu, cov, w, Pk, p, **kw) for p in ("f32", "f64")))
+
+
 def transition(M, seed=11):
     rng = np.random.default_rng(seed)
     P = 0.6 * np.eye(M) + 0.4 * rng.uniform(0.1, 1.0, (M, M))
@@ -162,6 +182,7 @@ def test_combine_and_mix_against_the_reference(spe, onp, model, pname, prec, wid
     print(f"bank parity {model} {pname} M={M} combine: mean {em:.3e} cov {ec:.3e} (no-transport reference: {soft:.3e})")
     assert soft > 1e-9, "the no-transport variant must be outside the fp64 gate, or this test cannot tell them apart"
     assert em <= tol and ec <= tol
+    scaled_combine(f"bank/{model}/{pname}/M={M}/combine", model, pname, m_g, C_g, m_r, C_r, mu, cov, w)
     # mean only
     m_only, _, st2, _ = combine_dev(e, M, w, want_cov=False)
     assert np.array_equal(m_only, m_g) and (st2 == 0).all()
@@ -178,6 +199,7 @@ def test_combine_and_mix_against_the_reference(spe, onp, model, pname, prec, wid
     em, ec, ew = scaled_err(mu_g, mu_r), scaled_err(cov_g, cov_r), scaled_err(wp, c_r)
     print(f"bank parity {model} {pname} M={M} mix:     mean {em:.3e} cov {ec:.3e} w_pred {ew:.3e}")
     assert em <= tol and ec <= tol and ew <= tol
+    scaled_mix(f"bank/{model}/{pname}/M={M}/mix", model, pname, mu_g, cov_g, mu_r, cov_r, mu, cov, w, Pk)
     # the mixed covariances factorise: a prediction has status 0 everywhere
     if model == "orient":
         n = T * M
@@ -223,6 +245,7 @@ def test_mean_iteration_cap_sets_noconv(spe, onp, model, pname, prec, wide, tol,
     m_g, C_g, st, _ = combine_dev(e, M, w)
     assert np.array_equal(st, np.full(T, spe.ST_WARN_MEAN_NOCONV))
     assert scaled_err(m_g, m_r) <= tol and scaled_err(C_g, C_r) <= tol
+    scaled_combine(f"bank/{model}/{pname}/cap={cap}/combine", model, pname, m_g, C_g, m_r, C_r, mu, cov, w, max_it=cap)
     P = transition(M)
     Pk = stored(e, P) if (prec == 1 and not wide) else P
     mu_r, cov_r, c_r, conv = br.mix(man, mu, cov, w, Pk, max_it=cap)
@@ -231,6 +254,7 @@ def test_mean_iteration_cap_sets_noconv(spe, onp, model, pname, prec, wide, tol,
     mu_g, cov_g, _ = downloaded(e, man, T, M)
     assert np.array_equal(st, np.full(T, spe.ST_WARN_MEAN_NOCONV))
     assert scaled_err(mu_g, mu_r) <= tol and scaled_err(cov_g, cov_r) <= tol and scaled_err(wp, c_r) <= tol
+    scaled_mix(f"bank/{model}/{pname}/cap={cap}/mix", model, pname, mu_g, cov_g, mu_r, cov_r, mu, cov, w, Pk, max_it=cap)
     e.close()
 
 
@@ -305,6 +329,8 @@ def test_zero_weight_hypothesis_never_reaches_the_result(spe, onp, model, pname,
             mu_d, cov_d = stored(e, mu), stored(e, cov)
             m_r, C_r, _ = br.mixture(man, mu_d[:, keep], cov_d[:, keep], ws[:, keep])
             assert scaled_err(m_g, m_r) <= tol and scaled_err(C_g, C_r) <= tol
+            scaled_combine(f"bank/{model}/{pname}/zero-weight/combine", model, pname, m_g, C_g, m_r, C_r, mu_d[:, keep], cov_d[:, keep],
+                           ws[:, keep])
         e.close()
     assert all(np.isfinite(x).all() for x in res[1])
     assert all(np.array_equal(a, b) for a, b in zip(*res))
@@ -505,6 +531,9 @@ def test_imm_run_end_to_end(spe, onp, pname, prec, wide, tol):
                 scaled_err(w.cpu().numpy().astype(np.float64).reshape(T, 2), w_r))
         worst = [max(a, b) for a, b in zip(worst, errs)]
         print(f"bank parity imm {pname} cycle {c:2d}: mean {errs[0]:.3e} cov {errs[1]:.3e} weights {errs[2]:.3e}")
+        if pname == "f64" and c in (0, cycles - 1):   # a chain of launches: the fp64 bound needs no count of roundings
+            fsp.judge_state(f"bank/pose/f64/imm/cycle={c}", "pose", "f64", mu_o.cpu().numpy(), unpack(cov_o.cpu().numpy().astype(np.float64), 12),
+                            m_r, C_r)
         if c < held and max(errs) > tol:
             late.append((c, errs))
         p_man.append(float(w.cpu().numpy().astype(np.float64).reshape(T, 2)[:, 1].mean()))

@@ -9,10 +9,20 @@ rounding of the state out of the comparison):
 Parity bound: |x - ref| <= tol (1 + |ref|), tol = the README's parity gates 1e-9 (fp64) / 1e-4 (fp32); fp32 engines with
 wide_arithmetic compute in fp64 and store fp32: 1e-9 + 2^-23 (one fp32 rounding of the stored value).  The per-model maxima that
 were measured on an MI355X are in profiles/innovation_parity.txt.
+
+Every parity comparison also makes the SCALED one (tests/feature_scaled_parity.py): z-bar, S and nu whitened by
+s^z_i = sqrt(S_ref[i, i]) -- |dS|_ij / (s^z_i s^z_j), |d nu_i| / s^z_i, |(z-bar (-) z-bar_ref)_i| / s^z_i with SO(3)'s own (-) for
+model 3 -- and held per output: fp64 1e-9; wide_arithmetic 2 u v + 1e-9 (v = 1 for S, |nu_i| / s^z_i, max(1, |z-bar_i|) / s^z_i, 2 / s^z_i for
+a rotation coordinate); plain fp32 max(M_feat d_32, 20 u v), d_32 the distance of the all-float32 evaluation of the same call
+(tests/feature_f32.py) from its float64 evaluation on the same batch.  It prints one SCALED line.  d^2 and the log-likelihood are
+dimensionless (or offset by logdet) and stay on the bound above.
 """
 import numpy as np
 import pytest
 import torch
+
+import feature_f32 as ff
+import feature_scaled_parity as fsp
 
 pytestmark = pytest.mark.gpu
 
@@ -135,8 +145,9 @@ def scaled_err(x, ref):
     return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref)))) if x.size else 0.0
 
 
-def compare(onp, kind, mid, out, sel, mu, cov, Q, z):
-    """scaled errors of the five float outputs for the filters `sel` (one model id), and the reference d2"""
+def compare(onp, kind, mid, out, sel, mu, cov, Q, z, scaled):
+    """scaled errors of the five float outputs for the filters `sel` (one model id), and the reference d2; scaled = (name,
+    precision name): z-bar, S and nu are also held to the scale of S (tests/feature_scaled_parity.py), before this returns"""
     m, manz, mz, S, ok, conv = reference(onp, kind, mid, mu[sel], cov[sel], Q[sel])
     assert ok.all() and conv.all()
     so3 = kind == "pose" and mid == 3
@@ -150,6 +161,8 @@ def compare(onp, kind, mid, out, sel, mu, cov, Q, z):
     Sp = np.zeros((len(S), 3, 3)); Sp[:, :m, :m] = S
     errs = {"z_pred": err_z, "S": scaled_err(out["S"][sel], Sp), "innov": scaled_err(out["innov"][:, sel, :m], nu),
             "maha": scaled_err(out["maha"][:, sel], d2), "loglik": scaled_err(out["loglik"][:, sel], ll)}
+    fsp.judge_meas(scaled[0], scaled[1], zp if so3 else zp[:, :m], out["S"][sel][:, :m, :m], out["innov"][:, sel, :m], mz, S, nu, so3,
+                   f32=lambda: tuple(ff.innovation_stats(kind, mid, mu[sel], cov[sel], Q[sel], z[:, sel], p) for p in ("f32", "f64")))
     return errs, d2
 
 
@@ -187,7 +200,8 @@ def test_parity_every_model_and_clutter_association(spe, onp, kind, name, prec, 
             Qh = np.broadcast_to(Q[0], Q.shape).copy() if uniform_q else Q
             out = run_innovation(e, mid, z, Q[0] if uniform_q else Q, uniform_q=uniform_q)
             assert (out["status"] == 0).all()
-            errs, d2 = compare(onp, kind, mid, out, np.arange(N), mu, cov, stored(e, Qh), stored(e, z))
+            errs, d2 = compare(onp, kind, mid, out, np.arange(N), mu, cov, stored(e, Qh), stored(e, z),
+                                   (f"innovation/{kind}/{name}/model={mid}/uniform_q={int(uniform_q)}", name))
             left_out = check_best(out["best"], d2, float(np.float32(gate)) if prec == 1 else gate)
             print(f"innovation parity {kind} {name} model={mid} uniform_q={int(uniform_q)} "
                   + " ".join(f"{k}={v:.3e}" for k, v in errs.items()) + f" best_left_out={left_out}")
@@ -218,7 +232,7 @@ def test_parity_per_filter_model_ids(spe, onp, name, prec, wide, tol):
     worst = {}
     for mid in POSE_MODELS:
         sel = np.nonzero(models == mid)[0]
-        errs, _ = compare(onp, "pose", mid, out, sel, mu, cov, stored(e, Q), stored(e, z))
+        errs, _ = compare(onp, "pose", mid, out, sel, mu, cov, stored(e, Q), stored(e, z), (f"innovation/pose/{name}/mixed-ids/model={mid}", name))
         print(f"innovation parity pose-mixed {name} model={mid} " + " ".join(f"{k}={v:.3e}" for k, v in errs.items()))
         for k, v in errs.items():
             worst[(mid, k)] = v

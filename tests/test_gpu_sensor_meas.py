@@ -9,6 +9,14 @@ tests/test_sensor_meas_reference.py) run on the state AS DOWNLOADED and the inpu
 |x - ref| <= tol (1 + |ref|), tol = 1e-9 (fp64) / 1e-4 (fp32) / 1e-9 + 2^-23 (fp32 engines with wide_arithmetic, against the
 reference's outputs rounded to fp32), on mean, covariance, z-bar, S, nu, d^2 and log-likelihood.  Every comparison prints a
 PARITY line with its maxima before it asserts.
+
+Every parity comparison also makes the SCALED one (tests/feature_scaled_parity.py): the updated state (mu, C) whitened by the
+reference's own sigmas and held block by block -- fp64 1e-9; wide_arithmetic 2 u v + 1e-9 against the float64 reference on the
+inputs as stored (the kernel narrows each stored output once); plain fp32 max(M_feat d_32, 20 u v), d_32 the distance of the
+all-float32 evaluation of the same call (tests/feature_f32.py) from its float64 evaluation on the same batch.  It prints one
+SCALED line: the largest fraction of a bound and the block it belongs to.  z-bar, S and nu are held
+the same way at the scale of S (s^z_i = sqrt(S_ref[i, i]); v = 1 for S, |nu_i| / s^z_i, max(1, |z-bar_i|) / s^z_i); d^2 and the
+log-likelihood stay on the bound above.
 """
 import os
 import shutil
@@ -18,6 +26,8 @@ import numpy as np
 import pytest
 import torch
 
+import feature_f32 as ff
+import feature_scaled_parity as fsp
 import sensor_meas_reference as sr
 from oracle import ukf_numpy as on
 
@@ -196,7 +206,10 @@ def scaled(x, ref):
     return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref)))) if x.size else 0.0
 
 
-def check_parity(name, c, got, ref, tol=None, rows=None):
+def check_parity(name, c, got, ref, tol=None, rows=None, ids=None):
+    """the file's bound on every output, then the scaled checks of tests/feature_scaled_parity.py: the updated state block by
+    block, and z-bar, S, nu at the scale of S; ids: the call's model id(s), for the fp32 evaluation behind a plain fp32
+    engine's bound (rows of one measurement dimension are judged together: POSE_RANGE has m = 1)"""
     tol = c.tol if tol is None else tol
     rows = np.ones(c.n, bool) if rows is None else rows
     r = {k: np.asarray(ref[k], dtype=np.float64) for k in ALL_KEYS[:-1]}
@@ -208,6 +221,23 @@ def check_parity(name, c, got, ref, tol=None, rows=None):
     err.update({k: scaled(got[k][scored], r[k][scored]) for k in OUT_KEYS})
     print(f"PARITY {name} n={int(rows.sum())} " + " ".join(f"max_scaled_d{k}={v:.3e}" for k, v in err.items()) + f" tol={tol:.3e}")
     assert all(v <= tol for v in err.values()), (name, err, tol)
+    idv = np.broadcast_to(np.asarray(ids, dtype=np.int64), (c.n,))
+    z = c.z[int(ids)] if np.isscalar(ids) else mixed_z(c, ids)
+    evals = {}
+
+    def f32():
+        if not evals:
+            for p in ("f32", "f64"):
+                evals[p] = ff.sensor_meas(c.model, c.mu, c.cov, idv, z, c.Q, c.mount, c.point, c.gyro, keep=ref["status"] != 0, prec=p)
+        return evals
+    fsp.judge_state("sensor_meas/" + name, c.model, c.pname, got["mu"][rows], got["cov"][rows], ref["mu"][rows], ref["cov"][rows],
+                    f32=lambda: tuple((f32()[p]["mu"][rows], f32()[p]["cov"][rows]) for p in ("f32", "f64")))
+    dims = np.array([sr.meas_dim(int(i)) if i in ids_of(c.model) else 0 for i in idv])
+    for m in (1, 3):
+        sel = scored & (dims == m)
+        if sel.any():
+            pick = lambda o: (o["z_pred"][sel][:, :m], o["S"][sel][:, :m, :m], o["innov"][sel][:, :m])   # noqa: E731
+            fsp.judge_meas(f"sensor_meas/{name}/m={m}", c.pname, *pick(got), *pick(ref), f32=lambda: tuple(pick(f32()[p]) for p in ("f32", "f64")))
 
 
 def same(a, b, keys=ALL_KEYS, rows=None):
@@ -233,7 +263,7 @@ def test_parity(spe, model, pname):
         e.close()
         assert (ref["status"] == 0).all(), (mid, np.unique(ref["status"]))
         assert (got["status"] == 0).all(), (mid, np.unique(got["status"]))
-        check_parity(f"{model}/{pname}/{sr.NAMES[mid]}", c, got, ref)
+        check_parity(f"{model}/{pname}/{sr.NAMES[mid]}", c, got, ref, ids=mid)
         m = sr.meas_dim(mid)
         assert (got["z_pred"][:, m:] == 0).all() and (got["innov"][:, m:] == 0).all()
         assert (got["S"][:, m:, :] == 0).all() and (got["S"][:, :, m:] == 0).all()
@@ -252,7 +282,7 @@ def test_parity(spe, model, pname):
     assert all(np.isnan(got[k][idle]).all() for k in OUT_KEYS)
     for mid in ids_of(model):
         assert same(got, uniform[mid], rows=per == mid), mid
-    check_parity(f"{model}/{pname}/per-filter-ids", c, got, reference(c, per))
+    check_parity(f"{model}/{pname}/per-filter-ids", c, got, reference(c, per), ids=per)
 
 
 @pytest.mark.parametrize("model", ["pose", "orient"])
@@ -276,7 +306,7 @@ def test_gate(spe, model, pname):
     assert rej.sum() > c.n // 4 and (rows & (ref["status"] == 0)).sum() > c.n // 4
     assert np.array_equal(got["mu"][rej], c.mu[rej]) and np.array_equal(got["cov"][rej], c.cov[rej])
     assert np.isfinite(got["maha"][rej]).all()
-    check_parity(f"{model}/{pname}/gate", c, got, ref, rows=rows)
+    check_parity(f"{model}/{pname}/gate", c, got, ref, rows=rows, ids=mid)
 
 
 # ------------------------------------------------------------------------------------------------------- bit-level properties
@@ -394,7 +424,7 @@ def test_small_batches(spe, model):
             e.close()
             ref = sr.update_sensor(man_of(model), c.mu, c.cov, mid, c.z[mid], c.Q, c.mount, c.point, c.gyro)
             assert (got["status"] == 0).all() and (ref["status"] == 0).all()
-            check_parity(f"{model}/f64/{sr.NAMES[mid]}/n={n}", c, got, ref)
+            check_parity(f"{model}/f64/{sr.NAMES[mid]}/n={n}", c, got, ref, ids=mid)
 
 
 @pytest.mark.parametrize("pname", ["f32", "f32w"])
@@ -512,6 +542,13 @@ def test_degenerate_mount_agrees_with_update_dev(spe, pname):
         em, ec = scaled(got["mu"], mu_t), scaled(got["cov"], cov_t)
         print(f"PARITY {model}/{pname}/{sr.NAMES[sid]}-vs-update_dev n={c.n} max_scaled_dmu={em:.3e} max_scaled_dcov={ec:.3e} tol={2 * c.tol:.3e}")
         assert em <= 2 * c.tol and ec <= 2 * c.tol, (sid, em, ec)
+        # and the sensor-frame kernel's result against the reference of ITS call
+        d = Case()
+        d.__dict__.update(c.__dict__)
+        d.z, d.mount, d.point = {sid: z}, np.tile(ident, (c.n, 1)), np.zeros((c.n, 3))
+        ref = sr.update_sensor(man_of(model), c.mu, c.cov, sid, z, c.Q, d.mount, d.point, c.gyro)
+        assert (ref["status"] == 0).all()
+        check_parity(f"{model}/{pname}/{sr.NAMES[sid]}-degenerate-mount", d, got, ref, ids=sid)
 
 
 def test_uniform_id_of_the_other_engine_is_refused(spe):

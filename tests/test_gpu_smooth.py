@@ -7,6 +7,14 @@ tests/test_smoother_reference.py) run on the history AS DOWNLOADED, so that stor
 comparison.  Parity bound: |x - ref| <= tol (1 + |ref|), tol = 1e-9 (fp64) / 1e-4 (fp32) / 1e-9 + 2^-23 (fp32 engines with
 wide_arithmetic, against the reference's outputs rounded to fp32).  The maxima measured on an MI355X are in
 profiles/smoother_parity.txt.
+
+Every parity comparison also makes the SCALED one (tests/feature_scaled_parity.py): every step of the smoothed window, whitened by the
+reference's own sigmas and held block by block -- fp64 1e-9; wide_arithmetic 2 u v + 1e-9 against the float64 reference on the
+inputs as stored (the kernel narrows each stored output once); plain fp32 max(M_feat d_32, 20 u v), d_32 the distance of the
+all-float32 evaluation of the same call (tests/feature_f32.py) from its float64 evaluation on the same batch.  It prints one
+SCALED line: the largest fraction of a bound and the block it belongs to.  The chain is never narrowed
+below the arithmetic type between steps (CSM / CSP of ukf_smooth.hpp), so every step's record is one rounding from the chain:
+c = 1 for every step of the window, whatever its length (6 steps, and 12 steps in test_parity_twelve_steps).
 """
 import os
 
@@ -14,6 +22,8 @@ import numpy as np
 import pytest
 import torch
 
+import feature_f32 as ff
+import feature_scaled_parity as fsp
 import smoother_reference as sr
 
 pytestmark = pytest.mark.gpu
@@ -119,12 +129,22 @@ def reference(spe, r, mu_hist=None, cov_hist=None, dt=None, steps=None, first=No
         a, b = r.latch_a, r.latch_b
     R = np.array([e.process_noise(i) for i in range(r.n)]) if r.per_filter_noise else e.process_noise()
     R = np.asarray(R, dtype=e.dtype).astype(np.float64)
+    dt = (r.dt if dt is None else dt)[:steps - 1]
     if r.model == "pose":
         p = sr.Params("pose", R, acc_cov=np.asarray(2.0 * ACC_COV, dtype=e.dtype).astype(np.float64) / 2.0)
-        return sr.smooth(p, mu, cov, r.dt if dt is None else dt, in_a=a, initialised=r.live)
+        return Reference(sr.smooth(p, mu, cov, dt, in_a=a, initialised=r.live), (p, mu, cov, dt, a, None))
     from oracle import ukf_numpy as on
     p = sr.Params("orient", R, tau_g=sy.ORIENT_TAU, tau_a=sy.ORIENT_TAU, earth=on.earth_rotation(sy.ORIENT_LATITUDE))
-    return sr.smooth(p, mu, cov, r.dt if dt is None else dt, in_a=a, in_b=b, initialised=r.live)
+    return Reference(sr.smooth(p, mu, cov, dt, in_a=a, in_b=b, initialised=r.live), (p, mu, cov, dt, a, b))
+
+
+class Reference(tuple):
+    """the result of smoother_reference.smooth, and in .call what it was called with (for the fp32 evaluation of the same call)"""
+
+    def __new__(cls, result, call):
+        self = super().__new__(cls, result)
+        self.call = call
+        return self
 
 
 def run(r, dt=None, steps=None, first=None, mu_hist=None, cov_hist=None, in_place=False, cov=True, rings=True):
@@ -153,7 +173,10 @@ def scaled(x, ref):
     return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref))))
 
 
-def check_parity(name, r, got, ref, tol, wide, rows=slice(None)):
+def check_parity(name, r, got, ref, tol, wide, rows=slice(None), unscaled=()):
+    """the file's bound, then the scaled check of every step of the window (tests/feature_scaled_parity.py).  unscaled:
+    (step, filter) records whose reference covariance is no covariance (a poisoned record is passed through as it is): they
+    have no sigma to be measured in and keep the file's bound alone"""
     mu_s, cov_s, _, _ = got
     mu_r, cov_r = ref[0], ref[1]
     if wide:   # the engine stores fp32
@@ -161,6 +184,16 @@ def check_parity(name, r, got, ref, tol, wide, rows=slice(None)):
     em, ec = scaled(mu_s[:, rows], mu_r[:, rows]), scaled(cov_s[:, rows], cov_r[:, rows])
     print(f"PARITY {name} n={r.n} steps={mu_s.shape[0]} max_scaled_dmu={em:.3e} max_scaled_dcov={ec:.3e} tol={tol:.3e}")
     assert em <= tol and ec <= tol, (name, em, ec, tol)
+    mode = "wide" if wide else ("f64" if r.e.dtype == np.float64 else "f32")
+    p, mu, cov, dt, a, b = ref.call
+    pick = np.zeros(mu_s.shape[:2], bool)
+    pick[:, rows] = True
+    for c, f in unscaled:
+        pick[c, f] = False
+
+    def f32():
+        return tuple(ff.smooth(p, mu, cov, dt, a, b, prec=q) for q in ("f32", "f64"))
+    fsp.judge_state("smooth/" + name, r.model, mode, mu_s, cov_s, ref[0], ref[1], f32=f32, rows=pick.reshape(-1))
 
 
 _CACHE = {}
@@ -187,6 +220,23 @@ def test_parity(spe, model, pname, prec, wide, tol):
     # the last step is the filtered record, bit for bit
     last = (FIRST + STEPS - 1) % SLOTS
     assert torch.equal(got[3][0][last], r.mu_hist[last]) and torch.equal(got[3][1][last], r.cov_hist[last])
+
+
+@pytest.mark.parametrize("model", ["pose", "orient"])
+@pytest.mark.parametrize("pname,prec,wide,tol", PRECS, ids=[p[0] for p in PRECS])
+def test_parity_twelve_steps(spe, model, pname, prec, wide, tol):
+    """12 steps in a ring of 16 that the window wraps (first slot 9), 203 filters, one launch: the backward chain passes eleven
+    steps through the small blocks (gyro bias, accelerometer bias, angular velocity), where the 6-step window passes five"""
+    steps, slots, first = 12, 16, 9
+    r = record(spe, model, 203, prec, wide, steps=steps, slots=slots, first=first)
+    got, ref = run(r), reference(spe, r)
+    assert (ref[2] == 0).all()
+    assert (got[2] == 0).all(), np.unique(got[2])
+    assert got[0].shape[0] == steps
+    check_parity(f"{model}/{pname}/12-steps", r, got, ref, tol, wide)
+    last = (first + steps - 1) % slots
+    assert torch.equal(got[3][0][last], r.mu_hist[last]) and torch.equal(got[3][1][last], r.cov_hist[last])
+    r.e.close()
 
 
 @pytest.mark.parametrize("model", ["pose", "orient"])
@@ -347,7 +397,8 @@ def test_failure_and_uninitialised_stay_inside_their_filter(spe, model):
     hist_mu = sr.window_order(r.mu_hist.cpu().numpy(), FIRST, STEPS)
     assert np.array_equal(got[0][step, bad], hist_mu[step, bad])
     assert np.array_equal(got[1][step, bad], -np.eye(D))
-    check_parity(f"{model}/f64/poisoned", r, got, ref, 1e-9, 0, rows=np.nonzero(others | (np.arange(64) == bad))[0])
+    check_parity(f"{model}/f64/poisoned", r, got, ref, 1e-9, 0, rows=np.nonzero(others | (np.arange(64) == bad))[0],
+                 unscaled=[(c, bad) for c in range(step + 1)])
     # wave-mates: the bits of the run without the poison
     assert np.array_equal(got[0][:, others], clean[0][:, others]) and np.array_equal(got[1][:, others], clean[1][:, others])
     # the uninitialised filter's output slots keep the sentinel

@@ -7,11 +7,20 @@ engine's storage.  The reference is tests/state_meas_reference.py (pinned by tes
 state AS DOWNLOADED and the inputs AS STORED.  Parity bound: |x - ref| <= tol (1 + |ref|), tol = 1e-9 (fp64) / 1e-4 (fp32) /
 1e-9 + 2^-23 (fp32 engines with wide_arithmetic, against the reference's outputs rounded to fp32), on mean, covariance, d^2
 and log-likelihood.  Every comparison prints a PARITY line with its maxima before it asserts.
+
+Every parity comparison also makes the SCALED one (tests/feature_scaled_parity.py): the updated state (mu, C), whitened by the
+reference's own sigmas and held block by block -- fp64 1e-9; wide_arithmetic 2 u v + 1e-9 against the float64 reference on the
+inputs as stored (the kernel narrows each stored output once); plain fp32 max(M_feat d_32, 20 u v), d_32 the distance of the
+all-float32 evaluation of the same call (tests/feature_f32.py) from its float64 evaluation on the same batch.  It prints one
+SCALED line: the largest fraction of a bound and the block it belongs to.  d^2 and the log-likelihood are
+dimensionless and stay on the bound above.
 """
 import numpy as np
 import pytest
 import torch
 
+import feature_f32 as ff
+import feature_scaled_parity as fsp
 import state_meas_reference as smr
 from oracle import ukf_numpy as on
 
@@ -156,7 +165,9 @@ def scaled(x, ref):
     return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref)))) if x.size else 0.0
 
 
-def check_parity(name, c, got, ref, tol=None, rows=None):
+def check_parity(name, c, got, ref, tol=None, rows=None, masks=None, z=None, Qz=None, a=1.0, b=1.0):
+    """the file's bound on mean, covariance, d^2 and log-likelihood, then the scaled check of the updated state
+    (tests/feature_scaled_parity.py); masks, z, Qz, a, b: the call, for the fp32 evaluation behind a plain fp32 engine's bound"""
     tol = c.tol if tol is None else tol
     rows = np.ones(c.n, bool) if rows is None else rows
     r = [np.asarray(x, dtype=np.float64) for x in ref[:4]]
@@ -169,6 +180,14 @@ def check_parity(name, c, got, ref, tol=None, rows=None):
     print(f"PARITY {name} n={int(rows.sum())} max_scaled_dmu={em:.3e} max_scaled_dcov={ec:.3e} max_scaled_dmaha={ed:.3e} "
           f"max_scaled_dloglik={el:.3e} tol={tol:.3e}")
     assert em <= tol and ec <= tol and ed <= tol and el <= tol, (name, em, ec, ed, el, tol)
+    z, Qz = (c.z if z is None else z), (c.Qz if Qz is None else Qz)
+    mk = np.broadcast_to(np.asarray(masks, dtype=np.int64), (c.n,))
+    keep = np.asarray(ref[4]) != 0   # not committed: gated, inactive
+
+    def f32():
+        return tuple(ff.state_meas(c.model, c.mu[rows], c.cov[rows], mk[rows], z[rows], Qz[rows], a, b, keep[rows], prec=p)
+                     for p in ("f32", "f64"))
+    fsp.judge_state("state_meas/" + name, c.model, c.pname, got[0][rows], got[1][rows], ref[0][rows], ref[1][rows], f32=f32)
 
 
 def cycling_masks(model, n):
@@ -189,7 +208,7 @@ def test_parity(spe, model, pname):
         e.close()
         assert (ref[4] == 0).all(), (m, np.unique(ref[4]))
         assert (got[4] == 0).all(), (m, np.unique(got[4]))
-        check_parity(f"{model}/{pname}/mask={m}", c, got, ref)
+        check_parity(f"{model}/{pname}/mask={m}", c, got, ref, masks=m)
     per = cycling_masks(model, c.n)
     e = engine_of(spe, c)
     got, ref = run(e, per, c.z, c.Qz), reference(c, per)
@@ -197,7 +216,7 @@ def test_parity(spe, model, pname):
     e.close()
     expect = np.where(per == 0, ST_INACTIVE, 0).astype(np.uint32)
     assert np.array_equal(ref[4], expect) and np.array_equal(got[4], expect)
-    check_parity(f"{model}/{pname}/per-filter-masks", c, got, ref)
+    check_parity(f"{model}/{pname}/per-filter-masks", c, got, ref, masks=per)
     idle = per == 0
     assert np.array_equal(got[0][idle], c.mu[idle]) and np.array_equal(got[1][idle], c.cov[idle])
 
@@ -212,7 +231,7 @@ def test_covariance_intersection(spe, model, pname):
     e.close()
     ref = reference(c, full_mask(model), a=1.0 / w, b=1.0 / (1.0 - w))
     assert (ref[4] == 0).all() and (got[4] == 0).all()
-    check_parity(f"{model}/{pname}/covariance-intersection", c, got, ref)
+    check_parity(f"{model}/{pname}/covariance-intersection", c, got, ref, masks=full_mask(model), a=1.0 / w, b=1.0 / (1.0 - w))
     assert np.linalg.eigvalsh(got[1]).min() > 0.0
     assert not np.array_equal(got[1], reference(c, full_mask(model))[1])
 
@@ -236,7 +255,7 @@ def test_gate(spe, model, pname):
     assert rej.sum() > c.n // 4 and (rows & (ref[4] == 0)).sum() > c.n // 4
     assert np.array_equal(got[0][rej], c.mu[rej]) and np.array_equal(got[1][rej], c.cov[rej])
     assert np.isfinite(got[2][rej]).all()
-    check_parity(f"{model}/{pname}/gate", c, got, ref, rows=rows)
+    check_parity(f"{model}/{pname}/gate", c, got, ref, rows=rows, masks=m)
 
 
 # ------------------------------------------------------------------------------------------------------- bit-level properties
@@ -404,6 +423,13 @@ def test_single_blocks_agree_with_update_dev(spe, pname):
         em, ec = scaled(got[0], mu_t), scaled(got[1], cov_t)
         print(f"PARITY pose/{pname}/block={block}-vs-update_dev n={c.n} max_scaled_dmu={em:.3e} max_scaled_dcov={ec:.3e} tol={2 * c.tol:.3e}")
         assert em <= 2 * c.tol and ec <= 2 * c.tol, (block, em, ec)
+        # and the joint kernel's result against the reference of ITS call, block by block
+        ref = smr.update_state(on.POSE, c.mu, c.cov, 1 << block, z, Qz)
+        assert (ref[4] == 0).all()
+
+        def f32():
+            return tuple(ff.state_meas("pose", c.mu, c.cov, 1 << block, z, Qz, prec=p) for p in ("f32", "f64"))
+        fsp.judge_state(f"state_meas/pose/{pname}/block={block}-single", "pose", pname, got[0], got[1], ref[0], ref[1], f32=f32)
 
 
 # ---------------------------------------------------------------------------------------------------- RigidBodyState records

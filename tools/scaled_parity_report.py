@@ -7,7 +7,13 @@
                                                        (fp64, fp32, fp32 wide), model and path (predict, update, fused cycle,
                                                        three cycles in one launch)
 
-M and every bound come from the CPU table alone; the GPU table is there to be read beside it."""
+    python tools/scaled_parity_report.py --features --cpu [out]   profiles/feature_scaled_parity.txt: the CPU table behind
+                                                       M_feat (tests/test_feature_scaled_reference.degenerate_spread), no GPU
+    python tools/scaled_parity_report.py --features [out]         on an MI355X: runs the parity tests of the five feature files and
+                                                       APPENDS, per family, model and mode, the largest distance of every
+                                                       block over all their comparisons beside the bound of that comparison
+
+M, M_feat and every bound come from the CPU tables alone; the GPU tables are there to be read beside them."""
 import os
 import sys
 
@@ -73,7 +79,52 @@ def gpu(out):
     print(text)
 
 
+def features_cpu(out):
+    import slam_pose_estimation_amd as spe
+    import test_feature_scaled_reference as t
+    text = t.spread_text(*t.degenerate_spread(spe)) + "\n"
+    with open(out, "w") as f:
+        f.write(text)
+    print(text)
+
+
+FEATURE_FILES = ("test_gpu_innovation.py", "test_gpu_bank.py", "test_gpu_smooth.py", "test_gpu_state_meas.py", "test_gpu_sensor_meas.py")
+
+
+def features_gpu(out):
+    import pytest
+    import feature_scaled_parity as fsp
+    del fsp.REPORT[:]
+    rc = pytest.main(["-q", "-m", "gpu", "-p", "no:cacheprovider", "-k", "parity or against_the_reference or agree or mean_iteration_cap"]
+                     + [os.path.join(ROOT, "tests", f) for f in FEATURE_FILES])
+    groups = {}
+    for name, mode, kind, rows in fsp.REPORT:   # names are family/model/...
+        family, model = name.split("/")[:2]
+        g = groups.setdefault((family, model, mode), {"n": 0, "rows": {}})
+        g["n"] += 1
+        for label, d, b in rows:
+            old = g["rows"].get(label)
+            if old is None or d / b > old[0] / old[1]:
+                g["rows"][label] = (d, b, name)
+    lines = ["", "# GPU (MI355X): engine <-> reference, whitened distances beside their bounds (tests/feature_scaled_parity.py), per family,",
+             "# model and mode: of all the comparisons the five feature files make, the one where each block comes closest to its bound",
+             f"# M_feat = {fsp.M_FEAT}; pytest exit code {int(rc)}"]
+    for (family, model, mode), g in sorted(groups.items()):
+        top = max(g["rows"].values(), key=lambda r: r[0] / r[1])
+        lines.append(f"## {family} {model} {mode}: {g['n']} comparisons, largest fraction of a bound {top[0] / top[1]:.3f}")
+        for label, (d, b, name) in g["rows"].items():
+            lines.append(f"  {label:38s} {d:10.3e}   bound {b:10.3e}   {d / b:7.3f}   {name}")
+    text = "\n".join(lines) + "\n"
+    with open(out, "a") as f:
+        f.write(text)
+    print(text)
+
+
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if a != "--cpu"]
-    out = args[0] if args else os.path.join(ROOT, "profiles", "scaled_parity.txt")
-    (cpu if "--cpu" in sys.argv else gpu)(out)
+    args = [a for a in sys.argv[1:] if a not in ("--cpu", "--features")]
+    feat = "--features" in sys.argv
+    out = args[0] if args else os.path.join(ROOT, "profiles", "feature_scaled_parity.txt" if feat else "scaled_parity.txt")
+    if feat:
+        (features_cpu if "--cpu" in sys.argv else features_gpu)(out)
+    else:
+        (cpu if "--cpu" in sys.argv else gpu)(out)
