@@ -207,6 +207,19 @@ public:
         check(ukfb_smooth(engine, steps, dt, mu, cov, in_a, in_b, st.data()));
         return st;
     }
+    /** Forecast (ukf_batch.h, "forecast"): `steps` predictions chained from the start record (start_mu [N][S], start_cov
+     *  [N][D][D]; both NULL: the filters' current state) WITHOUT committing them.  Exactly one of dt [steps] (every filter's
+     *  time step) and ts_us [steps] (stamps, measured against every filter's own last measurement time) is non-NULL; in_a /
+     *  in_b [steps][N][3] or NULL (the latched inputs, held over the horizon).  mu [steps][N][S] and cov [steps][N][D][D] (may
+     *  be NULL) receive the state after 1 ... steps predictions; steps <= UKFB_FORECAST_MAX_STEPS.  Returns the status. */
+    std::vector<uint32_t> forecast(int steps, const double* dt, const int64_t* ts_us, double* mu, double* cov = NULL,
+                                   const double* start_mu = NULL, const double* start_cov = NULL, const double* in_a = NULL,
+                                   const double* in_b = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_forecast(engine, steps, dt, ts_us, start_mu, start_cov, in_a, in_b, mu, cov, st.data()));
+        return st;
+    }
     std::vector<uint32_t> status()
     {
         std::vector<uint32_t> st(static_cast<size_t>(cap), 0u);

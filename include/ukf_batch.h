@@ -483,6 +483,60 @@ int ukfb_smooth_dev(ukfb_engine* e, int steps, const double* dt, int slots, int 
 int ukfb_smooth(ukfb_engine* e, int steps, const double* dt, double* mu, double* cov, const double* in_a, const double* in_b,
                 uint32_t* status);
 
+/* ---- forecast: read-only multi-step prediction into a ring ------------------------------------------------------------------ */
+/* Where every filter will be after the next 1 ... steps predictions, with covariance, WITHOUT committing them (collision
+ * checks, gating a scan that has not arrived yet, latency-compensated output at one common time for filters whose last samples
+ * have different stamps, a planner's horizon): the smoother's mirror image.
+ * A FORECAST RING has the history's format: mu_out_dev [slots][capacity][S], cov_out_dev [slots][capacity][PK] (packed lower
+ * triangle, as ukfb_device_views), engine precision.  Step c (0 ... steps - 1) is the state after c + 1 predictions and lives
+ * in slot (first_slot + c) % slots, so its records are valid inputs, as they lie, to ukfb_update_state_dev (commit = 0: the
+ * distance between tracks at the horizon), ukfb_smooth_dev's conventions and ukfb_bank_combine_dev's records as a start.
+ * in_a_dev / in_b_dev: optional input rings [slots][capacity][3] indexed like the forecast ring (the slot of step c = the
+ * inputs of the prediction that PRODUCES step c), with the meaning they have in ukfb_cycle_multi_dev, the per-filter NaN
+ * acceleration row that selects PoseUKF's constant-velocity branch included; NULL: the engine's latched inputs, held over the
+ * horizon.  The chain starts from the START RECORD: start_mu_dev [capacity][S] and start_cov_dev [capacity][PK], both NULL (the
+ * engine's own state) or both non-NULL (exactly one NULL: UKFB_ERR_INVALID_ARG).
+ *
+ * Each prediction is made exactly as ukfb_predict makes it (noise shaping and the acceleration-branch rule of
+ * PoseUKF.cpp:188-193, mean_tol / mean_max_iter included) with the engine's process noise (batch-uniform or per filter),
+ * acc.cov, taus and earth rotation at the time of the call: L = chol(Sigma), sigma points X_i, Y_i = g(X_i), the iterated mean
+ * mu^-, delta_i = Y_i (-) mu^-, Sigma^- = 1/2 sum_i delta_i delta_i^T + R.  The time step of step c:
+ *   dt form     every filter predicts by dt[c] (HOST, steps entries, passed to the kernel by value); the gate is
+ *               ukfb_predict's own;
+ *   ts_us form  what `steps` calls of predictionStepFromSampleTime(ts_us[c]) (UnscentedKalmanFilter.hpp:83-100; HOST, by
+ *               value) would do to a COPY of the filter: each filter starts from ITS OWN last measurement time, read on the
+ *               device, dt = double(ts - last) / 1000000.0 as the forward kernel computes it, and the copy's (shadow) last time
+ *               advances only where it was null or dt > min_time_delta.  The engine's stored times are not written.
+ * Exactly one of dt / ts_us is non-NULL (else UKFB_ERR_INVALID_ARG).  1 <= steps <= min(slots, UKFB_FORECAST_MAX_STEPS); a
+ * larger steps is UKFB_ERR_OUT_OF_RANGE and writes nothing.  A longer horizon is chained by the caller: the next call starts
+ * from the last slot of the previous one through start_*_dev (that needs cov_out_dev).
+ * Status of the call, written to the caller's array ([capacity], may be NULL) as the OR over the steps:
+ *   SKIPPED_FIRST_TS  (ts_us form) the filter's last measurement time is null: no prediction, the shadow time becomes ts_us[c];
+ *   SKIPPED_SMALL_DT / ERR_NEG_DT / ERR_DT_TOO_LARGE  the step is gated (<= min_time_delta, < 0, > max_time_delta);
+ *                     a step without a prediction receives the bits of the record before it, step 0 those of the start record;
+ *   ERR_CHOLESKY      the chain's covariance cannot be factorised at a step: the step receives the previous record's bits and
+ *                     the chain goes on from it;
+ *   WARN_MEAN_NOCONV  the mean iteration hit its cap (mean_max_iter); the last iterate is used;
+ *   UNINITIALISED     nothing is written for that filter.
+ * A filter that fails, is gated or is uninitialised never changes a bit of another filter.  The calls are READ-ONLY on the
+ * engine: mean, covariance, initialised flags, last measurement times, latches, noise and the engine's own status array keep
+ * every bit (the kernel holds no pointer through which it could store to them).
+ * Between the steps the chain stays in LDS in the arithmetic type; every record is narrowed to the storage type once, at its
+ * store.  mu_out_dev / cov_out_dev must not alias the start record's memory, unless the start record is a slot of those rings
+ * OUTSIDE the window (the chained call above).  Stream-ordered; joins split streams like every other call; no host
+ * synchronisation, no allocation at call time.  The same kernel serves every lanes_per_filter setting; fp32 engines compute in
+ * fp32, with wide_arithmetic in fp64 (stored fp32).  Device groups: per shard through ukfb_group_shard. */
+#define UKFB_FORECAST_MAX_STEPS 32
+int ukfb_forecast_dev(ukfb_engine* e, int steps, const double* dt, const int64_t* ts_us, int slots, int first_slot,
+                      const void* start_mu_dev, const void* start_cov_dev, const void* in_a_dev, const void* in_b_dev,
+                      void* mu_out_dev, void* cov_out_dev, uint32_t* status_dev);
+/* host arrays of doubles in window order: start_mu [capacity][S] and start_cov [capacity][D][D] (both NULL: the engine's
+ * state); in_a / in_b [steps][capacity][3] or NULL (the latched inputs); mu [steps][capacity][S], cov [steps][capacity][D][D]
+ * (may be NULL) and status [capacity] (may be NULL) receive the forecast (zeros for an UNINITIALISED filter);
+ * steps <= UKFB_FORECAST_MAX_STEPS; synchronises */
+int ukfb_forecast(ukfb_engine* e, int steps, const double* dt, const int64_t* ts_us, const double* start_mu,
+                  const double* start_cov, const double* in_a, const double* in_b, double* mu, double* cov, uint32_t* status);
+
 /* ---- joint state-block measurements: update and fuse with full covariance ------------------------------------------------ */
 /* ukf->update(z, h, Q) with z a SUB-MANIFOLD of the state and h the selection of blocks: a 6-DOF pose with its joint
  * covariance as ONE measurement, another estimate of the same state (a second engine's ukfb_device_views, a history slot, a

@@ -293,6 +293,42 @@ inline SmoothGeometry smooth_geometry(int S, int D, int64_t capacity, size_t com
             int(size_t(SMOOTH_FILTERS_PER_GROUP) * smooth_filter_scalars(S, D) * compute_size)};
 }
 
+// ---- forecast (ukfb_forecast_dev) -------------------------------------------------------------------------------------------
+// `steps` predictions chained from a start record into a window of a ring of `slots`: step c lives in slot
+// (first_slot + c) % slots.  One launch: the time steps (or stamps) of all steps travel in the kernel arguments, so a call
+// covers at most FORECAST_MAX_STEPS of them and a longer horizon is chained by the caller.
+constexpr int FORECAST_MAX_STEPS = UKFB_FORECAST_MAX_STEPS, FORECAST_FILTERS_PER_GROUP = 4;
+inline Verdict check_forecast_args(int steps, int slots, int first_slot, bool has_dt, bool has_ts, bool has_start_mu, bool has_start_cov,
+                                   bool has_mu_out) {
+    if (slots < 1 || steps < 1) return {UKFB_ERR_INVALID_ARG, "steps >= 1, slots >= 1"};
+    if (first_slot < 0 || first_slot >= slots) return {UKFB_ERR_INVALID_ARG, "0 <= first_slot < slots"};
+    if (has_dt == has_ts) return {UKFB_ERR_INVALID_ARG, "exactly one of dt and ts_us must be given"};
+    if (has_start_mu != has_start_cov) return {UKFB_ERR_INVALID_ARG, "start_mu and start_cov must be both NULL or both given"};
+    if (!has_mu_out) return {UKFB_ERR_INVALID_ARG, "mu_out must not be NULL"};
+    if (steps > std::min(slots, FORECAST_MAX_STEPS))
+        return {UKFB_ERR_OUT_OF_RANGE, "steps <= min(slots, 32): chain a longer horizon from the last slot of the call before"};
+    return {};
+}
+// LDS of one filter, in scalars of the compute type (ukf_forecast.hpp, ForecastLayout): the factor region with its reciprocal
+// pivots (the rows of Sigma^- are parked in it while the noise is added), the delta table of 2 D + 1 rows, the chain record (mean
+// padded to 16, packed covariance padded to even), the rotation matrix (9 + 1 pad), the sink of lane-predicated stores (16) and a
+// pad of four that keeps the four slices of a workgroup on different banks in either precision; rounded up to a multiple of
+// four.  Every scalar the kernel reads is one it wrote: the pads are never read.
+constexpr int FORECAST_SLICE_PAD = 4;
+constexpr int forecast_filter_scalars(int S, int D) {
+    return S > 16 ? -1
+                  : (D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 10 + 16 + FORECAST_SLICE_PAD + 3) / 4 * 4;
+}
+struct ForecastGeometry {
+    int64_t grid;    // workgroups of four filters
+    int lds_bytes;   // dynamic LDS of a workgroup
+};
+// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
+inline ForecastGeometry forecast_geometry(int S, int D, int64_t capacity, size_t compute_size) {
+    return {(capacity + FORECAST_FILTERS_PER_GROUP - 1) / FORECAST_FILTERS_PER_GROUP,
+            int(size_t(FORECAST_FILTERS_PER_GROUP) * forecast_filter_scalars(S, D) * compute_size)};
+}
+
 // ---- joint state-block measurements (ukfb_update_state_dev) --------------------------------------------------------------
 // A measurement is a sub-manifold of the state: the compound of the blocks a mask selects, in state order.  Every block but the
 // OrientationState's gravity has three tangent dimensions, so tangent dimension t belongs to block t / 3 in both models.

@@ -56,6 +56,8 @@ EXPORTS = [
     "ukfb_bank_weights_dev", "ukfb_bank_combine_dev", "ukfb_bank_mix_dev", "ukfb_bank_combine", "ukfb_bank_mix",
     # fixed-interval smoothing: history rings and the RTS backward pass (read-only)
     "ukfb_history_push_dev", "ukfb_smooth_dev", "ukfb_smooth",
+    # forecast: multi-step prediction from a start record into a ring of the history's format (read-only)
+    "ukfb_forecast_dev", "ukfb_forecast",
     # joint state-block measurements: update / fuse with full covariance, covariance intersection, track-to-track distance
     "ukfb_update_state_dev", "ukfb_update_state", "ukfb_pose_update_body_states",
     # sensor-frame measurements: lever arms, ranges, landmark fixes, nav-frame vectors
@@ -498,6 +500,48 @@ class BatchUKF:
         st = np.zeros(n, dtype=np.uint32)
         _chk(self._lib.ukfb_smooth(self._h, C.c_int(steps), _pd(d), _pd(mu), _pd(cov), _pd(a), _pd(b),
                                    st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_smooth")
+        return mu, cov, st
+
+    # ---- forecast: rings [slots, capacity, S] / [slots, capacity, PK] in engine precision, the history's format
+    @staticmethod
+    def _forecast_steps(dt, ts_us):
+        if (dt is None) == (ts_us is None):
+            raise UkfbError("forecast: exactly one of dt and ts_us")
+        d = np.ascontiguousarray(dt, dtype=np.float64).reshape(-1) if dt is not None else None
+        t = np.ascontiguousarray(ts_us, dtype=np.int64).reshape(-1) if ts_us is not None else None
+        return d, t, (d.size if d is not None else t.size), (t.ctypes.data_as(C.POINTER(C.c_int64)) if t is not None else None)
+
+    def forecast_dev(self, slots: int, first_slot: int, mu_out, cov_out=None, status=None, dt=None, ts_us=None, start_mu=None,
+                     start_cov=None, in_a_dev=None, in_b_dev=None):
+        """len(dt) (or len(ts_us)) predictions chained from the start record (start_mu / start_cov [capacity, S] /
+        [capacity, PK] on the device, None = the engine's current state) WITHOUT committing them: step c, the state after
+        c + 1 predictions, goes to slot (first_slot + c) % slots of mu_out / cov_out (cov_out may be None).  dt[c] (host) is
+        the time step of every filter; ts_us[c] (host) a stamp that every filter measures against its OWN last measurement
+        time, as predict_timestamps would on a copy.  in_a_dev / in_b_dev: input rings [slots, capacity, 3] (the slot of step c
+        = the inputs of the prediction that produces it) or None (the latched inputs, held over the horizon); status uint32 /
+        int32 [capacity] or None.  At most 32 steps a call; chain a longer horizon through start_mu / start_cov.
+        Caller-supplied buffers: nothing is allocated.  Read-only on the engine.  Returns (mu_out, cov_out)."""
+        d, t, steps, tp = self._forecast_steps(dt, ts_us)
+        _chk(self._lib.ukfb_forecast_dev(self._h, C.c_int(steps), _pd(d), tp, C.c_int(slots), C.c_int(first_slot),
+                                         _devptr(start_mu), _devptr(start_cov), _devptr(in_a_dev), _devptr(in_b_dev),
+                                         _devptr(mu_out), _devptr(cov_out), _devptr(status)), "ukfb_forecast_dev")
+        return mu_out, cov_out
+
+    def forecast(self, dt=None, ts_us=None, start_mu=None, start_cov=None, in_a=None, in_b=None, with_cov: bool = True):
+        """Host arrays in window order: dt or ts_us [steps], start_mu [capacity, S] and start_cov [capacity, D, D] (None: the
+        engine's state), in_a / in_b [steps, capacity, 3] or None -> (mu [steps, capacity, S], cov [steps, capacity, D, D] or
+        None, status [capacity]); synchronises"""
+        d, t, steps, tp = self._forecast_steps(dt, ts_us)
+        n = self.capacity
+        sm = _f64(start_mu, (n, self.S)) if start_mu is not None else None
+        sc = _f64(start_cov, (n, self.D, self.D)) if start_cov is not None else None
+        a = _f64(in_a, (steps, n, 3)) if in_a is not None else None
+        b = _f64(in_b, (steps, n, 3)) if in_b is not None else None
+        mu = np.zeros((steps, n, self.S))
+        cov = np.zeros((steps, n, self.D, self.D)) if with_cov else None
+        st = np.zeros(n, dtype=np.uint32)
+        _chk(self._lib.ukfb_forecast(self._h, C.c_int(steps), _pd(d), tp, _pd(sm), _pd(sc), _pd(a), _pd(b), _pd(mu), _pd(cov),
+                                     st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_forecast")
         return mu, cov, st
 
     # ---- joint state-block measurements: z in the state's own layout [capacity, S], Qz the packed lower triangle [capacity, PK]
