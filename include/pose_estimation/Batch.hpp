@@ -220,6 +220,36 @@ public:
         check(ukfb_forecast(engine, steps, dt, ts_us, start_mu, start_cov, in_a, in_b, mu, cov, st.data()));
         return st;
     }
+    /** Filter lifecycle (ukf_batch.h, "filter lifecycle"), host forms.  gatherFilters: record k <- filter index[k] (index NULL:
+     *  item k is filter k); mu [n][S], cov [n][D][D], last_ts_us [n], initialised [n], each may be NULL; an index outside
+     *  [0, capacity()) gives a record of zeros.  Read-only on the engine. */
+    void gatherFilters(int64_t n, const int32_t* index, double* mu, double* cov = NULL, int64_t* last_ts_us = NULL,
+                       uint8_t* initialised = NULL)
+    {
+        check(ukfb_gather_filters(engine, n, index, mu, cov, last_ts_us, initialised));
+    }
+    /** initializeFilter from records: filter index[k] <- (mu[k], cov[k], last_ts_us[k] or 0, initialised[k] or 1; a 0 retires the
+     *  filter).  Among the items that name one filter the lowest wins; returns the per-item status (UKFB_ST_INACTIVE: a loser,
+     *  or an index outside [0, capacity())). */
+    std::vector<uint32_t> scatterFilters(int64_t n, const int32_t* index, const double* mu, const double* cov,
+                                         const int64_t* last_ts_us = NULL, const uint8_t* initialised = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(n));
+        check(ukfb_scatter_filters(engine, n, index, mu, cov, last_ts_us, initialised, st.data()));
+        return st;
+    }
+    /** clears the initialised flag and the last measurement time of every filter with a non-zero byte in mask_dev [capacity()], a
+     *  DEVICE array; stream-ordered */
+    void retire(const uint8_t* mask_dev) { check(ukfb_retire_dev(engine, mask_dev)); }
+    /** moves the live groups of `group` consecutive filters to the front, in place; new_index / old_index [capacity()] (may be NULL)
+     *  receive the maps; returns the number of filters in live groups: the free slots start there.  Bound input buffers are not
+     *  moved: permute them with old_index. */
+    int64_t compact(int group = 1, int32_t* new_index = NULL, int32_t* old_index = NULL)
+    {
+        int64_t live = 0;
+        check(ukfb_compact(engine, group, new_index, old_index, &live));
+        return live;
+    }
     std::vector<uint32_t> status()
     {
         std::vector<uint32_t> st(static_cast<size_t>(cap), 0u);

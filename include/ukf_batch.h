@@ -537,6 +537,85 @@ int ukfb_forecast_dev(ukfb_engine* e, int steps, const double* dt, const int64_t
 int ukfb_forecast(ukfb_engine* e, int steps, const double* dt, const int64_t* ts_us, const double* start_mu,
                   const double* start_cov, const double* in_a, const double* in_b, double* mu, double* cov, uint32_t* status);
 
+/* ---- filter lifecycle: gather, scatter, retire, compact -------------------------------------------------------------------- */
+/* Birth, death, clone, move and defragmentation of filters ON THE DEVICE: the whole per-filter record -- mean, packed
+ * covariance, initialised flag, last measurement time, latched inputs, per-filter process noise -- read and written as a unit.
+ * All four device calls are stream-ordered on the engine's stream (split launches are joined first), need no host
+ * synchronisation and allocate nothing after an engine's first lifecycle call (that call creates one workspace, freed by
+ * ukfb_destroy).  A NULL engine is UKFB_ERR_INVALID_ARG.  Lists on the device are int32 filter indices, like the lists of
+ * ukfb_process_events_dev's rounds; scalars are in the engine's precision.  Device groups: per shard through ukfb_group_shard.
+ *
+ * A RECORD SET is n records in item order, field by field (ukfb_filter_records); a NULL field is skipped.
+ * index_dev [n] names the filter of every item; NULL: item k is filter k.  n < 0 or n > INT32_MAX is UKFB_ERR_OUT_OF_RANGE,
+ * n == 0 is UKFB_OK and launches nothing.  Item k is INVALID when index[k] < 0 or index[k] >= capacity (with a NULL index_dev:
+ * k >= capacity); an invalid item is refused per item, never an error of the call.
+ *
+ * ukfb_gather_filters_dev is READ-ONLY on the engine: state, flags, times, latches, noise and the engine's own status array keep
+ * every bit.  A valid item writes every non-NULL field of record k from filter index[k]: in_a / in_b are what that filter's next
+ * prediction would read (the bound buffer if one is bound, else the engine's latch); noise is the filter's matrix (the uniform
+ * matrix on an engine with batch-uniform noise); status[k] = 0.  An invalid item writes zeros to every field, initialised 0, and
+ * status[k] = UKFB_ST_INACTIVE.  Duplicate indices are fine.
+ *
+ * ukfb_scatter_filters_dev is initializeFilter (UnscentedKalmanFilter.hpp:40-44) from device records.  mu and cov_packed are
+ * required (else UKFB_ERR_INVALID_ARG).  A valid item writes mean and covariance as given -- nothing about them is checked, as in
+ * ukfb_initialize; a covariance that cannot be factorised is reported by the first prediction.  The flag becomes
+ * initialised[k] != 0 (a NULL field: 1) and the last measurement time last_ts_us[k] (a NULL field: 0, as initializeFilter
+ * zeroes it); a record with initialised[k] == 0 RETIRES the filter: flag 0, time 0.  in_a / in_b, if given, go into the
+ * engine-owned latch arrays (a bound buffer stays the caller's).  noise, if given, goes into the filter's per-filter entry: the
+ * engine must ALREADY store its noise per filter (ukfb_set_process_noise_per_filter), otherwise the call is
+ * UKFB_ERR_INVALID_ARG and writes nothing -- no storage is switched at call time; on Pose engines the filter's
+ * acceleration-branch matrix (block (6,6,3,3) replaced by 2 acc.cov, PoseUKF.cpp:190-191) is rebuilt in the same call with the
+ * bits ukfb_pose_set_acceleration would give.  The engine's own status word of the filter is not written.
+ * DUPLICATES ARE DECIDED, NOT RACED: among the valid items that name the same filter the LOWEST item index wins and writes the
+ * whole record (mean and covariance of a filter always come from the same item); every other such item writes nothing and gets
+ * status[k] = UKFB_ST_INACTIVE, as does an invalid item; a winner gets 0.  Filters that no winning item names keep every bit.
+ * The cost of a call follows n, not the capacity.  The records must not overlap the engine's own arrays.
+ *
+ * ukfb_retire_dev: every filter with a non-zero byte in retire_mask_dev [capacity] gets flag 0 and last measurement time 0; its
+ * mean, covariance and everything else, and every other filter, keep their bits.  A later cycle reports UKFB_ST_UNINITIALISED
+ * for it until a scatter (or ukfb_initialize) gives the slot a new filter.
+ *
+ * ukfb_compact_dev moves the live filters to the front IN PLACE, in groups of `group` consecutive filters: group = 1, or a bank's
+ * M, so that the hypotheses t * M + j of a track stay together (1 <= group <= 8, capacity % group == 0, else
+ * UKFB_ERR_INVALID_ARG).  With G = capacity / group, group g is LIVE if any of its filters is initialised and L is the number of
+ * live groups.  The HOLES are the dead groups g < L in ascending order h_0 < h_1 < ..., the MOVERS the live groups g >= L in
+ * ascending order m_0 < m_1 < ... (there are exactly as many): mover m_k is copied onto hole h_k, filter by filter -- mean and
+ * packed covariance, flag and last measurement time, the engine's status word, the engine-owned in_a / in_b latches and, when
+ * the noise is per filter, its process-noise and acceleration-branch entries -- and then the mover's flags are cleared and its
+ * times set to 0; its other bits stay.  Nothing else changes: live groups below L and dead groups at or above L keep every bit,
+ * and no buffer is reallocated or swapped, so the pointers of ukfb_device_views stay valid.  The mapping is fully determined by
+ * the flags.  Outputs on the device, each may be NULL:
+ *   new_index_dev [capacity]  for every filter i of a group that was live before the call its index after the call (i itself
+ *                             if it did not move), -1 for every other filter;
+ *   old_index_dev [capacity]  for j < L * group the index that filter had before the call, -1 for j >= L * group;
+ *   live_dev      [1]         L * group: the free slots start here, so that births need no host -- a caller forms
+ *                             index = live + arange(n) on the device and scatters; items beyond the capacity are refused per item.
+ * BOUND input buffers (ukfb_pose_bind_acceleration_dev, ukfb_orient_bind_inputs_dev) and every other per-filter array of the
+ * caller are the caller's: they are NOT moved, the caller permutes them with old_index_dev.  ukfb_last_model_groups refers to
+ * the numbering before the call.  A filter that moves gets other wave-mates: later results agree to rounding with those of the
+ * uncompacted engine, bit for bit only where placement is the same (the reproducibility rule at the top of this file). */
+typedef struct ukfb_filter_records {   /* device pointers, n records in item order; any may be NULL unless said otherwise */
+    void*     mu;           /* [n][S]                                                             */
+    void*     cov_packed;   /* [n][PK]  packed lower triangle, as ukfb_device_views               */
+    int64_t*  last_ts_us;   /* [n]                                                                */
+    uint8_t*  initialised;  /* [n]                                                                */
+    void*     in_a;         /* [n][3]   Pose acc.mu / Orient acceleration.mu                      */
+    void*     in_b;         /* [n][3]   Orient rotation_rate.mu                                   */
+    void*     noise;        /* [n][D][D] row-major process noise                                  */
+    uint32_t* status;       /* [n]      UKFB_ST_* of THIS call, per item                          */
+} ukfb_filter_records;
+int ukfb_gather_filters_dev(ukfb_engine* e, int64_t n, const int32_t* index_dev, const ukfb_filter_records* out);
+int ukfb_scatter_filters_dev(ukfb_engine* e, int64_t n, const int32_t* index_dev, const ukfb_filter_records* in);
+int ukfb_retire_dev(ukfb_engine* e, const uint8_t* retire_mask_dev /* [capacity] */);
+int ukfb_compact_dev(ukfb_engine* e, int group, int32_t* new_index_dev, int32_t* old_index_dev, int64_t* live_dev);
+/* host-array forms (doubles, full D x D covariances; index [n] host int32 or NULL; any output may be NULL; scatter: mu and cov
+ * required, last_ts_us / initialised / status may be NULL); they synchronise */
+int ukfb_gather_filters(ukfb_engine* e, int64_t n, const int32_t* index, double* mu, double* cov, int64_t* last_ts_us,
+                        uint8_t* initialised);
+int ukfb_scatter_filters(ukfb_engine* e, int64_t n, const int32_t* index, const double* mu, const double* cov,
+                         const int64_t* last_ts_us, const uint8_t* initialised, uint32_t* status);
+int ukfb_compact(ukfb_engine* e, int group, int32_t* new_index, int32_t* old_index, int64_t* live);
+
 /* ---- joint state-block measurements: update and fuse with full covariance ------------------------------------------------ */
 /* ukf->update(z, h, Q) with z a SUB-MANIFOLD of the state and h the selection of blocks: a 6-DOF pose with its joint
  * covariance as ONE measurement, another estimate of the same state (a second engine's ukfb_device_views, a history slot, a

@@ -926,7 +926,7 @@ int ukfb_destroy(ukfb_engine* e) {
     }
     void* bufs[] = {e->mu, e->cov, e->status, e->init, e->last_ts, e->Rn, e->Racc, e->acc_cov_dev, e->in_a, e->in_b, e->z_stage,
                     e->Q_stage, e->meas_stage, e->active_stage, e->dt_stage, e->ts_stage, e->reduce_word, e->ev_dev, e->cvt_dev,
-                    e->multi_dev, e->bucket_idx, e->bucket_counts, e->smooth_chain};
+                    e->multi_dev, e->bucket_idx, e->bucket_counts, e->smooth_chain, e->lifecycle_ws};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (e->ev0) (void)hipEventDestroy(e->ev0);

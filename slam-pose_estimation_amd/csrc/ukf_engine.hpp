@@ -91,6 +91,9 @@ struct ukfb_engine {
     // ukfb_process_events: device workspace (grow-only)
     void* ev_dev = nullptr;
     size_t ev_bytes = 0;
+    // filter lifecycle (ukf_lifecycle_api.hip): the owner array of scatter and compact's counts, prefix sums and pair list, one
+    // allocation made by the engine's first lifecycle call (ukfb::lifecycle_geometry carves it)
+    void* lifecycle_ws = nullptr;
 
     // last launch (for bench.py / profiles)
     std::string last_kernel;

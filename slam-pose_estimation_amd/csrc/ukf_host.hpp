@@ -1,5 +1,5 @@
 // ukf_host.hpp -- the engine's host decisions as pure functions of plain values: configuration checks, process-noise
-// classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, packed covariances, workspace sizing and
+// classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, packed covariances, workspace sizing, the filter lifecycle's checks and geometry and
 // the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
 #pragma once
 
@@ -518,6 +518,62 @@ struct Carver {   // bump allocator over a workspace (256-byte aligned pieces); 
         return p;
     }
 };
+
+// ---- filter lifecycle (ukfb_gather_filters_dev / scatter / retire / compact) ------------------------------------------------
+// Record movers: one 16-lane row per record, four records per wavefront, LC_THREADS / LC_ROW records per block.  Compact counts
+// and ranks groups in blocks of LC_COUNT_BLOCK; its move kernel has a FIXED grid (the pair count is known to the device only).
+constexpr int LC_THREADS = 256, LC_ROW = 16, LC_ROWS_PER_BLOCK = LC_THREADS / LC_ROW;
+constexpr int LC_PER_THREAD = 4, LC_COUNT_BLOCK = LC_THREADS * LC_PER_THREAD;
+constexpr int LC_MOVE_MAX_BLOCKS = 2048, LC_MAX_GROUP = 8;
+constexpr int64_t LC_MAX_ITEMS = 0x7fffffff;   // lists and filter indices are int32
+// gather and scatter.  has_records: the struct pointer; the has_* / noise flags are those of its fields
+inline Verdict check_lifecycle_args(int64_t capacity, int64_t n, bool has_records, bool scatter, bool has_mu, bool has_cov, bool has_noise,
+                                    bool noise_per_filter) {
+    if (!has_records) return {UKFB_ERR_INVALID_ARG, "the records must not be NULL"};
+    if (n < 0 || n > LC_MAX_ITEMS) return {UKFB_ERR_OUT_OF_RANGE, "0 <= n <= INT32_MAX"};
+    if (capacity < 1 || capacity > LC_MAX_ITEMS) return {UKFB_ERR_OUT_OF_RANGE, "filter indices are int32: capacity <= INT32_MAX"};
+    if (scatter && (!has_mu || !has_cov)) return {UKFB_ERR_INVALID_ARG, "scatter: mu and cov_packed must not be NULL"};
+    if (scatter && has_noise && !noise_per_filter)
+        return {UKFB_ERR_INVALID_ARG, "scatter: noise records need per-filter noise storage: call ukfb_set_process_noise_per_filter first"};
+    return {};
+}
+inline Verdict check_compact_args(int64_t capacity, int group) {
+    if (group < 1 || group > LC_MAX_GROUP) return {UKFB_ERR_INVALID_ARG, "1 <= group <= 8"};
+    if (capacity < 1 || capacity > LC_MAX_ITEMS) return {UKFB_ERR_OUT_OF_RANGE, "filter indices are int32: capacity <= INT32_MAX"};
+    if (capacity % group != 0) return {UKFB_ERR_INVALID_ARG, "capacity must be a multiple of group"};
+    return {};
+}
+inline int64_t lifecycle_record_blocks(int64_t n) { return (n + LC_ROWS_PER_BLOCK - 1) / LC_ROWS_PER_BLOCK; }
+inline int64_t lifecycle_item_blocks(int64_t n) { return (n + LC_THREADS - 1) / LC_THREADS; }
+struct LifecycleGeometry {
+    int64_t groups;        // G = capacity / group
+    int count_blocks;      // blocks of the count and rank kernels
+    int move_blocks;       // the move kernel's fixed grid: rows stride over the pairs the device counted
+    int64_t pair_cap;      // entries of each of the two pair arrays (holes, movers): min(L, G - L) <= G / 2
+    size_t ws_words;       // 32-bit words of the engine's lifecycle workspace (sized for group = 1, so that it serves every group)
+    size_t owner_off, counts_off, before_off, totals_off, hole_off, mover_off;   // word offsets of its pieces (64-word aligned)
+};
+inline LifecycleGeometry lifecycle_geometry(int64_t capacity, int group) {
+    LifecycleGeometry g{};
+    g.groups = capacity / group;
+    g.count_blocks = int((g.groups + LC_COUNT_BLOCK - 1) / LC_COUNT_BLOCK);
+    g.pair_cap = g.groups / 2 + 1;
+    const int64_t rows = (g.groups / 2) * group;   // the most filters a call can move
+    g.move_blocks = int(std::max<int64_t>(1, std::min<int64_t>(lifecycle_record_blocks(rows), LC_MOVE_MAX_BLOCKS)));
+    const size_t max_blocks = size_t((capacity + LC_COUNT_BLOCK - 1) / LC_COUNT_BLOCK), max_pairs = size_t(capacity / 2 + 1);
+    auto piece = [&g](size_t words) {
+        const size_t at = g.ws_words;
+        g.ws_words += (words + 63) / 64 * 64;
+        return at;
+    };
+    g.owner_off = piece(size_t(capacity));
+    g.counts_off = piece(max_blocks);
+    g.before_off = piece(max_blocks);
+    g.totals_off = piece(4);
+    g.hole_off = piece(max_pairs);
+    g.mover_off = piece(max_pairs);
+    return g;
+}
 
 // bytes of workspace process_events_device needs for n events (an upper bound that does not depend on hipCUB's
 // temporary-storage query: 4x the key/value arrays covers rocPRIM's double buffers)

@@ -58,6 +58,9 @@ EXPORTS = [
     "ukfb_history_push_dev", "ukfb_smooth_dev", "ukfb_smooth",
     # forecast: multi-step prediction from a start record into a ring of the history's format (read-only)
     "ukfb_forecast_dev", "ukfb_forecast",
+    # filter lifecycle: whole per-filter records gathered and scattered on the device, retirement, in-place compaction
+    "ukfb_gather_filters_dev", "ukfb_scatter_filters_dev", "ukfb_retire_dev", "ukfb_compact_dev",
+    "ukfb_gather_filters", "ukfb_scatter_filters", "ukfb_compact",
     # joint state-block measurements: update / fuse with full covariance, covariance intersection, track-to-track distance
     "ukfb_update_state_dev", "ukfb_update_state", "ukfb_pose_update_body_states",
     # sensor-frame measurements: lever arms, ranges, landmark fixes, nav-frame vectors
@@ -116,6 +119,13 @@ class SensorOut(C.Structure):
     """ukfb_sensor_out: device pointers in engine precision (status uint32), any may be NULL"""
     _fields_ = [("z_pred", C.c_void_p), ("S", C.c_void_p), ("innov", C.c_void_p), ("maha", C.c_void_p),
                 ("loglik", C.c_void_p), ("status", C.c_void_p)]
+
+
+class FilterRecords(C.Structure):
+    """ukfb_filter_records: device pointers, n records in item order, scalars in engine precision; any may be NULL (scatter needs
+    mu and cov_packed)"""
+    _fields_ = [("mu", C.c_void_p), ("cov_packed", C.c_void_p), ("last_ts_us", C.c_void_p), ("initialised", C.c_void_p),
+                ("in_a", C.c_void_p), ("in_b", C.c_void_p), ("noise", C.c_void_p), ("status", C.c_void_p)]
 
 
 class UkfbError(RuntimeError):
@@ -543,6 +553,93 @@ class BatchUKF:
         _chk(self._lib.ukfb_forecast(self._h, C.c_int(steps), _pd(d), tp, _pd(sm), _pd(sc), _pd(a), _pd(b), _pd(mu), _pd(cov),
                                      st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_forecast")
         return mu, cov, st
+
+    # ---- filter lifecycle: records [n, S] / [n, PK] / int64 [n] / uint8 [n] / [n, 3] / [n, 3] / [n, D, D] / uint32 [n] on the device
+    @staticmethod
+    def _records(mu, cov_packed, last_ts_us, initialised, in_a, in_b, noise, status):
+        rec = FilterRecords()
+        for name, x in (("mu", mu), ("cov_packed", cov_packed), ("last_ts_us", last_ts_us), ("initialised", initialised),
+                        ("in_a", in_a), ("in_b", in_b), ("noise", noise), ("status", status)):
+            p = _devptr(x)
+            setattr(rec, name, p.value if p is not None else None)
+        return rec
+
+    @staticmethod
+    def _items(index_dev, n, capacity):
+        if n is None:
+            n = int(index_dev.numel()) if hasattr(index_dev, "numel") else (capacity if index_dev is None else None)
+        if n is None:
+            raise UkfbError("n is needed with an index given as a device address")
+        return n
+
+    def gather_filters_dev(self, index_dev, mu=None, cov_packed=None, last_ts_us=None, initialised=None, in_a=None, in_b=None,
+                           noise=None, status=None, n: Optional[int] = None):
+        """Record k <- filter index_dev[k] (int32 on the device; None: item k is filter k), field by field, None = skipped:
+        mu [n, S], cov_packed [n, PK], last_ts_us int64 [n], initialised uint8 [n], in_a / in_b [n, 3] (what the filter's next
+        prediction would read), noise [n, D, D], status uint32 / int32 [n].  An index outside [0, capacity) writes zeros and
+        ST_INACTIVE.  Read-only on the engine; stream-ordered, no synchronisation.  Tensors or device addresses (then n)."""
+        n = self._items(index_dev, n, self.capacity)
+        rec = self._records(mu, cov_packed, last_ts_us, initialised, in_a, in_b, noise, status)
+        _chk(self._lib.ukfb_gather_filters_dev(self._h, C.c_int64(n), _devptr(index_dev), C.byref(rec)), "ukfb_gather_filters_dev")
+
+    def scatter_filters_dev(self, index_dev, mu, cov_packed, last_ts_us=None, initialised=None, in_a=None, in_b=None, noise=None,
+                            status=None, n: Optional[int] = None):
+        """initializeFilter from device records: filter index_dev[k] <- record k.  mu and cov_packed are required;
+        initialised None = 1 (a 0 retires the filter), last_ts_us None = 0; in_a / in_b go into the engine's latches, noise into
+        the filter's per-filter entry (the engine must already store its noise per filter).  Among the items that name one
+        filter the lowest wins; every other one, and every index outside [0, capacity), gets ST_INACTIVE in status.
+        Stream-ordered, no synchronisation."""
+        n = self._items(index_dev, n, self.capacity)
+        rec = self._records(mu, cov_packed, last_ts_us, initialised, in_a, in_b, noise, status)
+        _chk(self._lib.ukfb_scatter_filters_dev(self._h, C.c_int64(n), _devptr(index_dev), C.byref(rec)), "ukfb_scatter_filters_dev")
+
+    def retire_dev(self, retire_mask_dev):
+        """uint8 / bool [capacity] on the device: a non-zero byte clears the filter's initialised flag and last measurement time"""
+        _chk(self._lib.ukfb_retire_dev(self._h, _devptr(retire_mask_dev)), "ukfb_retire_dev")
+
+    def compact_dev(self, group: int = 1, new_index=None, old_index=None, live=None):
+        """Move the live groups of `group` consecutive filters to the front, in place (include/ukf_batch.h, "filter
+        lifecycle").  new_index / old_index int32 [capacity] and live int64 [1] on the device, each may be None.  Bound input
+        buffers are not moved: permute them with old_index."""
+        _chk(self._lib.ukfb_compact_dev(self._h, C.c_int(group), _devptr(new_index), _devptr(old_index), _devptr(live)),
+             "ukfb_compact_dev")
+
+    def gather_filters(self, index=None, n: Optional[int] = None):
+        """Host form: index int32 [n] or None (item k is filter k) -> (mu [n, S], cov [n, D, D], last_ts_us [n],
+        initialised bool [n]); synchronises"""
+        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1) if index is not None else None
+        n = (idx.size if idx is not None else self.capacity) if n is None else n
+        mu, cov = np.zeros((n, self.S)), np.zeros((n, self.D, self.D))
+        ts, init = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.uint8)
+        _chk(self._lib.ukfb_gather_filters(self._h, C.c_int64(n), idx.ctypes.data_as(C.POINTER(C.c_int32)) if idx is not None else None,
+                                           _pd(mu), _pd(cov), ts.ctypes.data_as(C.POINTER(C.c_int64)),
+                                           init.ctypes.data_as(C.POINTER(C.c_uint8))), "ukfb_gather_filters")
+        return mu, cov, ts, init.astype(bool)
+
+    def scatter_filters(self, index, mu, cov, last_ts_us=None, initialised=None):
+        """Host form: filter index[k] <- (mu[k], cov[k] full D x D, last_ts_us[k] or 0, initialised[k] or 1); returns the
+        per-item status; synchronises"""
+        mu = _f64(mu, (-1, self.S)); cov = _f64(cov, (-1, self.D, self.D))
+        n = mu.shape[0]
+        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1) if index is not None else None
+        ts = np.ascontiguousarray(last_ts_us, dtype=np.int64).reshape(n) if last_ts_us is not None else None
+        init = np.ascontiguousarray(initialised, dtype=np.uint8).reshape(n) if initialised is not None else None
+        if idx is not None and idx.size != n:
+            raise UkfbError("scatter_filters: one index per record")
+        st = np.zeros(n, dtype=np.uint32)
+        _chk(self._lib.ukfb_scatter_filters(self._h, C.c_int64(n), idx.ctypes.data_as(C.POINTER(C.c_int32)) if idx is not None else None,
+                                            _pd(mu), _pd(cov), ts.ctypes.data_as(C.POINTER(C.c_int64)) if ts is not None else None,
+                                            init.ctypes.data_as(C.POINTER(C.c_uint8)) if init is not None else None,
+                                            st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_scatter_filters")
+        return st
+
+    def compact(self, group: int = 1):
+        """Host form -> (new_index int32 [capacity], old_index int32 [capacity], live); synchronises"""
+        new, old = np.zeros(self.capacity, dtype=np.int32), np.zeros(self.capacity, dtype=np.int32)
+        live = C.c_int64(0)
+        _chk(self._lib.ukfb_compact(self._h, C.c_int(group), new.ctypes.data_as(C.POINTER(C.c_int32)),
+                                    old.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(live)), "ukfb_compact")
+        return new, old, int(live.value)
 
     # ---- joint state-block measurements: z in the state's own layout [capacity, S], Qz the packed lower triangle [capacity, PK]
     def update_state_dev(self, block_mask: int, z_dev, Qz_packed_dev, block_mask_dev=None, state_inflation: float = 1.0,

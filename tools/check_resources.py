@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Build gate for EVERY shipped kernel instantiation (ukf_kernel16, the generic ukf_kernel, ukf_innovation_kernel, ukf_bank_*_kernel, ukf_smooth_kernel, ukf_forecast_kernel, ukf_state_meas_kernel, ukf_sensor_meas_kernel): no scratch and no AGPRs, and
+"""Build gate for EVERY shipped kernel instantiation (ukf_kernel16, the generic ukf_kernel, ukf_innovation_kernel, ukf_bank_*_kernel, ukf_smooth_kernel, ukf_forecast_kernel, ukf_lifecycle_*_kernel, ukf_state_meas_kernel, ukf_sensor_meas_kernel): no scratch and no AGPRs, and
 the tuned kernels keep the wavefronts per SIMD their design counts on (fp64: three, fp32: five) -- a register regression
 that costs a wavefront fails the build instead of showing up as a slower bench line.
 
@@ -37,7 +37,7 @@ def main(paths):
     for p in paths:
         for k in parse(open(p).read()):
             if "ukf_kernel" not in k["name"] and "ukf_innovation_kernel" not in k["name"] and "ukf_bank_" not in k["name"] \
-                    and "ukf_smooth_kernel" not in k["name"] and "ukf_forecast_kernel" not in k["name"] and "ukf_state_meas_kernel" not in k["name"] and "ukf_sensor_meas_kernel" not in k["name"]:
+                    and "ukf_smooth_kernel" not in k["name"] and "ukf_forecast_kernel" not in k["name"] and "ukf_lifecycle_" not in k["name"] and "ukf_state_meas_kernel" not in k["name"] and "ukf_sensor_meas_kernel" not in k["name"]:
                 continue
             rows.append(k)
             if k.get("scratch", 0) or (k.get("agpr", 0) and not allow_agpr):
