@@ -199,6 +199,32 @@ public:
                                  z_pred, S, innov, maha, loglik, st.data()));
         return st;
     }
+    /** Late samples (ukf_batch.h, "late samples"): a sample taken in.lag steps ago corrects the CURRENT state through the history
+     *  ring -- no stored measurements, no replay, no waiting for the slowest sensor.  The window is smoothDev's with the
+     *  filters' own state as its last step; commit = false is read-only (only `out` is written, out->mu_out / cov_out showing
+     *  what a commit would store).  Stream-ordered. */
+    void updateDelayedDev(const ukfb_delayed_in& in, bool commit = true, const ukfb_delayed_out* out = NULL)
+    {
+        check(ukfb_update_delayed_dev(engine, &in, commit ? 1 : 0, out));
+    }
+    /** the lag of every filter's sample from its stamp: step_ts_us host [steps], sample_ts_us_dev int64 [N] -> lag_out_dev int32 [N] */
+    void delayedLagDev(int steps, const int64_t* step_ts_us, const int64_t* sample_ts_us_dev, int32_t* lag_out_dev)
+    {
+        check(ukfb_delayed_lag_dev(engine, steps, step_ts_us, sample_ts_us_dev, lag_out_dev));
+    }
+    /** host arrays in window order: mu_hist [steps][N][S], cov_hist [steps][N][D][D] (the last step is not read), dt [steps - 1],
+     *  in_a / in_b [steps][N][3] or NULL; lag / model_per_filter [N] or NULL (lag_uniform / model); z [N][3], Q [N][3][3];
+     *  mu_out [N][S] / cov_out [N][D][D] or NULL: the corrected present state.  Returns the status. */
+    std::vector<uint32_t> updateDelayed(int steps, const double* dt, const double* mu_hist, const double* cov_hist, int lag_uniform,
+                                        int model, const double* z, const double* Q, bool commit = true, const int32_t* lag = NULL,
+                                        const int32_t* model_per_filter = NULL, const double* in_a = NULL, const double* in_b = NULL,
+                                        double* mu_out = NULL, double* cov_out = NULL, double* maha = NULL, double* loglik = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_update_delayed(engine, steps, dt, mu_hist, cov_hist, in_a, in_b, lag_uniform, lag, model, model_per_filter, z, Q,
+                                  commit ? 1 : 0, NULL, NULL, NULL, maha, loglik, st.data(), mu_out, cov_out));
+        return st;
+    }
     /** host arrays in window order, smoothed in place: mu [steps][N][S], cov [steps][N][D][D]; returns the per-filter status */
     std::vector<uint32_t> smooth(int steps, const double* dt, double* mu, double* cov, const double* in_a = NULL,
                                  const double* in_b = NULL)

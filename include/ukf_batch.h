@@ -483,6 +483,106 @@ int ukfb_smooth_dev(ukfb_engine* e, int steps, const double* dt, int slots, int 
 int ukfb_smooth(ukfb_engine* e, int steps, const double* dt, double* mu, double* cov, const double* in_a, const double* in_b,
                 uint32_t* status);
 
+/* ---- late samples: a delayed-measurement update through the state history -------------------------------------------------- */
+/* A sample that was taken `lag` steps ago (a GPS, USBL or visual fix behind the inertial stream) corrects the CURRENT state,
+ * without storing measurements and without replaying cycles: the smoother's backward chain runs from the present down to the
+ * step of the sample, the product of its gains is the cross-covariance between that step and the present, and the sample's
+ * update of the smoothed past state is carried to the present through it.  For a linear system the result is what the filter
+ * would hold had the sample arrived in order; whatever mix of update calls produced the history, the call only needs the ring.
+ *
+ * WINDOW: ukfb_smooth_dev's -- `steps` consecutive slots of a history ring (mu_hist_dev [slots][capacity][S], cov_hist_dev
+ * [slots][capacity][PK], engine precision), oldest first, step c in slot (first_slot + c) % slots holding the filtered state of
+ * time c; dt[c] (HOST, steps - 1 entries, by value; may be NULL for steps = 1) the step of the prediction c -> c + 1; in_a_dev /
+ * in_b_dev optional input rings with the smoother's meaning, NULL: the engine's latches.  One difference: STEP n = steps - 1 IS
+ * THE ENGINE'S OWN CURRENT STATE, read from the engine; the ring's slot of step n is never read (a caller who pushes after every
+ * cycle has it there anyway).  1 <= steps <= min(slots, UKFB_DELAYED_MAX_STEPS); more steps is UKFB_ERR_OUT_OF_RANGE and
+ * writes nothing.  Keeping the engine's state, process noise and inputs consistent with what the ring recorded is the caller's
+ * responsibility.
+ * LAG: every filter has a lag l >= 0, its sample was taken at step s = n - l: lag_uniform, or lag_dev [capacity] (int32) when
+ * that pointer is non-NULL.  l = 0 is an ordinary update.  A negative lag: no sample for that filter (INACTIVE).  l > steps - 1:
+ * the sample is older than the window reaches -- UKFB_ST_ERR_NEG_DT, the status a late sample gets from the cycle calls, and
+ * the filter keeps every bit.
+ * SAMPLE: the measurement models of ukfb_update_dev, ids 0 ... 9, uniform or per filter (meas_model_dev; a negative id or one
+ * the engine's model does not have: INACTIVE); z_dev [capacity][3] (axis-angle for the SO(3) model, as ukfb_update_dev);
+ * Q_dev [capacity][9] or one 3 x 3 with q_is_uniform.  State-block and sensor-frame models are not served.
+ *
+ * Per filter ((+) / (-): the engine's; J(phi): the identity with Jr^-1(phi) on the SO(3) block, the smoother's transport;
+ * A(phi): the identity with Jr(phi) = I - (1 - cos t) / t^2 [phi]x + (t - sin t) / t^3 [phi]x^2 there):
+ *   1. (mu^s_n, Sigma^s_n) = the engine's (mu_n, Sigma_n), M_n = I (D x D);
+ *   2. for c = n - 1 ... s: the smoother's steps 1-6 exactly as ukfb_smooth_dev defines them (the redone prediction, C, G_c,
+ *      e = mu^s_(c+1) (-) mu^-_(c+1), the transport J(e_rot), Sigma~, the commit applyDelta(mu_c, Sigma~, delta_c = G_c e)) give
+ *      (mu^s_c, Sigma^s_c), and M_c = A(delta_c,rot) G_c J(e_rot) M_(c+1).  J re-expresses a deviation about mu^s_(c+1) as one
+ *      about mu^-_(c+1); A re-expresses a deviation about the filtered mu_c as one about mu^s_c = mu_c (+) delta_c, to first
+ *      order what applyDelta's re-sampling does to the covariance.  M_s Sigma_n is Cov(x_s about mu^s_s, x_n about mu_n | all
+ *      samples up to n).  A gated dt[c] (small, negative, too large) passes chain and M through, as the smoother passes its chain;
+ *   3. ukfom's update, first half, on (mu^s_s, Sigma^s_s): L = chol(Sigma^s_s), sigma points, Z_i = h(X_i), the iterated mean
+ *      z-bar, S = 1/2 sum dz dz^T + Q, C_z = sum_j (L col j) W_j^T, S = Ls Ls^T, Y_s = C_z Ls^-T, nu = z (-) z-bar,
+ *      y = Ls^-1 nu, d^2 = |y|^2, ln det S; the gate is ukfb_update_dev's (gate_chi2);
+ *   4. Y_n = Sigma_n M_s^T (Sigma^s_s)^-1 Y_s (two triangular solves with L per row of Sigma_n M_s^T); for l = 0 this is Y_s;
+ *   5. Sigma~_n = Sigma_n - Y_n Y_n^T, (mu_n, Sigma_n) <- applyDelta(mu_n, Sigma~_n, Y_n y), the update's own commit.
+ * The residual offset of a sample inside its step interval is ignored (ukfb_delayed_lag_dev picks the nearest step).
+ * LIMITATION: the ring is not rewritten after a commit.  A second late sample for the same filter inside the same window runs
+ * its chain over records that do not know the first: its result is approximate (tests/test_delayed_reference.py records by how
+ * much on a linear system).  The last measurement times of the engine are not moved: the sample is older than they are.
+ *
+ * commit = 0 is READ-ONLY on the engine (as ukfb_innovation_dev): only the outputs are written.  commit = 1 stores the corrected
+ * state into the engine; `out` may then be NULL.  Outputs (device, engine precision, any may be NULL): z_pred [capacity][4] (a
+ * quaternion for the SO(3) model, else the first m entries and zeros), S [capacity][9] (zeros beyond m), innov [capacity][3],
+ * maha, loglik [capacity], status [capacity] (uint32), and mu_out [capacity][S] / cov_out [capacity][PK], the corrected present
+ * state: commit = 0 shows there what commit = 1 would store.  mu_out / cov_out must NOT be the engine's own arrays or the ring.
+ * Status of the call (with commit = 1 also written to the engine's status array):
+ *   UNINITIALISED; INACTIVE (negative lag, no model); ERR_NEG_DT (out of the window); ERR_NONFINITE_MEAS (a used entry of z);
+ *   ERR_CHOLESKY      any factorisation of the filter's chain, Sigma^s_s, S or Sigma~_n fails -- unlike the smoother a failed
+ *                     chain step REFUSES the sample: the cross-covariance is broken;
+ *   WARN_MEAN_NOCONV; REJECTED_GATE (z_pred, S, innov, maha, loglik are still written);
+ *   SKIPPED_SMALL_DT / ERR_NEG_DT / ERR_DT_TOO_LARGE of gated dt[c], as an OR over the filter's chain.
+ * A filter that commits nothing keeps every bit and gets NaN in its float outputs (mu_out / cov_out of a gated-out sample too);
+ * it never changes a bit of another filter.  Stream-ordered, joins split streams, no host synchronisation, no allocation at
+ * call time; one kernel serves every lanes_per_filter setting; fp32 engines compute in fp32, with wide_arithmetic in fp64.
+ * Device groups: per shard through ukfb_group_shard. */
+#define UKFB_DELAYED_MAX_STEPS 33
+typedef struct ukfb_delayed_in {
+    int steps;                    /* window length, step steps - 1 is the present                                        */
+    const double* dt;             /* HOST [steps - 1]                                                                      */
+    int slots, first_slot;
+    const void* mu_hist_dev;      /* [slots][capacity][S]                                                                  */
+    const void* cov_hist_dev;     /* [slots][capacity][PK]                                                                 */
+    const void* in_a_dev;         /* [slots][capacity][3] or NULL                                                          */
+    const void* in_b_dev;
+    int lag_uniform;
+    const int32_t* lag_dev;       /* [capacity] or NULL: lag_uniform                                                       */
+    int meas_model_uniform;
+    const int32_t* meas_model_dev; /* [capacity] or NULL: meas_model_uniform                                               */
+    const void* z_dev;            /* [capacity][3]                                                                         */
+    const void* Q_dev;            /* [capacity][9], or [9] with q_is_uniform                                               */
+    int q_is_uniform;
+} ukfb_delayed_in;
+typedef struct ukfb_delayed_out { /* device pointers, engine precision; any may be NULL                                    */
+    void* z_pred;                 /* [capacity][4]                                                                         */
+    void* S;                      /* [capacity][9]                                                                         */
+    void* innov;                  /* [capacity][3]                                                                         */
+    void* maha;                   /* [capacity]                                                                            */
+    void* loglik;                 /* [capacity]                                                                            */
+    uint32_t* status;             /* [capacity]                                                                            */
+    void* mu_out;                 /* [capacity][S]                                                                         */
+    void* cov_out;                /* [capacity][PK]                                                                        */
+} ukfb_delayed_out;
+int ukfb_update_delayed_dev(ukfb_engine* e, const ukfb_delayed_in* in, int commit, const ukfb_delayed_out* out);
+/* Host arrays of doubles, window order: mu_hist [steps][capacity][S], cov_hist [steps][capacity][D][D] (step steps - 1 is not
+ * read), in_a / in_b [steps][capacity][3] or NULL; lag [capacity] or NULL (lag_uniform); meas_model_per_filter [capacity] or
+ * NULL; z [capacity][3], Q [capacity][3][3].  Outputs (any may be NULL): z_pred [capacity][4], S [capacity][9], innov
+ * [capacity][3], maha, loglik, status [capacity], mu_out [capacity][S], cov_out [capacity][D][D].  Synchronises. */
+int ukfb_update_delayed(ukfb_engine* e, int steps, const double* dt, const double* mu_hist, const double* cov_hist, const double* in_a,
+                        const double* in_b, int lag_uniform, const int32_t* lag, int meas_model, const int32_t* meas_model_per_filter,
+                        const double* z, const double* Q, int commit, double* z_pred, double* S, double* innov, double* maha,
+                        double* loglik, uint32_t* status, double* mu_out, double* cov_out);
+/* The lag of a sample from its time stamp: step_ts_us (HOST, `steps` strictly increasing stamps of the window's steps, by value,
+ * 1 <= steps <= UKFB_DELAYED_MAX_STEPS), sample_ts_us_dev [capacity] (int64) -> lag_out_dev [capacity] (int32): l = n - c*, c* the
+ * step whose stamp is nearest the sample's (ties go to the OLDER step); a sample newer than step n gives 0; a sample older than
+ * step 0 by more than half of step_ts[1] - step_ts[0] gives `steps`, which ukfb_update_delayed_dev reports as out of the
+ * window.  The residual offset inside a step interval is ignored.  Stream-ordered. */
+int ukfb_delayed_lag_dev(ukfb_engine* e, int steps, const int64_t* step_ts_us, const int64_t* sample_ts_us_dev, int32_t* lag_out_dev);
+
 /* ---- forecast: read-only multi-step prediction into a ring ------------------------------------------------------------------ */
 /* Where every filter will be after the next 1 ... steps predictions, with covariance, WITHOUT committing them (collision
  * checks, gating a scan that has not arrived yet, latency-compensated output at one common time for filters whose last samples

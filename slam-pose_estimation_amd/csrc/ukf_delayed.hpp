@@ -1,0 +1,836 @@
+// ukf_delayed.hpp -- late samples: the delayed-measurement update through the state history.  The smoother's backward chain
+// runs from the engine's present state down to the step a late sample was taken at, the operator M (the product of the chain's
+// gains and transports) is carried along it, ukfom's measurement half is made on the smoothed past state and the correction is
+// retrodicted to the present and committed there.  Definitions: include/ukf_batch.h ("late samples"), DESIGN.md 4.20.
+//
+// Layout: the smoother's (ukf_smooth.hpp) -- one filter per 16-lane DPP row, four per wavefront, one wavefront per workgroup, the
+// chain resident in LDS between the steps, the opaque lane move in the step loop -- and its device functions in its order.
+//  * M takes another D x LS region of LDS per filter; lane l < D owns row l.  One step's M <- A G J M is: the three rotation
+//    COLUMNS of the lane's row of G times Jr^-1 inside the lane (G J), one row x matrix product with broadcast reads of M from
+//    LDS (the row of G J goes through the dead factor region, as the smoother's (G M) row does), and the three rotation ROWS
+//    times Jr over the rotation's lanes (DPP broadcasts).  J and A are block identities, so the two "congruences" are 3 x 3 work.
+//  * Jr(phi) = I - a [phi]x + b [phi]x^2 in closed form from cos_sinc_fast: a = (1 - cos t) / t^2 = sinc(t / 2)^2 / 2 has no
+//    cancellation at any angle in the half-angle form, b = (t - sin t) / t^3 = (1 - sinc(t / 2) cos(t / 2)) / t^2 above
+//    t^2 = 1/4 and its series below (the split of bank_jrinv_coeff).  The alternative, a 3 x 3 inverse of the Jr^-1 the chain
+//    already forms, costs a determinant, a division and nine cofactors and inherits Jr^-1's rounding; the closed form is one
+//    more cos_sinc_fast and six multiply-adds.
+//  * per-filter lags: the step loop runs to the wavefront's largest lag; a row whose lag is reached (or whose chain broke, or
+//    that has no sample) freezes chain and M and rides along -- per-row selects, no divergence in what wave-mates compute.
+//  * after the loop every row runs the measurement half once on its chain record: the sigma points of (mu^s, Sigma^s), h = the
+//    model's M::measure (ids 0 ... 9, per-row selects between the vector models and the SO(3) one), the iterated mean, S in
+//    registers on every lane (six row all-reductions), C_z row = sum_j L[l][j] W_j, Y_s = C_z Ls^-T.
+//  * retrodiction, all row-local: lane l forms row l of N = Sigma_n M^T (broadcast reads of M), solves it against the factor of
+//    Sigma^s (the smoother's two triangular solves per row: P = N (Sigma^s)^-1) and takes Y_n row l = sum_j P[l][j] Y_s[j].
+//    For lag 0 M = I, N = Sigma^s and P = I to rounding.
+//  * commit: Sigma~_n = Sigma_n - Y_n Y_n^T, applyDelta(mu_n, Sigma~_n, Y_n y) as the sensor-measurement kernel.
+//  * commit = 0: the kernel gets NULL for the engine's state pointers -- it has nothing through which it could store there.
+//  * TS (storage) / T (compute) as in ukf_kernel16: TS = float with T = double is the wide-arithmetic mode.  Plain fp32 holds the
+//    1e-4 gate without any fp64 piece (tests/test_delayed_reference.py: the all-float32 evaluation is 2e-6 from the float64 one).
+// LDS per filter: delayed_filter_scalars (ukf_host.hpp) -- the smoother's slice and the rows of M behind it.
+#pragma once
+
+#include "ukf_sensor_meas.hpp"
+
+namespace ukfb {
+
+template <class T, class TS> struct DelayedArgs {
+    int64_t n;                   // filters
+    const TS* mu;                // [n][S]   the engine's state: the chain's start and what the commit corrects
+    const TS* cov;               // [n][PK]
+    TS* eng_mu;                  // the same arrays for commit = 1, null for commit = 0
+    TS* eng_cov;
+    uint32_t* engine_status;     // [n]; null for commit = 0
+    const TS* mu_hist;           // [slots][n][S]
+    const TS* cov_hist;          // [slots][n][PK]
+    int slots, top_slot, back;   // ring size, slot of step n (never read), backward steps of the window (steps - 1)
+    const uint8_t* initialised;  // [n]
+    const TS* Rn;                // process noise, D * D row-major; per filter if Rn_stride != 0
+    int64_t Rn_stride;
+    const TS* Racc;              // Pose: acceleration-branch noise (same stride)
+    const TS* in_a;              // [n][3], or [slots][n][3] when in_ring & 1
+    const TS* in_b;              // [n][3], or [slots][n][3] when in_ring & 2
+    int in_ring;
+    T ninv_tau_g, ninv_tau_a, earth[3];
+    T mean_tol;
+    int mean_max_it;
+    double min_dt, max_dt;
+    int lag_uniform;
+    const int32_t* lag;          // [n] or null
+    int model_uniform;
+    const int32_t* model;        // [n] or null
+    const TS* z;                 // [n][3]
+    const TS* Q;                 // [n][9], or [9] when q_uniform
+    int q_uniform;
+    T gate_chi2;                 // < 0: accept
+    TS* z_pred;                  // [n][4] or null
+    TS* S;                       // [n][9] or null
+    TS* innov;                   // [n][3] or null
+    TS* maha;                    // [n] or null
+    TS* loglik;                  // [n] or null
+    uint32_t* status;            // [n] or null
+    TS* mu_out;                  // [n][S] or null
+    TS* cov_out;                 // [n][PK] or null
+    double dt[SMOOTH_MAX_BACK];  // dt[k]: time step of the prediction redone by backward step k (step n - 1 - k -> n - k)
+};
+
+template <class M> struct DelayedLayout {
+    using SL = SmoothLayout<M>;
+    static constexpr int S = M::S, D = M::D, LS = SMOOTH_LS, ZS = 4;
+    static constexpr int MOP = SL::PF;                    // D * LS: the operator M, row l at MOP + l * LS
+    static constexpr int WT = SL::TAB, YM = SL::TAB + D * ZS, YN = SL::TAB + 2 * D * ZS;   // D x 3 matrices in the dead delta table
+    static constexpr int PF = (MOP + D * LS + 3) / 4 * 4;
+    static_assert(PF == delayed_filter_scalars(S, D), "LDS accounting of ukf_host.hpp");
+    static_assert(3 * D * ZS <= (2 * D + 1) * LS, "W, Y_s and Y_n fit the delta table");
+};
+
+// (a, b) of Jr(phi) = I - a [phi]x + b [phi]x^2 as functions of t = theta^2 (see the head of the file)
+template <class T> UKFB_DEV void delayed_jr_coeffs(T t, T& a, T& b) {
+    T ch, sh;
+    cos_sinc_fast(T(0.25) * t, ch, sh);   // cos(theta / 2), sinc(theta / 2)
+    a = T(0.5) * sh * sh;
+    T s = T(1. / 1307674368000.);
+    s = fma(s, t, T(-1. / 6227020800.));
+    s = fma(s, t, T(1. / 39916800.));
+    s = fma(s, t, T(-1. / 362880.));
+    s = fma(s, t, T(1. / 5040.));
+    s = fma(s, t, T(-1. / 120.));
+    s = fma(s, t, T(1. / 6.));
+    const bool big = !(t <= T(0.25));
+    const T closed = fma(-sh, ch, T(1)) * fast_rcp(big ? t : T(1));
+    b = big ? closed : s;
+}
+
+// rows li = 0 ... 2 of I + ca [phi]x + cb [phi]x^2 (Jr: ca = -a, cb = b; Jr^-1: ca = 1/2, cb = bank_jrinv_coeff), row-major
+template <class T> UKFB_DEV void delayed_rot_matrix(const T (&p)[3], T t, T ca, T cb, T (&B)[9]) {
+    const T p0 = p[0], p1 = p[1], p2 = p[2];
+    B[0] = fma(cb, p0 * p0 - t, T(1)); B[1] = fma(cb, p0 * p1, -ca * p2); B[2] = fma(cb, p0 * p2, ca * p1);
+    B[3] = fma(cb, p1 * p0, ca * p2); B[4] = fma(cb, p1 * p1 - t, T(1)); B[5] = fma(cb, p1 * p2, -ca * p0);
+    B[6] = fma(cb, p2 * p0, -ca * p1); B[7] = fma(cb, p2 * p1, ca * p0); B[8] = fma(cb, p2 * p2 - t, T(1));
+}
+
+// What a row derives from its lane index (the smoother's SmoothRow over the wider slice, and the rows of M)
+template <class T, class M, class TS> struct DelayedRow {
+    using LY = DelayedLayout<M>;
+    using SL = SmoothLayout<M>;
+    int l, lr, ls;
+    bool fvalid, live;
+    int64_t f;
+    T *FAC, *RSP, *TAB, *GM, *MM, *CSM, *CSP, *MUF, *PKF, *ROT, *DUMP, *SMR, *MUP, *MOP;
+    const TS *Rn, *Racc;
+    UKFB_DEV DelayedRow(const DelayedArgs<T, TS>& a, unsigned char* smem, int lane) {
+        const int g = lane >> 4;
+        l = lane & 15;
+        lr = (l < M::D) ? l : (M::D - 1);
+        ls = (l < M::S) ? l : (M::S - 1);
+        const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * DELAYED_FILTERS_PER_GROUP;
+        const int64_t n_here = a.n - wg0;
+        const int n_wg = int(n_here < DELAYED_FILTERS_PER_GROUP ? n_here : int64_t(DELAYED_FILTERS_PER_GROUP));
+        fvalid = g < n_wg;
+        f = wg0 + (fvalid ? g : (n_wg - 1));   // rows beyond the batch repeat its last filter and store nothing
+        live = fvalid && a.initialised[f] != 0;
+        T* const base = reinterpret_cast<T*>(smem) + g * LY::PF;
+        FAC = base + SL::FAC; RSP = base + SL::RSP; TAB = base + SL::TAB; GM = base + SL::GM; MM = base + SL::MM;
+        CSM = base + SL::CSM; CSP = base + SL::CSP; MUF = base + SL::MUF; PKF = base + SL::PKF; ROT = base + SL::ROT;
+        DUMP = base + SL::DUM; SMR = base + SL::SMR; MUP = base + SL::MUP; MOP = base + LY::MOP;
+        Rn = a.Rn + f * a.Rn_stride;
+        Racc = a.Racc + f * a.Rn_stride;
+    }
+};
+
+// What a row's sample asks for: model, lag and whether the row takes part at all (the same from every lane of the row)
+template <class T, class M, class TS> struct DelayedSample {
+    int midc, m, reach;
+    bool so3, mvalid, inactive, old, bad, do_u;
+    T zin[3];
+    UKFB_DEV DelayedSample(const DelayedArgs<T, TS>& a, int64_t f, bool live) {
+        const int mid = a.model ? a.model[f] : a.model_uniform;
+        const int lag = a.lag ? a.lag[f] : a.lag_uniform;
+        mvalid = M::meas_valid(mid);
+        midc = mvalid ? mid : (M::MODEL == 0 ? 0 : 9);
+        m = M::meas_dim(midc);
+        so3 = M::meas_is_so3(midc);
+        inactive = lag < 0 || !mvalid;
+        old = !inactive && lag > a.back;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) zin[c] = T(a.z[f * 3 + c]);
+        bad = !(m_finite(zin[0]) && (m < 2 || m_finite(zin[1])) && (m < 3 || m_finite(zin[2])));
+        do_u = live && !inactive && !old && !bad;
+        reach = do_u ? lag : 0;
+    }
+};
+
+// (the second bound: wavefronts per SIMD the register allocator must leave room for -- the LDS slices admit no more in fp64)
+template <class T> constexpr int delayed_waves() { return 2; }
+template <class T, class M, class TS>
+__global__ void __launch_bounds__(64, (delayed_waves<T>())) ukf_delayed_kernel(const DelayedArgs<T, TS> a) {
+    constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
+    using LY = DelayedLayout<M>;
+    constexpr int LS = LY::LS, ZS = LY::ZS, Q = MT<M>::Q, RT = MT<M>::RT;
+    extern __shared__ __attribute__((aligned(16))) unsigned char delayed_smem[];
+    uint32_t st = ST_OK;
+    bool chain_ok = true;
+    int slot = a.top_slot;
+    {
+        // ---- the chain's start: the engine's own state, and M = I
+        const DelayedRow<T, M, TS> r(a, delayed_smem, threadIdx.x);
+        r.CSM[r.l] = T(a.mu[r.f * S + r.ls]);
+        for (int i = r.l; i < PK; i += 16) r.CSP[i] = T(a.cov[r.f * PK + i]);
+#pragma unroll
+        for (int c = 0; c < D; ++c) r.MOP[r.lr * LS + c] = (c == r.lr) ? T(1) : T(0);   // (lanes >= D: row D - 1's own bits again)
+        wsync();
+    }
+#pragma nounroll
+    for (int k = 0; k < a.back; ++k) {
+        // (the lane index passes through an opaque move in every step and its derivatives are formed again: ukf_smooth.hpp)
+        int lane = threadIdx.x;
+        asm volatile("" : "+v"(lane));
+        const DelayedRow<T, M, TS> row(a, delayed_smem, lane);
+        const auto& [l, lr, ls, fvalid, live, f, FAC, RSP, TAB, GM, MM, CSM, CSP, MUF, PKF, ROT, DUMP, SMR, MUP, MOP, Rn, Racc] = row;
+        int reach;
+        {
+            const DelayedSample<T, M, TS> smp(a, f, live);
+            reach = smp.reach;
+        }
+        if (!wave_any(k < reach)) break;   // the wavefront's largest lag is reached
+        slot = (slot == 0) ? (a.slots - 1) : (slot - 1);
+        const int64_t rec = int64_t(slot) * a.n + f;
+        // ---- the filtered record of this step and its inputs
+        MUF[l] = T(a.mu_hist[rec * S + ls]);
+        for (int i = l; i < PK; i += 16) PKF[i] = T(a.cov_hist[rec * PK + i]);
+        ProcIn<T> pin;
+        {
+            const TS* pa = a.in_a + (((a.in_ring & 1) ? int64_t(slot) * a.n : int64_t(0)) + f) * 3;
+            const TS* pb = a.in_b + (((a.in_ring & 2) ? int64_t(slot) * a.n : int64_t(0)) + f) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                pin.a[c] = T(pa[c]);
+                pin.w[c] = T(pb[c]);
+            }
+        }
+        const double dt = a.dt[k];
+        const bool neg = dt < 0.0, small = dt <= a.min_dt, large = dt > a.max_dt;
+        const uint32_t code = neg ? ST_ERR_NEG_DT : (small ? ST_SKIPPED_SMALL_DT : (large ? ST_ERR_DT_TOO_LARGE : 0u));
+        const bool inchain = k < reach;         // (reach > 0 only for rows that take part)
+        st |= inchain ? code : 0u;
+        const bool dof = inchain && chain_ok && code == 0u;   // a gated step passes chain and M through; so does a frozen row
+        pin.dt = T(dt);
+        pin.ninv_tau_g = a.ninv_tau_g;
+        pin.ninv_tau_a = a.ninv_tau_a;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) pin.earth[c] = a.earth[c];
+        pin.use_acc = m_finite(pin.a[0]) && m_finite(pin.a[1]) && m_finite(pin.a[2]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) pin.adt[c] = pin.use_acc ? pin.dt * pin.a[c] : T(0);
+        wsync();
+
+        if (wave_any(dof)) {
+            UKFB_MARK("d_predict");
+            // ================================================================= 1. the prediction, redone (ukf_smooth.hpp)
+            T mu_r[S], xp[S], xm[S], ref[S];
+#pragma unroll
+            for (int s = 0; s < S; ++s) mu_r[s] = MUF[s];
+            {
+                T q[4], rot[9];
+                M::orientation(mu_r, q);
+                quat_to_matrix(q, rot);
+                T* dst = (l == 0) ? ROT : DUMP;
+#pragma unroll
+                for (int c = 0; c < 9; ++c) dst[c] = rot[c];
+            }
+            bool ok1;
+            {
+                T arow[D];
+                load_row<T, D>(PKF, l, arow);
+                const T rs = chol16<T, D, LS>(arow, FAC, l, ok1);
+                wsync();
+                sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);
+                T col[D];
+                load_column<T, D, LS>(FAC, l, T(1), col);
+                sigma_pair<T, M>(mu_r, col, xp, xm);
+            }
+            sfence();
+            process_fast((M*)nullptr, xp, pin);
+            sfence();
+            process_fast((M*)nullptr, xm, pin);
+            sfence();
+#pragma unroll
+            for (int s = 0; s < S; ++s) ref[s] = row_bcast<D>(xp[s]);
+            bool conv = true;
+            {
+                const T wp = (l <= D) ? T(1) : T(0), wm = (l < D) ? T(1) : T(0);
+                bool active = dof && ok1;
+                int it = 0;
+                while (wave_any(active)) {
+                    T dp[D], dm[D];
+                    sm_boxminus<T, M>(xp, ref, dp);
+                    sm_boxminus<T, M>(xm, ref, dm);
+#pragma unroll
+                    for (int c = 0; c < D; ++c) dp[c] = fma(wm, dm[c], wp * dp[c]);
+                    row_allreduce_n<T, D>(dp);
+                    T m2 = T(0);
+#pragma unroll
+                    for (int c = 0; c < D; ++c) {
+                        dp[c] *= T(1) / T(N);
+                        m2 = fma(dp[c], dp[c], m2);
+                    }
+                    T nr[S];
+                    sm_boxplus<T, M>(ref, dp, nr);
+#pragma unroll
+                    for (int s = 0; s < S; ++s) ref[s] = active ? nr[s] : ref[s];
+                    const bool more = m2 > a.mean_tol * a.mean_tol;
+                    const bool capped = more && (it + 1 >= a.mean_max_it);
+                    it += (active && more) ? 1 : 0;
+                    conv = conv && !(active && capped);
+                    active = active && more && !capped;
+                }
+            }
+            sm_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, ref);
+            wsync();
+            T sm[D];
+            sm_table_row<T, D, LS>(TAB, N, lr, sm);
+            sfence();
+#pragma unroll
+            for (int c = 0; c < D; ++c) SMR[lr * LS + c] = sm[c];
+            sfence();
+#pragma nounroll
+            for (int c = 0; c < D; ++c) {
+                const int hi = lr > c ? lr : c, lo = lr > c ? c : lr;
+                const T nz = (c < 6) ? process_noise_entry16<T, M, TS>(Rn, Racc, ROT, pin, hi, lo)
+                                     : plain_noise_entry16<T, M, TS>(Rn, Racc, pin, hi, lo);
+                SMR[lr * LS + c] += nz;
+            }
+            {
+                T* dst = (l == 0) ? MUP : DUMP;
+#pragma unroll
+                for (int s2 = 0; s2 < S; ++s2) dst[s2] = ref[s2];
+            }
+            sfence();
+            UKFB_MARK("d_cross");
+            // ================================================================= 2. C, 3. G = C (Sigma^-)^-1
+            T g_[D];
+            {
+                T cr[D];
+#pragma unroll
+                for (int c = 0; c < D; ++c) cr[c] = T(0);
+#pragma nounroll
+                for (int j = 0; j < D; ++j) {
+                    const T lj = FAC[j * LS + lr];
+                    const T* w = TAB + (D + j) * LS;
+#pragma unroll
+                    for (int c = 0; c < D; ++c) cr[c] = fma(lj, w[c], cr[c]);
+                }
+                wsync();
+                bool ok2;
+                {
+                    T tmp[D];
+#pragma unroll
+                    for (int c = 0; c < D; ++c) tmp[c] = SMR[lr * LS + c];
+                    const T rs = chol16<T, D, LS>(tmp, FAC, l, ok2);
+                    wsync();
+                    sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);
+                }
+                ok1 = ok1 && ok2;
+#pragma unroll
+                for (int k2 = 0; k2 < D; ++k2) {
+                    T v = cr[k2];
+#pragma unroll
+                    for (int j = 0; j < k2; ++j) v = fma(-FAC[j * LS + k2], cr[j], v);
+                    cr[k2] = v * RSP[k2];
+                    sfence();
+                }
+#pragma unroll
+                for (int k2 = D - 1; k2 >= 0; --k2) {
+                    T v = cr[k2];
+#pragma unroll
+                    for (int j = k2 + 1; j < D; ++j) v = fma(-FAC[k2 * LS + j], cr[j], v);
+                    cr[k2] = v * RSP[k2];
+                    sfence();
+                }
+#pragma unroll
+                for (int c = 0; c < D; ++c) g_[c] = cr[c];
+            }
+            wsync();
+#pragma unroll
+            for (int c = 0; c < D; ++c) GM[lr * LS + c] = g_[c];
+            UKFB_MARK("d_transport");
+            // ================================================================= 4. transport of the chain to the tangent space at mu^-
+            T e[D];
+            {
+                T cs[S], mp[S];
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    cs[s] = CSM[s];
+                    mp[s] = MUP[s];
+                }
+                sm_boxminus<T, M>(cs, mp, e);
+            }
+            const int li = lr - RT;
+            const bool inrot = li >= 0 && li < 3;
+            {
+                const T ph[3] = {e[RT], e[RT + 1], e[RT + 2]};
+                const T t = fma(ph[0], ph[0], fma(ph[1], ph[1], ph[2] * ph[2]));
+                T B[9];
+                delayed_rot_matrix(ph, t, T(0.5), bank_jrinv_coeff(t), B);
+                T s[D];
+#pragma unroll
+                for (int c = 0; c < D; ++c) {
+                    const int hi = lr > c ? lr : c, lo = lr > c ? c : lr;
+                    s[c] = CSP[hi * (hi + 1) / 2 + lo];
+                }
+                {
+                    const T s0 = s[RT], s1 = s[RT + 1], s2 = s[RT + 2];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) s[RT + i] = fma(s0, B[3 * i], fma(s1, B[3 * i + 1], s2 * B[3 * i + 2]));
+                }
+                const T b0 = (li == 1) ? B[3] : ((li == 2) ? B[6] : B[0]);
+                const T b1 = (li == 1) ? B[4] : ((li == 2) ? B[7] : B[1]);
+                const T b2 = (li == 1) ? B[5] : ((li == 2) ? B[8] : B[2]);
+#pragma unroll
+                for (int c = 0; c < D; ++c) {
+                    const T r0 = row_bcast<RT>(s[c]), r1 = row_bcast<RT + 1>(s[c]), r2 = row_bcast<RT + 2>(s[c]);
+                    const T rot = fma(b0, r0, fma(b1, r1, b2 * r2));
+                    MM[lr * LS + c] = (inrot ? rot : s[c]) - SMR[lr * LS + c];
+                }
+                // ============================================================= 4b. row lr of G J: the rotation columns of G times Jr^-1,
+                // through the dead factor region (the product below indexes it by a loop variable)
+                {
+                    const T g0 = g_[RT], g1 = g_[RT + 1], g2 = g_[RT + 2];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) g_[RT + i] = fma(g0, B[i], fma(g1, B[3 + i], g2 * B[6 + i]));
+                }
+#pragma unroll
+                for (int c = 0; c < D; ++c) FAC[lr * LS + c] = g_[c];
+            }
+            wsync();
+            UKFB_MARK("d_operator");
+            // ================================================================= 4c. M <- A (G J) M: row lr
+            {
+                T tr[D];
+#pragma unroll
+                for (int c = 0; c < D; ++c) tr[c] = T(0);
+#pragma nounroll
+                for (int j = 0; j < D; ++j) {
+                    const T gj = FAC[lr * LS + j];
+                    const T* mrow = MOP + j * LS;
+#pragma unroll
+                    for (int c = 0; c < D; ++c) tr[c] = fma(gj, mrow[c], tr[c]);
+                }
+                // delta = G e (its rotation part: A's argument)
+                T dl = T(0);
+#pragma unroll
+                for (int c = 0; c < D; ++c) dl = fma(GM[lr * LS + c], e[c], dl);
+                const T dr[3] = {row_bcast<RT>(dl), row_bcast<RT + 1>(dl), row_bcast<RT + 2>(dl)};
+                const T t = fma(dr[0], dr[0], fma(dr[1], dr[1], dr[2] * dr[2]));
+                T ja, jb, A[9];
+                delayed_jr_coeffs(t, ja, jb);
+                delayed_rot_matrix(dr, t, -ja, jb, A);
+                const T a0 = (li == 1) ? A[3] : ((li == 2) ? A[6] : A[0]);
+                const T a1 = (li == 1) ? A[4] : ((li == 2) ? A[7] : A[1]);
+                const T a2 = (li == 1) ? A[5] : ((li == 2) ? A[8] : A[2]);
+                wsync();   // every lane has read the rows of M
+                T* const dst = dof ? (MOP + lr * LS) : DUMP;   // a frozen, gated or broken row keeps its M
+#pragma unroll
+                for (int c = 0; c < D; ++c) {
+                    const T r0 = row_bcast<RT>(tr[c]), r1 = row_bcast<RT + 1>(tr[c]), r2 = row_bcast<RT + 2>(tr[c]);
+                    const T rot = fma(a0, r0, fma(a1, r1, a2 * r2));
+                    dst[dof ? c : 0] = inrot ? rot : tr[c];
+                }
+            }
+            wsync();
+            UKFB_MARK("d_cov");
+            // ================================================================= 5. Sigma~ = Sigma + (G M) G^T: row lr, and delta = G e
+            T sg[D], del[D];
+            {
+                T tr[D];
+#pragma unroll
+                for (int c = 0; c < D; ++c) tr[c] = T(0);
+#pragma nounroll
+                for (int j = 0; j < D; ++j) {
+                    const T gj = GM[lr * LS + j];
+                    const T* m = MM + j * LS;
+#pragma unroll
+                    for (int c = 0; c < D; ++c) tr[c] = fma(gj, m[c], tr[c]);
+                }
+#pragma unroll
+                for (int c = 0; c < D; ++c) {
+                    const int hi = lr > c ? lr : c, lo = lr > c ? c : lr;
+                    sg[c] = PKF[hi * (hi + 1) / 2 + lo];
+                }
+#pragma unroll
+                for (int c = 0; c < D; ++c) FAC[lr * LS + c] = tr[c];
+                sfence();
+#pragma nounroll
+                for (int j = 0; j < D; ++j) {
+                    const T tj = FAC[lr * LS + j];
+                    const T* gc = GM + j;
+#pragma unroll
+                    for (int c = 0; c < D; ++c) sg[c] = fma(tj, gc[c * LS], sg[c]);
+                }
+                sfence();
+                T dl = T(0);
+#pragma unroll
+                for (int c = 0; c < D; ++c) dl = fma(GM[lr * LS + c], e[c], dl);
+                static_for<0, D>([&](auto cc) {
+                    constexpr int c = decltype(cc)::value;
+                    del[c] = row_bcast<c>(dl);
+                });
+            }
+            wsync();
+            UKFB_MARK("d_commit");
+            // ================================================================= 6. commit: applyDelta(mu, Sigma~, delta)
+            bool ok3;
+            T mnew[S];
+            {
+                const T rs = chol16<T, D, LS>(sg, FAC, l, ok3);
+                wsync();
+                T col[D], dpl[D], dmi[D];
+                load_column<T, D, LS>(FAC, l, rs, col);
+#pragma unroll
+                for (int c = 0; c < D; ++c) {
+                    dpl[c] = del[c] + col[c];
+                    dmi[c] = del[c] - col[c];
+                }
+#pragma unroll
+                for (int s2 = 0; s2 < S; ++s2) mu_r[s2] = MUF[s2];
+                sfence();
+                sm_boxplus<T, M>(mu_r, del, mnew);
+                sm_boxplus<T, M>(mu_r, dpl, xp);
+                sm_boxplus<T, M>(mu_r, dmi, xm);
+                sm_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, mnew);
+            }
+            wsync();
+            sm_table_row<T, D, LS>(TAB, 2 * D, lr, sg);
+            bool inf = false;   // (the chain must stay finite: an Inf that the factorisations let through would poison M)
+#pragma unroll
+            for (int c = 0; c < D; ++c) inf = inf || !m_finite(sg[c]);
+            const bool good = dof && ok1 && ok3 && !bank_row_any(inf);
+            st |= (dof && !good) ? ST_ERR_CHOLESKY : 0u;
+            st |= (dof && good && !conv) ? ST_WARN_MEAN_NOCONV : 0u;
+            chain_ok = chain_ok && !(dof && !good);   // a broken chain refuses the sample
+            {
+                T v = mnew[0];
+#pragma unroll
+                for (int s = 1; s < S; ++s) v = (ls == s) ? mnew[s] : v;
+                T* dst = (good && l < S) ? (CSM + l) : DUMP;
+                *dst = v;
+#pragma unroll
+                for (int c = 0; c < D; ++c) {
+                    const int idx = lr * (lr + 1) / 2 + c;
+                    const bool own = good && l < D && c <= l;
+                    T* dc = own ? (CSP + idx) : DUMP;
+                    *dc = sg[c];
+                }
+            }
+            wsync();
+        }
+    }
+
+    // ======================================================================= after the loop: the sample meets the smoothed past state
+    const DelayedRow<T, M, TS> row(a, delayed_smem, threadIdx.x);
+    const auto& [l, lr, ls, fvalid, live, f, FAC, RSP, TAB, GM, MM, CSM, CSP, MUF, PKF, ROT, DUMP, SMR, MUP, MOP, Rn, Racc] = row;
+    const DelayedSample<T, M, TS> smp(a, f, live);
+    const int midc = smp.midc, m = smp.m;
+    const bool so3 = smp.so3, do_u = smp.do_u;
+    T* const WT = TAB + (LY::WT - LY::SL::TAB);
+    T* const YM = TAB + (LY::YM - LY::SL::TAB);
+    T* const YN = TAB + (LY::YN - LY::SL::TAB);
+    // the engine's present state into the (dead) filtered-record region
+    MUF[l] = T(a.mu[f * S + ls]);
+    for (int i = l; i < PK; i += 16) PKF[i] = T(a.cov[f * PK + i]);
+    wsync();
+    UKFB_MARK("d_sigma");
+    // ================================================================= 3a. sigma points of (mu^s, Sigma^s) and Z = h(X)
+    bool ok1;
+    T zp[4], zm[4], z0[4];
+    {
+        T mu_r[S], xp[S], xm[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) mu_r[s] = CSM[s];
+        T arow[D];
+        load_row<T, D>(CSP, l, arow);
+        const T rs = chol16<T, D, LS>(arow, FAC, l, ok1);
+        wsync();
+        sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);   // the scaled columns stay: C_z and the retrodiction's solves read them
+        T col[D];
+        load_column<T, D, LS>(FAC, l, T(1), col);
+        sigma_pair<T, M>(mu_r, col, xp, xm);          // lanes >= D: the centre twice
+        sfence();
+        M::measure(xp, midc, zp);
+        M::measure(xm, midc, zm);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) z0[c] = row_bcast<D>(zp[c]);
+    }
+    sfence();
+    UKFB_MARK("d_mean");
+    // ================================================================= 3b. z-bar: ukfom's iterated mean (R^m, or SO(3) for model 3)
+    const bool any_so3 = wave_any(so3);
+    const T wp = (l <= D) ? T(1) : T(0), wm = (l < D) ? T(1) : T(0);
+    T ref[4] = {z0[0], z0[1], z0[2], z0[3]};
+    bool conv = true;
+    {
+        bool active = do_u && chain_ok && ok1;
+        int it = 0;
+        while (wave_any(active)) {
+            T rp[3] = {T(0), T(0), T(0)}, rm[3] = {T(0), T(0), T(0)};
+            if (any_so3) {
+                rot_minus(zp, ref, rp);
+                rot_minus(zm, ref, rm);
+            }
+            T dp[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dp[c] = fma(wm, so3 ? rm[c] : (zm[c] - ref[c]), wp * (so3 ? rp[c] : (zp[c] - ref[c])));
+            row_allreduce_n<T, 3>(dp);
+            T m2 = T(0);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                dp[c] *= T(1) / T(N);
+                m2 = fma(dp[c], dp[c], m2);
+            }
+            T nq[4] = {T(0), T(0), T(0), T(1)};
+            if (any_so3) {
+                T ex[4];
+                so3_exp_fast(dp, T(1), ex);
+                quat_mul(ref, ex, nq);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) ref[c] = active ? (so3 ? nq[c] : (ref[c] + dp[c])) : ref[c];
+            ref[3] = (active && so3) ? nq[3] : ref[3];
+            const bool more = m2 > a.mean_tol * a.mean_tol;
+            const bool capped = more && (it + 1 >= a.mean_max_it);
+            it += (active && more) ? 1 : 0;
+            conv = conv && !(active && capped);
+            active = active && more && !capped;
+        }
+    }
+    UKFB_MARK("d_stats");
+    // ================================================================= 3c. S = 1/2 sum dz dz^T + Q (identity beyond m), nu, W to LDS
+    T s6[6], nu[3];
+    {
+        T dpv[3], dmv[3], nv[3];
+        {
+            T rp[3] = {T(0), T(0), T(0)}, rm[3] = {T(0), T(0), T(0)}, rn[3] = {T(0), T(0), T(0)};
+            if (any_so3) {
+                rot_minus(zp, ref, rp);
+                rot_minus(zm, ref, rm);
+                T zq[4];
+                so3_exp_fast(smp.zin, T(1), zq);   // RotationType(SO3::exp(z)), as ukfb_update_dev
+                rot_minus(zq, ref, rn);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                dpv[c] = so3 ? rp[c] : (zp[c] - ref[c]);
+                dmv[c] = so3 ? rm[c] : (zm[c] - ref[c]);
+                nv[c] = so3 ? rn[c] : ((c < m) ? (smp.zin[c] - ref[c]) : T(0));
+            }
+        }
+        T u[3], w[3];
+        const T fu = (l == D) ? T(0.70710678118654752440) : T(1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            u[c] = wp * (fu * (T(0.5) * (dpv[c] + dmv[c])));   // the centre's row: delta_0 / sqrt 2; lanes beyond it: nothing
+            w[c] = wm * (T(0.5) * (dpv[c] - dmv[c]));
+            nu[c] = nv[c];
+        }
+        T* const dst = (l < D) ? (WT + l * ZS) : DUMP;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dst[c] = w[c];
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c <= r; ++c) s6[r * (r + 1) / 2 + c] = fma(u[r], u[c], w[r] * w[c]);
+        row_allreduce_n<T, 6>(s6);
+        const TS* qp = a.Q + (a.q_uniform ? int64_t(0) : f * 9);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c <= r; ++c) {
+                const T q = T(qp[3 * r + c]);
+                s6[r * (r + 1) / 2 + c] = (r < m) ? (s6[r * (r + 1) / 2 + c] + q) : ((r == c) ? T(1) : T(0));   // (c <= r < m)
+            }
+    }
+    wsync();
+    UKFB_MARK("d_cross_z");
+    // ================================================================= 3d. C_z row lr, S = Ls Ls^T in registers, Y_s = C_z Ls^-T, y = Ls^-1 nu
+    bool ok2;
+    T lndet, d2, yn[3];
+    {
+        T cr[3] = {T(0), T(0), T(0)};
+#pragma nounroll
+        for (int j = 0; j < D; ++j) {
+            const T lj = FAC[j * LS + lr];
+            const T* w = WT + j * ZS;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) cr[c] = fma(lj, w[c], cr[c]);
+        }
+        const T d0 = s6[0], i0 = fast_rcp(d0);
+        const T t10 = s6[1] * i0, t20 = s6[3] * i0;
+        const T d1 = fma(-t10, s6[1], s6[2]), a21 = fma(-t20, s6[1], s6[4]);
+        const T i1 = fast_rcp(d1);
+        const T d2p = fma(-(a21 * i1), a21, fma(-t20, s6[3], s6[5]));
+        ok2 = (d0 > T(0)) && (d1 > T(0)) && (d2p > T(0));   // (NaN fails every comparison)
+        lndet = m_log(d0) + m_log(d1) + m_log(d2p);          // a pivot beyond m is exactly 1
+        const T rs[3] = {fast_rsqrt(d0), fast_rsqrt(d1), fast_rsqrt(d2p)};
+        const T l10 = s6[1] * rs[0], l20 = s6[3] * rs[0], l21 = a21 * rs[1];
+        sensor_solve3(cr, l10, l20, l21, rs);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) yn[c] = nu[c];
+        sensor_solve3(yn, l10, l20, l21, rs);
+        d2 = fma(yn[0], yn[0], fma(yn[1], yn[1], yn[2] * yn[2]));
+        T* const dst = (l < D) ? (YM + l * ZS) : DUMP;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dst[c] = cr[c];
+    }
+    const bool accept = (a.gate_chi2 < T(0)) || (d2 <= a.gate_chi2);
+    wsync();
+    UKFB_MARK("d_retro");
+    // ================================================================= 4. Y_n = Sigma_n M^T (Sigma^s)^-1 Y_s: row lr
+    T yr[3] = {T(0), T(0), T(0)};
+    {
+        T nr[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) nr[c] = T(0);
+#pragma nounroll
+        for (int j = 0; j < D; ++j) {   // N[lr][c] = sum_j Sigma_n[lr][j] M[c][j]
+            const int hi = lr > j ? lr : j, lo = lr > j ? j : lr;
+            const T sj = PKF[hi * (hi + 1) / 2 + lo];
+            const T* mc = MOP + j;
+#pragma unroll
+            for (int c = 0; c < D; ++c) nr[c] = fma(sj, mc[c * LS], nr[c]);
+        }
+        // P = N (Sigma^s)^-1: the smoother's two triangular solves per row, against the factor of Sigma^s
+#pragma unroll
+        for (int k2 = 0; k2 < D; ++k2) {
+            T v = nr[k2];
+#pragma unroll
+            for (int j = 0; j < k2; ++j) v = fma(-FAC[j * LS + k2], nr[j], v);
+            nr[k2] = v * RSP[k2];
+            sfence();
+        }
+#pragma unroll
+        for (int k2 = D - 1; k2 >= 0; --k2) {
+            T v = nr[k2];
+#pragma unroll
+            for (int j = k2 + 1; j < D; ++j) v = fma(-FAC[k2 * LS + j], nr[j], v);
+            nr[k2] = v * RSP[k2];
+            sfence();
+        }
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            const T* ys = YM + j * ZS;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) yr[c] = fma(nr[j], ys[c], yr[c]);
+        }
+        T* const dst = (l < D) ? (YN + l * ZS) : DUMP;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dst[c] = yr[c];
+    }
+    wsync();
+    UKFB_MARK("d_cov_n");
+    // ================================================================= 5. Sigma~_n = Sigma_n - Y_n Y_n^T: row lr, and delta = Y_n y
+    T sg[D], del[D];
+    {
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            const int hi = lr > c ? lr : c, lo = lr > c ? c : lr;
+            const T* yc = YN + c * ZS;   // the rows other lanes wrote
+            sg[c] = fma(-yr[2], yc[2], fma(-yr[1], yc[1], fma(-yr[0], yc[0], PKF[hi * (hi + 1) / 2 + lo])));
+        }
+        const T dl = fma(yr[2], yn[2], fma(yr[1], yn[1], yr[0] * yn[0]));
+        static_for<0, D>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            del[c] = row_bcast<c>(dl);
+        });
+    }
+    wsync();   // W, Y_s, Y_n and the factor of Sigma^s are dead
+    UKFB_MARK("d_commit_n");
+    bool ok3;
+    T mnew[S];
+    {
+        const T rs = chol16<T, D, LS>(sg, FAC, l, ok3);
+        wsync();
+        T col[D], dpl[D], dmi[D], mu_r[S], xp[S], xm[S];
+        load_column<T, D, LS>(FAC, l, rs, col);
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            dpl[c] = del[c] + col[c];
+            dmi[c] = del[c] - col[c];
+        }
+#pragma unroll
+        for (int s2 = 0; s2 < S; ++s2) mu_r[s2] = MUF[s2];
+        sfence();
+        sm_boxplus<T, M>(mu_r, del, mnew);
+        sm_boxplus<T, M>(mu_r, dpl, xp);
+        sm_boxplus<T, M>(mu_r, dmi, xm);
+        sm_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, mnew);
+    }
+    wsync();
+    sm_table_row<T, D, LS>(TAB, 2 * D, lr, sg);
+    bool inf = false;
+#pragma unroll
+    for (int c = 0; c < D; ++c) inf = inf || !m_finite(sg[c]);
+    const bool fin = !bank_row_any(inf);
+    const bool okc = chain_ok && ok1 && ok2 && (!accept || (ok3 && fin));
+    const bool good = do_u && okc && accept;
+    st |= !fvalid ? ST_OK : (!live ? ST_UNINITIALISED : (smp.inactive ? ST_INACTIVE : (smp.old ? ST_ERR_NEG_DT : (smp.bad ? ST_ERR_NONFINITE_MEAS : ST_OK))));
+    st |= (do_u && !okc) ? ST_ERR_CHOLESKY : 0u;
+    st |= (do_u && chain_ok && ok1 && !conv) ? ST_WARN_MEAN_NOCONV : 0u;
+    st |= (do_u && okc && !accept) ? ST_REJECTED_GATE : 0u;
+
+    UKFB_MARK("d_store");
+    // ---- the new state through LDS (the records are dead), then whole rows of the packed arrays
+    {
+        T v = mnew[0];
+#pragma unroll
+        for (int s = 1; s < S; ++s) v = (ls == s) ? mnew[s] : v;
+        T* const dm = (l < S) ? (MUF + l) : DUMP;
+        *dm = v;
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            const bool own = l < D && c <= l;
+            T* const dc = own ? (PKF + lr * (lr + 1) / 2 + c) : DUMP;
+            *dc = sg[c];
+        }
+    }
+    wsync();
+    const T nanv = m_nan<T>();
+    if (good && a.eng_mu) {
+        if (l < S) a.eng_mu[f * S + l] = TS(MUF[l]);
+        for (int i = l; i < PK; i += 16) a.eng_cov[f * PK + i] = TS(PKF[i]);
+    }
+    if (fvalid) {
+        if (a.mu_out && l < S) a.mu_out[f * S + l] = TS(good ? MUF[l] : nanv);
+        if (a.cov_out)
+            for (int i = l; i < PK; i += 16) a.cov_out[f * PK + i] = TS(good ? PKF[i] : nanv);
+        const bool scored = do_u && okc;
+        if (a.z_pred && l < 4) {
+            T v = ref[0];
+#pragma unroll
+            for (int c = 1; c < 4; ++c) v = (l == c) ? ref[c] : v;
+            a.z_pred[f * 4 + l] = TS(scored ? ((so3 || l < m) ? v : T(0)) : nanv);
+        }
+        if (a.innov && l < 3) {
+            T v = nu[0];
+#pragma unroll
+            for (int c = 1; c < 3; ++c) v = (l == c) ? nu[c] : v;
+            a.innov[f * 3 + l] = TS(scored ? ((l < m) ? v : T(0)) : nanv);
+        }
+        if (a.S && l < 9) {
+            T v = T(0);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const int r = k / 3, c = k % 3, hi = r > c ? r : c, lo = r > c ? c : r;
+                v = (l == k) ? ((hi < m) ? s6[hi * (hi + 1) / 2 + lo] : T(0)) : v;
+            }
+            a.S[f * 9 + l] = TS(scored ? v : nanv);
+        }
+        if (l == 0) {
+            const T m_ln2pi = T(m) * T(1.8378770664093454835606594728112);
+            if (a.maha) a.maha[f] = TS(scored ? d2 : nanv);
+            if (a.loglik) a.loglik[f] = TS(scored ? T(-0.5) * (d2 + lndet + m_ln2pi) : nanv);
+            if (a.status) a.status[f] = st;
+            if (a.engine_status) a.engine_status[f] = st;
+        }
+    }
+}
+
+}  // namespace ukfb

@@ -1,6 +1,6 @@
 // ukf_host.hpp -- the engine's host decisions as pure functions of plain values: configuration checks, process-noise
-// classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, packed covariances, workspace sizing, the filter lifecycle's checks and geometry and
-// the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
+// classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, packed covariances, workspace sizing, the filter lifecycle's checks and geometry, the delayed-measurement
+// update's checks, geometry and lag rule, and the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
 #pragma once
 
 #include <stddef.h>
@@ -443,6 +443,70 @@ struct SensorGeometry {
 inline SensorGeometry sensor_geometry(int S, int D, int64_t capacity, size_t compute_size) {
     return {(capacity + SENSOR_FILTERS_PER_GROUP - 1) / SENSOR_FILTERS_PER_GROUP,
             int(size_t(SENSOR_FILTERS_PER_GROUP) * sensor_filter_scalars(S, D) * compute_size)};
+}
+
+// ---- late samples (ukfb_update_delayed_dev, ukfb_delayed_lag_dev) -----------------------------------------------------------
+// The smoother's window with the engine's own state as its last step: the chain runs at most steps - 1 <= SMOOTH_MAX_BACK
+// backward steps, all in one launch (their dt travel in the kernel arguments), so steps <= DELAYED_MAX_STEPS.
+constexpr int DELAYED_MAX_STEPS = UKFB_DELAYED_MAX_STEPS, DELAYED_FILTERS_PER_GROUP = 4;
+static_assert(DELAYED_MAX_STEPS == SMOOTH_MAX_BACK + 1, "one launch covers the longest window");
+inline Verdict check_delayed_args(const ukfb_delayed_in* in, int commit, const ukfb_delayed_out* out) {
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    if (in->slots < 1 || in->steps < 1) return {UKFB_ERR_INVALID_ARG, "steps >= 1, slots >= 1"};
+    if (in->first_slot < 0 || in->first_slot >= in->slots) return {UKFB_ERR_INVALID_ARG, "0 <= first_slot < slots"};
+    if (in->steps > 1 && !in->dt) return {UKFB_ERR_INVALID_ARG, "dt must not be NULL for a window of more than one step"};
+    if (!in->mu_hist_dev || !in->cov_hist_dev) return {UKFB_ERR_INVALID_ARG, "mu_hist_dev and cov_hist_dev must not be NULL"};
+    if (!in->z_dev || !in->Q_dev) return {UKFB_ERR_INVALID_ARG, "z_dev and Q_dev must not be NULL"};
+    if (in->q_is_uniform != 0 && in->q_is_uniform != 1) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
+    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    if (commit == 0 && (!out || (!out->z_pred && !out->S && !out->innov && !out->maha && !out->loglik && !out->status && !out->mu_out &&
+                                 !out->cov_out)))
+        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
+    if (in->steps > std::min(in->slots, DELAYED_MAX_STEPS))
+        return {UKFB_ERR_OUT_OF_RANGE, "steps <= min(slots, 33): a sample older than that is out of the window"};
+    return {};
+}
+inline Verdict check_delayed_lag_args(int steps, const int64_t* step_ts_us, bool has_samples, bool has_out) {
+    if (steps < 1 || !step_ts_us) return {UKFB_ERR_INVALID_ARG, "steps >= 1 and step_ts_us must not be NULL"};
+    if (!has_samples || !has_out) return {UKFB_ERR_INVALID_ARG, "sample_ts_us_dev and lag_out_dev must not be NULL"};
+    if (steps > DELAYED_MAX_STEPS) return {UKFB_ERR_OUT_OF_RANGE, "steps <= 33"};
+    for (int c = 1; c < steps; ++c)
+        if (step_ts_us[c] <= step_ts_us[c - 1]) return {UKFB_ERR_INVALID_ARG, "step_ts_us must be strictly increasing"};
+    return {};
+}
+// The lag rule (host and device): l = n - c*, c* the step nearest the sample, ties to the older step; newer than step n: 0;
+// older than step 0 by more than half of the first interval: steps (out of the window).  Differences of stamps that are 2^62
+// apart would overflow: stamps are microseconds since an epoch, as everywhere in the engine.
+UKFB_HD int32_t delayed_lag_of(int steps, const int64_t* step_ts_us, int64_t t) {
+    const int n = steps - 1;
+    if (t >= step_ts_us[n]) return 0;
+    const int64_t first = steps > 1 ? step_ts_us[1] - step_ts_us[0] : 0;
+    if (t < step_ts_us[0] && 2 * (step_ts_us[0] - t) > first) return int32_t(steps);
+    int best = 0;
+    int64_t bd = t > step_ts_us[0] ? t - step_ts_us[0] : step_ts_us[0] - t;
+    for (int c = 1; c < steps; ++c) {
+        const int64_t d = t > step_ts_us[c] ? t - step_ts_us[c] : step_ts_us[c] - t;
+        if (d < bd) {   // strictly nearer: a tie stays with the older step
+            bd = d;
+            best = c;
+        }
+    }
+    return int32_t(n - best);
+}
+// LDS of one filter, in scalars of the compute type (ukf_delayed.hpp, DelayedLayout): the smoother's slice and behind it the D
+// rows (stride SMOOTH_LS) of the operator M; rounded up to a multiple of four so that every filter's slice starts 16-byte
+// aligned in either precision.  Every scalar the kernel reads is one it wrote.
+constexpr int delayed_filter_scalars(int S, int D) {
+    return S > 16 ? -1 : (smooth_filter_scalars(S, D) + D * SMOOTH_LS + 3) / 4 * 4;
+}
+struct DelayedGeometry {
+    int64_t grid;    // workgroups of four filters
+    int lds_bytes;   // dynamic LDS of a workgroup
+};
+// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
+inline DelayedGeometry delayed_geometry(int S, int D, int64_t capacity, size_t compute_size) {
+    return {(capacity + DELAYED_FILTERS_PER_GROUP - 1) / DELAYED_FILTERS_PER_GROUP,
+            int(size_t(DELAYED_FILTERS_PER_GROUP) * delayed_filter_scalars(S, D) * compute_size)};
 }
 
 // ---- packed covariances of the host-array forms ---------------------------------------------------------------------------

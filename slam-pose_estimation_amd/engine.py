@@ -65,6 +65,8 @@ EXPORTS = [
     "ukfb_update_state_dev", "ukfb_update_state", "ukfb_pose_update_body_states",
     # sensor-frame measurements: lever arms, ranges, landmark fixes, nav-frame vectors
     "ukfb_update_sensor_dev", "ukfb_update_sensor",
+    # late samples: the delayed-measurement update through the state history
+    "ukfb_update_delayed_dev", "ukfb_update_delayed", "ukfb_delayed_lag_dev",
     # device groups (one process, several GPUs)
     "ukfb_group_shard_range", "ukfb_group_create", "ukfb_group_destroy", "ukfb_group_size", "ukfb_group_shard",
     "ukfb_group_set_config", "ukfb_group_initialize", "ukfb_group_get_state", "ukfb_group_get_status",
@@ -119,6 +121,20 @@ class SensorOut(C.Structure):
     """ukfb_sensor_out: device pointers in engine precision (status uint32), any may be NULL"""
     _fields_ = [("z_pred", C.c_void_p), ("S", C.c_void_p), ("innov", C.c_void_p), ("maha", C.c_void_p),
                 ("loglik", C.c_void_p), ("status", C.c_void_p)]
+
+
+class DelayedIn(C.Structure):
+    """ukfb_delayed_in: the window (dt a HOST array), the lags, the models and the sample; device pointers in engine precision"""
+    _fields_ = [("steps", C.c_int), ("dt", C.POINTER(C.c_double)), ("slots", C.c_int), ("first_slot", C.c_int),
+                ("mu_hist_dev", C.c_void_p), ("cov_hist_dev", C.c_void_p), ("in_a_dev", C.c_void_p), ("in_b_dev", C.c_void_p),
+                ("lag_uniform", C.c_int), ("lag_dev", C.c_void_p), ("meas_model_uniform", C.c_int), ("meas_model_dev", C.c_void_p),
+                ("z_dev", C.c_void_p), ("Q_dev", C.c_void_p), ("q_is_uniform", C.c_int)]
+
+
+class DelayedOut(C.Structure):
+    """ukfb_delayed_out: device pointers in engine precision (status uint32), any may be NULL"""
+    _fields_ = [("z_pred", C.c_void_p), ("S", C.c_void_p), ("innov", C.c_void_p), ("maha", C.c_void_p), ("loglik", C.c_void_p),
+                ("status", C.c_void_p), ("mu_out", C.c_void_p), ("cov_out", C.c_void_p)]
 
 
 class FilterRecords(C.Structure):
@@ -710,6 +726,60 @@ class BatchUKF:
                                           _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]),
                                           o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_update_sensor")
         return o
+
+    # ---- late samples: the window of smooth_dev with the engine's own state as its last step
+    def update_delayed_dev(self, dt, slots: int, first_slot: int, mu_hist, cov_hist, lag, meas_model, z_dev, Q_dev,
+                           q_is_uniform: bool = False, in_a_dev=None, in_b_dev=None, commit: bool = True, z_pred=None, S=None,
+                           innov=None, maha=None, loglik=None, status=None, mu_out=None, cov_out=None):
+        """A sample taken `lag` steps ago corrects the current state through the history ring (include/ukf_batch.h, "late
+        samples").  The window has len(dt) + 1 steps, step c in slot (first_slot + c) % slots, the last step being the engine's
+        own state (its slot is not read).  lag / meas_model: an int for the whole batch or an int32 device array [capacity].
+        z_dev [capacity, 3], Q_dev [capacity, 9] (9 scalars with q_is_uniform).  commit=False is read-only: only the keyword
+        outputs (device buffers in engine precision, status uint32 / int32; mu_out [capacity, S] / cov_out [capacity, PK] = the
+        corrected present state) are written.  Stream-ordered, nothing is allocated."""
+        d = np.ascontiguousarray(dt, dtype=np.float64).reshape(-1)
+        ptr = lambda x: None if x is None else _devptr(x).value
+        per = lambda x: (0, ptr(x)) if hasattr(x, "data_ptr") else (int(x), None)
+        (lag_u, lag_p), (mod_u, mod_p) = per(lag), per(meas_model)
+        din = DelayedIn(d.size + 1, d.ctypes.data_as(C.POINTER(C.c_double)) if d.size else None, int(slots), int(first_slot),
+                        ptr(mu_hist), ptr(cov_hist), ptr(in_a_dev), ptr(in_b_dev), lag_u, lag_p, mod_u, mod_p, ptr(z_dev), ptr(Q_dev),
+                        1 if q_is_uniform else 0)
+        out = DelayedOut(ptr(z_pred), ptr(S), ptr(innov), ptr(maha), ptr(loglik), ptr(status), ptr(mu_out), ptr(cov_out))
+        _chk(self._lib.ukfb_update_delayed_dev(self._h, C.byref(din), C.c_int(1 if commit else 0), C.byref(out)),
+             "ukfb_update_delayed_dev")
+
+    def update_delayed(self, dt, mu_hist, cov_hist, lag, meas_model, z, Q, in_a=None, in_b=None, commit: bool = True):
+        """Host arrays in window order: mu_hist [steps, capacity, S], cov_hist [steps, capacity, D, D] (the last step is not
+        read), dt [steps - 1], in_a / in_b [steps, capacity, 3] or None; lag / meas_model an int or an int32 array [capacity];
+        z [capacity, 3], Q [capacity, 3, 3].  Returns a dict of NumPy arrays: z_pred [n, 4], S [n, 3, 3], innov [n, 3], maha,
+        loglik, status [n], mu_out [n, S], cov_out [n, D, D]; synchronises"""
+        d = np.ascontiguousarray(dt, dtype=np.float64).reshape(-1)
+        steps, n = d.size + 1, self.capacity
+        mu_hist = _f64(mu_hist, (steps, n, self.S)); cov_hist = _f64(cov_hist, (steps, n, self.D, self.D))
+        a = _f64(in_a, (steps, n, 3)) if in_a is not None else None
+        b = _f64(in_b, (steps, n, 3)) if in_b is not None else None
+        z = _f64(z, (n, 3)); Q = _f64(Q, (n, 3, 3))
+        i32 = lambda x: None if np.isscalar(x) else np.ascontiguousarray(x, dtype=np.int32).reshape(n)
+        lag_p, mod_p = i32(lag), i32(meas_model)
+        ip = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32)) if x is not None else None
+        o = {"z_pred": np.empty((n, 4)), "S": np.empty((n, 3, 3)), "innov": np.empty((n, 3)), "maha": np.empty(n),
+             "loglik": np.empty(n), "status": np.empty(n, dtype=np.uint32), "mu_out": np.empty((n, self.S)),
+             "cov_out": np.empty((n, self.D, self.D))}
+        _chk(self._lib.ukfb_update_delayed(self._h, C.c_int(steps), _pd(d) if d.size else None, _pd(mu_hist), _pd(cov_hist), _pd(a),
+                                           _pd(b), C.c_int(0 if lag_p is not None else int(lag)), ip(lag_p),
+                                           C.c_int(0 if mod_p is not None else int(meas_model)), ip(mod_p), _pd(z), _pd(Q),
+                                           C.c_int(1 if commit else 0), _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]),
+                                           _pd(o["loglik"]), o["status"].ctypes.data_as(C.POINTER(C.c_uint32)), _pd(o["mu_out"]),
+                                           _pd(o["cov_out"])), "ukfb_update_delayed")
+        return o
+
+    def delayed_lag_dev(self, step_ts_us, sample_ts_us_dev, lag_out_dev):
+        """step_ts_us: host int64 stamps of the window's steps (strictly increasing); sample_ts_us_dev int64 [capacity] ->
+        lag_out_dev int32 [capacity]: the step nearest each sample (ties: the older), 0 for a sample newer than the present,
+        len(step_ts_us) (out of the window) for one older than the first step by more than half a step.  Stream-ordered."""
+        ts = np.ascontiguousarray(step_ts_us, dtype=np.int64).reshape(-1)
+        _chk(self._lib.ukfb_delayed_lag_dev(self._h, C.c_int(ts.size), ts.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            _devptr(sample_ts_us_dev), _devptr(lag_out_dev)), "ukfb_delayed_lag_dev")
 
     # ---- fused cycle
     def cycle(self, dt: float, meas_model: int, z, Q):
