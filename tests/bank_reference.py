@@ -21,11 +21,13 @@ def hat(p):
 
 
 def jr_inv(p):
-    """Jr^-1(phi) = I + [phi]x / 2 + c(theta) [phi]x^2, c = 1/theta^2 - (1 + cos theta) / (2 theta sin theta)"""
+    """Jr^-1(phi) = I + [phi]x / 2 + c(theta) [phi]x^2, c = (1 - (theta/2) cot(theta/2)) / theta^2 in the half-angle form
+    (sin(theta/2) - (theta/2) cos(theta/2)) / (theta^2 sin(theta/2)): no cancellation towards theta = pi (c = 1/pi^2) and no
+    zero denominator below the pole of Jr^-1 at 2 pi; 1/theta^2 - (1 + cos theta) / (2 theta sin theta) is 0/0 at pi"""
     th = np.sqrt(np.sum(p * p, axis=-1))
     small = th < 1e-2
-    t = np.where(small, 1.0, th)
-    c = np.where(small, 1.0 / 12.0 + th * th / 720.0, 1.0 / (t * t) - (1.0 + np.cos(t)) / (2.0 * t * np.sin(t)))
+    h = 0.5 * np.where(small, 1.0, th)
+    c = np.where(small, 1.0 / 12.0 + th * th / 720.0, (np.sin(h) - h * np.cos(h)) / (4.0 * h * h * np.sin(h)))
     H = hat(p)
     return np.eye(3) + 0.5 * H + c[..., None, None] * (H @ H)
 

@@ -233,8 +233,8 @@ def jr_inv(p):
     t = p.dtype.type
     th = np.sqrt((p * p).sum(-1))
     small = th < t(1e-2)
-    ts = np.where(small, t(1), th)
-    c = np.where(small, t(1.0 / 12.0) + th * th * t(1.0 / 720.0), t(1) / (ts * ts) - (t(1) + np.cos(ts)) / (t(2) * ts * np.sin(ts)))
+    h = t(0.5) * np.where(small, t(1), th)
+    c = np.where(small, t(1.0 / 12.0) + th * th * t(1.0 / 720.0), (np.sin(h) - h * np.cos(h)) / (t(4) * h * h * np.sin(h)))
     H = np.zeros(p.shape[:-1] + (3, 3), dtype=p.dtype)
     H[..., 0, 1], H[..., 0, 2] = -p[..., 2], p[..., 1]
     H[..., 1, 0], H[..., 1, 2] = p[..., 2], -p[..., 0]

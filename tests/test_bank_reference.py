@@ -116,3 +116,43 @@ def test_log_sum_exp_with_tiny_likelihoods_and_dead_hypotheses():
     assert np.abs(w[2] - [0.2, 0.3, 0.5]).max() <= 1e-15          # every hypothesis dead: the prior, normalised
     assert np.abs(br.weights(None, ll[3:])[1] - np.exp(ll[3]) / np.exp(ll[3]).sum()).max() <= 1e-15
     assert np.abs(br.weights(lw[:1] + 5.0, None)[1] - [0.2, 0.3, 0.5]).max() <= 1e-15
+
+
+# ------------------------------------------------------------------------------------------------ Jr^-1 against 40 digits
+def jr_inv_mp(mp, phi):
+    """Jr^-1(phi) = I + [phi]x / 2 + (1 - (theta/2) cot(theta/2)) / theta^2 [phi]x^2 at 40 digits from the exact binary phi"""
+    p = [mp.mpf(float(x)) for x in phi]
+    th = mp.sqrt(sum(x * x for x in p))
+    H = mp.matrix([[0, -p[2], p[1]], [p[2], 0, -p[0]], [-p[1], p[0], 0]])
+    c = mp.mpf(1) / 12
+    if th != 0:
+        with mp.extradps(10 + max(0, -2 * int(mp.floor(mp.log10(th))))):   # 1 - (theta/2) cot(theta/2) = theta^2 / 12 + ...
+            c = (1 - (th / 2) * mp.cot(th / 2)) / th ** 2
+    return mp.eye(3) + H / 2 + c * (H * H)
+
+
+def test_jr_inv_against_mpmath_up_to_pi():
+    """The theta list of test_delayed_reference.test_jr_against_mpmath_at_branch_edges (3.5 and 6.0 lie beyond the range of the
+    logarithm, but below the pole of Jr^-1 at 2 pi), extended by the switch to the series and towards and at fl(pi); the Jr
+    test's bound, a few roundings per coefficient times [phi]x and [phi]x^2.  (1/t^2 - (1 + cos t) / (2 t sin t), the form this
+    replaced, misses it from pi - 1e-3 on and is 75 % wrong at fl(pi).)"""
+    mp = pytest.importorskip("mpmath")
+    rng = np.random.default_rng(4)
+    pi = float(np.pi)
+    thetas = [0.0, 1e-300, 1e-12, 1e-6, 1e-3, np.nextafter(1e-2, 0), 1e-2, 0.3, np.nextafter(0.5, 0), 0.5, np.nextafter(0.5, 1), 0.5 + 1e-9,
+              1.0, 2.5, pi - 1e-1, pi - 1e-3, pi - 1e-6, pi - 1e-9, np.nextafter(np.nextafter(pi, 0), 0), np.nextafter(pi, 0), pi,
+              np.nextafter(pi, 4), np.nextafter(np.nextafter(pi, 4), 4), 3.5, 6.0]
+    worst = 0.0
+    with mp.workdps(40):
+        for th in thetas:
+            dirs = [d / np.linalg.norm(d) for d in rng.normal(size=(4, 3))] + [np.array([1.0, 0.0, 0.0]), np.array([0.0, 0.0, -1.0])]
+            for d in dirs:
+                phi = th * d
+                got, ref = br.jr_inv(phi), jr_inv_mp(mp, phi)
+                err = float(max(abs(mp.mpf(float(got[i, j])) - ref[i, j]) for i in range(3) for j in range(3)))
+                worst = max(worst, err / (2.0 ** -52 * (1.0 + th * th)))
+                assert np.isfinite(got).all() and err <= 8 * 2.0 ** -52 * (1.0 + th * th), (th, err)
+    print(f"BANK Jr^-1 against mpmath at 40 digits: largest error {worst:.2f} eps (1 + theta^2)")
+    # batched, as the references call it
+    P = np.array([[pi, 0.0, 0.0], [0.0, 0.0, 0.0], [0.0, 1e-3, 0.0]])
+    assert np.array_equal(br.jr_inv(P), np.stack([br.jr_inv(p) for p in P]))

@@ -299,6 +299,6 @@ def test_jr_against_mpmath_at_branch_edges():
             assert err <= 8 * 2.0 ** -52 * (1.0 + th * th), (th, float(err))   # a few roundings per coefficient, times [phi]x, [phi]x^2
     print(f"DELAYED Jr against mpmath at 40 digits: largest absolute error {worst:.3e}")
     # Jr is the inverse of the Jr^-1 the chain already uses
-    for th in (1e-3, 0.3, 2.5):
+    for th in (1e-3, 0.3, 2.5, 3.0, np.pi - 1e-3, np.pi - 1e-6, np.nextafter(np.pi, 0), np.pi):
         phi = th * np.array([0.6, -0.48, 0.64])
         assert np.abs(dr.jr(phi) @ dr.jr_inv(phi) - np.eye(3)).max() <= 1e-14

@@ -277,6 +277,103 @@ def test_host_mix_equals_device_mix(spe, onp, model, pname, prec, wide, tol):
     assert all(np.array_equal(a, b) for a, b in zip(*out))
 
 
+# ---------------------------------------------------------------------------------------------------------------- opposed hypotheses
+def opposed_tracks(spe, onp, model, T, M, even, lattice, seed=23):
+    """T tracks in which hypothesis t % M + 1 is hypothesis t % M turned by pi: q and q * (axis, 0), everything else equal.
+    Weights: the turned one 2^-10, 2^-20, 2^-30, 2^-40 across the tracks, a third one 0.25 a step of make_tracks away, the rest
+    on the first; or (even) 0.5 / 0.5 and 0 for the third.
+    lattice: q = (+-1/2, +-1/2, +-1/2, +-1/2) and a signed coordinate axis, so that conj(q) (q (axis, 0)) = (axis, +0) without
+    a rounding in any precision and any order of the products, and the logarithm is +pi axis for the engine and the reference
+    alike.  About a random axis the scalar part is rounding noise of either sign, the logarithm +-pi axis, and the mixture
+    mean -- which has two equally good values there -- a coin toss between two correct programs: such tracks (lattice = False)
+    can be held to finite results and status, not to parity."""
+    man, mu, cov, _ = make_tracks(spe, onp, model, T, M, seed=seed)
+    so = [s_ for kind, s_, _, _ in man.fields if kind == "so3"][0]
+    rng = np.random.default_rng(seed + M)
+    w = np.zeros((T, M))
+    for t in range(T):
+        a, b = t % M, (t + 1) % M
+        step = [man.boxminus(mu[t, c], mu[t, a]) for c in range(M)]
+        if lattice:
+            mu[t, a, so:so + 4] = 0.5 * rng.choice([-1.0, 1.0], 4)
+            turn = np.zeros(4)
+            turn[rng.integers(3)] = rng.choice([-1.0, 1.0])
+        else:
+            ax = rng.normal(size=3)
+            turn = np.concatenate([ax / np.linalg.norm(ax), [0.0]])
+        for c in range(M):
+            mu[t, c] = man.boxplus(mu[t, a], step[c]) if c not in (a, b) else mu[t, a]
+        mu[t, b, so:so + 4] = onp.quat_mul(mu[t, a, so:so + 4], turn)
+        w[t, b] = 0.5 if even else 2.0 ** (-10 * (1 + t % 4))
+        if M > 2:
+            w[t, (t + 2) % M] = 0.0 if even else 0.25
+        w[t, a] = 1.0 - w[t].sum()
+    return man, mu, cov, w, so
+
+
+@pytest.mark.parametrize("M", [2, 3])
+@pytest.mark.parametrize("pname,prec,wide,tol", PRECS, ids=[p[0] for p in PRECS])
+@pytest.mark.parametrize("model", ["pose", "orient"])
+def test_hypothesis_opposite_the_heaviest_one(spe, onp, model, pname, prec, wide, tol, M):
+    """A hypothesis exactly pi away from the heaviest one, the edge of the logarithm's range, where the transport Jr^-1 used to
+    be 0/0: seven tracks (a ragged last wavefront).  Its weight is tiny, so a converged mixture hardly feels it -- but a NaN in
+    its transport would poison the track whatever its weight.  Then the same tracks at 0.5 / 0.5 with mean_max_iter = 1: the
+    moments published under WARN_MEAN_NOCONV are those of the reference stopped at the same cap.
+    (The sharp test of Jr^-1 towards pi is tests/test_gpu_jacobian_primitives.py.)"""
+    T = 7
+    P = transition(M)
+    for even in (False, True):
+        kw = dict(max_it=1) if even else {}
+        man, mu0, cov0, w0, so = opposed_tracks(spe, onp, model, T, M, even, lattice=True)
+        e = new_engine(spe, model, T * M, prec, wide)
+        e.initialize(mu0.reshape(T * M, man.S), cov0.reshape(T * M, man.D, man.D))
+        latch_inputs(spe, e, model)
+        if even:
+            e.configure(mean_max_iter=1)
+        w = stored(e, w0)
+        mu, cov, init = downloaded(e, man, T, M)
+        tr = np.arange(T)
+        for j in (tr % M, (tr + 1) % M):
+            assert np.array_equal(mu[tr, j, so:so + 4], mu0[tr, j, so:so + 4]), "the lattice quaternions are stored to the bit"
+        assert init.all()
+        turned = man.boxminus(mu[tr, (tr + 1) % M], mu[tr, tr % M])[:, br.rot_offset(man):br.rot_offset(man) + 3]
+        assert np.array_equal(np.linalg.norm(turned, axis=1), np.full(T, np.pi)), "exactly pi away"
+        want = np.full(T, spe.ST_WARN_MEAN_NOCONV if even else 0)
+        # ---- combine
+        m_r, C_r, conv = br.mixture(man, mu, cov, w, **kw)
+        assert (conv == (not even)).all()
+        m_g, C_g, st, _ = combine_dev(e, M, w)
+        assert np.isfinite(m_g).all() and np.isfinite(C_g).all() and np.array_equal(st, want)
+        em, ec = scaled_err(m_g, m_r), scaled_err(C_g, C_r)
+        print(f"bank parity {model} {pname} M={M} opposed {'0.5/0.5 cap=1' if even else 'tiny weight'} combine: mean {em:.3e} cov {ec:.3e}")
+        assert em <= tol and ec <= tol
+        name = f"bank/{model}/{pname}/M={M}/opposed{'-cap=1' if even else ''}"
+        scaled_combine(name + "/combine", model, pname, m_g, C_g, m_r, C_r, mu, cov, w, **kw)
+        # ---- mix
+        Pk = stored(e, P) if (prec == 1 and not wide) else P
+        mu_r, cov_r, c_r, conv = br.mix(man, mu, cov, w, Pk, **kw)
+        assert (conv == (not even)).all()
+        wp, st = mix_dev(e, M, w, P)
+        mu_g, cov_g, _ = downloaded(e, man, T, M)
+        assert np.isfinite(mu_g).all() and np.isfinite(cov_g).all() and np.array_equal(st, want)
+        em, ec, ew = scaled_err(mu_g, mu_r), scaled_err(cov_g, cov_r), scaled_err(wp, c_r)
+        print(f"bank parity {model} {pname} M={M} opposed {'0.5/0.5 cap=1' if even else 'tiny weight'} mix:     mean {em:.3e} cov {ec:.3e}")
+        assert em <= tol and ec <= tol and ew <= tol
+        scaled_mix(name + "/mix", model, pname, mu_g, cov_g, mu_r, cov_r, mu, cov, w, Pk, **kw)
+        e.close()
+    # about a random axis: no poisoning, whichever sign the logarithm takes
+    man, mu0, cov0, w0, so = opposed_tracks(spe, onp, model, T, M, even=False, lattice=False)
+    e = new_engine(spe, model, T * M, prec, wide)
+    e.initialize(mu0.reshape(T * M, man.S), cov0.reshape(T * M, man.D, man.D))
+    w = stored(e, w0)
+    m_g, C_g, st, _ = combine_dev(e, M, w)
+    assert np.isfinite(m_g).all() and np.isfinite(C_g).all() and (st == 0).all()
+    wp, st = mix_dev(e, M, w, P)
+    mu_g, cov_g, _ = downloaded(e, man, T, M)
+    assert np.isfinite(mu_g).all() and np.isfinite(cov_g).all() and np.isfinite(wp).all() and (st == 0).all()
+    e.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------- exact cases
 @pytest.mark.parametrize("pname,prec,wide,tol", PRECS, ids=[p[0] for p in PRECS])
 @pytest.mark.parametrize("model", ["pose", "orient"])
