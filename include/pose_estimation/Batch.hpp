@@ -199,6 +199,39 @@ public:
                                  z_pred, S, innov, maha, loglik, st.data()));
         return st;
     }
+    /** User-defined measurement models (ukf_batch.h, "user-defined measurement models"): ukf->update(z, h, Q) for an h of the
+     *  caller's.  sigmaPointsDev exports every filter's sigma points, filter-major: X_out_dev [N][2 D + 1][S] (point 0 = mu,
+     *  1 + 2 j = mu (+) L col j, 2 + 2 j = mu (+) (-L col j)), delta_out_dev [N][2 D + 1][D] the tangent offsets; either may be
+     *  NULL, not both; read-only on the filters.  The caller evaluates Z = h(X) and integrateSampledMeasurementDev finishes the
+     *  update from in.Z_dev [N][2 D + 1][m], m = 1 ... UKFB_SAMPLED_MAX_M; commit = false is read-only (only `out` is written).
+     *  The state must not change between the two calls.  Stream-ordered. */
+    void sigmaPointsDev(void* X_out_dev, void* delta_out_dev = NULL, uint32_t* status_dev = NULL)
+    {
+        check(ukfb_sigma_points_dev(engine, X_out_dev, delta_out_dev, status_dev));
+    }
+    void integrateSampledMeasurementDev(const ukfb_sampled_in& in, bool commit = true, const ukfb_sampled_out* out = NULL)
+    {
+        check(ukfb_update_sampled_dev(engine, &in, commit ? 1 : 0, out));
+    }
+    /** host arrays: X [N][2 D + 1][S], delta [N][2 D + 1][D] (either may be NULL, not both); returns the status */
+    std::vector<uint32_t> sigmaPoints(double* X, double* delta = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_sigma_points(engine, X, delta, st.data()));
+        return st;
+    }
+    /** host arrays: Z [N][2 D + 1][m] = h(X) in the order of sigmaPoints, z [N][m], Q [N][m][m] (ONE m x m with q_is_uniform);
+     *  active [N] or NULL; z_pred [N][m], S [N][m][m], innov [N][m], maha / loglik [N] or NULL; returns the status */
+    std::vector<uint32_t> integrateSampledMeasurement(int m, const double* Z, const double* z, const double* Q,
+                                                      bool q_is_uniform = false, const uint8_t* active = NULL, bool commit = true,
+                                                      double* z_pred = NULL, double* S = NULL, double* innov = NULL,
+                                                      double* maha = NULL, double* loglik = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_update_sampled(engine, m, Z, z, Q, q_is_uniform ? 1 : 0, active, commit ? 1 : 0, z_pred, S, innov, maha, loglik,
+                                  st.data()));
+        return st;
+    }
     /** Late samples (ukf_batch.h, "late samples"): a sample taken in.lag steps ago corrects the CURRENT state through the history
      *  ring -- no stored measurements, no replay, no waiting for the slowest sensor.  The window is smoothDev's with the
      *  filters' own state as its last step; commit = false is read-only (only `out` is written, out->mu_out / cov_out showing

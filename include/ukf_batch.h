@@ -879,6 +879,78 @@ int ukfb_update_sensor(ukfb_engine* e, int model, const int32_t* model_per_filte
                        const double* point /* or NULL */, const double* point_uniform /* or NULL */, int commit,
                        double* z_pred, double* S, double* innov, double* maha, double* loglik, uint32_t* status);
 
+/* ---- user-defined measurement models: sigma-point export, sampled update ------------------------------------------------- */
+/* ukf->update(z, h, Q) for an h the library does not know (four DVL beams, a camera pixel of a known landmark, range plus
+ * range rate, two antennas at once, ...).  The library hands out the sigma points of every filter, the caller evaluates h on
+ * them with whatever they like (a torch expression, a kernel of their own), and the library finishes the update from the
+ * samples Z_i = h(X_i) with the device functions, the commit, the statuses and the read-only mode of the built-in models.
+ * The measurement space is R^m, m = 1 ... UKFB_SAMPLED_MAX_M, ONE m for the call (an angle goes in as a unit vector).
+ *
+ * LAYOUT: filter-major.  One filter's 2 D + 1 points are one contiguous record: X [capacity][2 D + 1][S], delta
+ * [capacity][2 D + 1][D], Z [capacity][2 D + 1][m].  This departs ON PURPOSE from the slot-major rings of the multi-cycle,
+ * history and forecast calls ([slots][capacity][...]): a caller's h is then an elementwise expression over the last axis with
+ * two leading batch axes, and the four filters of a wavefront read one contiguous stretch.
+ * POINT ORDER: ukfom's.  L = the lower Cholesky factor of Sigma; point 0 = mu, point 1 + 2 j = mu (+) L col j, point 2 + 2 j =
+ * mu (+) (-L col j).  delta holds the tangent offsets themselves (0, +L col j, -L col j): a caller who wants h(mu (+) delta) in
+ * a higher precision than the engine stores can form the points from these.
+ *
+ * ukfb_sigma_points_dev: READ-ONLY on the engine (mean, covariance, times, latches, noise and the engine's status array keep
+ * every bit).  Point 0 is mu bit for bit.  status_dev [capacity] (may be NULL): 0, UNINITIALISED, or ERR_CHOLESKY (Sigma is not
+ * positive definite); such a filter's rows of X and delta are NaN.  Either of X_out_dev / delta_out_dev may be NULL, not both.
+ *
+ * ukfb_update_sampled_dev, per active filter (the steps of the sensor-frame measurements with h replaced by a load):
+ *   1. L = chol(Sigma): the same device function in the same order as the export, so that X_i (-) mu = +-L col j holds for the
+ *      points the caller evaluated.  The X themselves are never read;
+ *   2. z-bar = the iterated mean of the Z_i from Z_0 (mean_tol / mean_max_iter);
+ *   3. S = 1/2 sum dz_i dz_i^T + Q;  C = 1/2 sum (X_i (-) mu) dz_i^T = sum_j (L col j) W_j^T;
+ *   4. S = Ls Ls^T; Y = C Ls^-T;
+ *   5. nu = z - z-bar, y = Ls^-1 nu, d^2 = |y|^2, ln det S from the pivots;
+ *   6. the gate of ukfb_update_dev (gate_chi2): REJECTED_GATE keeps the state, the outputs are still written;
+ *   7. Sigma~ = Sigma - Y Y^T; (mu, Sigma) = applyDelta(mu, Sigma~, Y y), the update's own commit.
+ * THE STATE MUST NOT CHANGE BETWEEN THE EXPORT AND THE UPDATE: the samples belong to the sigma points of the state they were
+ * exported from.  That is the caller's responsibility (as with the history ring of the delayed update); nothing checks it.
+ * ARITHMETIC: the differences Z_i - Z_0 and z - Z_0 are formed first, in fp64, in every mode, and the mean iteration, S and nu
+ * work on those differences.  The update is therefore invariant under a per-filter translation of z and all Z_i together
+ * (only z_pred moves, by that translation).  A caller with an fp32 engine should write z and Z relative to an origin near the
+ * values (h(mu), say) instead of storing tens of metres in fp32: the stored samples then resolve the deltas.
+ * commit = 1: mean, covariance and the engine's own status array are written; out may be NULL.  commit = 0: READ-ONLY like
+ * ukfb_innovation_dev, only `out` is written (the same numbers).
+ * Status of THIS call (out->status, and with commit = 1 the engine's status array):
+ *   UNINITIALISED       the filter is uninitialised;
+ *   INACTIVE            active_dev says 0 for this filter;
+ *   ERR_NONFINITE_MEAS  a non-finite value among z, the lower triangle of Q or any of the filter's (2 D + 1) m samples;
+ *   ERR_CHOLESKY        Sigma, S or (an accepted update's) Sigma~ is not positive definite;
+ *   WARN_MEAN_NOCONV    the mean iteration hit its cap;
+ *   REJECTED_GATE       the gate rejected the update.
+ * A filter with one of the first four keeps its state bit for bit and writes NaN to its float outputs; it never changes a bit
+ * of another filter.  m outside 1 ... UKFB_SAMPLED_MAX_M: UKFB_ERR_OUT_OF_RANGE, nothing is written.  NULL in, Z_dev, z_dev or
+ * Q_dev, or commit = 0 with nowhere to write: UKFB_ERR_INVALID_ARG.  Stream-ordered, joins split streams, no host
+ * synchronisation, no allocation at call time.  The same kernel serves every lanes_per_filter setting; fp32 engines compute in
+ * fp32, with wide_arithmetic in fp64 (stored fp32).  Device groups: per shard through ukfb_group_shard. */
+#define UKFB_SAMPLED_MAX_M 6
+int ukfb_sigma_points_dev(ukfb_engine* e, void* X_out_dev, void* delta_out_dev, uint32_t* status_dev);
+typedef struct ukfb_sampled_in {
+    int m;                      /* 1 ... UKFB_SAMPLED_MAX_M, one value for the call */
+    const void* Z_dev;          /* [capacity][2D+1][m]  Z_i = h(X_i), the order of ukfb_sigma_points_dev */
+    const void* z_dev;          /* [capacity][m] */
+    const void* Q_dev;          /* [capacity][m][m] row-major, or ONE m x m with q_is_uniform; the lower triangle is read */
+    int q_is_uniform;
+    const uint8_t* active_dev;  /* [capacity] or NULL = all; 0: no measurement for that filter (INACTIVE) */
+} ukfb_sampled_in;
+typedef struct ukfb_sampled_out {   /* device, engine precision, any may be NULL */
+    void* z_pred;  /* [capacity][m] */   void* S;      /* [capacity][m][m] */   void* innov; /* [capacity][m] */
+    void* maha;    /* [capacity] */      void* loglik; /* [capacity] */         uint32_t* status; /* [capacity] */
+} ukfb_sampled_out;
+int ukfb_update_sampled_dev(ukfb_engine* e, const ukfb_sampled_in* in, int commit, const ukfb_sampled_out* out);
+/* host arrays of doubles, synchronising: X [capacity][2D+1][S], delta [capacity][2D+1][D], status [capacity] (X or delta may be
+ * NULL, not both; status may be NULL); Z [capacity][2D+1][m], z [capacity][m], Q [capacity][m][m] (ONE m x m with q_is_uniform),
+ * active [capacity] or NULL; z_pred [capacity][m], S [capacity][m][m], innov [capacity][m], maha / loglik / status [capacity]:
+ * any may be NULL */
+int ukfb_sigma_points(ukfb_engine* e, double* X, double* delta, uint32_t* status);
+int ukfb_update_sampled(ukfb_engine* e, int m, const double* Z, const double* z, const double* Q, int q_is_uniform,
+                        const uint8_t* active, int commit, double* z_pred, double* S, double* innov, double* maha,
+                        double* loglik, uint32_t* status);
+
 
 /* ---- device groups: one host process, several MI355X ------------------------------------------------------------------ */
 /* north_star's multi-GPU shape for a C++ host.  The filters of a batch are independent -- every filter of the reference owns

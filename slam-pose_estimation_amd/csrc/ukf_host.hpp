@@ -445,6 +445,60 @@ inline SensorGeometry sensor_geometry(int S, int D, int64_t capacity, size_t com
             int(size_t(SENSOR_FILTERS_PER_GROUP) * sensor_filter_scalars(S, D) * compute_size)};
 }
 
+// ---- user-defined measurement models (ukfb_sigma_points_dev, ukfb_update_sampled_dev) --------------------------------------
+// The caller evaluates h on the exported sigma points; the update is finished from the samples Z_i = h(X_i), m = 1 ...
+// SAMPLED_MAX_M, one m for the call.
+constexpr int SAMPLED_MAX_M = UKFB_SAMPLED_MAX_M, SAMPLED_FILTERS_PER_GROUP = 4;
+// The record of one filter's inputs and of S as the kernel keeps them: z (SAMPLED_MAX_M), Q row-major m x m (up to
+// SAMPLED_MAX_M^2), then S row-major with row stride SAMPLED_MAX_M, z-bar and nu (SAMPLED_MAX_M each; parked for the outputs)
+constexpr int SAMPLED_INPUT_Z = 0, SAMPLED_INPUT_Q = SAMPLED_MAX_M, SAMPLED_INPUT_S = SAMPLED_INPUT_Q + SAMPLED_MAX_M * SAMPLED_MAX_M;
+constexpr int SAMPLED_INPUT_ZBAR = SAMPLED_INPUT_S + SAMPLED_MAX_M * SAMPLED_MAX_M, SAMPLED_INPUT_NU = SAMPLED_INPUT_ZBAR + SAMPLED_MAX_M;
+constexpr int SAMPLED_INPUT_SCALARS = SAMPLED_INPUT_NU + SAMPLED_MAX_M;
+constexpr int SAMPLED_INPUT_REGION = (SAMPLED_INPUT_SCALARS + 15) / 16 * 16;
+constexpr bool sampled_m_ok(int64_t m) { return m >= 1 && m <= SAMPLED_MAX_M; }
+// scalars of one filter's sigma-point record ([2 D + 1][S]), of its tangent offsets ([2 D + 1][D]) and of its samples ([2 D + 1][m])
+constexpr int64_t sampled_points(int D) { return 2 * int64_t(D) + 1; }
+inline Verdict check_sigma_points_args(bool has_X, bool has_delta) {
+    if (!has_X && !has_delta) return {UKFB_ERR_INVALID_ARG, "X_out_dev and delta_out_dev must not both be NULL"};
+    return {};
+}
+inline Verdict check_sampled_args(const ukfb_sampled_in* in, int commit, const ukfb_sampled_out* out) {
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    if (!in->Z_dev || !in->z_dev || !in->Q_dev) return {UKFB_ERR_INVALID_ARG, "Z_dev, z_dev and Q_dev must not be NULL"};
+    if (in->q_is_uniform != 0 && in->q_is_uniform != 1) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
+    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    if (commit == 0 && (!out || (!out->z_pred && !out->S && !out->innov && !out->maha && !out->loglik && !out->status)))
+        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
+    if (!sampled_m_ok(in->m)) return {UKFB_ERR_OUT_OF_RANGE, "m must be 1 ... 6 (UKFB_SAMPLED_MAX_M)"};
+    return {};
+}
+// LDS of one filter of the update, in scalars of the compute type (ukf_sampled.hpp, SampledLayout): the factor region with its
+// reciprocal pivots, the delta table of the commit (2 D + 1 rows; the D x 6 half differences W, the D x 6 solved
+// cross-covariance Y and the staged samples, (2 D + 1) x 6 at most, alias it), the state's record (mean padded to 16, packed
+// covariance padded to even), the input record with S, z-bar and nu behind it (SAMPLED_INPUT_REGION) and the sink of lane-predicated stores
+// (16); rounded up to a multiple of four so that every filter's slice starts 16-byte aligned in either precision.  Every scalar
+// the kernel reads is one it wrote: the pads are never read.
+constexpr int sampled_filter_scalars(int S, int D) {
+    return S > 16 ? -1 : (D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + SAMPLED_INPUT_REGION + 16 + 3) / 4 * 4;
+}
+// and of the export (SigmaPointsLayout): the factor region with its reciprocal pivots, the state's record and the sink
+constexpr int sigma_points_filter_scalars(int S, int D) {
+    return S > 16 ? -1 : (D * SMOOTH_LS + 16 + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 16 + 3) / 4 * 4;
+}
+struct SampledGeometry {
+    int64_t grid;    // workgroups of four filters
+    int lds_bytes;   // dynamic LDS of a workgroup
+};
+// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
+inline SampledGeometry sampled_geometry(int S, int D, int64_t capacity, size_t compute_size) {
+    return {(capacity + SAMPLED_FILTERS_PER_GROUP - 1) / SAMPLED_FILTERS_PER_GROUP,
+            int(size_t(SAMPLED_FILTERS_PER_GROUP) * sampled_filter_scalars(S, D) * compute_size)};
+}
+inline SampledGeometry sigma_points_geometry(int S, int D, int64_t capacity, size_t compute_size) {
+    return {(capacity + SAMPLED_FILTERS_PER_GROUP - 1) / SAMPLED_FILTERS_PER_GROUP,
+            int(size_t(SAMPLED_FILTERS_PER_GROUP) * sigma_points_filter_scalars(S, D) * compute_size)};
+}
+
 // ---- late samples (ukfb_update_delayed_dev, ukfb_delayed_lag_dev) -----------------------------------------------------------
 // The smoother's window with the engine's own state as its last step: the chain runs at most steps - 1 <= SMOOTH_MAX_BACK
 // backward steps, all in one launch (their dt travel in the kernel arguments), so steps <= DELAYED_MAX_STEPS.

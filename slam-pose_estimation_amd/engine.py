@@ -65,6 +65,8 @@ EXPORTS = [
     "ukfb_update_state_dev", "ukfb_update_state", "ukfb_pose_update_body_states",
     # sensor-frame measurements: lever arms, ranges, landmark fixes, nav-frame vectors
     "ukfb_update_sensor_dev", "ukfb_update_sensor",
+    # user-defined measurement models: sigma-point export, the update finished from the caller's samples
+    "ukfb_sigma_points_dev", "ukfb_update_sampled_dev", "ukfb_sigma_points", "ukfb_update_sampled",
     # late samples: the delayed-measurement update through the state history
     "ukfb_update_delayed_dev", "ukfb_update_delayed", "ukfb_delayed_lag_dev",
     # device groups (one process, several GPUs)
@@ -90,6 +92,9 @@ SENSOR_NONE = -1
 SENSOR_POSE_POSITION, SENSOR_POSE_RANGE, SENSOR_POSE_POINT, SENSOR_POSE_VELOCITY, SENSOR_POSE_NAV_VELOCITY = 0, 1, 2, 3, 4
 SENSOR_ORIENT_VELOCITY, SENSOR_ORIENT_NAV_VECTOR, SENSOR_ORIENT_SPECIFIC_FORCE = 5, 6, 7
 SENSOR_MOUNT_IDENTITY = (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0)   # r = 0, qs = (0, 0, 0, 1)
+
+# largest measurement dimension of ukfb_update_sampled_dev (UKFB_SAMPLED_MAX_M)
+SAMPLED_MAX_M = 6
 
 
 class Config(C.Structure):
@@ -119,6 +124,19 @@ class SensorIn(C.Structure):
 
 class SensorOut(C.Structure):
     """ukfb_sensor_out: device pointers in engine precision (status uint32), any may be NULL"""
+    _fields_ = [("z_pred", C.c_void_p), ("S", C.c_void_p), ("innov", C.c_void_p), ("maha", C.c_void_p),
+                ("loglik", C.c_void_p), ("status", C.c_void_p)]
+
+
+class SampledIn(C.Structure):
+    """ukfb_sampled_in: the samples Z [capacity, 2 D + 1, m], z [capacity, m], Q [capacity, m, m] (or one m x m) as device
+    pointers in engine precision; active_dev uint8 [capacity] or NULL"""
+    _fields_ = [("m", C.c_int), ("Z_dev", C.c_void_p), ("z_dev", C.c_void_p), ("Q_dev", C.c_void_p), ("q_is_uniform", C.c_int),
+                ("active_dev", C.c_void_p)]
+
+
+class SampledOut(C.Structure):
+    """ukfb_sampled_out: device pointers in engine precision (status uint32), any may be NULL"""
     _fields_ = [("z_pred", C.c_void_p), ("S", C.c_void_p), ("innov", C.c_void_p), ("maha", C.c_void_p),
                 ("loglik", C.c_void_p), ("status", C.c_void_p)]
 
@@ -725,6 +743,53 @@ class BatchUKF:
                                           _pd(mp), _pd(mu_), _pd(pp), _pd(pu), C.c_int(1 if commit else 0), _pd(o["z_pred"]),
                                           _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]),
                                           o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_update_sensor")
+        return o
+
+    # ---- user-defined measurement models: X [capacity, 2 D + 1, S], delta [capacity, 2 D + 1, D], Z [capacity, 2 D + 1, m]
+    def sigma_points_dev(self, X_out=None, delta_out=None, status=None):
+        """The sigma points of every filter into device buffers in engine precision, filter-major: X_out [capacity, 2 D + 1, S]
+        (point 0 = mu, 1 + 2 j = mu (+) L col j, 2 + 2 j = mu (+) (-L col j)), delta_out [capacity, 2 D + 1, D] the tangent
+        offsets themselves; either may be None, not both.  status uint32 / int32 [capacity] or None: 0, ST_UNINITIALISED or
+        ST_ERR_CHOLESKY (rows of NaN).  Read-only on the engine.  Stream-ordered."""
+        _chk(self._lib.ukfb_sigma_points_dev(self._h, _devptr(X_out), _devptr(delta_out), _devptr(status)), "ukfb_sigma_points_dev")
+
+    def update_sampled_dev(self, m: int, Z_dev, z_dev, Q_dev, q_is_uniform: bool = False, active_dev=None, commit: bool = True,
+                           z_pred=None, S=None, innov=None, maha=None, loglik=None, status=None):
+        """ukfom's update finished from the caller's samples Z_dev [capacity, 2 D + 1, m] = h(X) of sigma_points_dev's X
+        (m = 1 ... SAMPLED_MAX_M); z_dev [capacity, m], Q_dev [capacity, m, m] (one m x m with q_is_uniform), active_dev uint8
+        [capacity] or None.  The state must not change between the export and this call.  z and Z may be written relative to
+        any per-filter origin (fp32 engines: one near the values).  commit=False is read-only: only the keyword outputs
+        (device buffers in engine precision, status uint32 / int32) are written.  Stream-ordered."""
+        ptr = lambda x: None if x is None else _devptr(x).value
+        sin = SampledIn(int(m), ptr(Z_dev), ptr(z_dev), ptr(Q_dev), 1 if q_is_uniform else 0, ptr(active_dev))
+        out = SampledOut(ptr(z_pred), ptr(S), ptr(innov), ptr(maha), ptr(loglik), ptr(status))
+        _chk(self._lib.ukfb_update_sampled_dev(self._h, C.byref(sin), C.c_int(1 if commit else 0), C.byref(out)),
+             "ukfb_update_sampled_dev")
+
+    def sigma_points(self):
+        """Host form -> (X [capacity, 2 D + 1, S], delta [capacity, 2 D + 1, D], status [capacity]); synchronises"""
+        n, pts = self.capacity, 2 * self.D + 1
+        X, delta, st = np.empty((n, pts, self.S)), np.empty((n, pts, self.D)), np.empty(n, dtype=np.uint32)
+        _chk(self._lib.ukfb_sigma_points(self._h, _pd(X), _pd(delta), st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_sigma_points")
+        return X, delta, st
+
+    def update_sampled(self, Z, z, Q, active=None, commit: bool = True):
+        """Host arrays: Z [capacity, 2 D + 1, m], z [capacity, m], Q [capacity, m, m] or [m, m] (one for the batch); active
+        uint8 [capacity] or None.  Returns a dict of NumPy arrays: z_pred [n, m], S [n, m, m], innov [n, m], maha [n],
+        loglik [n], status [n]; synchronises"""
+        n, pts = self.capacity, 2 * self.D + 1
+        Z = _f64(Z)
+        m = int(Z.shape[-1]) if Z.ndim == 3 else Z.size // max(n * pts, 1)
+        Z = Z.reshape(n, pts, m); z = _f64(z, (n, m)); Q = _f64(Q)
+        uniform = Q.ndim == 2
+        Q = Q.reshape(m, m) if uniform else Q.reshape(n, m, m)
+        act = np.ascontiguousarray(active, dtype=np.uint8).reshape(n) if active is not None else None
+        o = {"z_pred": np.empty((n, m)), "S": np.empty((n, m, m)), "innov": np.empty((n, m)), "maha": np.empty(n),
+             "loglik": np.empty(n), "status": np.empty(n, dtype=np.uint32)}
+        _chk(self._lib.ukfb_update_sampled(self._h, C.c_int(m), _pd(Z), _pd(z), _pd(Q), C.c_int(1 if uniform else 0),
+                                           act.ctypes.data_as(C.POINTER(C.c_uint8)) if act is not None else None,
+                                           C.c_int(1 if commit else 0), _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]),
+                                           _pd(o["loglik"]), o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_update_sampled")
         return o
 
     # ---- late samples: the window of smooth_dev with the engine's own state as its last step

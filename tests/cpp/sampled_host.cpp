@@ -1,0 +1,113 @@
+// sampled_host.cpp -- the host decisions of the user-defined measurement models (ukf_host.hpp) on the CPU (g++ under ASan / UBSan,
+// compiled by tests/test_sampled_host.py): the range of m, NULL combinations, commit / out, and the launch geometry of the
+// sigma-point export and of the sampled update.
+#include <cstdio>
+
+#include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
+
+static int failures = 0;
+#define EXPECT(cond)                                                        \
+    do {                                                                    \
+        if (!(cond)) {                                                      \
+            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
+            ++failures;                                                     \
+        }                                                                   \
+    } while (0)
+
+int main() {
+    using namespace ukfb;
+    double buf[16] = {0};
+    uint32_t word = 0;
+    ukfb_sampled_in in{};
+    in.m = 3;
+    in.Z_dev = buf;
+    in.z_dev = buf;
+    in.Q_dev = buf;
+    ukfb_sampled_out none{};
+    ukfb_sampled_out st_only{};
+    st_only.status = &word;
+    // the range of m: checked on the host, nothing is launched outside it
+    EXPECT(UKFB_SAMPLED_MAX_M == 6 && SAMPLED_MAX_M == 6 && SAMPLED_FILTERS_PER_GROUP == 4);
+    for (int m = -3; m <= 12; ++m) {
+        ukfb_sampled_in v = in;
+        v.m = m;
+        EXPECT(sampled_m_ok(m) == (m >= 1 && m <= 6));
+        EXPECT(check_sampled_args(&v, 1, nullptr).rc == ((m >= 1 && m <= 6) ? UKFB_OK : UKFB_ERR_OUT_OF_RANGE));
+    }
+    EXPECT(!sampled_m_ok(int64_t(1) << 40) && !sampled_m_ok(INT64_MIN));
+    {
+        ukfb_sampled_in v = in;
+        v.m = 7;
+        EXPECT(check_sampled_args(&v, 1, nullptr).msg != nullptr);
+        v.Z_dev = nullptr;   // an invalid argument is reported before the range
+        EXPECT(check_sampled_args(&v, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    }
+    // NULL combinations
+    EXPECT(check_sampled_args(nullptr, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    {
+        ukfb_sampled_in bad = in;
+        bad.Z_dev = nullptr;
+        EXPECT(check_sampled_args(&bad, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+        bad = in;
+        bad.z_dev = nullptr;
+        EXPECT(check_sampled_args(&bad, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+        bad = in;
+        bad.Q_dev = nullptr;
+        EXPECT(check_sampled_args(&bad, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+        bad = in;
+        bad.q_is_uniform = 2;
+        EXPECT(check_sampled_args(&bad, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+        bad.q_is_uniform = 1;
+        EXPECT(check_sampled_args(&bad, 1, nullptr).rc == UKFB_OK);
+        bad = in;   // active_dev NULL: every filter takes part; given: per filter
+        const uint8_t act[4] = {1, 0, 1, 1};
+        bad.active_dev = act;
+        EXPECT(check_sampled_args(&bad, 1, nullptr).rc == UKFB_OK);
+    }
+    // commit is 0 or 1; a read-only call needs somewhere to write
+    EXPECT(check_sampled_args(&in, 2, &st_only).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_sampled_args(&in, -1, &st_only).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_sampled_args(&in, 0, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_sampled_args(&in, 0, &none).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_sampled_args(&in, 0, &st_only).rc == UKFB_OK);
+    EXPECT(check_sampled_args(&in, 1, &none).rc == UKFB_OK);
+    {
+        ukfb_sampled_out o{};
+        o.S = buf;
+        EXPECT(check_sampled_args(&in, 0, &o).rc == UKFB_OK);
+    }
+    // the export needs one of its two outputs
+    EXPECT(check_sigma_points_args(false, false).rc == UKFB_ERR_INVALID_ARG && check_sigma_points_args(false, false).msg != nullptr);
+    EXPECT(check_sigma_points_args(true, false).rc == UKFB_OK && check_sigma_points_args(false, true).rc == UKFB_OK);
+    EXPECT(check_sigma_points_args(true, true).rc == UKFB_OK);
+    EXPECT(sampled_points(12) == 25 && sampled_points(13) == 27);
+    // the record behind the state: z, Q, S, z-bar, nu
+    EXPECT(SAMPLED_INPUT_Z == 0 && SAMPLED_INPUT_Q == 6 && SAMPLED_INPUT_S == 42 && SAMPLED_INPUT_ZBAR == 78 && SAMPLED_INPUT_NU == 84);
+    EXPECT(SAMPLED_INPUT_SCALARS == 90 && SAMPLED_INPUT_REGION == 96);
+    // LDS per model and precision: four filters per workgroup
+    struct { int S, D; } models[2] = {{13, 12}, {14, 13}};
+    for (const auto& m : models) {
+        const int PK = m.D * (m.D + 1) / 2, N = 2 * m.D + 1;
+        const int sc = sampled_filter_scalars(m.S, m.D), se = sigma_points_filter_scalars(m.S, m.D);
+        // the update: the sensor kernel's slice with the larger input record; W, Y (D x 6) and the staged samples ((2 D + 1) x 6)
+        // fit the commit's table they alias
+        EXPECT(sc == sensor_filter_scalars(m.S, m.D) + (SAMPLED_INPUT_REGION - 32) && sc % 4 == 0);
+        EXPECT(2 * m.D * SAMPLED_MAX_M + N * SAMPLED_MAX_M <= N * SMOOTH_LS);
+        // the export: one D x 14 matrix, one record, and no more than 15 % on top
+        const int floor_se = m.D * SMOOTH_LS + m.S + PK;
+        EXPECT(se >= floor_se && se <= floor_se * 115 / 100 + 32 && se % 4 == 0 && se < sc);
+        for (size_t bytes : {size_t(4), size_t(8)}) {
+            const SampledGeometry g = sampled_geometry(m.S, m.D, 1022, bytes), x = sigma_points_geometry(m.S, m.D, 1022, bytes);
+            EXPECT(g.grid == 256 && g.lds_bytes == int(4 * sc * bytes) && x.grid == 256 && x.lds_bytes == int(4 * se * bytes));
+            EXPECT(g.lds_bytes <= 65536 && g.lds_bytes % 16 == 0 && (sc * int(bytes)) % 16 == 0 && (se * int(bytes)) % 16 == 0);
+            EXPECT((sc * int(bytes) / 4) % 32 != 0 && (se * int(bytes) / 4) % 32 != 0);   // the four slices start on different banks
+        }
+        EXPECT(sampled_geometry(m.S, m.D, 0, 8).grid == 0 && sampled_geometry(m.S, m.D, 5, 8).grid == 2);
+        EXPECT(sigma_points_geometry(m.S, m.D, 1, 4).grid == 1 && sigma_points_geometry(m.S, m.D, 4, 4).grid == 1);
+    }
+    EXPECT(sampled_filter_scalars(13, 12) == 740 && sampled_filter_scalars(14, 13) == 796);
+    EXPECT(sigma_points_filter_scalars(13, 12) == 296 && sigma_points_filter_scalars(14, 13) == 324);
+    EXPECT(sampled_filter_scalars(17, 16) == -1 && sigma_points_filter_scalars(17, 16) == -1);
+    std::printf("OK: %d failure(s)\n", failures);
+    return failures ? 1 : 0;
+}
