@@ -232,6 +232,23 @@ public:
                                   st.data()));
         return st;
     }
+    /** User-defined process models (ukf_batch.h, "user-defined process models"): ukf->predict(f, R) for an f of the caller's.
+     *  The caller evaluates XX = f(X) on the export of sigmaPointsDev and predictSampledDev finishes the prediction from
+     *  in.XX_dev [N][2 D + 1][S] and in.R_dev [N][D][D] (ONE D x D with r_is_uniform; taken as given: no rotation, no dt).
+     *  Times are not touched.  commit = false is read-only (only `out` is written).  Stream-ordered. */
+    void predictSampledDev(const ukfb_predict_sampled_in& in, bool commit = true, const ukfb_predict_sampled_out* out = NULL)
+    {
+        check(ukfb_predict_sampled_dev(engine, &in, commit ? 1 : 0, out));
+    }
+    /** host arrays: XX [N][2 D + 1][S] = f(X) in the order of sigmaPoints, R [N][D][D] (ONE D x D with r_is_uniform); active [N]
+     *  or NULL; mu [N][S], cov [N][D][D] or NULL; returns the status */
+    std::vector<uint32_t> predictSampled(const double* XX, const double* R, bool r_is_uniform = false, const uint8_t* active = NULL,
+                                         bool commit = true, double* mu = NULL, double* cov = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_predict_sampled(engine, XX, R, r_is_uniform ? 1 : 0, active, commit ? 1 : 0, mu, cov, st.data()));
+        return st;
+    }
     /** Late samples (ukf_batch.h, "late samples"): a sample taken in.lag steps ago corrects the CURRENT state through the history
      *  ring -- no stored measurements, no replay, no waiting for the slowest sensor.  The window is smoothDev's with the
      *  filters' own state as its last step; commit = false is read-only (only `out` is written, out->mu_out / cov_out showing

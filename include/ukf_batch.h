@@ -951,6 +951,55 @@ int ukfb_update_sampled(ukfb_engine* e, int m, const double* Z, const double* z,
                         const uint8_t* active, int commit, double* z_pred, double* S, double* innov, double* maha,
                         double* loglik, uint32_t* status);
 
+/* ---- user-defined process models: predict from propagated sigma points ---------------------------------------------------- */
+/* ukf->predict(f, R) for an f the library does not know (drag and thrusters, a coordinated turn, another bias model, any control
+ * input).  The caller exports the sigma points (ukfb_sigma_points_dev), evaluates f on them with whatever they like and hands the
+ * propagated points XX_i = f(X_i) back, in the export's layout and point order ([capacity][2 D + 1][S], filter-major); the
+ * library finishes the prediction.  Per active, initialised filter:
+ *   1. mu^- = the iterated mean of the XX_i, started at XX_0 (mean_tol / mean_max_iter, one count per move above the tolerance);
+ *   2. Sigma^- = 1/2 sum (XX_i (-) mu^-)(XX_i (-) mu^-)^T + R.
+ * R IS TAKEN AS GIVEN: [capacity][D][D] row-major (or ONE D x D with r_is_uniform), the lower triangle is read, the upper never.
+ * There is no rotation into the body frame and no scaling by dt or dt^2; those belong to the built-in models'
+ * predictionStepImpl, and a caller who wants them forms R that way.
+ * NOTHING IS FACTORISED: the call reads neither Sigma nor its factor, the engine's covariance is only overwritten.  A filter
+ * whose export reported ERR_CHOLESKY has rows of NaN and is caught here as ERR_NONFINITE_MEAS.
+ * TIMES ARE NOT TOUCHED: last measurement times, noise tables, input bindings and latches keep every bit.  The caller knows the
+ * dt they evaluated f with; a filter whose step the time gate would have skipped is passed active = 0, and a caller who tracks
+ * stamps in the engine advances them with ukfb_set_last_measurement_time.
+ * QUATERNION BLOCKS ARE USED AS GIVEN (unit to the rounding of the storage type; ukfom does not renormalise, neither does this).
+ * ARITHMETIC: the differences XX_i - XX_0 of every vector block are formed first, in fp64, in every mode; the mean iteration
+ * and the deltas of those blocks work on the differences, and the committed vector blocks are XX_0 + the mean difference.  The
+ * call is therefore invariant under a per-filter translation of a vector block of all XX_i together (only that block of mu^-
+ * moves).
+ * commit = 1: mean, covariance and the engine's own status array are written; out may be NULL.  commit = 0: READ-ONLY like
+ * ukfb_innovation_dev, only `out` is written (the same numbers).
+ * Status of THIS call (out->status, and with commit = 1 the engine's status array):
+ *   UNINITIALISED       the filter is uninitialised;
+ *   INACTIVE            active_dev says 0 for this filter;
+ *   ERR_NONFINITE_MEAS  a non-finite value among the filter's (2 D + 1) S samples or in the lower triangle of its R;
+ *   WARN_MEAN_NOCONV    the mean iteration hit its cap (the prediction is still made).
+ * A filter with one of the first three keeps its state bit for bit and writes NaN to its float outputs; it never changes a bit
+ * of another filter.  NULL in, XX_dev or R_dev, commit outside 0 / 1, or commit = 0 with nowhere to write:
+ * UKFB_ERR_INVALID_ARG, nothing is written.  Stream-ordered, joins split streams, no host synchronisation, no allocation at
+ * call time, capturable.  The same kernel serves every lanes_per_filter setting; fp32 engines compute in fp32, with
+ * wide_arithmetic in fp64 (stored fp32).  Device groups: per shard through ukfb_group_shard. */
+typedef struct ukfb_predict_sampled_in {
+    const void* XX_dev;         /* [capacity][2D+1][S]  XX_i = f(X_i), layout and point order of ukfb_sigma_points_dev */
+    const void* R_dev;          /* [capacity][D][D] row-major, or ONE D x D with r_is_uniform; the lower triangle is read */
+    int r_is_uniform;
+    const uint8_t* active_dev;  /* [capacity] or NULL = all; 0: no prediction for that filter (INACTIVE) */
+} ukfb_predict_sampled_in;
+typedef struct ukfb_predict_sampled_out {   /* device, engine precision, any may be NULL */
+    void* mu;          /* [capacity][S] */
+    void* cov_packed;  /* [capacity][PK], the packed lower triangle of ukfb_device_views / the forecast ring */
+    uint32_t* status;  /* [capacity] */
+} ukfb_predict_sampled_out;
+int ukfb_predict_sampled_dev(ukfb_engine* e, const ukfb_predict_sampled_in* in, int commit, const ukfb_predict_sampled_out* out);
+/* host arrays of doubles, synchronising: XX [capacity][2D+1][S], R [capacity][D][D] (ONE D x D with r_is_uniform), active
+ * [capacity] or NULL; mu [capacity][S], cov [capacity][D][D] (full, symmetric), status [capacity]: any may be NULL */
+int ukfb_predict_sampled(ukfb_engine* e, const double* XX, const double* R, int r_is_uniform, const uint8_t* active,
+                         int commit, double* mu /* [capacity][S] */, double* cov /* [capacity][D][D] */, uint32_t* status);
+
 
 /* ---- device groups: one host process, several MI355X ------------------------------------------------------------------ */
 /* north_star's multi-GPU shape for a C++ host.  The filters of a batch are independent -- every filter of the reference owns

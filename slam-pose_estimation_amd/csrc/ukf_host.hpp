@@ -499,6 +499,33 @@ inline SampledGeometry sigma_points_geometry(int S, int D, int64_t capacity, siz
             int(size_t(SAMPLED_FILTERS_PER_GROUP) * sigma_points_filter_scalars(S, D) * compute_size)};
 }
 
+// ---- user-defined process models (ukfb_predict_sampled_dev) ----------------------------------------------------------------
+// The caller evaluates f on the exported sigma points; the prediction is finished from the samples XX_i = f(X_i) and the caller's
+// R.  The launch is the sampled update's: four filters per workgroup, one wavefront.
+inline Verdict check_predict_sampled_args(const ukfb_predict_sampled_in* in, int commit, const ukfb_predict_sampled_out* out) {
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    if (!in->XX_dev || !in->R_dev) return {UKFB_ERR_INVALID_ARG, "XX_dev and R_dev must not be NULL"};
+    if (in->r_is_uniform != 0 && in->r_is_uniform != 1) return {UKFB_ERR_INVALID_ARG, "r_is_uniform must be 0 or 1"};
+    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    if (commit == 0 && (!out || (!out->mu && !out->cov_packed && !out->status)))
+        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
+    return {};
+}
+// LDS of one filter, in scalars of the compute type (ukf_predict_sampled.hpp, PredictSampledLayout): the D rows of Sigma^- (stride
+// SMOOTH_LS; parked while R is added), the delta table of 2 D + 1 rows (the staged samples, (2 D + 1) S scalars, alias it), the
+// predicted record (mean padded to 16 -- XX_0 waits there until the mean is formed --, packed covariance padded to even) and the
+// sink of lane-predicated stores (16); rounded up to a multiple of four so that every filter's slice starts 16-byte aligned in
+// either precision.  No factor, no reciprocal pivots, no rotation matrix: the kernel factorises nothing.  Every scalar the kernel
+// reads is one it wrote: the pads are never read.
+constexpr int predict_sampled_filter_scalars(int S, int D) {
+    return S > 16 ? -1 : (D * SMOOTH_LS + (2 * D + 1) * SMOOTH_LS + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 16 + 3) / 4 * 4;
+}
+// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
+inline SampledGeometry predict_sampled_geometry(int S, int D, int64_t capacity, size_t compute_size) {
+    return {(capacity + SAMPLED_FILTERS_PER_GROUP - 1) / SAMPLED_FILTERS_PER_GROUP,
+            int(size_t(SAMPLED_FILTERS_PER_GROUP) * predict_sampled_filter_scalars(S, D) * compute_size)};
+}
+
 // ---- late samples (ukfb_update_delayed_dev, ukfb_delayed_lag_dev) -----------------------------------------------------------
 // The smoother's window with the engine's own state as its last step: the chain runs at most steps - 1 <= SMOOTH_MAX_BACK
 // backward steps, all in one launch (their dt travel in the kernel arguments), so steps <= DELAYED_MAX_STEPS.

@@ -67,6 +67,8 @@ EXPORTS = [
     "ukfb_update_sensor_dev", "ukfb_update_sensor",
     # user-defined measurement models: sigma-point export, the update finished from the caller's samples
     "ukfb_sigma_points_dev", "ukfb_update_sampled_dev", "ukfb_sigma_points", "ukfb_update_sampled",
+    # user-defined process models: the prediction finished from the caller's propagated sigma points
+    "ukfb_predict_sampled_dev", "ukfb_predict_sampled",
     # late samples: the delayed-measurement update through the state history
     "ukfb_update_delayed_dev", "ukfb_update_delayed", "ukfb_delayed_lag_dev",
     # device groups (one process, several GPUs)
@@ -139,6 +141,17 @@ class SampledOut(C.Structure):
     """ukfb_sampled_out: device pointers in engine precision (status uint32), any may be NULL"""
     _fields_ = [("z_pred", C.c_void_p), ("S", C.c_void_p), ("innov", C.c_void_p), ("maha", C.c_void_p),
                 ("loglik", C.c_void_p), ("status", C.c_void_p)]
+
+
+class PredictSampledIn(C.Structure):
+    """ukfb_predict_sampled_in: the propagated points XX [capacity, 2 D + 1, S], R [capacity, D, D] (or one D x D) as device
+    pointers in engine precision; active_dev uint8 [capacity] or NULL"""
+    _fields_ = [("XX_dev", C.c_void_p), ("R_dev", C.c_void_p), ("r_is_uniform", C.c_int), ("active_dev", C.c_void_p)]
+
+
+class PredictSampledOut(C.Structure):
+    """ukfb_predict_sampled_out: device pointers in engine precision (status uint32), any may be NULL"""
+    _fields_ = [("mu", C.c_void_p), ("cov_packed", C.c_void_p), ("status", C.c_void_p)]
 
 
 class DelayedIn(C.Structure):
@@ -790,6 +803,35 @@ class BatchUKF:
                                            act.ctypes.data_as(C.POINTER(C.c_uint8)) if act is not None else None,
                                            C.c_int(1 if commit else 0), _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]),
                                            _pd(o["loglik"]), o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_update_sampled")
+        return o
+
+    # ---- user-defined process models: XX [capacity, 2 D + 1, S] = f(X) of sigma_points_dev's X, R [capacity, D, D]
+    def predict_sampled_dev(self, XX, R, r_is_uniform: bool = False, active_dev=None, commit: bool = True, mu=None,
+                            cov_packed=None, status=None):
+        """ukfom's predict finished from the caller's propagated sigma points XX [capacity, 2 D + 1, S] = f(X) of
+        sigma_points_dev's X and the caller's R [capacity, D, D] (one D x D with r_is_uniform; taken as given, the lower triangle
+        is read); active_dev uint8 [capacity] or None.  Times, noise tables and latches are not touched.  commit=False is
+        read-only: only the keyword outputs (device buffers in engine precision: mu [capacity, S], cov_packed [capacity, PK];
+        status uint32 / int32) are written.  Stream-ordered, nothing is allocated."""
+        ptr = lambda x: None if x is None else _devptr(x).value
+        pin = PredictSampledIn(ptr(XX), ptr(R), 1 if r_is_uniform else 0, ptr(active_dev))
+        out = PredictSampledOut(ptr(mu), ptr(cov_packed), ptr(status))
+        _chk(self._lib.ukfb_predict_sampled_dev(self._h, C.byref(pin), C.c_int(1 if commit else 0), C.byref(out)),
+             "ukfb_predict_sampled_dev")
+
+    def predict_sampled(self, XX, R, active=None, commit: bool = True):
+        """Host arrays: XX [capacity, 2 D + 1, S], R [capacity, D, D] or [D, D] (one for the batch); active uint8 [capacity] or
+        None.  Returns a dict of NumPy arrays: mu [n, S], cov [n, D, D], status [n]; synchronises"""
+        n, pts, S, D = self.capacity, 2 * self.D + 1, self.S, self.D
+        XX = _f64(XX, (n, pts, S)); R = _f64(R)
+        uniform = R.ndim == 2
+        R = R.reshape(D, D) if uniform else R.reshape(n, D, D)
+        act = np.ascontiguousarray(active, dtype=np.uint8).reshape(n) if active is not None else None
+        o = {"mu": np.empty((n, S)), "cov": np.empty((n, D, D)), "status": np.empty(n, dtype=np.uint32)}
+        _chk(self._lib.ukfb_predict_sampled(self._h, _pd(XX), _pd(R), C.c_int(1 if uniform else 0),
+                                            act.ctypes.data_as(C.POINTER(C.c_uint8)) if act is not None else None,
+                                            C.c_int(1 if commit else 0), _pd(o["mu"]), _pd(o["cov"]),
+                                            o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_predict_sampled")
         return o
 
     # ---- late samples: the window of smooth_dev with the engine's own state as its last step

@@ -1,0 +1,89 @@
+// predict_sampled_host.cpp -- the host decisions of the user-defined process models (ukf_host.hpp) on the CPU (g++ under ASan /
+// UBSan, compiled by tests/test_predict_sampled_host.py): every refusal, the LDS accounting against hand-computed values for both
+// models, and the launch geometry.
+#include <cstdio>
+
+#include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
+
+static int failures = 0;
+#define EXPECT(cond)                                                        \
+    do {                                                                    \
+        if (!(cond)) {                                                      \
+            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
+            ++failures;                                                     \
+        }                                                                   \
+    } while (0)
+
+int main() {
+    using namespace ukfb;
+    double buf[16] = {0};
+    uint32_t word = 0;
+    ukfb_predict_sampled_in in{};
+    in.XX_dev = buf;
+    in.R_dev = buf;
+    ukfb_predict_sampled_out none{};
+    ukfb_predict_sampled_out st_only{};
+    st_only.status = &word;
+    // NULL combinations
+    EXPECT(check_predict_sampled_args(nullptr, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_predict_sampled_args(nullptr, 1, nullptr).msg != nullptr);
+    {
+        ukfb_predict_sampled_in bad = in;
+        bad.XX_dev = nullptr;
+        EXPECT(check_predict_sampled_args(&bad, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+        bad = in;
+        bad.R_dev = nullptr;
+        EXPECT(check_predict_sampled_args(&bad, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+        bad = in;
+        bad.r_is_uniform = 2;
+        EXPECT(check_predict_sampled_args(&bad, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+        bad.r_is_uniform = -1;
+        EXPECT(check_predict_sampled_args(&bad, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+        bad.r_is_uniform = 1;
+        EXPECT(check_predict_sampled_args(&bad, 1, nullptr).rc == UKFB_OK);
+        bad = in;   // active_dev NULL: every filter takes part; given: per filter
+        const uint8_t act[4] = {1, 0, 1, 1};
+        bad.active_dev = act;
+        EXPECT(check_predict_sampled_args(&bad, 1, nullptr).rc == UKFB_OK);
+    }
+    // commit is 0 or 1; a read-only call needs somewhere to write
+    EXPECT(check_predict_sampled_args(&in, 2, &st_only).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_predict_sampled_args(&in, -1, &st_only).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_predict_sampled_args(&in, 0, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_predict_sampled_args(&in, 0, &none).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_predict_sampled_args(&in, 0, &st_only).rc == UKFB_OK);
+    EXPECT(check_predict_sampled_args(&in, 1, &none).rc == UKFB_OK);
+    EXPECT(check_predict_sampled_args(&in, 1, nullptr).rc == UKFB_OK);
+    {
+        ukfb_predict_sampled_out o{};
+        o.mu = buf;
+        EXPECT(check_predict_sampled_args(&in, 0, &o).rc == UKFB_OK);
+        o = {};
+        o.cov_packed = buf;
+        EXPECT(check_predict_sampled_args(&in, 0, &o).rc == UKFB_OK);
+    }
+    // LDS by hand.  Pose (S 13, D 12): 12 * 14 rows of Sigma^- + 25 * 14 table + 16 mean + 78 packed + 16 sink = 628;
+    // OrientationState (S 14, D 13): 13 * 14 + 27 * 14 + 16 + 92 (91 padded to even) + 16 = 684
+    EXPECT(predict_sampled_filter_scalars(13, 12) == 168 + 350 + 16 + 78 + 16 && predict_sampled_filter_scalars(13, 12) == 628);
+    EXPECT(predict_sampled_filter_scalars(14, 13) == 182 + 378 + 16 + 92 + 16 && predict_sampled_filter_scalars(14, 13) == 684);
+    EXPECT(predict_sampled_filter_scalars(17, 16) == -1);
+    struct { int S, D; } models[2] = {{13, 12}, {14, 13}};
+    for (const auto& m : models) {
+        const int N = 2 * m.D + 1, sc = predict_sampled_filter_scalars(m.S, m.D);
+        EXPECT(N * m.S <= N * SMOOTH_LS);   // the staged samples fit the table they alias (equality for OrientationState)
+        EXPECT(sc % 4 == 0 && sc < forecast_filter_scalars(m.S, m.D) && sc < sampled_filter_scalars(m.S, m.D));
+        for (size_t bytes : {size_t(4), size_t(8)}) {
+            EXPECT((sc * int(bytes)) % 16 == 0);
+            EXPECT((sc * int(bytes) / 4) % 32 != 0);   // the four slices start on different banks
+            const struct { int64_t n, grid; } cases[] = {{0, 0}, {1, 1}, {4, 1}, {5, 2}, {1022, 256}};
+            for (const auto& c : cases) {
+                const SampledGeometry g = predict_sampled_geometry(m.S, m.D, c.n, bytes);
+                EXPECT(g.grid == c.grid && g.lds_bytes == int(4 * sc * bytes) && g.lds_bytes <= 65536 && g.lds_bytes % 16 == 0);
+            }
+        }
+    }
+    EXPECT(14 * 27 == 27 * SMOOTH_LS);
+    EXPECT(predict_sampled_geometry(13, 12, 1022, 8).lds_bytes == 20096 && predict_sampled_geometry(14, 13, 1022, 4).lds_bytes == 10944);
+    std::printf("OK: %d failure(s)\n", failures);
+    return failures ? 1 : 0;
+}

@@ -1,0 +1,172 @@
+"""NumPy float64 statement of the user-defined process models of include/ukf_batch.h ("user-defined process models"):
+oracle.ukf_numpy.ukf_predict(POSE | ORIENT, ..., g = the caller's propagated points, R) without its factorisation -- the call
+reads neither Sigma nor its factor -- built from on.mean_sigma_points and on.cov_sigma_points, with the status rules of the header
+and R mirrored from its lower triangle.  Behind it a small family of user process models and their inputs.  A helper, not
+collected; tests/test_predict_sampled_reference.py pins it."""
+import numpy as np
+
+from oracle import ukf_numpy as on
+
+
+def predict_sampled(man, mu, cov, XX, R, active=None, initialised=None, tol=on.MEAN_TOL, max_it=on.MEAN_MAX_IT):
+    """mu [B, S], cov [B, D, D], XX [B, 2 D + 1, S], R [B, D, D] (or [D, D]), active [B] or None -> dict(mu, cov, status [B]):
+    the filters that take part get the iterated mean of their XX_i and 1/2 sum delta delta^T + R, the others keep their state"""
+    B, D = mu.shape[0], man.D
+    assert XX.shape == (B, 2 * D + 1, man.S)
+    R = np.broadcast_to(np.asarray(R, dtype=np.float64), (B, D, D))
+    init = np.ones(B, bool) if initialised is None else np.asarray(initialised, dtype=bool)
+    act = np.ones(B, bool) if active is None else np.asarray(active) != 0
+    o = {"mu": mu.copy(), "cov": cov.copy(), "status": np.zeros(B, dtype=np.uint32)}
+    o["status"][~init] = on.ST_UNINITIALISED
+    o["status"][init & ~act] = on.ST_INACTIVE
+    lower = np.tril(np.ones((D, D), bool))
+    fin = np.isfinite(R[:, lower]).all(axis=1) & np.isfinite(XX).all(axis=(1, 2))
+    o["status"][init & act & ~fin] = on.ST_ERR_NONFINITE_MEAS
+    idx = np.nonzero(init & act & fin)[0]
+    if idx.size == 0:
+        return o
+    RR = np.where(lower, R[idx], np.swapaxes(R[idx], 1, 2))   # the lower triangle is what is read
+    m, conv = on.mean_sigma_points(man, XX[idx], tol, max_it)
+    o["mu"][idx] = m
+    o["cov"][idx] = on.cov_sigma_points(man, m, XX[idx]) + RR
+    o["status"][idx] = np.where(conv, 0, on.ST_WARN_MEAN_NOCONV)
+    return o
+
+
+def mean_trips(man, XX, tol=on.MEAN_TOL):
+    """-> [B] the moves above the tolerance on.mean_sigma_points makes per filter (its `it`), recounted alone"""
+    B = XX.shape[0]
+    ref, active, it = XX[:, 0].copy(), np.ones(B, bool), np.zeros(B, dtype=np.int64)
+    while active.any():
+        md = man.boxminus(XX, ref[:, None, :])
+        s = np.zeros((B, man.D))
+        for i in range(XX.shape[1]):
+            s = s + md[:, i]
+        s = s / float(XX.shape[1])
+        ref = np.where(active[:, None], man.boxplus(ref, s), ref)
+        big = np.sqrt(np.sum(s * s, axis=-1)) > tol
+        it = np.where(active & big, it + 1, it)
+        active = active & big
+    return it
+
+
+# ------------------------------------------------------------------------------------------------ a family of user process models
+# The f functions the tests evaluate on exported sigma points: written once, over slices and arithmetic (and the sine, cosine and
+# select of whichever library the points come from), so that NumPy (the CPU tests) and torch on the device (the GPU tests:
+# "XX = f(X) as a torch expression") run the same statements.  Parameters broadcast against X's leading axes.
+USER_MODELS = {"pose": ("drag", "turn"), "orient": ("markov",)}
+DT = 0.01
+
+
+def _lib(x):
+    return np if isinstance(x, np.ndarray) else __import__("torch")
+
+
+def _cat(parts):
+    lib = _lib(parts[0])
+    return lib.concatenate(parts, axis=-1) if lib is np else lib.cat(parts, dim=-1)
+
+
+def _cross(a, b):
+    return _cat([a[..., 1:2] * b[..., 2:3] - a[..., 2:3] * b[..., 1:2], a[..., 2:3] * b[..., 0:1] - a[..., 0:1] * b[..., 2:3],
+                 a[..., 0:1] * b[..., 1:2] - a[..., 1:2] * b[..., 0:1]])
+
+
+def rot(q, v):
+    """R(q) v as oracle.ukf_numpy.quat_rotate"""
+    qv = q[..., 0:3]
+    uv = _cross(qv, v + 0.0 * qv)
+    uv = uv + uv
+    return v + q[..., 3:4] * uv + _cross(qv, uv)
+
+
+def qmul(a, b):
+    """a * b as oracle.ukf_numpy.quat_mul, (x, y, z, w)"""
+    ax, ay, az, aw = a[..., 0:1], a[..., 1:2], a[..., 2:3], a[..., 3:4]
+    bx, by, bz, bw = b[..., 0:1], b[..., 1:2], b[..., 2:3], b[..., 3:4]
+    return _cat([aw * bx + ax * bw + ay * bz - az * by, aw * by + ay * bw + az * bx - ax * bz,
+                 aw * bz + az * bw + ax * by - ay * bx, aw * bw - ax * bx - ay * by - az * bz])
+
+
+def qexp(v):
+    """exp of the rotation vector v as a quaternion: (sin(|v| / 2) v / |v|, cos(|v| / 2)), the series below |v|^2 = 1e-8"""
+    lib = _lib(v)
+    n2 = v[..., 0:1] * v[..., 0:1] + v[..., 1:2] * v[..., 1:2] + v[..., 2:3] * v[..., 2:3]
+    small = n2 < 1e-8
+    n = (n2 + small * 1.0) ** 0.5   # (a safe divisor where the series is taken)
+    mult = lib.where(small, 0.5 - n2 / 48.0, lib.sin(0.5 * n) / n)
+    return _cat([mult * v, lib.cos(0.5 * (n2 ** 0.5))])
+
+
+def pose_builtin(X, acc, dt):
+    """oracle.ukf_numpy.pose_process (acc None: the constant-velocity model)"""
+    p, q, v, w = X[..., 0:3], X[..., 3:7], X[..., 7:10], X[..., 10:13]
+    if acc is not None:
+        v = v + dt * acc
+    return _cat([p + dt * rot(q, v), qmul(q, qexp(dt * rot(q, w))), v, w])
+
+
+def orient_builtin(X, acc, omega, ninv_tau_g, ninv_tau_a, earth, dt):
+    """oracle.ukf_numpy.orient_process; ninv_tau = -1 / tau (a number or per filter)"""
+    q, v, bg, ba, g = X[..., 0:4], X[..., 4:7], X[..., 7:10], X[..., 10:13], X[..., 13:14]
+    q2 = qmul(q, qexp(dt * (rot(q, omega - bg) - earth)))
+    a = rot(q2, acc - ba)
+    a = _cat([a[..., 0:2], a[..., 2:3] - g])
+    return _cat([q2, v + dt * a, bg + dt * (ninv_tau_g * bg), ba + dt * (ninv_tau_a * ba), g])
+
+
+def user_f(model, name, X, par, dt=DT):
+    """Pose "drag": body-frame thrust a_b with linear drag k, v' = v + dt (a_b - k v), then the built-in position and orientation
+    steps.  Pose "turn": a coordinated turn, the orientation advanced by the world-frame rate W + gain R(q) v (q' = exp(dt rate) q:
+    the faster, the tighter) and the velocity rotated with it, the position by the built-in step.  OrientationState "markov": the built-in strap-down step with
+    first-order Gauss-Markov biases of per-filter time constants and a constant-gravity state."""
+    if model == "pose":
+        p, q, v, w = X[..., 0:3], X[..., 3:7], X[..., 7:10], X[..., 10:13]
+        if name == "drag":
+            v2 = v + dt * (par["a_b"] - par["k"] * v)
+            return _cat([p + dt * rot(q, v2), qmul(q, qexp(dt * rot(q, w))), v2, w])
+        dq = qexp(dt * (par["W"] + par["gain"] * rot(q, v)))
+        return _cat([p + dt * rot(q, v), qmul(dq, q), rot(dq, v), w])
+    return orient_builtin(X, par["acc"], par["omega"], par["ninv_tau_g"], par["ninv_tau_a"], par["earth"], dt)
+
+
+def make_inputs(model, mu, dtype, seed=17):
+    """-> ({user model: {parameter: [n, k]}}, R [n, D, D]) as the engine stores them.  R = diag(s) (I + G G^T / (4 D)) diag(s)
+    with G ~ N(0, 1)^(D x D): dense, symmetric as stored; s per block = the square roots of synth's process noise (Pose: the
+    PoseUKF defaults, OrientationState: synth.orient_process_noise), undivided by any dt, so that R matters beside Sigma"""
+    from slam_pose_estimation_amd import synth
+    n = mu.shape[0]
+    D = 12 if model == "pose" else 13
+    rng = np.random.default_rng(seed)
+    st = lambda x: np.asarray(x, dtype=np.float64).astype(dtype).astype(np.float64)   # noqa: E731
+    if model == "pose":
+        par = {"drag": {"a_b": st(0.5 * rng.standard_normal((n, 3))), "k": st(rng.uniform(0.05, 0.5, (n, 1)))},
+               "turn": {"W": st(0.3 * rng.standard_normal((n, 3))), "gain": st(rng.uniform(0.0, 0.5, (n, 1)))}}
+        s = np.sqrt(np.diag(synth.pose_default_process_noise()))
+    else:
+        tau_g, tau_a = rng.uniform(50.0, 500.0, (n, 1)), rng.uniform(50.0, 500.0, (n, 1))
+        acc = 0.3 * rng.standard_normal((n, 3))
+        acc[:, 2] += synth.ORIENT_G
+        par = {"markov": {"acc": st(acc), "omega": st(0.1 * rng.standard_normal((n, 3))), "ninv_tau_g": st(-1.0 / tau_g),
+                          "ninv_tau_a": st(-1.0 / tau_a), "earth": st(np.broadcast_to(on.earth_rotation(synth.ORIENT_LATITUDE), (n, 3)))}}
+        s = np.sqrt(np.diag(synth.orient_process_noise()))
+    G = rng.standard_normal((n, D, D))
+    R = st(s[:, None] * (np.eye(D) + G @ np.swapaxes(G, 1, 2) / (4.0 * D)) * s[None, :])
+    R = np.where(np.tril(np.ones((D, D), bool)), R, np.swapaxes(R, 1, 2))   # symmetric as stored
+    return par, R
+
+
+WIDE_TURN_DT = 1.0
+
+
+def wide_turn(par, gain=12.0):
+    """the "turn" parameters with a gain whose product with WIDE_TURN_DT and the velocity's sigma (~ 0.2 m/s) spreads the
+    propagated orientations by radians (the farthest point of a filter lies 2 ... 2.7 rad from its centre, below the branch of
+    the logarithm at pi): the mean iteration then needs more than two trips for most filters.  A smaller spread does not: the
+    pairs of sigma points are symmetric about the centre to first order, and at ~ 1 rad two trips already reach the tolerance."""
+    return {"W": par["W"], "gain": 0.0 * par["gain"] + gain}
+
+
+def expand(par):
+    """the parameters of one user model with the axis of the sigma points: [n, k] -> [n, 1, k]"""
+    return {k: v[:, None, :] for k, v in par.items()}

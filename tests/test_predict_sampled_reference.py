@@ -1,0 +1,182 @@
+"""Pins for tests/predict_sampled_reference.py, the NumPy statement of the user-defined process models (include/ukf_batch.h) the
+GPU tests compare with: fed the propagated points of a built-in process model and the R that model's predict forms, it returns
+what on.pose_predict / on.orient_predict return bit for bit; the status rules hold one by one; the upper triangle of R is never
+read; a translation of a vector block moves that block of the mean and nothing else; the user models of the GPU file run the
+same statements in NumPy and torch; and the all-float64 evaluation of tests/predict_sampled_f32.py is the reference."""
+import numpy as np
+import pytest
+
+import predict_sampled_f32 as pf
+import predict_sampled_reference as pr
+import slam_pose_estimation_amd as spe
+from oracle import ukf_numpy as on
+from test_sensor_meas_reference import states
+
+N = 1022
+ACC_COV = 0.01 * np.eye(3)
+sy = spe.synth
+
+
+def man_of(model):
+    return on.POSE if model == "pose" else on.ORIENT
+
+
+def builtin(model, with_acc=True, n=N):
+    """-> (mu, cov, XX, R, (mu', cov', status) of the oracle's predict) for the built-in process model of `model`"""
+    mu, cov, _ = states(model)
+    mu, cov = mu[:n], cov[:n]
+    X, ok = on.sigma_points(man_of(model), mu, cov)
+    assert ok.all()
+    dt = 0.01
+    if model == "pose":
+        Rn = np.broadcast_to(sy.pose_default_process_noise(), (n, 12, 12))
+        acc = sy.pose_cycle_inputs(n, 2, mu[:, :3])[0] if with_acc else None
+        XX = on.pose_process(X, None if acc is None else acc[:, None, :], np.full((n, 1), dt))
+        R = Rn.copy()
+        if with_acc:
+            R[:, 6:9, 6:9] = 2.0 * ACC_COV
+        else:
+            rot = on.quat_to_matrix(mu[:, 3:7])
+            R[:, 0:3, 0:3] = on._rotate_block(rot, Rn, 0)
+            R[:, 3:6, 3:6] = on._rotate_block(rot, Rn, 3)
+            R = np.full(n, dt)[:, None, None] * R
+        return mu, cov, XX, R, on.pose_predict(mu, cov, sy.pose_default_process_noise(), acc, ACC_COV, dt)
+    earth = on.earth_rotation(sy.ORIENT_LATITUDE)
+    gyro, acc, _, _ = sy.orient_cycle_inputs(n, 2, mu[:, 0:4])
+    XX = on.orient_process(X, acc[:, None, :], gyro[:, None, :], sy.ORIENT_TAU, sy.ORIENT_TAU, earth, np.full((n, 1), dt))
+    Rn = np.broadcast_to(sy.orient_process_noise(), (n, 13, 13))
+    rot = on.quat_to_matrix(mu[:, 0:4])
+    R = Rn.copy()
+    R[:, 0:3, 0:3] = on._rotate_block(rot, Rn, 0)
+    R[:, 3:6, 3:6] = on._rotate_block(rot, Rn, 3)
+    R = np.power(np.full(n, dt), 2.0)[:, None, None] * R
+    return mu, cov, XX, R, on.orient_predict(mu, cov, sy.orient_process_noise(), acc, gyro, sy.ORIENT_TAU, sy.ORIENT_TAU, earth, dt)
+
+
+@pytest.mark.parametrize("model,with_acc", [("pose", True), ("pose", False), ("orient", True)])
+def test_built_in_model_bit_for_bit(model, with_acc):
+    """The mean and the lower triangle of the covariance are the oracle's bits.  The rotated noise blocks are symmetric only to
+    rounding (rot R rot^T), and the call reads the lower triangle of R alone: the upper triangle of the result is the mirror of
+    the lower one, the oracle's own upper triangle within an ulp of the block."""
+    mu, cov, XX, R, (mu_o, cov_o, st_o) = builtin(model, with_acc)
+    got = pr.predict_sampled(man_of(model), mu, cov, XX, R)
+    assert (st_o == 0).all() and np.array_equal(got["status"], st_o)
+    assert np.array_equal(got["mu"], mu_o) and not np.array_equal(mu_o, mu)
+    lower = np.tril(np.ones(cov.shape[1:], bool))
+    assert np.array_equal(got["cov"][:, lower], cov_o[:, lower])
+    assert np.array_equal(got["cov"], np.swapaxes(got["cov"], 1, 2))
+    assert np.abs(got["cov"] - cov_o).max() <= 1e-18
+    sym = np.where(lower, R, np.swapaxes(R, 1, 2))   # a symmetric R as stored: every bit
+    full = on.ukf_predict(man_of(model), mu, cov, lambda X: XX, sym)
+    assert np.array_equal(pr.predict_sampled(man_of(model), mu, cov, XX, sym)["cov"], full[1])
+
+
+@pytest.mark.parametrize("model", ["pose", "orient"])
+def test_status_rules(model):
+    man = man_of(model)
+    mu, cov, XX, R, _ = builtin(model, n=64)
+    clean = pr.predict_sampled(man, mu, cov, XX, R)
+    assert (clean["status"] == 0).all()
+    dead, idle, nan_s, nan_r, upper, both = 5, 9, 13, 17, 21, 25
+    init, act = np.ones(64, bool), np.ones(64, np.uint8)
+    init[[dead, both]], act[[idle, both]] = False, 0
+    XXb, Rb = XX.copy(), R.copy()
+    XXb[nan_s, -1, -1] = np.nan
+    XXb[dead, 3, 2] = np.inf          # uninitialised comes first
+    Rb[nan_r, man.D - 1, 0] = np.inf
+    Rb[idle, 2, 1] = np.nan           # inactive comes before the samples are judged
+    Rb[upper, 0, man.D - 1] = np.nan
+    got = pr.predict_sampled(man, mu, cov, XXb, Rb, active=act, initialised=init)
+    expect = np.zeros(64, dtype=np.uint32)
+    expect[[dead, both]], expect[idle], expect[[nan_s, nan_r]] = on.ST_UNINITIALISED, on.ST_INACTIVE, on.ST_ERR_NONFINITE_MEAS
+    assert np.array_equal(got["status"], expect)
+    bad = expect != 0
+    assert np.array_equal(got["mu"][bad], mu[bad]) and np.array_equal(got["cov"][bad], cov[bad])
+    assert np.array_equal(got["mu"][~bad], clean["mu"][~bad]) and np.array_equal(got["cov"][~bad], clean["cov"][~bad])
+    # the cap of the mean iteration: WARN_MEAN_NOCONV, the prediction is still made
+    capped = pr.predict_sampled(man, mu, cov, XX, R, max_it=1)
+    trips = pr.mean_trips(man, XX)
+    assert np.array_equal(capped["status"] != 0, trips >= 1) and set(np.unique(capped["status"])) <= {0, on.ST_WARN_MEAN_NOCONV}
+    assert not np.array_equal(capped["mu"], mu)
+    # one R for the batch
+    one = pr.predict_sampled(man, mu, cov, XX, R[3])
+    assert np.array_equal(one["cov"][3], clean["cov"][3]) and np.array_equal(one["mu"], clean["mu"])
+
+
+@pytest.mark.parametrize("model", ["pose", "orient"])
+def test_upper_triangle_of_r_is_ignored(model):
+    man = man_of(model)
+    mu, cov, XX, R, _ = builtin(model, n=64)
+    junk = R + np.triu(np.random.default_rng(1).standard_normal(R.shape), 1)
+    a, b = pr.predict_sampled(man, mu, cov, XX, R), pr.predict_sampled(man, mu, cov, XX, junk)
+    lower = np.tril(np.ones(R.shape[1:], bool))
+    assert np.array_equal(b["mu"], a["mu"]) and np.array_equal(b["cov"][:, lower], a["cov"][:, lower])
+    assert np.array_equal(b["cov"], np.swapaxes(b["cov"], 1, 2))
+
+
+@pytest.mark.parametrize("model", ["pose", "orient"])
+def test_translation_moves_only_its_block(model):
+    man = man_of(model)
+    mu, cov, XX, R, _ = builtin(model, n=64)
+    sl = slice(0, 3) if model == "pose" else slice(4, 7)
+    t = np.random.default_rng(2).uniform(-1000.0, 1000.0, (64, 3))
+    moved = XX.copy()
+    moved[:, :, sl] += t[:, None, :]
+    a, b = pr.predict_sampled(man, mu, cov, XX, R), pr.predict_sampled(man, mu, cov, moved, R)
+    others = np.ones(man.S, bool)
+    others[sl] = False
+    assert np.abs(b["mu"][:, sl] - (a["mu"][:, sl] + t)).max() <= 1e-12 * 1000.0
+    assert np.abs(b["mu"][:, others] - a["mu"][:, others]).max() <= 1e-12
+    assert np.abs(b["cov"] - a["cov"]).max() <= 1e-12 * 1000.0 * np.sqrt(np.abs(a["cov"]).max())
+
+
+@pytest.mark.parametrize("model", ["pose", "orient"])
+def test_user_models(model):
+    """the built-in formulas of the helper are the oracle's to rounding; NumPy and torch run the same statements; every user
+    model moves the points, keeps the quaternions unit and gives status 0 with the helper's R"""
+    import torch
+    man = man_of(model)
+    mu, cov, XXo, _, _ = builtin(model, n=64)
+    X, _ = on.sigma_points(man, mu, cov)
+    if model == "pose":
+        acc = sy.pose_cycle_inputs(64, 2, mu[:, :3])[0]
+        assert np.abs(pr.pose_builtin(X, acc[:, None, :], 0.01) - XXo).max() <= 1e-13
+    else:
+        gyro, acc, _, _ = sy.orient_cycle_inputs(64, 2, mu[:, 0:4])
+        earth = on.earth_rotation(sy.ORIENT_LATITUDE)
+        mine = pr.orient_builtin(X, acc[:, None, :], gyro[:, None, :], -1.0 / sy.ORIENT_TAU, -1.0 / sy.ORIENT_TAU, earth, 0.01)
+        assert np.abs(mine - XXo).max() <= 1e-13
+    par, R = pr.make_inputs(model, mu, np.float64)
+    assert np.array_equal(R, np.swapaxes(R, 1, 2)) and (np.linalg.eigvalsh(R) > 0).all()
+    q = slice(3, 7) if model == "pose" else slice(0, 4)
+    for name in pr.USER_MODELS[model]:
+        XX = pr.user_f(model, name, X, pr.expand(par[name]))
+        tp = {k: torch.from_numpy(v) for k, v in pr.expand(par[name]).items()}
+        XXt = pr.user_f(model, name, torch.from_numpy(X), tp).numpy()
+        assert XX.shape == X.shape and np.abs(XXt - XX).max() <= 1e-14
+        assert np.abs(np.linalg.norm(XX[..., q], axis=-1) - 1.0).max() <= 1e-14 and not np.array_equal(XX, X)
+        o = pr.predict_sampled(man, mu, cov, XX, R)
+        assert (o["status"] == 0).all() and (np.linalg.eigvalsh(o["cov"]) > 0).all()
+        ratio = np.diagonal(R, axis1=1, axis2=2) / np.diagonal(o["cov"], axis1=1, axis2=2)
+        assert ratio.max() > 1e-4   # R matters beside Sigma
+        # the all-float64 evaluation of the dtype-per-stage helper is this reference
+        e = pf.predict_sampled(model, mu, cov, XX, R, prec="f64")
+        assert np.abs(e["mu"] - o["mu"]).max() <= 1e-12 and np.abs(e["cov"] - o["cov"]).max() <= 1e-12
+        e32 = pf.predict_sampled(model, mu, cov, XX, R, prec="f32")
+        assert np.abs(e32["mu"] - o["mu"]).max() <= 1e-4 * (1.0 + np.abs(o["mu"]).max())
+
+
+def test_a_wide_turn_needs_several_trips():
+    """the GPU file's mean-iteration case: a coordinated turn whose rate x dt spreads the propagated orientations by radians"""
+    mu, cov, _ = states("pose")
+    mu, cov = mu[:64], cov[:64]
+    X, _ = on.sigma_points(on.POSE, mu, cov)
+    par, _ = pr.make_inputs("pose", mu, np.float64)
+    XX = pr.user_f("pose", "turn", X, pr.expand(pr.wide_turn(par["turn"])), dt=pr.WIDE_TURN_DT)
+    d = on.POSE.boxminus(XX, XX[:, 0:1])[..., 3:6]
+    spread = np.linalg.norm(d, axis=-1).max(axis=1)
+    assert 1.0 < np.median(spread) and spread.max() < 3.0
+    trips = pr.mean_trips(on.POSE, XX)
+    assert (trips > 2).mean() > 0.5
+    capped = pr.predict_sampled(on.POSE, mu, cov, XX, np.eye(12) * 1e-3, max_it=1)
+    assert np.array_equal(capped["status"] == on.ST_WARN_MEAN_NOCONV, trips >= 1)

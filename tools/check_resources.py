@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Build gate for EVERY shipped kernel instantiation (ukf_kernel16, the generic ukf_kernel, ukf_innovation_kernel, ukf_bank_*_kernel, ukf_smooth_kernel, ukf_forecast_kernel, ukf_lifecycle_*_kernel, ukf_state_meas_kernel, ukf_sensor_meas_kernel, ukf_sampled_kernel, ukf_sigma_points_kernel, ukf_delayed_kernel): no scratch and no AGPRs, and
+"""Build gate for EVERY shipped kernel instantiation (ukf_kernel16, the generic ukf_kernel, ukf_innovation_kernel, ukf_bank_*_kernel, ukf_smooth_kernel, ukf_forecast_kernel, ukf_lifecycle_*_kernel, ukf_state_meas_kernel, ukf_sensor_meas_kernel, ukf_sampled_kernel, ukf_sigma_points_kernel, ukf_predict_sampled_kernel, ukf_delayed_kernel): no scratch and no AGPRs, and
 the tuned kernels keep the wavefronts per SIMD their design counts on (fp64: three, fp32: five) -- a register regression
 that costs a wavefront fails the build instead of showing up as a slower bench line.
 
@@ -38,7 +38,7 @@ def main(paths):
         for k in parse(open(p).read()):
             if "ukf_kernel" not in k["name"] and "ukf_innovation_kernel" not in k["name"] and "ukf_bank_" not in k["name"] \
                     and "ukf_smooth_kernel" not in k["name"] and "ukf_forecast_kernel" not in k["name"] and "ukf_lifecycle_" not in k["name"] and "ukf_state_meas_kernel" not in k["name"] and "ukf_sensor_meas_kernel" not in k["name"] \
-                    and "ukf_sampled_kernel" not in k["name"] and "ukf_sigma_points_kernel" not in k["name"] \
+                    and "ukf_sampled_kernel" not in k["name"] and "ukf_sigma_points_kernel" not in k["name"] and "ukf_predict_sampled_kernel" not in k["name"] \
                     and "ukf_delayed_kernel" not in k["name"]:
                 continue
             rows.append(k)
@@ -74,6 +74,11 @@ def main(paths):
     low = [k for k in rows if ("ukf_sampled_kernel" in k["name"] or "ukf_sigma_points_kernel" in k["name"]) and k.get("occupancy", 0) < 2]
     if low:
         print("ERROR: sampled-update / sigma-point kernels below two wavefronts per SIMD:", [(k["name"], k.get("vgpr")) for k in low])
+        return 1
+    # and the sampled prediction (its launch bound; fp64: 19.6 ... 21.4 KB of LDS per workgroup, fp32 half of it)
+    low = [k for k in rows if "ukf_predict_sampled_kernel" in k["name"] and k.get("occupancy", 0) < 2]
+    if low:
+        print("ERROR: sampled-prediction kernels below two wavefronts per SIMD:", [(k["name"], k.get("vgpr")) for k in low])
         return 1
     # the delayed-measurement kernels: two wavefronts per SIMD in either precision (their launch bound; fp64: 35 ... 38 KB of LDS
     # per workgroup admit four workgroups a compute unit, one wavefront per SIMD resident, fp32 two)

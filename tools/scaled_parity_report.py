@@ -9,9 +9,10 @@
 
     python tools/scaled_parity_report.py --features --cpu [out]   profiles/feature_scaled_parity.txt: the CPU table behind
                                                        M_feat (tests/test_feature_scaled_reference.degenerate_spread), no GPU
-    python tools/scaled_parity_report.py --features [out]         on an MI355X: runs the parity tests of the five feature files and
+    python tools/scaled_parity_report.py --features [out]         on an MI355X: runs the parity tests of the feature files and
                                                        APPENDS, per family, model and mode, the largest distance of every
                                                        block over all their comparisons beside the bound of that comparison
+                                                       (--only=NAME: the files whose name contains NAME, e.g. a new family)
 
 M, M_feat and every bound come from the CPU tables alone; the GPU tables are there to be read beside them."""
 import os
@@ -88,15 +89,19 @@ def features_cpu(out):
     print(text)
 
 
-FEATURE_FILES = ("test_gpu_innovation.py", "test_gpu_bank.py", "test_gpu_smooth.py", "test_gpu_state_meas.py", "test_gpu_sensor_meas.py")
+FEATURE_FILES = ("test_gpu_innovation.py", "test_gpu_bank.py", "test_gpu_smooth.py", "test_gpu_state_meas.py", "test_gpu_sensor_meas.py",
+                 "test_gpu_predict_sampled.py")
+
+
+ONLY = [a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--only=")]   # --only=predict_sampled: that family's file alone
 
 
 def features_gpu(out):
     import pytest
     import feature_scaled_parity as fsp
     del fsp.REPORT[:]
-    rc = pytest.main(["-q", "-m", "gpu", "-p", "no:cacheprovider", "-k", "parity or against_the_reference or agree or mean_iteration_cap"]
-                     + [os.path.join(ROOT, "tests", f) for f in FEATURE_FILES])
+    rc = pytest.main(["-q", "-m", "gpu", "-p", "no:cacheprovider", "-k", "parity or against_the_reference or agree or mean_iteration_cap or several_mean_iterations"]
+                     + [os.path.join(ROOT, "tests", f) for f in FEATURE_FILES if not ONLY or any(o in f for o in ONLY)])
     groups = {}
     for name, mode, kind, rows in fsp.REPORT:   # names are family/model/...
         family, model = name.split("/")[:2]
@@ -107,7 +112,8 @@ def features_gpu(out):
             if old is None or d / b > old[0] / old[1]:
                 g["rows"][label] = (d, b, name)
     lines = ["", "# GPU (MI355X): engine <-> reference, whitened distances beside their bounds (tests/feature_scaled_parity.py), per family,",
-             "# model and mode: of all the comparisons the five feature files make, the one where each block comes closest to its bound",
+             "# model and mode: of all the comparisons the feature files make, the one where each block comes closest to its bound"
+             + (f" (only: {', '.join(ONLY)})" if ONLY else ""),
              f"# M_feat = {fsp.M_FEAT}; pytest exit code {int(rc)}"]
     for (family, model, mode), g in sorted(groups.items()):
         top = max(g["rows"].values(), key=lambda r: r[0] / r[1])
@@ -121,7 +127,7 @@ def features_gpu(out):
 
 
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if a not in ("--cpu", "--features")]
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
     feat = "--features" in sys.argv
     out = args[0] if args else os.path.join(ROOT, "profiles", "feature_scaled_parity.txt" if feat else "scaled_parity.txt")
     if feat:
