@@ -249,6 +249,26 @@ public:
         check(ukfb_predict_sampled(engine, XX, R, r_is_uniform ? 1 : 0, active, commit ? 1 : 0, mu, cov, st.data()));
         return st;
     }
+    /** Covariance conditioning (ukf_batch.h, "covariance conditioning"): the covariance of every selected filter is judged in its
+     *  correlation scaling; one whose smallest correlation eigenvalue is below in.eig_floor / 2, or with a variance below
+     *  in.var_floor_dev [D], is repaired where it lives (UKFB_ST_REPAIRED), a healthy one keeps every bit; with
+     *  in.renormalize_quaternion the stored quaternion is brought back to unit length.  commit = false is read-only (only `out` is
+     *  written).  Stream-ordered. */
+    void conditionDev(const ukfb_condition_in& in, bool commit = true, const ukfb_condition_out* out = NULL)
+    {
+        check(ukfb_condition_dev(engine, &in, commit ? 1 : 0, out));
+    }
+    /** host arrays: var_floor [D] (finite, > 0), select [N] or NULL; eig_min / eig_max [N], mu [N][S], cov [N][D][D] or NULL;
+     *  returns the status */
+    std::vector<uint32_t> condition(const double* var_floor, double eig_floor, const uint8_t* select = NULL,
+                                    bool renormalize_quaternion = false, bool commit = true, double* eig_min = NULL,
+                                    double* eig_max = NULL, double* mu = NULL, double* cov = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_condition(engine, var_floor, eig_floor, select, renormalize_quaternion ? 1 : 0, commit ? 1 : 0, eig_min, eig_max, mu,
+                             cov, st.data()));
+        return st;
+    }
     /** Late samples (ukf_batch.h, "late samples"): a sample taken in.lag steps ago corrects the CURRENT state through the history
      *  ring -- no stored measurements, no replay, no waiting for the slowest sensor.  The window is smoothDev's with the
      *  filters' own state as its last step; commit = false is read-only (only `out` is written, out->mu_out / cov_out showing

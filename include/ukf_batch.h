@@ -96,7 +96,8 @@ enum {
     UKFB_ST_UNINITIALISED = 1u << 7,      /* UnscentedKalmanFilter.hpp:53,59                 */
     UKFB_ST_INACTIVE = 1u << 8,           /* filter masked out of this call                  */
     UKFB_ST_REJECTED_GATE = 1u << 9,      /* mahalanobis gate rejected the update            */
-    UKFB_ST_ERR_WEIGHTS = 1u << 10        /* filter banks: the weights of a track are not a distribution */
+    UKFB_ST_ERR_WEIGHTS = 1u << 10,       /* filter banks: the weights of a track are not a distribution */
+    UKFB_ST_REPAIRED = 1u << 11           /* covariance conditioning: the covariance or the quaternion was repaired */
 };
 
 /* ---- configuration ---------------------------------------------------------------------- */
@@ -999,6 +1000,78 @@ int ukfb_predict_sampled_dev(ukfb_engine* e, const ukfb_predict_sampled_in* in, 
  * [capacity] or NULL; mu [capacity][S], cov [capacity][D][D] (full, symmetric), status [capacity]: any may be NULL */
 int ukfb_predict_sampled(ukfb_engine* e, const double* XX, const double* R, int r_is_uniform, const uint8_t* active,
                          int commit, double* mu /* [capacity][S] */, double* cov /* [capacity][D][D] */, uint32_t* status);
+
+
+/* ---- covariance conditioning: eigenvalue repair of failed filters -------------------------------------------------------- */
+/* A filter whose covariance has stopped being positive definite reports ERR_CHOLESKY, keeps its state, and fails again at the
+ * next call.  This call repairs such filters where they live, without a round trip to the host, and keeps the stored quaternion
+ * on the unit sphere.  Per selected, initialised filter, with the batch-uniform variance floor v [D] > 0 and the correlation
+ * eigenvalue floor eps, 0 < eps < 1:
+ *   1. a non-finite entry in the lower triangle of Sigma: the filter cannot be repaired (ERR_CHOLESKY below);
+ *   2. d_t = Sigma_tt if Sigma_tt >= v_t, else v_t (a comparison of stored numbers); s_t = sqrt(d_t);
+ *   3. C_ij = Sigma_ij / (s_i s_j) for i != j, C_ii = 1: the conditioning is judged in the filter's own sigmas, a position block
+ *      in m^2 and a gyro-bias block in (rad/s)^2 each on its own scale;
+ *   4. C = V Lambda V^T by cyclic Jacobi; eig_min / eig_max = the smallest / largest eigenvalue of C as it came in;
+ *   5. the filter is DEFICIENT iff a diagonal was raised in step 2 or eig_min < eps / 2, else HEALTHY: status 0, nothing of its
+ *      state is written, its covariance output is its input bit for bit;
+ *   6. a deficient filter gets C' = C + sum_{k: lambda_k < eps} (eps - lambda_k) v_k v_k^T (mathematically V max(Lambda, eps)
+ *      V^T; in this additive form the healthy subspace is touched by the rounding of the correction only) and
+ *      Sigma'_ij = s_i s_j C'_ij, formed as the lower triangle and stored packed (symmetric by construction); the diagonal is
+ *      formed as d_i C'_ii with C'_ii = 1 + a sum of non-negative terms, so that it never rounds below the floor.  Status
+ *      REPAIRED.  The eps / 2 trigger and the eps target make the call idempotent: a repaired filter is healthy at the next call
+ *      (as long as no eigenvalue was below eps - 1: the diagonal of C' stays below 2);
+ *   7. with renormalize_quaternion = 1 the orientation quaternion of the mean becomes q / |q|, computed in the kernel's compute
+ *      type (|q|^2 as fma(q3, q3, fma(q2, q2, fma(q1, q1, q0 q0))), q_i * (1 / sqrt(|q|^2))).  RULE: a quaternion with
+ *      | |q|^2 - 1 | <= 8 u, u the unit roundoff of the STORAGE type (2^-24 / 2^-53), is unit to the rounding of the storage
+ *      type and keeps every bit (a unit quaternion rounded to storage is within 2 u, the fp32 evaluation of |q|^2 adds at most
+ *      4 u; a renormalised one is within the rule, so the flag is idempotent too).  A zero or non-finite quaternion is treated
+ *      like step 1.  A filter whose only change is the renormalisation also reports REPAIRED.  Nothing else of the mean is ever
+ *      touched, and with the flag 0 the mean is not touched at all.
+ * JACOBI: round-robin ordering (every pair once per sweep), at most 12 sweeps; converged = the off-diagonal Frobenius norm
+ * (both triangles) is at most 4 D u in front of a sweep, u the unit roundoff of the compute type; a pair with |m_pq| <= u is
+ * not rotated ((m_qq - m_pp) / (2 m_pq) would overflow).  A filter that has not converged after the 12th sweep is treated like
+ * step 1.  tests/condition_reference.py is the same definition in NumPy.
+ * CHOOSING eps: storing Sigma' moves the eigenvalues of its correlation matrix by up to about D u_storage (8e-7 in fp32, 1.4e-15
+ * in fp64).  An eps meant to make the next factorisation succeed should sit two orders above that: 1e-4 for fp32 storage, 1e-10
+ * for fp64.
+ * commit = 1: the covariance of deficient filters, a renormalised quaternion and the engine's own status array are written; out
+ * may be NULL.  commit = 0: READ-ONLY like ukfb_predict_sampled_dev (the kernel is launched without a pointer through which it
+ * could store to the engine), only `out` is written, the same numbers.
+ * Status of THIS call (out->status, and with commit = 1 the engine's status array):
+ *   UNINITIALISED       the filter is uninitialised;
+ *   INACTIVE            select_dev says 0 for this filter;
+ *   ERR_NONFINITE_MEAS  an entry of var_floor_dev is non-finite or not > 0: every selected filter, nothing is conditioned;
+ *   ERR_CHOLESKY        steps 1 and 7 and the sweep cap: the filter cannot be repaired;
+ *   REPAIRED            the covariance (step 6) or the quaternion (step 7) was repaired.
+ * A filter with one of the first four keeps its state bit for bit and writes NaN to its float outputs; a filter that commits
+ * nothing never changes a bit of another filter.  Times, noise tables, input bindings and latches are not touched.
+ * NULL in or var_floor_dev, eig_floor outside (0, 1) or non-finite, commit or renormalize_quaternion outside 0 / 1, or
+ * commit = 0 with nowhere to write: UKFB_ERR_INVALID_ARG, nothing is written.  Stream-ordered, joins split streams, no host
+ * synchronisation, no allocation at call time, capturable.  The same kernel serves every lanes_per_filter setting; fp32 engines
+ * compute in fp32, with wide_arithmetic in fp64 (stored fp32).  Device groups: per shard through ukfb_group_shard. */
+typedef struct ukfb_condition_in {
+    const void* var_floor_dev;      /* [D] engine precision, the variance floor per tangent dimension.  The device call cannot read
+                                       it without synchronising, so it is judged in the kernel: every entry must be finite and > 0,
+                                       else every selected filter reports ERR_NONFINITE_MEAS and keeps its state (the sampled
+                                       calls' treatment of a bad R) */
+    double eig_floor;               /* epsilon, 0 < eps < 1 */
+    const uint8_t* select_dev;      /* [capacity] or NULL = all; 0: the filter is not conditioned (INACTIVE) */
+    int renormalize_quaternion;     /* 0 / 1 */
+} ukfb_condition_in;
+typedef struct ukfb_condition_out { /* device, engine precision, any may be NULL */
+    void* eig_min;     /* [capacity]  of C as it came in */
+    void* eig_max;     /* [capacity] */
+    void* mu;          /* [capacity][S]  the mean after the call */
+    void* cov_packed;  /* [capacity][PK] the covariance after the call, the packed lower triangle of ukfb_device_views */
+    uint32_t* status;  /* [capacity] */
+} ukfb_condition_out;
+int ukfb_condition_dev(ukfb_engine* e, const ukfb_condition_in* in, int commit, const ukfb_condition_out* out);
+/* host arrays of doubles, synchronising: var_floor [D] (an entry that is non-finite or not > 0: UKFB_ERR_INVALID_ARG before
+ * anything is uploaded), select [capacity] or NULL; eig_min / eig_max [capacity], mu [capacity][S], cov [capacity][D][D] (full,
+ * symmetric), status [capacity]: any may be NULL */
+int ukfb_condition(ukfb_engine* e, const double* var_floor /* [D] */, double eig_floor, const uint8_t* select,
+                   int renormalize_quaternion, int commit, double* eig_min, double* eig_max, double* mu,
+                   double* cov /* [capacity][D][D] */, uint32_t* status);
 
 
 /* ---- device groups: one host process, several MI355X ------------------------------------------------------------------ */

@@ -526,6 +526,50 @@ inline SampledGeometry predict_sampled_geometry(int S, int D, int64_t capacity, 
             int(size_t(SAMPLED_FILTERS_PER_GROUP) * predict_sampled_filter_scalars(S, D) * compute_size)};
 }
 
+// ---- covariance conditioning (ukfb_condition_dev) ----------------------------------------------------------------------------
+// Eigenvalue repair of the covariance in its correlation scaling by cyclic Jacobi, round-robin ordering.  The launch is the
+// sampled update's: four filters per workgroup, one wavefront.
+constexpr int CONDITION_FILTERS_PER_GROUP = 4, CONDITION_MAX_SWEEPS = 12, CONDITION_SLICE_PAD = 4;
+// players of the round-robin schedule (D rounded up to even; the odd D is padded with a decoupled unit row), pairs per step and
+// steps per sweep; the first pair of a step is the one that holds the last player: where that player is the padding, the pair is
+// the identity and is dropped
+constexpr int condition_players(int D) { return (D + 1) / 2 * 2; }
+constexpr int condition_first_pair(int D) { return condition_players(D) != D ? 1 : 0; }
+constexpr int condition_pairs_per_step(int D) { return condition_players(D) / 2; }
+constexpr int condition_steps(int D) { return condition_players(D) - 1; }
+inline Verdict check_condition_args(const ukfb_condition_in* in, int commit, const ukfb_condition_out* out) {
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    if (!in->var_floor_dev) return {UKFB_ERR_INVALID_ARG, "var_floor_dev must not be NULL"};
+    if (!(in->eig_floor > 0.0 && in->eig_floor < 1.0)) return {UKFB_ERR_INVALID_ARG, "eig_floor must lie in (0, 1)"};   // (NaN fails both)
+    if (in->renormalize_quaternion != 0 && in->renormalize_quaternion != 1)
+        return {UKFB_ERR_INVALID_ARG, "renormalize_quaternion must be 0 or 1"};
+    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    if (commit == 0 && (!out || (!out->eig_min && !out->eig_max && !out->mu && !out->cov_packed && !out->status)))
+        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
+    return {};
+}
+// the host form's floor: every entry finite and > 0
+inline Verdict check_condition_floor(const double* var_floor, int D) {
+    if (!var_floor) return {UKFB_ERR_INVALID_ARG, "var_floor must not be NULL"};
+    for (int t = 0; t < D; ++t)
+        if (!(var_floor[t] > 0.0 && var_floor[t] <= 1.7976931348623157e308))
+            return {UKFB_ERR_INVALID_ARG, "every entry of var_floor must be finite and > 0"};
+    return {};
+}
+// LDS of one filter, in scalars of the compute type (ukf_condition.hpp, ConditionLayout): the D parked rows of the row phase and
+// the D published rows of V (stride SMOOTH_LS each), the eigenvalues (16), the sigmas s_t (16), the state's record (mean padded
+// to 16, packed covariance padded to even), the sink of lane-predicated stores (16) and CONDITION_SLICE_PAD scalars that keep the
+// four slices of a workgroup off each other's banks in either precision; rounded up to a multiple of four so that every filter's
+// slice starts 16-byte aligned.  Every scalar the kernel reads is one it wrote: the pads are never read.
+constexpr int condition_filter_scalars(int S, int D) {
+    return S > 16 ? -1 : (2 * D * SMOOTH_LS + 16 + 16 + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 16 + CONDITION_SLICE_PAD + 3) / 4 * 4;
+}
+// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
+inline SampledGeometry condition_geometry(int S, int D, int64_t capacity, size_t compute_size) {
+    return {(capacity + CONDITION_FILTERS_PER_GROUP - 1) / CONDITION_FILTERS_PER_GROUP,
+            int(size_t(CONDITION_FILTERS_PER_GROUP) * condition_filter_scalars(S, D) * compute_size)};
+}
+
 // ---- late samples (ukfb_update_delayed_dev, ukfb_delayed_lag_dev) -----------------------------------------------------------
 // The smoother's window with the engine's own state as its last step: the chain runs at most steps - 1 <= SMOOTH_MAX_BACK
 // backward steps, all in one launch (their dt travel in the kernel arguments), so steps <= DELAYED_MAX_STEPS.

@@ -33,6 +33,7 @@ ST_UNINITIALISED = 1 << 7
 ST_INACTIVE = 1 << 8
 ST_REJECTED_GATE = 1 << 9
 ST_ERR_WEIGHTS = 1 << 10   # filter banks: the weights of a track are not a distribution
+ST_REPAIRED = 1 << 11      # covariance conditioning: the covariance or the quaternion was repaired
 
 # every symbol include/ukf_batch.h declares (tests check the library exports all of them)
 EXPORTS = [
@@ -71,6 +72,8 @@ EXPORTS = [
     "ukfb_predict_sampled_dev", "ukfb_predict_sampled",
     # late samples: the delayed-measurement update through the state history
     "ukfb_update_delayed_dev", "ukfb_update_delayed", "ukfb_delayed_lag_dev",
+    # covariance conditioning: eigenvalue repair of failed filters, quaternion renormalisation
+    "ukfb_condition_dev", "ukfb_condition",
     # device groups (one process, several GPUs)
     "ukfb_group_shard_range", "ukfb_group_create", "ukfb_group_destroy", "ukfb_group_size", "ukfb_group_shard",
     "ukfb_group_set_config", "ukfb_group_initialize", "ukfb_group_get_state", "ukfb_group_get_status",
@@ -152,6 +155,17 @@ class PredictSampledIn(C.Structure):
 class PredictSampledOut(C.Structure):
     """ukfb_predict_sampled_out: device pointers in engine precision (status uint32), any may be NULL"""
     _fields_ = [("mu", C.c_void_p), ("cov_packed", C.c_void_p), ("status", C.c_void_p)]
+
+
+class ConditionIn(C.Structure):
+    """ukfb_condition_in: the variance floor [D] as a device pointer in engine precision, the correlation-eigenvalue floor (a host
+    double), select_dev uint8 [capacity] or NULL, the renormalisation flag"""
+    _fields_ = [("var_floor_dev", C.c_void_p), ("eig_floor", C.c_double), ("select_dev", C.c_void_p), ("renormalize_quaternion", C.c_int)]
+
+
+class ConditionOut(C.Structure):
+    """ukfb_condition_out: device pointers in engine precision (status uint32), any may be NULL"""
+    _fields_ = [("eig_min", C.c_void_p), ("eig_max", C.c_void_p), ("mu", C.c_void_p), ("cov_packed", C.c_void_p), ("status", C.c_void_p)]
 
 
 class DelayedIn(C.Structure):
@@ -832,6 +846,36 @@ class BatchUKF:
                                             act.ctypes.data_as(C.POINTER(C.c_uint8)) if act is not None else None,
                                             C.c_int(1 if commit else 0), _pd(o["mu"]), _pd(o["cov"]),
                                             o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_predict_sampled")
+        return o
+
+    # ---- covariance conditioning: var_floor [D], eig_floor in (0, 1)
+    def condition_dev(self, var_floor_dev, eig_floor: float, select_dev=None, renormalize_quaternion: bool = False, commit: bool = True,
+                      eig_min=None, eig_max=None, mu=None, cov_packed=None, status=None):
+        """Eigenvalue repair of every selected filter's covariance in its correlation scaling (include/ukf_batch.h, "covariance
+        conditioning"): var_floor_dev [D] a device buffer in engine precision, eig_floor the floor of the correlation eigenvalues
+        (1e-4 suits fp32 storage, 1e-10 fp64), select_dev uint8 [capacity] or None.  A filter whose smallest correlation
+        eigenvalue is below eig_floor / 2, or one of whose variances is below the floor, is repaired (ST_REPAIRED); a healthy one
+        keeps every bit.  renormalize_quaternion also brings the stored quaternion back to unit length.  commit=False is
+        read-only: only the keyword outputs (device buffers in engine precision: eig_min / eig_max [capacity], mu [capacity, S],
+        cov_packed [capacity, PK]; status uint32 / int32) are written.  Stream-ordered, nothing is allocated."""
+        ptr = lambda x: None if x is None else _devptr(x).value
+        cin = ConditionIn(ptr(var_floor_dev), float(eig_floor), ptr(select_dev), 1 if renormalize_quaternion else 0)
+        out = ConditionOut(ptr(eig_min), ptr(eig_max), ptr(mu), ptr(cov_packed), ptr(status))
+        _chk(self._lib.ukfb_condition_dev(self._h, C.byref(cin), C.c_int(1 if commit else 0), C.byref(out)), "ukfb_condition_dev")
+
+    def condition(self, var_floor, eig_floor: float, select=None, renormalize_quaternion: bool = False, commit: bool = True):
+        """Host arrays: var_floor [D] (every entry finite and > 0), select uint8 [capacity] or None.  Returns a dict of NumPy
+        arrays: eig_min [n], eig_max [n], mu [n, S], cov [n, D, D], status [n]; synchronises"""
+        n, S, D = self.capacity, self.S, self.D
+        v = _f64(var_floor, (D,))
+        sel = np.ascontiguousarray(select, dtype=np.uint8).reshape(n) if select is not None else None
+        o = {"eig_min": np.empty(n), "eig_max": np.empty(n), "mu": np.empty((n, S)), "cov": np.empty((n, D, D)),
+             "status": np.empty(n, dtype=np.uint32)}
+        _chk(self._lib.ukfb_condition(self._h, _pd(v), C.c_double(float(eig_floor)),
+                                      sel.ctypes.data_as(C.POINTER(C.c_uint8)) if sel is not None else None,
+                                      C.c_int(1 if renormalize_quaternion else 0), C.c_int(1 if commit else 0), _pd(o["eig_min"]),
+                                      _pd(o["eig_max"]), _pd(o["mu"]), _pd(o["cov"]),
+                                      o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_condition")
         return o
 
     # ---- late samples: the window of smooth_dev with the engine's own state as its last step

@@ -1,0 +1,125 @@
+// condition_host.cpp -- the host decisions of the covariance conditioning (ukf_host.hpp) on the CPU (g++ under ASan / UBSan,
+// compiled by tests/test_condition_host.py): every refusal, the floor check of the host form, the round-robin schedule's
+// counts, the LDS accounting against hand-computed values for both models, and the launch geometry.
+#include <cmath>
+#include <cstdio>
+#include <limits>
+
+#include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
+
+static int failures = 0;
+#define EXPECT(cond)                                                        \
+    do {                                                                    \
+        if (!(cond)) {                                                      \
+            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
+            ++failures;                                                     \
+        }                                                                   \
+    } while (0)
+
+int main() {
+    using namespace ukfb;
+    double buf[16] = {0};
+    uint32_t word = 0;
+    ukfb_condition_in in{};
+    in.var_floor_dev = buf;
+    in.eig_floor = 1e-4;
+    ukfb_condition_out none{};
+    ukfb_condition_out st_only{};
+    st_only.status = &word;
+    // NULL combinations
+    EXPECT(check_condition_args(nullptr, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_condition_args(nullptr, 1, nullptr).msg != nullptr);
+    {
+        ukfb_condition_in bad = in;
+        bad.var_floor_dev = nullptr;
+        EXPECT(check_condition_args(&bad, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+        // eig_floor in the open interval (0, 1), finite
+        const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+        for (double eps : {0.0, -1e-4, 1.0, 1.5, inf, -inf, nan}) {
+            bad = in;
+            bad.eig_floor = eps;
+            EXPECT(check_condition_args(&bad, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+            EXPECT(check_condition_args(&bad, 0, &st_only).rc == UKFB_ERR_INVALID_ARG);
+        }
+        for (double eps : {1e-300, 1e-10, 1e-4, 0.5, std::nextafter(1.0, 0.0)}) {
+            bad = in;
+            bad.eig_floor = eps;
+            EXPECT(check_condition_args(&bad, 1, nullptr).rc == UKFB_OK);
+        }
+        for (int flag : {2, -1, 7}) {
+            bad = in;
+            bad.renormalize_quaternion = flag;
+            EXPECT(check_condition_args(&bad, 1, nullptr).rc == UKFB_ERR_INVALID_ARG);
+        }
+        bad = in;
+        bad.renormalize_quaternion = 1;
+        EXPECT(check_condition_args(&bad, 1, nullptr).rc == UKFB_OK);
+        const uint8_t sel[4] = {1, 0, 1, 1};   // select_dev NULL: every filter; given: per filter
+        bad.select_dev = sel;
+        EXPECT(check_condition_args(&bad, 1, nullptr).rc == UKFB_OK);
+    }
+    // commit is 0 or 1; a read-only call needs somewhere to write
+    EXPECT(check_condition_args(&in, 2, &st_only).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_condition_args(&in, -1, &st_only).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_condition_args(&in, 0, nullptr).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_condition_args(&in, 0, &none).rc == UKFB_ERR_INVALID_ARG);
+    EXPECT(check_condition_args(&in, 0, &st_only).rc == UKFB_OK);
+    EXPECT(check_condition_args(&in, 1, &none).rc == UKFB_OK);
+    EXPECT(check_condition_args(&in, 1, nullptr).rc == UKFB_OK);
+    for (int which = 0; which < 4; ++which) {
+        ukfb_condition_out o{};
+        (which == 0 ? o.eig_min : which == 1 ? o.eig_max : which == 2 ? o.mu : o.cov_packed) = buf;
+        EXPECT(check_condition_args(&in, 0, &o).rc == UKFB_OK);
+    }
+    // the host form's floor
+    {
+        double v[13];
+        for (double& x : v) x = 1e-6;
+        EXPECT(check_condition_floor(v, 12).rc == UKFB_OK && check_condition_floor(v, 13).rc == UKFB_OK);
+        EXPECT(check_condition_floor(nullptr, 12).rc == UKFB_ERR_INVALID_ARG);
+        const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+        for (double x : {0.0, -0.0, -1e-6, inf, -inf, nan}) {
+            v[12] = x;
+            EXPECT(check_condition_floor(v, 13).rc == UKFB_ERR_INVALID_ARG);
+            EXPECT(check_condition_floor(v, 12).rc == UKFB_OK);   // entry 12 is not the Pose engine's
+            v[12] = 1e-6;
+            v[0] = x;
+            EXPECT(check_condition_floor(v, 12).rc == UKFB_ERR_INVALID_ARG);
+            v[0] = 1e-6;
+        }
+        v[3] = std::numeric_limits<double>::denorm_min();
+        v[4] = std::numeric_limits<double>::max();
+        EXPECT(check_condition_floor(v, 12).rc == UKFB_OK);
+    }
+    // the schedule: D = 12 plays 6 pairs in 11 steps; D = 13 is padded to 14 players, 13 steps, and the padding's pair is dropped
+    EXPECT(condition_players(12) == 12 && condition_steps(12) == 11 && condition_pairs_per_step(12) == 6 && condition_first_pair(12) == 0);
+    EXPECT(condition_players(13) == 14 && condition_steps(13) == 13 && condition_pairs_per_step(13) == 7 && condition_first_pair(13) == 1);
+    EXPECT(condition_steps(12) * (condition_pairs_per_step(12) - condition_first_pair(12)) == 12 * 11 / 2);
+    EXPECT(condition_steps(13) * (condition_pairs_per_step(13) - condition_first_pair(13)) == 13 * 12 / 2);
+    EXPECT(CONDITION_MAX_SWEEPS == 12 && CONDITION_FILTERS_PER_GROUP == 4);
+    // LDS by hand.  Pose (S 13, D 12): 2 * 12 * 14 rows + 3 * 16 + 78 packed + 16 sink + 4 pad = 482 -> 484;
+    // OrientationState (S 14, D 13): 2 * 13 * 14 + 48 + 92 (91 padded to even) + 16 + 4 = 524
+    EXPECT(condition_filter_scalars(13, 12) == (336 + 48 + 78 + 16 + 4 + 3) / 4 * 4 && condition_filter_scalars(13, 12) == 484);
+    EXPECT(condition_filter_scalars(14, 13) == 364 + 48 + 92 + 16 + 4 && condition_filter_scalars(14, 13) == 524);
+    EXPECT(condition_filter_scalars(17, 16) == -1);
+    // (without the pad the fp64 Pose slice would be 480 scalars = 960 dwords, a multiple of 32: four slices on the same banks)
+    EXPECT(((336 + 48 + 78 + 16 + 3) / 4 * 4 * 2) % 32 == 0);
+    struct { int S, D; } models[2] = {{13, 12}, {14, 13}};
+    for (const auto& m : models) {
+        const int sc = condition_filter_scalars(m.S, m.D);
+        EXPECT(sc % 4 == 0 && sc < sampled_filter_scalars(m.S, m.D));
+        for (size_t bytes : {size_t(4), size_t(8)}) {
+            EXPECT((sc * int(bytes)) % 16 == 0);
+            EXPECT((sc * int(bytes) / 4) % 32 != 0);   // the four slices start on different banks
+            EXPECT((SMOOTH_LS * int(bytes)) % 8 == 0); // the parked rows start 8-byte aligned
+            const struct { int64_t n, grid; } cases[] = {{0, 0}, {1, 1}, {3, 1}, {4, 1}, {5, 2}, {1022, 256}, {1048576, 262144}};
+            for (const auto& c : cases) {
+                const SampledGeometry g = condition_geometry(m.S, m.D, c.n, bytes);
+                EXPECT(g.grid == c.grid && g.lds_bytes == int(4 * sc * bytes) && g.lds_bytes <= 65536 && g.lds_bytes % 16 == 0);
+            }
+        }
+    }
+    EXPECT(condition_geometry(13, 12, 1022, 8).lds_bytes == 15488 && condition_geometry(14, 13, 1022, 4).lds_bytes == 8384);
+    std::printf("OK: %d failure(s)\n", failures);
+    return failures ? 1 : 0;
+}

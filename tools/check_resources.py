@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Build gate for EVERY shipped kernel instantiation (ukf_kernel16, the generic ukf_kernel, ukf_innovation_kernel, ukf_bank_*_kernel, ukf_smooth_kernel, ukf_forecast_kernel, ukf_lifecycle_*_kernel, ukf_state_meas_kernel, ukf_sensor_meas_kernel, ukf_sampled_kernel, ukf_sigma_points_kernel, ukf_predict_sampled_kernel, ukf_delayed_kernel): no scratch and no AGPRs, and
+"""Build gate for EVERY shipped kernel instantiation (ukf_kernel16, the generic ukf_kernel, ukf_innovation_kernel, ukf_bank_*_kernel, ukf_smooth_kernel, ukf_forecast_kernel, ukf_lifecycle_*_kernel, ukf_state_meas_kernel, ukf_sensor_meas_kernel, ukf_sampled_kernel, ukf_sigma_points_kernel, ukf_predict_sampled_kernel, ukf_delayed_kernel, ukf_condition_kernel): no scratch and no AGPRs, and
 the tuned kernels keep the wavefronts per SIMD their design counts on (fp64: three, fp32: five) -- a register regression
 that costs a wavefront fails the build instead of showing up as a slower bench line.
 
@@ -39,7 +39,7 @@ def main(paths):
             if "ukf_kernel" not in k["name"] and "ukf_innovation_kernel" not in k["name"] and "ukf_bank_" not in k["name"] \
                     and "ukf_smooth_kernel" not in k["name"] and "ukf_forecast_kernel" not in k["name"] and "ukf_lifecycle_" not in k["name"] and "ukf_state_meas_kernel" not in k["name"] and "ukf_sensor_meas_kernel" not in k["name"] \
                     and "ukf_sampled_kernel" not in k["name"] and "ukf_sigma_points_kernel" not in k["name"] and "ukf_predict_sampled_kernel" not in k["name"] \
-                    and "ukf_delayed_kernel" not in k["name"]:
+                    and "ukf_delayed_kernel" not in k["name"] and "ukf_condition_kernel" not in k["name"]:
                 continue
             rows.append(k)
             if k.get("scratch", 0) or (k.get("agpr", 0) and not allow_agpr):
@@ -85,6 +85,11 @@ def main(paths):
     low = [k for k in rows if "ukf_delayed_kernel" in k["name"] and k.get("occupancy", 0) < 2]
     if low:
         print("ERROR: delayed-measurement kernels below two wavefronts per SIMD:", [(k["name"], k.get("vgpr")) for k in low])
+        return 1
+    # the conditioning kernels (their launch bound; fp64: 15.5 ... 16.8 KB of LDS per workgroup, fp32 half of it)
+    low = [k for k in rows if "ukf_condition_kernel" in k["name"] and k.get("occupancy", 0) < 2]
+    if low:
+        print("ERROR: conditioning kernels below two wavefronts per SIMD:", [(k["name"], k.get("vgpr")) for k in low])
         return 1
     # and the forecast kernels (their launch bound; fp64: 21 ... 23 KB of LDS per workgroup, fp32 half of it)
     low = [k for k in rows if "ukf_forecast_kernel" in k["name"] and k.get("occupancy", 0) < 2]
