@@ -1,6 +1,5 @@
-// ukf_api_common.hpp -- the host plumbing the feature C-ABI files share (ukf_innovation_api.hip, ukf_bank_api.hip,
-// ukf_smooth_api.hip, ukf_forecast_api.hip, ukf_lifecycle_api.hip, ukf_state_meas_api.hip, ukf_sensor_meas_api.hip, ukf_sampled_api.hip, ukf_predict_sampled_api.hip, ukf_delayed_api.hip, ukf_condition_api.hip): the error macro, the argument verdict, the poisoned-engine refusal and the
-// temporaries and copies of the host-array forms.  Not for ukf_batch.hip / ukf_group.hip: their HIP_TRY knows the timed-out
+// ukf_api_common.hpp -- the host plumbing the feature C-ABI files share (every ukf_*_api.hip: the Makefile's FEATURES): the
+// error macro, the argument verdict, the poisoned-engine refusal and the temporaries and copies of the host-array forms.  Not for ukf_batch.hip / ukf_group.hip: their HIP_TRY knows the timed-out
 // wait and their fail has another signature.
 #pragma once
 

@@ -18,8 +18,7 @@
 //  * TS (storage) / T (compute) as in ukf_kernel16: TS = float with T = double is the wide-arithmetic mode.
 #pragma once
 
-#include "ukf_kernel16.hpp"
-#include "ukf_host.hpp"
+#include "ukf_row.hpp"
 
 namespace ukfb {
 
@@ -42,9 +41,6 @@ template <class T, class TS> struct BankArgs {
     uint32_t* status;            // [tracks], may be null
     T Pi[BANK_GROUP_SCALARS];    // mix: transition [M][M], row-major
 };
-
-UKFB_DEV double bank_nan(double) { return __builtin_nan(""); }
-UKFB_DEV float bank_nan(float) { return __builtin_nanf(""); }
 
 // c(theta) of Jr^-1(phi) = I + [phi]x / 2 + c [phi]x^2, as a function of t = theta^2:
 // c = (1 - (theta/2) cot(theta/2)) / t = (sinc(theta/2) - cos(theta/2)) / (t sinc(theta/2)) above t = 0.25: the half-angle form
@@ -195,9 +191,6 @@ UKFB_DEV void bank_mixture(const T* MUL, const T* CVL, T* DEL, int Mh, int l, T 
     }
 }
 
-// the row's OR of a per-lane flag
-UKFB_DEV bool bank_row_any(bool b) { return row_allreduce(b ? 1.0f : 0.0f) != 0.0f; }
-
 // Loads the records of the row's track into LDS, validates it (status bits) and returns the weight of hypothesis l on lane l
 template <class T, class M, class TS>
 UKFB_DEV T bank_stage(const BankArgs<T, TS>& a, int64_t trk, int l, T* MUL, T* CVL, uint32_t& st) {
@@ -214,8 +207,8 @@ UKFB_DEV T bank_stage(const BankArgs<T, TS>& a, int64_t trk, int l, T* MUL, T* C
     if constexpr (sizeof(T) == 8) sum = row_allreduce<3>(sum);
     else sum = row_allreduce(sum);
     st = ST_OK;
-    st |= bank_row_any(uninit) ? ST_UNINITIALISED : 0u;
-    st |= (bank_row_any(wbad) || !(m_abs(sum - T(1)) <= a.sum_tol)) ? ST_ERR_WEIGHTS : 0u;
+    st |= row_any(uninit) ? ST_UNINITIALISED : 0u;
+    st |= (row_any(wbad) || !(m_abs(sum - T(1)) <= a.sum_tol)) ? ST_ERR_WEIGHTS : 0u;
     return wl;
 }
 
@@ -268,7 +261,7 @@ __global__ void __launch_bounds__(64) ukf_bank_combine_kernel(const BankArgs<T, 
     bank_publish<T, M>(ls.OUT, l, ref, acc);
     wsync();
     if (tvalid) {
-        const T nanv = bank_nan(T(0));
+        const T nanv = m_nan<T>();
         if (l < S) a.mu_out[trk * S + l] = TS(bad ? nanv : ls.OUT[l]);
         if (a.cov_out)
             for (int i = l; i < PK; i += 16) a.cov_out[trk * PK + i] = TS(bad ? nanv : ls.OUT[S + i]);
@@ -338,10 +331,6 @@ template <class T, class TS> struct BankWeightArgs {
     TS* w_out;           // [tracks * M] or null
     uint32_t* status;    // [tracks] or null
 };
-UKFB_DEV double bank_exp(double x) { return exp(x); }
-UKFB_DEV float bank_exp(float x) { return expf(x); }
-UKFB_DEV double bank_log(double x) { return log(x); }
-UKFB_DEV float bank_log(float x) { return logf(x); }
 
 template <class T, class TS> __global__ void __launch_bounds__(256) ukf_bank_weights_kernel(const BankWeightArgs<T, TS> a) {
     const int64_t trk = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
@@ -375,11 +364,11 @@ template <class T, class TS> __global__ void __launch_bounds__(256) ukf_bank_wei
             if (a.loglik && pass == 0) v += T(a.loglik[f0 + j]);
             v = (v == v) ? v : ninf;
             d[j] = v - mx;             // <= 0, exactly 0 for the largest
-            e[j] = bank_exp(d[j]);     // exp(-inf) = 0: a dead hypothesis
+            e[j] = m_exp(d[j]);     // exp(-inf) = 0: a dead hypothesis
             sum += e[j];
         }
     }
-    const T ls = bank_log(sum), rs = T(1) / sum;
+    const T ls = m_log(sum), rs = T(1) / sum;
 #pragma unroll
     for (int j = 0; j < BANK_MAX_HYPOTHESES; ++j)
         if (j < Mh) {

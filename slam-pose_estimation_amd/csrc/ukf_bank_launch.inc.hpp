@@ -4,6 +4,7 @@
 
 #include <limits>
 
+#include "ukf_feature_launch.hpp"
 #include "ukf_bank.hpp"
 #include "ukf_bank_req.hpp"
 
@@ -40,9 +41,10 @@ template <class TS, class M, class TC> static int launch_bank_typed(ukfb_engine*
 }
 
 template <class M64, class M32> static int launch_bank_model(ukfb_engine* e, const BankReq& r) {
-    if (e->prec == UKFB_F64) return launch_bank_typed<double, M64, double>(e, r);
-    if (e->cfg.wide_arithmetic) return launch_bank_typed<float, M32, double>(e, r);
-    return launch_bank_typed<float, M32, float>(e, r);
+    return dispatch_precision<M64, M32>(e, [&](auto p) {
+        using P = decltype(p);
+        return launch_bank_typed<typename P::TS, typename P::M, typename P::TC>(e, r);
+    });
 }
 
 template <class TS, class TC> static int launch_bank_weights_typed(ukfb_engine* e, const BankWeightsReq& r) {

@@ -28,7 +28,7 @@
 // Global stores are plain vector stores.  LDS per filter: condition_filter_scalars (ukf_host.hpp).
 #pragma once
 
-#include "ukf_sampled.hpp"
+#include "ukf_row.hpp"
 
 namespace ukfb {
 
@@ -54,7 +54,7 @@ template <class T, class TS> struct ConditionArgs {
 };
 
 template <class M> struct ConditionLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = SMOOTH_LS;
+    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS;
     static constexpr int PKE = (PK + 1) / 2 * 2;
     static constexpr int ROW = 0;                         // D * LS: the rows of M J of a step (the row phase's exchange)
     static constexpr int VPB = ROW + D * LS;              // D * LS: V as every row published it
@@ -71,23 +71,6 @@ template <class M> struct ConditionLayout {
 template <class T> struct CondNum;
 template <> struct CondNum<double> { static constexpr double u = 1.1102230246251565404e-16; };   // 2^-53
 template <> struct CondNum<float> { static constexpr float u = 5.9604644775390625e-8f; };        // 2^-24
-UKFB_DEV double cond_copysign(double m, double s) { return __builtin_copysign(m, s); }
-UKFB_DEV float cond_copysign(float m, float s) { return __builtin_copysignf(m, s); }
-UKFB_DEV double cond_min(double a, double b) { return __builtin_fmin(a, b); }
-UKFB_DEV float cond_min(float a, float b) { return __builtin_fminf(a, b); }
-UKFB_DEV double cond_max(double a, double b) { return __builtin_fmax(a, b); }
-UKFB_DEV float cond_max(float a, float b) { return __builtin_fmaxf(a, b); }
-// min / max over a 16-lane row, the butterflies of row_allreduce(float): every lane of the row ends with the same bits
-template <class T> UKFB_DEV void cond_row_minmax(T& lo, T& hi) {
-    lo = cond_min(lo, dpp_mov<0xB1>(lo));
-    hi = cond_max(hi, dpp_mov<0xB1>(hi));
-    lo = cond_min(lo, dpp_mov<0x4E>(lo));
-    hi = cond_max(hi, dpp_mov<0x4E>(hi));
-    lo = cond_min(lo, dpp_mov<0x141>(lo));
-    hi = cond_max(hi, dpp_mov<0x141>(hi));
-    lo = cond_min(lo, dpp_mov<0x140>(lo));
-    hi = cond_max(hi, dpp_mov<0x140>(hi));
-}
 
 // The round-robin schedule (the circle method): DP = D rounded up to even players, player DP - 1 fixed, the others rotating; step
 // r = 0 ... DP - 2 plays (DP - 1, r) and ((r + k) mod (DP - 1), (r - k) mod (DP - 1)), k = 1 ... DP / 2 - 1.  Every pair of
@@ -125,7 +108,7 @@ template <int R, class T, int D, int LS> UKFB_DEV void cond_jacobi_step(T (&Mr)[
         const bool rot = m_abs(x) > guard;   // (NaN: no rotation)
         const T xs = rot ? x : T(1);
         const T th = (b - a) / (T(2) * xs);
-        const T t = cond_copysign(T(1), th) / (m_abs(th) + m_sqrt(fma(th, th, T(1))));
+        const T t = m_copysign(T(1), th) / (m_abs(th) + m_sqrt(fma(th, th, T(1))));
         const T cc = T(1) / m_sqrt(fma(t, t, T(1)));
         c = rot ? cc : T(1);
         s = rot ? t * cc : T(0);
@@ -156,18 +139,19 @@ template <int R, class T, int D, int LS> UKFB_DEV void cond_jacobi_step(T (&Mr)[
 
 // (the second bound: wavefronts per SIMD the register allocator must leave room for)
 template <class T, class M, class TS>
-__global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_condition_kernel(const ConditionArgs<T, TS> a) {
+__global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_condition_kernel(const ConditionArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, Q = MT<M>::Q;
     using LY = ConditionLayout<M>;
     using SC = CondSchedule<D>;
     constexpr int LS = LY::LS;
     extern __shared__ __attribute__((aligned(16))) unsigned char cnd_smem[];
 
+    // (RowCoords' statements in place: built on it, this kernel left the spread of the parent's own runs -- profiles/row_toolkit_rates.txt)
     const int lane = threadIdx.x, g = lane >> 4, l = lane & 15;
     const int lr = (l < D) ? l : (D - 1), ls = (l < S) ? l : (S - 1);
-    const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * CONDITION_FILTERS_PER_GROUP;
+    const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * ROW_FILTERS_PER_GROUP;
     const int64_t n_here = a.n - wg0;
-    const int n_wg = int(n_here < CONDITION_FILTERS_PER_GROUP ? n_here : int64_t(CONDITION_FILTERS_PER_GROUP));
+    const int n_wg = int(n_here < ROW_FILTERS_PER_GROUP ? n_here : int64_t(ROW_FILTERS_PER_GROUP));
     const bool fvalid = g < n_wg;
     const int64_t f = wg0 + (fvalid ? g : (n_wg - 1));   // rows beyond the batch repeat its last filter and store nothing
     T* const base = reinterpret_cast<T*>(cnd_smem) + g * LY::PF;
@@ -177,7 +161,7 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_condition_kernel
     // ---- the row's filter: the state to LDS, the lower triangle judged on the way; the floor judged where it lies
     const bool live = fvalid && a.initialised[f] != 0;
     const bool sel = !a.select || a.select[f] != 0;
-    MUF[l] = T(a.mu[f * S + ls]);
+    MUF[l] = T(a.mu[f * S + ls]);   // (not row_stage_state: the packed covariance is judged on the way)
     const T vfl = T(a.var_floor[lr]);
     bool nonfin, floor_bad;
     {
@@ -187,8 +171,8 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_condition_kernel
             b = b || !m_finite(v);
             PKF[i] = v;
         }
-        nonfin = bank_row_any(b);
-        floor_bad = bank_row_any(!pos_finite(vfl));
+        nonfin = row_any(b);
+        floor_bad = row_any(!pos_finite(vfl));
     }
     wsync();
     UKFB_MARK("c_scale");
@@ -197,7 +181,7 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_condition_kernel
     const bool raised_l = dl_in < vfl;
     const T d_l = raised_l ? vfl : dl_in, s_l = m_sqrt(d_l);
     SDV[lr] = s_l;
-    const bool raised = bank_row_any(raised_l);
+    const bool raised = row_any(raised_l);
     // ---- the quaternion of the mean, on every lane of the row
     T qrn = T(1);
     bool qbad = false, qmove = false;
@@ -244,7 +228,7 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_condition_kernel
                 off2 = fma(t, t, off2);
                 dg = (lr == j) ? Mr[j] : dg;
             }
-            off2 = sampled_row_sum(off2);
+            off2 = row_sum(off2);
             const bool newly = !done && (off2 <= thr2);   // (NaN fails the comparison)
             {
                 const bool pub = newly && l < D;
@@ -269,7 +253,7 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_condition_kernel
         emax = emin;
         emin = good ? emin : T(0);
         emax = good ? emax : T(0);
-        cond_row_minmax(emin, emax);
+        row_minmax(emin, emax);
     }
     const bool fix = good && (raised || emin < T(0.5) * a.eig_floor);
     const bool rq = good && qmove;

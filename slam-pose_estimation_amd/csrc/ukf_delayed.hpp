@@ -29,7 +29,10 @@
 // LDS per filter: delayed_filter_scalars (ukf_host.hpp) -- the smoother's slice and the rows of M behind it.
 #pragma once
 
-#include "ukf_sensor_meas.hpp"
+#include "ukf_row.hpp"
+#include "ukf_bank.hpp"          // bank_jrinv_coeff
+#include "ukf_smooth.hpp"        // SmoothLayout: the slice is the smoother's, widened
+#include "ukf_sensor_meas.hpp"   // sensor_solve3
 
 namespace ukfb {
 
@@ -75,7 +78,7 @@ template <class T, class TS> struct DelayedArgs {
 
 template <class M> struct DelayedLayout {
     using SL = SmoothLayout<M>;
-    static constexpr int S = M::S, D = M::D, LS = SMOOTH_LS, ZS = 4;
+    static constexpr int S = M::S, D = M::D, LS = ROW_LS, ZS = 4;
     static constexpr int MOP = SL::PF;                    // D * LS: the operator M, row l at MOP + l * LS
     static constexpr int WT = SL::TAB, YM = SL::TAB + D * ZS, YN = SL::TAB + 2 * D * ZS;   // D x 3 matrices in the dead delta table
     static constexpr int PF = (MOP + D * LS + 3) / 4 * 4;
@@ -122,9 +125,9 @@ template <class T, class M, class TS> struct DelayedRow {
         l = lane & 15;
         lr = (l < M::D) ? l : (M::D - 1);
         ls = (l < M::S) ? l : (M::S - 1);
-        const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * DELAYED_FILTERS_PER_GROUP;
+        const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * ROW_FILTERS_PER_GROUP;
         const int64_t n_here = a.n - wg0;
-        const int n_wg = int(n_here < DELAYED_FILTERS_PER_GROUP ? n_here : int64_t(DELAYED_FILTERS_PER_GROUP));
+        const int n_wg = int(n_here < ROW_FILTERS_PER_GROUP ? n_here : int64_t(ROW_FILTERS_PER_GROUP));
         fvalid = g < n_wg;
         f = wg0 + (fvalid ? g : (n_wg - 1));   // rows beyond the batch repeat its last filter and store nothing
         live = fvalid && a.initialised[f] != 0;
@@ -159,10 +162,12 @@ template <class T, class M, class TS> struct DelayedSample {
     }
 };
 
-// (the second bound: wavefronts per SIMD the register allocator must leave room for -- the LDS slices admit no more in fp64)
-template <class T> constexpr int delayed_waves() { return 2; }
+// The row's coordinates above, the factorisations and the two commits below are the statements of RowCoords, row_factorise and
+// row_apply_delta (ukf_row.hpp) in place: called from here they change this kernel's instruction mix (branch layout, lane
+// reads) and the fp32 instantiation left the spread of the parent's own runs (profiles/row_toolkit_rates.txt), so it keeps them
+// as it was tuned.
 template <class T, class M, class TS>
-__global__ void __launch_bounds__(64, (delayed_waves<T>())) ukf_delayed_kernel(const DelayedArgs<T, TS> a) {
+__global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_delayed_kernel(const DelayedArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
     using LY = DelayedLayout<M>;
     constexpr int LS = LY::LS, ZS = LY::ZS, Q = MT<M>::Q, RT = MT<M>::RT;
@@ -243,7 +248,7 @@ __global__ void __launch_bounds__(64, (delayed_waves<T>())) ukf_delayed_kernel(c
                 load_row<T, D>(PKF, l, arow);
                 const T rs = chol16<T, D, LS>(arow, FAC, l, ok1);
                 wsync();
-                sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);
+                row_scale_factor<T, D, LS>(FAC, RSP, l, rs);
                 T col[D];
                 load_column<T, D, LS>(FAC, l, T(1), col);
                 sigma_pair<T, M>(mu_r, col, xp, xm);
@@ -262,8 +267,8 @@ __global__ void __launch_bounds__(64, (delayed_waves<T>())) ukf_delayed_kernel(c
                 int it = 0;
                 while (wave_any(active)) {
                     T dp[D], dm[D];
-                    sm_boxminus<T, M>(xp, ref, dp);
-                    sm_boxminus<T, M>(xm, ref, dm);
+                    row_boxminus<T, M>(xp, ref, dp);
+                    row_boxminus<T, M>(xm, ref, dm);
 #pragma unroll
                     for (int c = 0; c < D; ++c) dp[c] = fma(wm, dm[c], wp * dp[c]);
                     row_allreduce_n<T, D>(dp);
@@ -274,7 +279,7 @@ __global__ void __launch_bounds__(64, (delayed_waves<T>())) ukf_delayed_kernel(c
                         m2 = fma(dp[c], dp[c], m2);
                     }
                     T nr[S];
-                    sm_boxplus<T, M>(ref, dp, nr);
+                    row_boxplus<T, M>(ref, dp, nr);
 #pragma unroll
                     for (int s = 0; s < S; ++s) ref[s] = active ? nr[s] : ref[s];
                     const bool more = m2 > a.mean_tol * a.mean_tol;
@@ -284,10 +289,10 @@ __global__ void __launch_bounds__(64, (delayed_waves<T>())) ukf_delayed_kernel(c
                     active = active && more && !capped;
                 }
             }
-            sm_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, ref);
+            row_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, ref);
             wsync();
             T sm[D];
-            sm_table_row<T, D, LS>(TAB, N, lr, sm);
+            row_table_row<T, D, LS>(TAB, N, lr, sm);
             sfence();
 #pragma unroll
             for (int c = 0; c < D; ++c) SMR[lr * LS + c] = sm[c];
@@ -327,7 +332,7 @@ __global__ void __launch_bounds__(64, (delayed_waves<T>())) ukf_delayed_kernel(c
                     for (int c = 0; c < D; ++c) tmp[c] = SMR[lr * LS + c];
                     const T rs = chol16<T, D, LS>(tmp, FAC, l, ok2);
                     wsync();
-                    sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);
+                    row_scale_factor<T, D, LS>(FAC, RSP, l, rs);
                 }
                 ok1 = ok1 && ok2;
 #pragma unroll
@@ -362,7 +367,7 @@ __global__ void __launch_bounds__(64, (delayed_waves<T>())) ukf_delayed_kernel(c
                     cs[s] = CSM[s];
                     mp[s] = MUP[s];
                 }
-                sm_boxminus<T, M>(cs, mp, e);
+                row_boxminus<T, M>(cs, mp, e);
             }
             const int li = lr - RT;
             const bool inrot = li >= 0 && li < 3;
@@ -493,17 +498,17 @@ __global__ void __launch_bounds__(64, (delayed_waves<T>())) ukf_delayed_kernel(c
 #pragma unroll
                 for (int s2 = 0; s2 < S; ++s2) mu_r[s2] = MUF[s2];
                 sfence();
-                sm_boxplus<T, M>(mu_r, del, mnew);
-                sm_boxplus<T, M>(mu_r, dpl, xp);
-                sm_boxplus<T, M>(mu_r, dmi, xm);
-                sm_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, mnew);
+                row_boxplus<T, M>(mu_r, del, mnew);
+                row_boxplus<T, M>(mu_r, dpl, xp);
+                row_boxplus<T, M>(mu_r, dmi, xm);
+                row_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, mnew);
             }
             wsync();
-            sm_table_row<T, D, LS>(TAB, 2 * D, lr, sg);
+            row_table_row<T, D, LS>(TAB, 2 * D, lr, sg);
             bool inf = false;   // (the chain must stay finite: an Inf that the factorisations let through would poison M)
 #pragma unroll
             for (int c = 0; c < D; ++c) inf = inf || !m_finite(sg[c]);
-            const bool good = dof && ok1 && ok3 && !bank_row_any(inf);
+            const bool good = dof && ok1 && ok3 && !row_any(inf);
             st |= (dof && !good) ? ST_ERR_CHOLESKY : 0u;
             st |= (dof && good && !conv) ? ST_WARN_MEAN_NOCONV : 0u;
             chain_ok = chain_ok && !(dof && !good);   // a broken chain refuses the sample
@@ -550,7 +555,7 @@ __global__ void __launch_bounds__(64, (delayed_waves<T>())) ukf_delayed_kernel(c
         load_row<T, D>(CSP, l, arow);
         const T rs = chol16<T, D, LS>(arow, FAC, l, ok1);
         wsync();
-        sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);   // the scaled columns stay: C_z and the retrodiction's solves read them
+        row_scale_factor<T, D, LS>(FAC, RSP, l, rs);   // the scaled columns stay: C_z and the retrodiction's solves read them
         T col[D];
         load_column<T, D, LS>(FAC, l, T(1), col);
         sigma_pair<T, M>(mu_r, col, xp, xm);          // lanes >= D: the centre twice
@@ -758,17 +763,17 @@ __global__ void __launch_bounds__(64, (delayed_waves<T>())) ukf_delayed_kernel(c
 #pragma unroll
         for (int s2 = 0; s2 < S; ++s2) mu_r[s2] = MUF[s2];
         sfence();
-        sm_boxplus<T, M>(mu_r, del, mnew);
-        sm_boxplus<T, M>(mu_r, dpl, xp);
-        sm_boxplus<T, M>(mu_r, dmi, xm);
-        sm_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, mnew);
+        row_boxplus<T, M>(mu_r, del, mnew);
+        row_boxplus<T, M>(mu_r, dpl, xp);
+        row_boxplus<T, M>(mu_r, dmi, xm);
+        row_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, mnew);
     }
     wsync();
-    sm_table_row<T, D, LS>(TAB, 2 * D, lr, sg);
+    row_table_row<T, D, LS>(TAB, 2 * D, lr, sg);
     bool inf = false;
 #pragma unroll
     for (int c = 0; c < D; ++c) inf = inf || !m_finite(sg[c]);
-    const bool fin = !bank_row_any(inf);
+    const bool fin = !row_any(inf);
     const bool okc = chain_ok && ok1 && ok2 && (!accept || (ok3 && fin));
     const bool good = do_u && okc && accept;
     st |= !fvalid ? ST_OK : (!live ? ST_UNINITIALISED : (smp.inactive ? ST_INACTIVE : (smp.old ? ST_ERR_NEG_DT : (smp.bad ? ST_ERR_NONFINITE_MEAS : ST_OK))));
@@ -778,6 +783,7 @@ __global__ void __launch_bounds__(64, (delayed_waves<T>())) ukf_delayed_kernel(c
 
     UKFB_MARK("d_store");
     // ---- the new state through LDS (the records are dead), then whole rows of the packed arrays
+    // (in place in every kernel: as a shared function the block spilled to scratch, which the build gate refuses)
     {
         T v = mnew[0];
 #pragma unroll

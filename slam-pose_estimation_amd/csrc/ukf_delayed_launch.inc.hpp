@@ -2,6 +2,7 @@
 // The three instantiations of a model: fp64, fp32, fp32 arrays with fp64 arithmetic (wide_arithmetic).
 #pragma once
 
+#include "ukf_feature_launch.hpp"
 #include "ukf_delayed.hpp"
 #include "ukf_delayed_req.hpp"
 
@@ -61,9 +62,10 @@ template <class TS, class M, class TC> static int launch_delayed_typed(ukfb_engi
 }
 
 template <class M64, class M32> static int launch_delayed_model(ukfb_engine* e, const DelayedReq& r) {
-    if (e->prec == UKFB_F64) return launch_delayed_typed<double, M64, double>(e, r);
-    if (e->cfg.wide_arithmetic) return launch_delayed_typed<float, M32, double>(e, r);
-    return launch_delayed_typed<float, M32, float>(e, r);
+    return dispatch_precision<M64, M32>(e, [&](auto p) {
+        using P = decltype(p);
+        return launch_delayed_typed<typename P::TS, typename P::M, typename P::TC>(e, r);
+    });
 }
 
 }  // namespace ukfb

@@ -6,8 +6,8 @@
 //  * chain residency: the start record is loaded once; the chain (mean, packed covariance) stays in LDS in the compute type
 //    between the steps of a launch; per step only the inputs come in from HBM and only one record leaves, narrowed TS(...) once
 //    at its store.  The chain itself is never narrowed.
-//  * the step is the smoother's phase 1 with its device functions in its order (chol16, sm_scale_factor, load_column,
-//    sigma_pair, process_fast, the iterated mean, sm_publish_deltas, sm_table_row, process_noise_entry16): lane l < D owns the
+//  * the step is the smoother's phase 1 with the row toolkit's device functions (ukf_row.hpp) in its order (row_factorise, load_column,
+//    sigma_pair, process_fast, the iterated mean, row_publish_deltas, row_table_row, process_noise_entry16): lane l < D owns the
 //    sigma pair of factor column l, lane D the centre, and afterwards row l of Sigma^-, whose lower triangle goes to the chain.
 //    No cross-covariance, no solve, no transport, no applyDelta.
 //  * the time step of a row: dt[c] by value, or (ts form) from the step's stamp and the row's SHADOW last measurement time,
@@ -19,7 +19,7 @@
 // delta table, the chain record, the rotation matrix, a sink.
 #pragma once
 
-#include "ukf_smooth.hpp"
+#include "ukf_row.hpp"
 
 namespace ukfb {
 
@@ -49,7 +49,7 @@ template <class T, class TS> struct ForecastArgs {
 };
 
 template <class M> struct ForecastLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = SMOOTH_LS;
+    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS;
     static constexpr int PKE = (PK + 1) / 2 * 2;
     static constexpr int FAC = 0;                         // D * LS factor columns (later the rows of Sigma^-), then 16 reciprocal pivots
     static constexpr int RSP = FAC + D * LS;
@@ -72,17 +72,10 @@ template <class T, class M, class TS> struct ForecastRow {
     T *FAC, *RSP, *TAB, *CSM, *CSP, *ROT, *DUMP;
     const TS *Rn, *Racc;
     UKFB_DEV ForecastRow(const ForecastArgs<T, TS>& a, unsigned char* smem, int lane) {
-        const int g = lane >> 4;
-        l = lane & 15;
-        lr = (l < M::D) ? l : (M::D - 1);
-        ls = (l < M::S) ? l : (M::S - 1);
-        const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * FORECAST_FILTERS_PER_GROUP;
-        const int64_t n_here = a.n - wg0;
-        const int n_wg = int(n_here < FORECAST_FILTERS_PER_GROUP ? n_here : int64_t(FORECAST_FILTERS_PER_GROUP));
-        fvalid = g < n_wg;
-        f = wg0 + (fvalid ? g : (n_wg - 1));
+        const RowCoords<M> rc(a.n, lane);
+        l = rc.l; lr = rc.lr; ls = rc.ls; fvalid = rc.fvalid; f = rc.f;
         live = fvalid && a.initialised[f] != 0;
-        T* const base = reinterpret_cast<T*>(smem) + g * LY::PF;
+        T* const base = row_slice<T, LY::PF>(smem, rc.g);
         FAC = base + LY::FAC; RSP = base + LY::RSP; TAB = base + LY::TAB; CSM = base + LY::CSM; CSP = base + LY::CSP;
         ROT = base + LY::ROT; DUMP = base + LY::DUM;
         Rn = a.Rn + f * a.Rn_stride;
@@ -92,7 +85,7 @@ template <class T, class M, class TS> struct ForecastRow {
 
 // (the second bound: wavefronts per SIMD the register allocator must leave room for)
 template <class T, class M, class TS>
-__global__ void __launch_bounds__(64, 2) ukf_forecast_kernel(const ForecastArgs<T, TS> a) {
+__global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_forecast_kernel(const ForecastArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
     using LY = ForecastLayout<M>;
     constexpr int LS = LY::LS;
@@ -168,11 +161,7 @@ __global__ void __launch_bounds__(64, 2) ukf_forecast_kernel(const ForecastArgs<
             }
             bool ok;
             {
-                T arow[D];
-                load_row<T, D>(CSP, l, arow);
-                const T rs = chol16<T, D, LS>(arow, FAC, l, ok);
-                wsync();
-                sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);
+                ok = row_factorise<T, D, LS>(CSP, FAC, RSP, l);
                 T col[D];
                 load_column<T, D, LS>(FAC, l, T(1), col);
                 sigma_pair<T, M>(mu_r, col, xp, xm);          // lanes >= D: the centre twice (their column is zero)
@@ -193,8 +182,8 @@ __global__ void __launch_bounds__(64, 2) ukf_forecast_kernel(const ForecastArgs<
                 int it = 0;
                 while (wave_any(active)) {
                     T dp[D], dm[D];
-                    sm_boxminus<T, M>(xp, ref, dp);
-                    sm_boxminus<T, M>(xm, ref, dm);
+                    row_boxminus<T, M>(xp, ref, dp);
+                    row_boxminus<T, M>(xm, ref, dm);
 #pragma unroll
                     for (int c = 0; c < D; ++c) dp[c] = fma(wm, dm[c], wp * dp[c]);
                     row_allreduce_n<T, D>(dp);
@@ -205,7 +194,7 @@ __global__ void __launch_bounds__(64, 2) ukf_forecast_kernel(const ForecastArgs<
                         m2 = fma(dp[c], dp[c], m2);
                     }
                     T nr[S];
-                    sm_boxplus<T, M>(ref, dp, nr);
+                    row_boxplus<T, M>(ref, dp, nr);
 #pragma unroll
                     for (int s = 0; s < S; ++s) ref[s] = active ? nr[s] : ref[s];
                     const bool more = m2 > a.mean_tol * a.mean_tol;
@@ -216,12 +205,12 @@ __global__ void __launch_bounds__(64, 2) ukf_forecast_kernel(const ForecastArgs<
                 }
             }
             UKFB_MARK("f_deltas");
-            sm_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, ref);
+            row_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, ref);
             wsync();   // (the factor is dead: every lane has its column)
             // Sigma^- = 1/2 sum delta delta^T + R: row lr, parked in the factor region while the noise is added entry by entry
             {
                 T sm[D];
-                sm_table_row<T, D, LS>(TAB, N, lr, sm);
+                row_table_row<T, D, LS>(TAB, N, lr, sm);
                 sfence();
 #pragma unroll
                 for (int c = 0; c < D; ++c) FAC[lr * LS + c] = sm[c];   // (lanes >= D: row D - 1's own bits again)

@@ -199,6 +199,20 @@ inline Verdict check_select_args(int engine_model, bool per_filter_models, int m
     return {};
 }
 
+// ---- the row layout of the feature kernels (ukf_row.hpp) ---------------------------------------------------------------------
+// One filter per 16-lane row, ROW_FILTERS_PER_GROUP rows per workgroup (one wavefront), every filter with a slice of the
+// workgroup's dynamic LDS; ROW_LS: the stride of the columns of a factor and of the rows of a delta table in that slice.
+constexpr int ROW_LS = 14, ROW_FILTERS_PER_GROUP = 4;
+struct RowGeometry {
+    int64_t grid;    // workgroups of four filters
+    int lds_bytes;   // dynamic LDS of a workgroup
+};
+// filter_scalars: LDS of one filter in scalars of the compute type (the *_filter_scalars functions below); compute_size: bytes
+// of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
+inline RowGeometry row_geometry(int filter_scalars, int64_t capacity, size_t compute_size) {
+    return {(capacity + ROW_FILTERS_PER_GROUP - 1) / ROW_FILTERS_PER_GROUP, int(size_t(ROW_FILTERS_PER_GROUP) * filter_scalars * compute_size)};
+}
+
 // ---- filter banks (ukfb_bank_weights_dev, ukfb_bank_combine_dev, ukfb_bank_mix_dev) ---------------------------------------
 // An engine of `capacity` filters read as capacity / M tracks of M hypotheses, track-major (hypothesis j of track t = filter
 // t * M + j).  One track per 16-lane row, four per wavefront, one wavefront per workgroup (ukf_bank.hpp).
@@ -248,7 +262,7 @@ inline BankGeometry bank_geometry(int S, int D, int hypotheses, int64_t capacity
 // A window of `steps` consecutive slots of a ring of `slots`, oldest first: step c lives in slot (first_slot + c) % slots.  The
 // backward pass has steps - 1 steps; a launch covers at most SMOOTH_MAX_BACK of them (their dt travel in the kernel arguments)
 // and the next launch starts from the smoothed record the previous one stored.
-constexpr int SMOOTH_MAX_BACK = 32, SMOOTH_LS = 14, SMOOTH_FILTERS_PER_GROUP = 4;
+constexpr int SMOOTH_MAX_BACK = 32, SMOOTH_LS = ROW_LS, SMOOTH_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
 inline Verdict check_history_args(int slots, int slot, bool has_mu_hist, bool has_cov_hist) {
     if (slots < 1 || slot < 0 || slot >= slots) return {UKFB_ERR_INVALID_ARG, "slots >= 1, 0 <= slot < slots"};
     if (!has_mu_hist || !has_cov_hist) return {UKFB_ERR_INVALID_ARG, "mu_hist and cov_hist must not be NULL"};
@@ -283,21 +297,14 @@ struct SmoothPlan {
 constexpr int smooth_filter_scalars(int S, int D) {
     return S > 16 ? -1 : 2 * D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 2 * (16 + (D * (D + 1) / 2 + 1) / 2 * 2) + 10 + 16 + 16;
 }
-struct SmoothGeometry {
-    int64_t grid;    // workgroups of four filters
-    int lds_bytes;   // dynamic LDS of a workgroup
-};
-// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
-inline SmoothGeometry smooth_geometry(int S, int D, int64_t capacity, size_t compute_size) {
-    return {(capacity + SMOOTH_FILTERS_PER_GROUP - 1) / SMOOTH_FILTERS_PER_GROUP,
-            int(size_t(SMOOTH_FILTERS_PER_GROUP) * smooth_filter_scalars(S, D) * compute_size)};
-}
+using SmoothGeometry = RowGeometry;
+inline RowGeometry smooth_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(smooth_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- forecast (ukfb_forecast_dev) -------------------------------------------------------------------------------------------
 // `steps` predictions chained from a start record into a window of a ring of `slots`: step c lives in slot
 // (first_slot + c) % slots.  One launch: the time steps (or stamps) of all steps travel in the kernel arguments, so a call
 // covers at most FORECAST_MAX_STEPS of them and a longer horizon is chained by the caller.
-constexpr int FORECAST_MAX_STEPS = UKFB_FORECAST_MAX_STEPS, FORECAST_FILTERS_PER_GROUP = 4;
+constexpr int FORECAST_MAX_STEPS = UKFB_FORECAST_MAX_STEPS, FORECAST_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
 inline Verdict check_forecast_args(int steps, int slots, int first_slot, bool has_dt, bool has_ts, bool has_start_mu, bool has_start_cov,
                                    bool has_mu_out) {
     if (slots < 1 || steps < 1) return {UKFB_ERR_INVALID_ARG, "steps >= 1, slots >= 1"};
@@ -319,20 +326,13 @@ constexpr int forecast_filter_scalars(int S, int D) {
     return S > 16 ? -1
                   : (D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 10 + 16 + FORECAST_SLICE_PAD + 3) / 4 * 4;
 }
-struct ForecastGeometry {
-    int64_t grid;    // workgroups of four filters
-    int lds_bytes;   // dynamic LDS of a workgroup
-};
-// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
-inline ForecastGeometry forecast_geometry(int S, int D, int64_t capacity, size_t compute_size) {
-    return {(capacity + FORECAST_FILTERS_PER_GROUP - 1) / FORECAST_FILTERS_PER_GROUP,
-            int(size_t(FORECAST_FILTERS_PER_GROUP) * forecast_filter_scalars(S, D) * compute_size)};
-}
+using ForecastGeometry = RowGeometry;
+inline RowGeometry forecast_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(forecast_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- joint state-block measurements (ukfb_update_state_dev) --------------------------------------------------------------
 // A measurement is a sub-manifold of the state: the compound of the blocks a mask selects, in state order.  Every block but the
 // OrientationState's gravity has three tangent dimensions, so tangent dimension t belongs to block t / 3 in both models.
-constexpr int STATE_MEAS_FILTERS_PER_GROUP = 4;
+constexpr int STATE_MEAS_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
 constexpr int state_meas_blocks(int engine_model) { return engine_model == UKFB_MODEL_POSE ? 4 : 5; }
 constexpr bool state_meas_mask_ok(int blocks, int64_t mask) { return mask > 0 && (mask >> blocks) == 0; }
 // tangent dimensions of a mask (D: 12 / 13; the last block of OrientationState has one)
@@ -363,15 +363,8 @@ inline Verdict check_state_meas_args(int engine_model, bool per_filter_masks, ui
 constexpr int state_meas_filter_scalars(int S, int D) {
     return S > 16 ? -1 : (D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 2 * (16 + (D * (D + 1) / 2 + 1) / 2 * 2) + 16 + 3) / 4 * 4;
 }
-struct StateMeasGeometry {
-    int64_t grid;    // workgroups of four filters
-    int lds_bytes;   // dynamic LDS of a workgroup
-};
-// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
-inline StateMeasGeometry state_meas_geometry(int S, int D, int64_t capacity, size_t compute_size) {
-    return {(capacity + STATE_MEAS_FILTERS_PER_GROUP - 1) / STATE_MEAS_FILTERS_PER_GROUP,
-            int(size_t(STATE_MEAS_FILTERS_PER_GROUP) * state_meas_filter_scalars(S, D) * compute_size)};
-}
+using StateMeasGeometry = RowGeometry;
+inline RowGeometry state_meas_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(state_meas_filter_scalars(S, D), capacity, compute_size); }
 // A base::samples::RigidBodyState record (49 scalars: position, orientation x y z w, velocity, angular velocity, then the four
 // 3 x 3 covariances in that order) as a Pose measurement: z = the record's first 13 scalars as they are, Qz = the four blocks
 // on the diagonal of a 12 x 12 matrix (row-major), zero elsewhere
@@ -386,7 +379,7 @@ inline void body_state_to_measurement(const double* rec, double* z, double* Qz) 
 // ---- sensor-frame measurements (ukfb_update_sensor_dev) -------------------------------------------------------------------
 // Measurement models with a mount (lever arm r, sensor -> body rotation qs) and / or a nav-frame point b: ids 0 ... 4 are the
 // Pose engine's, 5 ... 7 the OrientationState engine's (UKFB_SENSOR_*).  Bit id of each set: the model reads that input.
-constexpr int SENSOR_MODELS = 8, SENSOR_FILTERS_PER_GROUP = 4;
+constexpr int SENSOR_MODELS = 8, SENSOR_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
 constexpr unsigned SENSOR_READS_LEVER = 0x2fu;      // POSE_POSITION, POSE_RANGE, POSE_POINT, POSE_VELOCITY, ORIENT_VELOCITY
 constexpr unsigned SENSOR_READS_ROTATION = 0x6cu;   // POSE_POINT, POSE_VELOCITY, ORIENT_VELOCITY, ORIENT_NAV_VECTOR
 constexpr unsigned SENSOR_READS_POINT = 0x46u;      // POSE_RANGE, POSE_POINT, ORIENT_NAV_VECTOR
@@ -435,20 +428,13 @@ inline Verdict check_sensor_args(int engine_model, bool per_filter_models, int m
 constexpr int sensor_filter_scalars(int S, int D) {
     return S > 16 ? -1 : (D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 32 + 16 + 3) / 4 * 4;
 }
-struct SensorGeometry {
-    int64_t grid;    // workgroups of four filters
-    int lds_bytes;   // dynamic LDS of a workgroup
-};
-// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
-inline SensorGeometry sensor_geometry(int S, int D, int64_t capacity, size_t compute_size) {
-    return {(capacity + SENSOR_FILTERS_PER_GROUP - 1) / SENSOR_FILTERS_PER_GROUP,
-            int(size_t(SENSOR_FILTERS_PER_GROUP) * sensor_filter_scalars(S, D) * compute_size)};
-}
+using SensorGeometry = RowGeometry;
+inline RowGeometry sensor_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(sensor_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- user-defined measurement models (ukfb_sigma_points_dev, ukfb_update_sampled_dev) --------------------------------------
 // The caller evaluates h on the exported sigma points; the update is finished from the samples Z_i = h(X_i), m = 1 ...
 // SAMPLED_MAX_M, one m for the call.
-constexpr int SAMPLED_MAX_M = UKFB_SAMPLED_MAX_M, SAMPLED_FILTERS_PER_GROUP = 4;
+constexpr int SAMPLED_MAX_M = UKFB_SAMPLED_MAX_M, SAMPLED_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
 // The record of one filter's inputs and of S as the kernel keeps them: z (SAMPLED_MAX_M), Q row-major m x m (up to
 // SAMPLED_MAX_M^2), then S row-major with row stride SAMPLED_MAX_M, z-bar and nu (SAMPLED_MAX_M each; parked for the outputs)
 constexpr int SAMPLED_INPUT_Z = 0, SAMPLED_INPUT_Q = SAMPLED_MAX_M, SAMPLED_INPUT_S = SAMPLED_INPUT_Q + SAMPLED_MAX_M * SAMPLED_MAX_M;
@@ -485,19 +471,9 @@ constexpr int sampled_filter_scalars(int S, int D) {
 constexpr int sigma_points_filter_scalars(int S, int D) {
     return S > 16 ? -1 : (D * SMOOTH_LS + 16 + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 16 + 3) / 4 * 4;
 }
-struct SampledGeometry {
-    int64_t grid;    // workgroups of four filters
-    int lds_bytes;   // dynamic LDS of a workgroup
-};
-// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
-inline SampledGeometry sampled_geometry(int S, int D, int64_t capacity, size_t compute_size) {
-    return {(capacity + SAMPLED_FILTERS_PER_GROUP - 1) / SAMPLED_FILTERS_PER_GROUP,
-            int(size_t(SAMPLED_FILTERS_PER_GROUP) * sampled_filter_scalars(S, D) * compute_size)};
-}
-inline SampledGeometry sigma_points_geometry(int S, int D, int64_t capacity, size_t compute_size) {
-    return {(capacity + SAMPLED_FILTERS_PER_GROUP - 1) / SAMPLED_FILTERS_PER_GROUP,
-            int(size_t(SAMPLED_FILTERS_PER_GROUP) * sigma_points_filter_scalars(S, D) * compute_size)};
-}
+using SampledGeometry = RowGeometry;
+inline RowGeometry sampled_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(sampled_filter_scalars(S, D), capacity, compute_size); }
+inline RowGeometry sigma_points_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(sigma_points_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- user-defined process models (ukfb_predict_sampled_dev) ----------------------------------------------------------------
 // The caller evaluates f on the exported sigma points; the prediction is finished from the samples XX_i = f(X_i) and the caller's
@@ -520,16 +496,12 @@ inline Verdict check_predict_sampled_args(const ukfb_predict_sampled_in* in, int
 constexpr int predict_sampled_filter_scalars(int S, int D) {
     return S > 16 ? -1 : (D * SMOOTH_LS + (2 * D + 1) * SMOOTH_LS + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 16 + 3) / 4 * 4;
 }
-// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
-inline SampledGeometry predict_sampled_geometry(int S, int D, int64_t capacity, size_t compute_size) {
-    return {(capacity + SAMPLED_FILTERS_PER_GROUP - 1) / SAMPLED_FILTERS_PER_GROUP,
-            int(size_t(SAMPLED_FILTERS_PER_GROUP) * predict_sampled_filter_scalars(S, D) * compute_size)};
-}
+inline RowGeometry predict_sampled_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(predict_sampled_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- covariance conditioning (ukfb_condition_dev) ----------------------------------------------------------------------------
 // Eigenvalue repair of the covariance in its correlation scaling by cyclic Jacobi, round-robin ordering.  The launch is the
 // sampled update's: four filters per workgroup, one wavefront.
-constexpr int CONDITION_FILTERS_PER_GROUP = 4, CONDITION_MAX_SWEEPS = 12, CONDITION_SLICE_PAD = 4;
+constexpr int CONDITION_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP, CONDITION_MAX_SWEEPS = 12, CONDITION_SLICE_PAD = 4;
 // players of the round-robin schedule (D rounded up to even; the odd D is padded with a decoupled unit row), pairs per step and
 // steps per sweep; the first pair of a step is the one that holds the last player: where that player is the padding, the pair is
 // the identity and is dropped
@@ -564,16 +536,12 @@ inline Verdict check_condition_floor(const double* var_floor, int D) {
 constexpr int condition_filter_scalars(int S, int D) {
     return S > 16 ? -1 : (2 * D * SMOOTH_LS + 16 + 16 + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 16 + CONDITION_SLICE_PAD + 3) / 4 * 4;
 }
-// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
-inline SampledGeometry condition_geometry(int S, int D, int64_t capacity, size_t compute_size) {
-    return {(capacity + CONDITION_FILTERS_PER_GROUP - 1) / CONDITION_FILTERS_PER_GROUP,
-            int(size_t(CONDITION_FILTERS_PER_GROUP) * condition_filter_scalars(S, D) * compute_size)};
-}
+inline RowGeometry condition_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(condition_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- late samples (ukfb_update_delayed_dev, ukfb_delayed_lag_dev) -----------------------------------------------------------
 // The smoother's window with the engine's own state as its last step: the chain runs at most steps - 1 <= SMOOTH_MAX_BACK
 // backward steps, all in one launch (their dt travel in the kernel arguments), so steps <= DELAYED_MAX_STEPS.
-constexpr int DELAYED_MAX_STEPS = UKFB_DELAYED_MAX_STEPS, DELAYED_FILTERS_PER_GROUP = 4;
+constexpr int DELAYED_MAX_STEPS = UKFB_DELAYED_MAX_STEPS, DELAYED_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
 static_assert(DELAYED_MAX_STEPS == SMOOTH_MAX_BACK + 1, "one launch covers the longest window");
 inline Verdict check_delayed_args(const ukfb_delayed_in* in, int commit, const ukfb_delayed_out* out) {
     if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
@@ -624,15 +592,8 @@ UKFB_HD int32_t delayed_lag_of(int steps, const int64_t* step_ts_us, int64_t t) 
 constexpr int delayed_filter_scalars(int S, int D) {
     return S > 16 ? -1 : (smooth_filter_scalars(S, D) + D * SMOOTH_LS + 3) / 4 * 4;
 }
-struct DelayedGeometry {
-    int64_t grid;    // workgroups of four filters
-    int lds_bytes;   // dynamic LDS of a workgroup
-};
-// compute_size: bytes of the scalar the kernel computes in (8: fp64 engines and fp32 engines with wide_arithmetic, else 4)
-inline DelayedGeometry delayed_geometry(int S, int D, int64_t capacity, size_t compute_size) {
-    return {(capacity + DELAYED_FILTERS_PER_GROUP - 1) / DELAYED_FILTERS_PER_GROUP,
-            int(size_t(DELAYED_FILTERS_PER_GROUP) * delayed_filter_scalars(S, D) * compute_size)};
-}
+using DelayedGeometry = RowGeometry;
+inline RowGeometry delayed_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(delayed_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- packed covariances of the host-array forms ---------------------------------------------------------------------------
 // `count` row-major D x D matrices <-> their lower triangles, row by row (entry (r, c), c <= r, at r (r + 1) / 2 + c of D (D + 1) / 2).

@@ -21,7 +21,7 @@
 // Per-filter model ids take the same kernel: both paths are wave-uniform branches.
 #pragma once
 
-#include "ukf_kernel16.hpp"
+#include "ukf_row.hpp"
 
 namespace ukfb {
 
@@ -57,10 +57,6 @@ template <class M> struct InnovLayout {
     static constexpr int PF = MUS + 16;                 // 100 scalars: the four slices start on different banks
     static_assert(M::S <= 16 && M::D <= LS, "a filter fits one row");
 };
-
-UKFB_DEV double m_log(double x) { return log(x); }
-UKFB_DEV float m_log(float x) { return logf(x); }
-template <class T> UKFB_DEV T m_nan() { return T(__builtin_nanf("")); }
 
 template <class T, class M, class TS>
 __global__ void __launch_bounds__(64) ukf_innovation_kernel(const InnovArgs<TS> a) {

@@ -13,8 +13,8 @@
 //    reason), and the mean iteration and the deltas work on those differences: the prediction is invariant under a translation
 //    of a vector block of all XX_i together.  XX_0 waits in the record's mean slot; the predicted vector blocks are XX_0 + the
 //    mean difference, summed in fp64.  Quaternion blocks are used as given.
-//  * from there the forecast kernel's statements in their order: the iterated mean with per-row `active`, sm_publish_deltas,
-//    sm_table_row, the row of Sigma^- parked in LDS while the noise is added entry by entry.  The noise is R's lower-triangle
+//  * from there the forecast kernel's statements in their order: the iterated mean with per-row `active`, row_publish_deltas,
+//    row_table_row, the row of Sigma^- parked in LDS while the noise is added entry by entry.  The noise is R's lower-triangle
 //    entry as it is stored; a uniform R is a stride of zero.
 //  * nothing is factorised: the kernel reads neither Sigma nor the mean, and has no pointer to them but the output's.
 //  * a filter that fails, is inactive or uninitialised rides along: every select is per row, no row's bits depend on its
@@ -24,7 +24,7 @@
 // LDS per filter: predict_sampled_filter_scalars (ukf_host.hpp).
 #pragma once
 
-#include "ukf_sampled.hpp"
+#include "ukf_row.hpp"
 
 namespace ukfb {
 
@@ -46,7 +46,7 @@ template <class T, class TS> struct PredictSampledArgs {
 };
 
 template <class M> struct PredictSampledLayout {
-    static constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2, LS = SMOOTH_LS;
+    static constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2, LS = ROW_LS;
     static constexpr int PKE = (PK + 1) / 2 * 2;
     static constexpr int SMR = 0;                         // D * LS: the rows of Sigma^-
     static constexpr int TAB = SMR + D * LS;              // (2 D + 1) * LS delta table; the staged samples (N * S) alias it
@@ -62,17 +62,18 @@ template <class M> struct PredictSampledLayout {
 
 // (the second bound: wavefronts per SIMD the register allocator must leave room for)
 template <class T, class M, class TS>
-__global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_predict_sampled_kernel(const PredictSampledArgs<T, TS> a) {
+__global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_predict_sampled_kernel(const PredictSampledArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2, Q = MT<M>::Q;
     using LY = PredictSampledLayout<M>;
     constexpr int LS = LY::LS;
     extern __shared__ __attribute__((aligned(16))) unsigned char psm_smem[];
 
+    // (RowCoords' statements in place: built on it, this kernel left the spread of the parent's own runs -- profiles/row_toolkit_rates.txt)
     const int lane = threadIdx.x, g = lane >> 4, l = lane & 15;
     const int lr = (l < D) ? l : (D - 1), ls = (l < S) ? l : (S - 1);
-    const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * SAMPLED_FILTERS_PER_GROUP;
+    const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * ROW_FILTERS_PER_GROUP;
     const int64_t n_here = a.n - wg0;
-    const int n_wg = int(n_here < SAMPLED_FILTERS_PER_GROUP ? n_here : int64_t(SAMPLED_FILTERS_PER_GROUP));
+    const int n_wg = int(n_here < ROW_FILTERS_PER_GROUP ? n_here : int64_t(ROW_FILTERS_PER_GROUP));
     const bool fvalid = g < n_wg;
     const int64_t f = wg0 + (fvalid ? g : (n_wg - 1));   // rows beyond the batch repeat its last filter and store nothing
     T* const base = reinterpret_cast<T*>(psm_smem) + g * LY::PF;
@@ -105,7 +106,7 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_predict_sampled_
             const int hi = lr > c ? lr : c, lo = lr > c ? c : lr;
             b = b || !m_finite(T(Rf[hi * D + lo]));
         }
-        bad = bank_row_any(b);
+        bad = row_any(b);
     }
     wsync();
     const bool dof = live && act && !bad;
@@ -138,8 +139,8 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_predict_sampled_
         int it = 0;
         while (wave_any(active)) {
             T dp[D], dm[D];
-            sm_boxminus<T, M>(xp, ref, dp);
-            sm_boxminus<T, M>(xm, ref, dm);
+            row_boxminus<T, M>(xp, ref, dp);
+            row_boxminus<T, M>(xm, ref, dm);
 #pragma unroll
             for (int c = 0; c < D; ++c) dp[c] = fma(wm, dm[c], wp * dp[c]);
             row_allreduce_n<T, D>(dp);
@@ -150,7 +151,7 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_predict_sampled_
                 m2 = fma(dp[c], dp[c], m2);
             }
             T nr[S];
-            sm_boxplus<T, M>(ref, dp, nr);
+            row_boxplus<T, M>(ref, dp, nr);
 #pragma unroll
             for (int s = 0; s < S; ++s) ref[s] = active ? nr[s] : ref[s];
             const bool more = m2 > a.mean_tol * a.mean_tol;
@@ -161,12 +162,12 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_predict_sampled_
         }
     }
     UKFB_MARK("p_deltas");
-    sm_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, ref);
+    row_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, ref);
     wsync();
     // Sigma^- = 1/2 sum delta delta^T + R: row lr, parked while the noise is added entry by entry
     {
         T sm[D];
-        sm_table_row<T, D, LS>(TAB, N, lr, sm);
+        row_table_row<T, D, LS>(TAB, N, lr, sm);
         sfence();
 #pragma unroll
         for (int c = 0; c < D; ++c) SMR[lr * LS + c] = sm[c];   // (lanes >= D: row D - 1's own bits again)
@@ -182,6 +183,7 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_predict_sampled_
     uint32_t st = !fvalid ? ST_OK : (!live ? ST_UNINITIALISED : (!act ? ST_INACTIVE : (bad ? ST_ERR_NONFINITE_MEAS : ST_OK)));
     st |= (dof && !conv) ? ST_WARN_MEAN_NOCONV : 0u;
     // ---- the predicted record through LDS: vector blocks XX_0 + the mean difference (summed in fp64), then whole rows
+    // (the store block of the updates, but the mean's entry is formed on the way and the rows come from LDS)
     {
         T v = ref[0];
 #pragma unroll

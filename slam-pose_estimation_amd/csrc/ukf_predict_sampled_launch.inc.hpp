@@ -2,6 +2,7 @@
 // translation units.  The three instantiations of a model: fp64, fp32, fp32 arrays with fp64 arithmetic (wide_arithmetic).
 #pragma once
 
+#include "ukf_feature_launch.hpp"
 #include "ukf_predict_sampled.hpp"
 #include "ukf_predict_sampled_req.hpp"
 
@@ -32,9 +33,10 @@ template <class TS, class M, class TC> static int launch_predict_sampled_typed(u
 }
 
 template <class M64, class M32> static int launch_predict_sampled_model(ukfb_engine* e, const PredictSampledReq& r) {
-    if (e->prec == UKFB_F64) return launch_predict_sampled_typed<double, M64, double>(e, r);
-    if (e->cfg.wide_arithmetic) return launch_predict_sampled_typed<float, M32, double>(e, r);
-    return launch_predict_sampled_typed<float, M32, float>(e, r);
+    return dispatch_precision<M64, M32>(e, [&](auto p) {
+        using P = decltype(p);
+        return launch_predict_sampled_typed<typename P::TS, typename P::M, typename P::TC>(e, r);
+    });
 }
 
 }  // namespace ukfb

@@ -3,13 +3,13 @@
 // launch), a read-only mode.  Definitions: include/ukf_batch.h ("user-defined measurement models"), DESIGN.md 4.21.
 //
 // Layout: the sensor-measurement kernel's (ukf_sensor_meas.hpp) -- one filter per 16-lane DPP row, four per wavefront, one
-// wavefront per workgroup -- and its device functions: chol16 / load_column / sigma_pair, sm_boxplus, the applyDelta commit.
+// wavefront per workgroup -- and the row toolkit's device functions (ukf_row.hpp): row_factorise, row_apply_delta.
 // The update IS that kernel with Z_i = h(X_i) replaced by a load:
 //  * the records in global memory are filter-major ([n][2 D + 1][...]): lane l < D owns the sigma pair of factor column l, rows
 //    1 + 2 l and 2 + 2 l of its filter's record, adjacent, so that the export's lane writes 2 S contiguous scalars; lane D owns
 //    the centre, row 0.  The update's row copies its filter's (2 D + 1) m contiguous samples into LDS with coalesced loads (and
 //    judges them: ERR_NONFINITE_MEAS), then every lane takes its two.
-//  * both kernels factorise Sigma with the same statements in the same order (load_row, chol16, sm_scale_factor, load_column),
+//  * both kernels factorise Sigma with the same statements in the same order (load_row, chol16, row_scale_factor, load_column),
 //    so that X_i (-) mu = +-L col j holds bit for bit for the points the caller evaluated; the update never reads X.
 //  * the measurement side is SAMPLED_MAX_M-dimensional whatever m: m < 6 is embedded with zero deltas, identity rows / columns
 //    of S and nu = 0 there (the argument of ukf_state_meas.hpp for unselected dimensions), so that every m takes one code path.
@@ -29,7 +29,7 @@
 // LDS per filter: sampled_filter_scalars, sigma_points_filter_scalars (ukf_host.hpp).
 #pragma once
 
-#include "ukf_state_meas.hpp"
+#include "ukf_row.hpp"
 
 namespace ukfb {
 
@@ -69,7 +69,7 @@ template <class T, class TS> struct SampledArgs {
 };
 
 template <class M> struct SigmaPointsLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = SMOOTH_LS;
+    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS;
     static constexpr int PKE = (PK + 1) / 2 * 2;
     static constexpr int FAC = 0;                         // D * LS factor columns, then 16 reciprocal pivots
     static constexpr int RSP = FAC + D * LS;
@@ -82,7 +82,7 @@ template <class M> struct SigmaPointsLayout {
 };
 
 template <class M> struct SampledLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = SMOOTH_LS, MM = SAMPLED_MAX_M;
+    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS, MM = SAMPLED_MAX_M;
     static constexpr int PKE = (PK + 1) / 2 * 2;
     static constexpr int ZS = MM;                         // row stride of the D x 6 matrices and of nothing else
     static constexpr int FAC = 0;                         // D * LS factor columns, then 16 reciprocal pivots
@@ -102,28 +102,22 @@ template <class M> struct SampledLayout {
 };
 
 // ---------------------------------------------------------------------------------------------------------------- the export
-// (the second bound: wavefronts per SIMD the register allocator must leave room for)
-template <class T> constexpr int sampled_waves() { return 2; }
 template <class T, class M, class TS>
-__global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_sigma_points_kernel(const SigmaPointsArgs<T, TS> a) {
+__global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_sigma_points_kernel(const SigmaPointsArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
     using LY = SigmaPointsLayout<M>;
     constexpr int LS = LY::LS;
     extern __shared__ __attribute__((aligned(16))) unsigned char sgp_smem[];
 
-    const int lane = threadIdx.x, g = lane >> 4, l = lane & 15;
-    const int ls = (l < S) ? l : (S - 1);
-    const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * SAMPLED_FILTERS_PER_GROUP;
-    const int64_t n_here = a.n - wg0;
-    const int n_wg = int(n_here < SAMPLED_FILTERS_PER_GROUP ? n_here : int64_t(SAMPLED_FILTERS_PER_GROUP));
-    const bool fvalid = g < n_wg;
-    const int64_t f = wg0 + (fvalid ? g : (n_wg - 1));   // rows beyond the batch repeat its last filter and store nothing
-    T* const base = reinterpret_cast<T*>(sgp_smem) + g * LY::PF;
+    const RowCoords<M> rc(a.n, threadIdx.x);
+    const int l = rc.l, ls = rc.ls;
+    const bool fvalid = rc.fvalid;
+    const int64_t f = rc.f;
+    T* const base = row_slice<T, LY::PF>(sgp_smem, rc.g);
     T *const FAC = base + LY::FAC, *const RSP = base + LY::RSP, *const MUF = base + LY::MUF, *const PKF = base + LY::PKF;
 
     const bool live = fvalid && a.initialised[f] != 0;
-    MUF[l] = T(a.mu[f * S + ls]);
-    for (int i = l; i < PK; i += 16) PKF[i] = T(a.cov[f * PK + i]);
+    row_stage_state<T, PK>(MUF, PKF, a.mu, a.cov, f * S, f * PK, l, ls);
     wsync();
     // ---- the sigma points of (mu, Sigma): the statements of the update's step 1 (and of ukf_sensor_meas.hpp), in their order
     T xp[S], xm[S], mu_r[S], col[D];
@@ -131,11 +125,7 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_sigma_points_ker
     {
 #pragma unroll
         for (int s = 0; s < S; ++s) mu_r[s] = MUF[s];
-        T arow[D];
-        load_row<T, D>(PKF, l, arow);
-        const T rs = chol16<T, D, LS>(arow, FAC, l, ok1);
-        wsync();
-        sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);
+        ok1 = row_factorise<T, D, LS>(PKF, FAC, RSP, l);
         load_column<T, D, LS>(FAC, l, T(1), col);
         sigma_pair<T, M>(mu_r, col, xp, xm);          // lanes >= D: their column is zero
     }
@@ -189,25 +179,20 @@ template <class T> UKFB_DEV void sampled_solve6(T (&c)[SAMPLED_MAX_M], const T (
         }
     }
 }
-// one row all-reduction (the butterflies need all 64 lanes: callers branch on wave-uniform conditions only)
-template <class T> UKFB_DEV T sampled_row_sum(T v) {
-    T one[1] = {v};
-    row_allreduce_n<T, 1>(one);
-    return one[0];
-}
 
 template <class T, class M, class TS>
-__global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_sampled_kernel(const SampledArgs<T, TS> a) {
+__global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_sampled_kernel(const SampledArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
     using LY = SampledLayout<M>;
     constexpr int LS = LY::LS, ZS = LY::ZS, MM = LY::MM;
     extern __shared__ __attribute__((aligned(16))) unsigned char smp_smem[];
 
+    // (RowCoords' statements in place: built on it, this kernel left the spread of the parent's own runs -- profiles/row_toolkit_rates.txt)
     const int lane = threadIdx.x, g = lane >> 4, l = lane & 15;
     const int lr = (l < D) ? l : (D - 1), ls = (l < S) ? l : (S - 1);
-    const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * SAMPLED_FILTERS_PER_GROUP;
+    const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * ROW_FILTERS_PER_GROUP;
     const int64_t n_here = a.n - wg0;
-    const int n_wg = int(n_here < SAMPLED_FILTERS_PER_GROUP ? n_here : int64_t(SAMPLED_FILTERS_PER_GROUP));
+    const int n_wg = int(n_here < ROW_FILTERS_PER_GROUP ? n_here : int64_t(ROW_FILTERS_PER_GROUP));
     const bool fvalid = g < n_wg;
     const int64_t f = wg0 + (fvalid ? g : (n_wg - 1));   // rows beyond the batch repeat its last filter and store nothing
     T* const base = reinterpret_cast<T*>(smp_smem) + g * LY::PF;
@@ -245,7 +230,7 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_sampled_kernel(c
             b = b || !m_finite(v);
             ZST[i] = v;
         }
-        bad = bank_row_any(b);
+        bad = row_any(b);
     }
     wsync();
     const bool do_u = live && act && !bad;
@@ -254,11 +239,13 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_sampled_kernel(c
     // ================================================================= 1. L = chol(Sigma): the export's statements in their order
     bool ok1;
     {
+        // (row_factorise's statements in place, in the export's order: called from here the fp32 instantiation left the spread
+        // of the parent's own runs -- profiles/row_toolkit_rates.txt)
         T arow[D];
         load_row<T, D>(PKF, l, arow);
         const T rs = chol16<T, D, LS>(arow, FAC, l, ok1);
         wsync();
-        sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);   // the scaled columns stay: C reads them
+        row_scale_factor<T, D, LS>(FAC, RSP, l, rs);   // the scaled columns stay: C reads them
     }
     sfence();
     UKFB_MARK("u_measure");
@@ -296,7 +283,7 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_sampled_kernel(c
             for (int c = 0; c < MM; ++c) dp[c] = fma(wm, zm[c] - ref[c], wp * (zp[c] - ref[c]));
 #pragma unroll
             for (int c = 0; c < MM; ++c)
-                if (c < m) dp[c] = sampled_row_sum(dp[c]);   // (beyond m every lane holds an exact zero: so is their sum)
+                if (c < m) dp[c] = row_sum(dp[c]);   // (beyond m every lane holds an exact zero: so is their sum)
             T m2 = T(0);
 #pragma unroll
             for (int c = 0; c < MM; ++c) {
@@ -336,7 +323,7 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_sampled_kernel(c
         for (int r = 0; r < MM; ++r)
             if (r < m) {   // (wave-uniform; a row beyond m is replaced below)
 #pragma unroll
-                for (int c = 0; c <= r; ++c) s21[r * (r + 1) / 2 + c] = sampled_row_sum(s21[r * (r + 1) / 2 + c]);
+                for (int c = 0; c <= r; ++c) s21[r * (r + 1) / 2 + c] = row_sum(s21[r * (r + 1) / 2 + c]);
             }
 #pragma unroll
         for (int r = 0; r < MM; ++r)
@@ -442,28 +429,8 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_sampled_kernel(c
     sfence();
     UKFB_MARK("u_commit");
     // ================================================================= 8. commit: applyDelta(mu, Sigma~, delta)
-    bool ok3;
     T mnew[S];
-    {
-        const T rs = chol16<T, D, LS>(sg, FAC, l, ok3);
-        wsync();
-        T col[D], dpl[D], dmi[D], mu_r[S], xp[S], xm[S];
-        load_column<T, D, LS>(FAC, l, rs, col);
-#pragma unroll
-        for (int c = 0; c < D; ++c) {
-            dpl[c] = del[c] + col[c];
-            dmi[c] = del[c] - col[c];
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < S; ++s2) mu_r[s2] = MUF[s2];
-        sfence();
-        sm_boxplus<T, M>(mu_r, del, mnew);
-        sm_boxplus<T, M>(mu_r, dpl, xp);
-        sm_boxplus<T, M>(mu_r, dmi, xm);
-        sm_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, mnew);
-    }
-    wsync();
-    sm_table_row<T, D, LS>(TAB, 2 * D, lr, sg);
+    const bool ok3 = row_apply_delta<T, M, LS>(FAC, TAB, MUF, DUMP, l, lr, del, sg, mnew);
     const bool okc = ok1 && ok2 && (!accept || ok3);
     const bool good = do_u && okc && accept;
     uint32_t st = !fvalid ? ST_OK : (!live ? ST_UNINITIALISED : (!act ? ST_INACTIVE : (bad ? ST_ERR_NONFINITE_MEAS : ST_OK)));
@@ -473,6 +440,7 @@ __global__ void __launch_bounds__(64, (sampled_waves<T>())) ukf_sampled_kernel(c
 
     UKFB_MARK("u_store");
     // ---- the new state through LDS (the records are dead), then whole rows of the packed arrays
+    // (in place in every kernel: as a shared function the block spilled to scratch, which the build gate refuses)
     {
         T v = mnew[0];
 #pragma unroll

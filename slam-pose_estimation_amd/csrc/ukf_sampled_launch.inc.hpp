@@ -3,6 +3,7 @@
 // (wide_arithmetic).
 #pragma once
 
+#include "ukf_feature_launch.hpp"
 #include "ukf_sampled.hpp"
 #include "ukf_sampled_req.hpp"
 
@@ -57,15 +58,17 @@ template <class TS, class M, class TC> static int launch_sampled_typed(ukfb_engi
 }
 
 template <class M64, class M32> static int launch_sigma_points_model(ukfb_engine* e, const SigmaPointsReq& r) {
-    if (e->prec == UKFB_F64) return launch_sigma_points_typed<double, M64, double>(e, r);
-    if (e->cfg.wide_arithmetic) return launch_sigma_points_typed<float, M32, double>(e, r);
-    return launch_sigma_points_typed<float, M32, float>(e, r);
+    return dispatch_precision<M64, M32>(e, [&](auto p) {
+        using P = decltype(p);
+        return launch_sigma_points_typed<typename P::TS, typename P::M, typename P::TC>(e, r);
+    });
 }
 
 template <class M64, class M32> static int launch_sampled_model(ukfb_engine* e, const SampledReq& r) {
-    if (e->prec == UKFB_F64) return launch_sampled_typed<double, M64, double>(e, r);
-    if (e->cfg.wide_arithmetic) return launch_sampled_typed<float, M32, double>(e, r);
-    return launch_sampled_typed<float, M32, float>(e, r);
+    return dispatch_precision<M64, M32>(e, [&](auto p) {
+        using P = decltype(p);
+        return launch_sampled_typed<typename P::TS, typename P::M, typename P::TC>(e, r);
+    });
 }
 
 }  // namespace ukfb

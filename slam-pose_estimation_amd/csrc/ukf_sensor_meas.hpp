@@ -3,7 +3,7 @@
 // model ids, a read-only mode.  Definitions: include/ukf_batch.h ("sensor-frame measurements"), DESIGN.md 4.17.
 //
 // Layout: the state-measurement kernel's (ukf_state_meas.hpp) -- one filter per 16-lane DPP row, four per wavefront, one
-// wavefront per workgroup -- and its device functions: chol16 / load_column / sigma_pair, sm_boxplus, the applyDelta commit.
+// wavefront per workgroup -- and its device functions: chol16 / load_column / sigma_pair, row_boxplus, the applyDelta commit.
 //  * lane l < D owns the sigma pair of factor column l and evaluates h on both points; lane D owns the centre.
 //  * the measurement side is three-dimensional whatever the model: m = 1 is embedded with zero deltas, identity rows / columns
 //    of S and nu = 0 there (the argument of ukf_state_meas.hpp for unselected dimensions), so that four wave-mates with four
@@ -27,7 +27,7 @@
 // LDS per filter: sensor_filter_scalars (ukf_host.hpp).
 #pragma once
 
-#include "ukf_state_meas.hpp"
+#include "ukf_row.hpp"
 
 namespace ukfb {
 
@@ -60,7 +60,7 @@ template <class T, class TS> struct SensorArgs {
 };
 
 template <class M> struct SensorLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = SMOOTH_LS;
+    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS;
     static constexpr int PKE = (PK + 1) / 2 * 2;
     static constexpr int ZS = 4;                          // row stride of the D x 3 matrices
     static constexpr int FAC = 0;                         // D * LS factor columns, then 16 reciprocal pivots
@@ -146,20 +146,21 @@ template <class T> UKFB_DEV void sensor_solve3(T (&c)[3], T l10, T l20, T l21, c
     c[2] = fma(-l21, c[1], fma(-l20, c[0], c[2])) * rs[2];
 }
 
-// (the second bound: wavefronts per SIMD the register allocator must leave room for)
-template <class T> constexpr int sensor_waves() { return 2; }
+// The factorisation and the commit below are the statements of row_factorise / row_apply_delta (ukf_row.hpp) in place: built
+// on them this kernel left the spread of the parent's own runs (profiles/row_toolkit_rates.txt), so it keeps them as tuned.
 template <class T, class M, class TS>
-__global__ void __launch_bounds__(64, (sensor_waves<T>())) ukf_sensor_meas_kernel(const SensorArgs<T, TS> a) {
+__global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_sensor_meas_kernel(const SensorArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
     using LY = SensorLayout<M>;
     constexpr int LS = LY::LS, ZS = LY::ZS, Q = MT<M>::Q;
     extern __shared__ __attribute__((aligned(16))) unsigned char sen_smem[];
 
+    // (RowCoords' statements in place: built on it, this kernel left the spread of the parent's own runs -- profiles/row_toolkit_rates.txt)
     const int lane = threadIdx.x, g = lane >> 4, l = lane & 15;
     const int lr = (l < D) ? l : (D - 1), ls = (l < S) ? l : (S - 1);
-    const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * SENSOR_FILTERS_PER_GROUP;
+    const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * ROW_FILTERS_PER_GROUP;
     const int64_t n_here = a.n - wg0;
-    const int n_wg = int(n_here < SENSOR_FILTERS_PER_GROUP ? n_here : int64_t(SENSOR_FILTERS_PER_GROUP));
+    const int n_wg = int(n_here < ROW_FILTERS_PER_GROUP ? n_here : int64_t(ROW_FILTERS_PER_GROUP));
     const bool fvalid = g < n_wg;
     const int64_t f = wg0 + (fvalid ? g : (n_wg - 1));   // rows beyond the batch repeat its last filter and store nothing
     T* const base = reinterpret_cast<T*>(sen_smem) + g * LY::PF;
@@ -201,7 +202,7 @@ __global__ void __launch_bounds__(64, (sensor_waves<T>())) ukf_sensor_meas_kerne
             b = b || (used && !m_finite(v));
             INP[i] = used ? v : ((i == SENSOR_INPUT_MOUNT + 6) ? T(1) : T(0));
         }
-        bad = bank_row_any(b);
+        bad = row_any(b);
     }
     wsync();
     const bool do_u = live && mvalid && !bad;
@@ -226,7 +227,7 @@ __global__ void __launch_bounds__(64, (sensor_waves<T>())) ukf_sensor_meas_kerne
         load_row<T, D>(PKF, l, arow);
         const T rs = chol16<T, D, LS>(arow, FAC, l, ok1);
         wsync();
-        sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);   // the scaled columns stay: C reads them
+        row_scale_factor<T, D, LS>(FAC, RSP, l, rs);   // the scaled columns stay: C reads them
         T col[D];
         load_column<T, D, LS>(FAC, l, T(1), col);
         sigma_pair<T, M>(mu_r, col, xp, xm);          // lanes >= D: the centre twice (their column is zero)
@@ -411,13 +412,13 @@ __global__ void __launch_bounds__(64, (sensor_waves<T>())) ukf_sensor_meas_kerne
 #pragma unroll
         for (int s2 = 0; s2 < S; ++s2) mu_r[s2] = MUF[s2];   // (reloaded: not kept live across the kernel)
         sfence();
-        sm_boxplus<T, M>(mu_r, del, mnew);
-        sm_boxplus<T, M>(mu_r, dpl, xp);
-        sm_boxplus<T, M>(mu_r, dmi, xm);
-        sm_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, mnew);
+        row_boxplus<T, M>(mu_r, del, mnew);
+        row_boxplus<T, M>(mu_r, dpl, xp);
+        row_boxplus<T, M>(mu_r, dmi, xm);
+        row_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, mnew);
     }
     wsync();
-    sm_table_row<T, D, LS>(TAB, 2 * D, lr, sg);
+    row_table_row<T, D, LS>(TAB, 2 * D, lr, sg);
     const bool okc = ok1 && ok2 && (!accept || ok3);
     const bool good = do_u && okc && accept;
     uint32_t st = !fvalid ? ST_OK : (!live ? ST_UNINITIALISED : (!mvalid ? ST_INACTIVE : (bad ? ST_ERR_NONFINITE_MEAS : ST_OK)));
@@ -427,6 +428,7 @@ __global__ void __launch_bounds__(64, (sensor_waves<T>())) ukf_sensor_meas_kerne
 
     UKFB_MARK("n_store");
     // ---- the new state through LDS (the records are dead), then whole rows of the packed arrays
+    // (in place in every kernel: as a shared function the block spilled to scratch, which the build gate refuses)
     {
         T v = mnew[0];
 #pragma unroll

@@ -25,7 +25,8 @@
 // table (aliased by G and M once C and Sigma^- are formed), the chain record, the filtered record, the rotation matrix, a sink.
 #pragma once
 
-#include "ukf_bank.hpp"
+#include "ukf_row.hpp"
+#include "ukf_bank.hpp"   // bank_jrinv_coeff
 
 namespace ukfb {
 
@@ -57,7 +58,7 @@ template <class T, class TS> struct SmoothArgs {
 };
 
 template <class M> struct SmoothLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = SMOOTH_LS;
+    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS;
     static constexpr int PKE = (PK + 1) / 2 * 2;
     static constexpr int FAC = 0;                         // D * LS factor columns, then 16 reciprocal pivots
     static constexpr int RSP = FAC + D * LS;
@@ -76,80 +77,6 @@ template <class M> struct SmoothLayout {
     static_assert(LS >= D && S <= 16 && D + 1 <= 16, "a filter fits one row");
 };
 
-// x (-) y and x (+) d with the fast SO(3) maps of the forward kernel
-template <class T, class M> UKFB_DEV void sm_boxminus(const T (&x)[M::S], const T (&y)[M::S], T (&d)[M::D]) {
-    constexpr int Q = MT<M>::Q, RT = MT<M>::RT, D = M::D;
-#pragma unroll
-    for (int t = 0; t < D; ++t) {
-        if (t < RT) d[t] = x[t] - y[t];
-        else if (t >= RT + 3) d[t] = x[t + 1] - y[t + 1];
-    }
-    const T qx[4] = {x[Q], x[Q + 1], x[Q + 2], x[Q + 3]}, qy[4] = {y[Q], y[Q + 1], y[Q + 2], y[Q + 3]};
-    T r[3];
-    rot_minus(qx, qy, r);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) d[RT + k] = r[k];
-}
-template <class T, class M> UKFB_DEV void sm_boxplus(const T (&x)[M::S], const T (&d)[M::D], T (&o)[M::S]) {
-    constexpr int Q = MT<M>::Q, RT = MT<M>::RT, D = M::D;
-#pragma unroll
-    for (int t = 0; t < D; ++t) {
-        if (t < RT) o[t] = x[t] + d[t];
-        else if (t >= RT + 3) o[t + 1] = x[t + 1] + d[t];
-    }
-    const T q[4] = {x[Q], x[Q + 1], x[Q + 2], x[Q + 3]};
-    const T v[3] = {d[RT], d[RT + 1], d[RT + 2]};
-    T e[4], r[4];
-    so3_exp_fast(v, T(1), e);
-    quat_mul(q, e, r);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[Q + k] = r[k];
-}
-
-// Deltas of the lane's sigma pair to `ref` into the table: row l = U_l, row D + l = W_l, the centre lane's row 2 D = delta_0 / sqrt 2
-template <class T, class M, int LS>
-UKFB_DEV void sm_publish_deltas(T* TAB, T* DUMP, int l, const T (&xp)[M::S], const T (&xm)[M::S], const T (&ref)[M::S]) {
-    constexpr int D = M::D;
-    T dp[D], dm[D];
-    sm_boxminus<T, M>(xp, ref, dp);
-    sm_boxminus<T, M>(xm, ref, dm);
-    T* const rowu = (l < D) ? (TAB + l * LS) : ((l == D) ? (TAB + 2 * D * LS) : DUMP);
-    T* const roww = (l < D) ? (TAB + (D + l) * LS) : DUMP;
-    const T fu = (l == D) ? T(0.70710678118654752440) : T(1);
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        rowu[k] = fu * (T(0.5) * (dp[k] + dm[k]));
-        roww[k] = T(0.5) * (dp[k] - dm[k]);
-    }
-}
-
-// row lr of sum_{i < rows} TAB_i TAB_i^T (all D columns; the same bits at (r, c) and (c, r))
-template <class T, int D, int LS> UKFB_DEV void sm_table_row(const T* TAB, int rows, int lr, T (&out)[D]) {
-#pragma unroll
-    for (int c = 0; c < D; ++c) out[c] = T(0);
-#pragma nounroll
-    for (int i = 0; i < rows; ++i) {
-        const T* r = TAB + i * LS;
-        const T own = r[lr];
-#pragma unroll
-        for (int c = 0; c < D; ++c) out[c] = fma(own, r[c], out[c]);
-    }
-}
-
-// scaled factor in place of chol16's unscaled columns (zeros above the diagonal), reciprocal pivots behind it
-template <class T, int D, int LS> UKFB_DEV void sm_scale_factor(T* FAC, T* RSP, int l, T rs) {
-    T col[D];
-    load_column<T, D, LS>(FAC, l, rs, col);
-    wsync();
-    T* dst = FAC + ((l < D) ? l : (D - 1)) * LS;
-    if (l < D) {
-#pragma unroll
-        for (int c = 0; c < D; ++c) dst[c] = col[c];
-        RSP[l] = rs;
-    }
-    wsync();
-}
-
 // What a row derives from its lane index: its filter, its predicates and its LDS slice (public members in this order: the step
 // loop binds them by name)
 template <class T, class M, class TS> struct SmoothRow {
@@ -160,18 +87,11 @@ template <class T, class M, class TS> struct SmoothRow {
     T *FAC, *RSP, *TAB, *GM, *MM, *CSM, *CSP, *MUF, *PKF, *ROT, *DUMP, *SMR, *MUP;
     const TS *Rn, *Racc;
     UKFB_DEV SmoothRow(const SmoothArgs<T, TS>& a, unsigned char* smem, int lane) {
-        const int g = lane >> 4;
-        l = lane & 15;
-        lr = (l < M::D) ? l : (M::D - 1);
-        ls = (l < M::S) ? l : (M::S - 1);
-        const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * SMOOTH_FILTERS_PER_GROUP;
-        const int64_t n_here = a.n - wg0;
-        const int n_wg = int(n_here < SMOOTH_FILTERS_PER_GROUP ? n_here : int64_t(SMOOTH_FILTERS_PER_GROUP));
-        fvalid = g < n_wg;
-        f = wg0 + (fvalid ? g : (n_wg - 1));
+        const RowCoords<M> rc(a.n, lane);
+        l = rc.l; lr = rc.lr; ls = rc.ls; fvalid = rc.fvalid; f = rc.f;
         live = fvalid && a.initialised[f] != 0;
         wr = live;
-        T* const base = reinterpret_cast<T*>(smem) + g * LY::PF;
+        T* const base = row_slice<T, LY::PF>(smem, rc.g);
         FAC = base + LY::FAC; RSP = base + LY::RSP; TAB = base + LY::TAB; GM = base + LY::GM; MM = base + LY::MM;
         CSM = base + LY::CSM; CSP = base + LY::CSP; MUF = base + LY::MUF; PKF = base + LY::PKF; ROT = base + LY::ROT;
         DUMP = base + LY::DUM; SMR = base + LY::SMR; MUP = base + LY::MUP;
@@ -180,10 +100,8 @@ template <class T, class M, class TS> struct SmoothRow {
     }
 };
 
-// (the second bound: wavefronts per SIMD the register allocator must leave room for -- the LDS slices admit no more)
-template <class T> constexpr int smooth_waves() { return 2; }
 template <class T, class M, class TS>
-__global__ void __launch_bounds__(64, (smooth_waves<T>())) ukf_smooth_kernel(const SmoothArgs<T, TS> a) {
+__global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_smooth_kernel(const SmoothArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
     using LY = SmoothLayout<M>;
     constexpr int LS = LY::LS, Q = MT<M>::Q, RT = MT<M>::RT;
@@ -258,11 +176,7 @@ __global__ void __launch_bounds__(64, (smooth_waves<T>())) ukf_smooth_kernel(con
             }
             bool ok1;
             {
-                T arow[D];
-                load_row<T, D>(PKF, l, arow);
-                const T rs = chol16<T, D, LS>(arow, FAC, l, ok1);
-                wsync();
-                sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);   // the scaled columns stay: C reads them
+                ok1 = row_factorise<T, D, LS>(PKF, FAC, RSP, l);   // the scaled columns stay: C reads them
                 T col[D];
                 load_column<T, D, LS>(FAC, l, T(1), col);
                 sigma_pair<T, M>(mu_r, col, xp, xm);          // lanes >= D: the centre twice (their column is zero)
@@ -283,8 +197,8 @@ __global__ void __launch_bounds__(64, (smooth_waves<T>())) ukf_smooth_kernel(con
                 int it = 0;
                 while (wave_any(active)) {
                     T dp[D], dm[D];
-                    sm_boxminus<T, M>(xp, ref, dp);
-                    sm_boxminus<T, M>(xm, ref, dm);
+                    row_boxminus<T, M>(xp, ref, dp);
+                    row_boxminus<T, M>(xm, ref, dm);
 #pragma unroll
                     for (int c = 0; c < D; ++c) dp[c] = fma(wm, dm[c], wp * dp[c]);
                     row_allreduce_n<T, D>(dp);
@@ -295,7 +209,7 @@ __global__ void __launch_bounds__(64, (smooth_waves<T>())) ukf_smooth_kernel(con
                         m2 = fma(dp[c], dp[c], m2);
                     }
                     T nr[S];
-                    sm_boxplus<T, M>(ref, dp, nr);
+                    row_boxplus<T, M>(ref, dp, nr);
 #pragma unroll
                     for (int s = 0; s < S; ++s) ref[s] = active ? nr[s] : ref[s];
                     const bool more = m2 > a.mean_tol * a.mean_tol;
@@ -306,11 +220,11 @@ __global__ void __launch_bounds__(64, (smooth_waves<T>())) ukf_smooth_kernel(con
                 }
             }
             UKFB_MARK("s_deltas");
-            sm_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, ref);
+            row_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, ref);
             wsync();
             // Sigma^- = 1/2 sum delta delta^T + R: row lr
             T sm[D];
-            sm_table_row<T, D, LS>(TAB, N, lr, sm);
+            row_table_row<T, D, LS>(TAB, N, lr, sm);
             sfence();
 #pragma unroll
             for (int c = 0; c < D; ++c) SMR[lr * LS + c] = sm[c];   // parked in LDS until M is formed (lanes >= D: row D - 1's own bits again)
@@ -350,9 +264,7 @@ __global__ void __launch_bounds__(64, (smooth_waves<T>())) ukf_smooth_kernel(con
                     T tmp[D];
 #pragma unroll
                     for (int c = 0; c < D; ++c) tmp[c] = SMR[lr * LS + c];
-                    const T rs = chol16<T, D, LS>(tmp, FAC, l, ok2);
-                    wsync();
-                    sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);
+                    ok2 = row_factorise_row<T, D, LS>(tmp, FAC, RSP, l);
                 }
                 ok1 = ok1 && ok2;
                 // L y = c
@@ -389,7 +301,7 @@ __global__ void __launch_bounds__(64, (smooth_waves<T>())) ukf_smooth_kernel(con
                     cs[s] = CSM[s];
                     mp[s] = MUP[s];
                 }
-                sm_boxminus<T, M>(cs, mp, e);
+                row_boxminus<T, M>(cs, mp, e);
             }
             {
                 const T p0 = e[RT], p1 = e[RT + 1], p2 = e[RT + 2];
@@ -465,32 +377,13 @@ __global__ void __launch_bounds__(64, (smooth_waves<T>())) ukf_smooth_kernel(con
             wsync();   // G and M are dead
             UKFB_MARK("s_commit");
             // ================================================================= 6. commit: applyDelta(mu, Sigma~, delta)
-            bool ok3;
             T mnew[S];
-            {
-                const T rs = chol16<T, D, LS>(sg, FAC, l, ok3);
-                wsync();
-                T col[D], dpl[D], dmi[D];
-                load_column<T, D, LS>(FAC, l, rs, col);
-#pragma unroll
-                for (int c = 0; c < D; ++c) {
-                    dpl[c] = del[c] + col[c];
-                    dmi[c] = del[c] - col[c];
-                }
-#pragma unroll
-                for (int s2 = 0; s2 < S; ++s2) mu_r[s2] = MUF[s2];   // (reloaded: not kept live across the step)
-                sfence();
-                sm_boxplus<T, M>(mu_r, del, mnew);
-                sm_boxplus<T, M>(mu_r, dpl, xp);
-                sm_boxplus<T, M>(mu_r, dmi, xm);
-                sm_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, mnew);   // (the centre's row: exact zeros but for log(conj(q) q))
-            }
-            wsync();
-            sm_table_row<T, D, LS>(TAB, 2 * D, lr, sg);
+            const bool ok3 = row_apply_delta<T, M, LS>(FAC, TAB, MUF, DUMP, l, lr, del, sg, mu_r, mnew);   // (mu_r: reloaded, not kept live across the step)
             const bool good = dof && ok1 && ok3;
             st |= (dof && !good) ? ST_ERR_CHOLESKY : 0u;
             st |= (dof && good && !conv) ? ST_WARN_MEAN_NOCONV : 0u;
             // the chain moves on: the smoothed record, or (a failure) the filtered one bit for bit; a gated row keeps it
+            // (the store block of the updates, but a failure's values come from LDS entry by entry)
             {
                 T v = good ? mnew[0] : mu_r[0];
 #pragma unroll

@@ -2,9 +2,9 @@
 // blocks, m up to D dimensions with a full covariance, per-filter block masks, covariance inflation (covariance intersection)
 // and a read-only mode.  Definitions: include/ukf_batch.h ("joint state-block measurements"), DESIGN.md 4.16.
 //
-// Layout: the smoother's (ukf_smooth.hpp) -- one filter per 16-lane DPP row, four per wavefront, one wavefront per workgroup --
-// and its device functions: chol16 / load_column / sigma_pair, sm_boxminus / sm_boxplus, the D-column delta table, row-owned
-// products and solves, the applyDelta commit.
+// Layout: the row layout (ukf_row.hpp) -- one filter per 16-lane DPP row, four per wavefront, one wavefront per workgroup -- and
+// its device functions: chol16 / load_column / sigma_pair, row_boxminus / row_boxplus, the D-column delta table, row-owned
+// products and solves, row_factorise, the applyDelta commit (row_apply_delta).
 //  * EVERY row works in all D dimensions whatever its mask: for an unselected dimension t column t of the table's deltas is zero,
 //    row / column t of S is that of the identity and nu[t] = 0.  S is then blockdiag(S_sel, I) up to a permutation; the
 //    subtractions of exact zeros leave the selected pivots' bits alone, column t of the solved cross-covariance is zero, and
@@ -19,8 +19,7 @@
 // LDS per filter: state_meas_filter_scalars (ukf_host.hpp).
 #pragma once
 
-#include "ukf_innovation.hpp"
-#include "ukf_smooth.hpp"
+#include "ukf_row.hpp"
 
 namespace ukfb {
 
@@ -46,7 +45,7 @@ template <class T, class TS> struct StateMeasArgs {
 };
 
 template <class M> struct StateMeasLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = SMOOTH_LS;
+    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS;
     static constexpr int PKE = (PK + 1) / 2 * 2;
     static constexpr int FAC = 0;                         // D * LS factor columns, then 16 reciprocal pivots
     static constexpr int RSP = FAC + D * LS;
@@ -63,13 +62,13 @@ template <class M> struct StateMeasLayout {
     static_assert(state_meas_blocks(M::MODEL) == (D + 2) / 3, "tangent dimension t belongs to block t / 3");
 };
 
-// sm_publish_deltas with the unselected columns zeroed (tsel: bit t = tangent dimension t is measured)
+// row_publish_deltas with the unselected columns zeroed (tsel: bit t = tangent dimension t is measured)
 template <class T, class M, int LS>
 UKFB_DEV void stm_publish_deltas(T* TAB, T* DUMP, int l, uint32_t tsel, const T (&xp)[M::S], const T (&xm)[M::S], const T (&ref)[M::S]) {
     constexpr int D = M::D;
     T dp[D], dm[D];
-    sm_boxminus<T, M>(xp, ref, dp);
-    sm_boxminus<T, M>(xm, ref, dm);
+    row_boxminus<T, M>(xp, ref, dp);
+    row_boxminus<T, M>(xm, ref, dm);
     T* const rowu = (l < D) ? (TAB + l * LS) : ((l == D) ? (TAB + 2 * D * LS) : DUMP);
     T* const roww = (l < D) ? (TAB + (D + l) * LS) : DUMP;
     const T fu = (l == D) ? T(0.70710678118654752440) : T(1);
@@ -81,23 +80,18 @@ UKFB_DEV void stm_publish_deltas(T* TAB, T* DUMP, int l, uint32_t tsel, const T 
     }
 }
 
-// (the second bound: wavefronts per SIMD the register allocator must leave room for)
-template <class T> constexpr int state_meas_waves() { return 2; }
 template <class T, class M, class TS>
-__global__ void __launch_bounds__(64, (state_meas_waves<T>())) ukf_state_meas_kernel(const StateMeasArgs<T, TS> a) {
+__global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_state_meas_kernel(const StateMeasArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
     using LY = StateMeasLayout<M>;
     constexpr int LS = LY::LS, Q = MT<M>::Q, RT = MT<M>::RT, NB = (D + 2) / 3;
     extern __shared__ __attribute__((aligned(16))) unsigned char stm_smem[];
 
-    const int lane = threadIdx.x, g = lane >> 4, l = lane & 15;
-    const int lr = (l < D) ? l : (D - 1), ls = (l < S) ? l : (S - 1);
-    const int64_t wg0 = int64_t(group_of_block(blockIdx.x, gridDim.x)) * STATE_MEAS_FILTERS_PER_GROUP;
-    const int64_t n_here = a.n - wg0;
-    const int n_wg = int(n_here < STATE_MEAS_FILTERS_PER_GROUP ? n_here : int64_t(STATE_MEAS_FILTERS_PER_GROUP));
-    const bool fvalid = g < n_wg;
-    const int64_t f = wg0 + (fvalid ? g : (n_wg - 1));   // rows beyond the batch repeat its last filter and store nothing
-    T* const base = reinterpret_cast<T*>(stm_smem) + g * LY::PF;
+    const RowCoords<M> rc(a.n, threadIdx.x);
+    const int l = rc.l, lr = rc.lr, ls = rc.ls;
+    const bool fvalid = rc.fvalid;
+    const int64_t f = rc.f;
+    T* const base = row_slice<T, LY::PF>(stm_smem, rc.g);
     T *const FAC = base + LY::FAC, *const RSP = base + LY::RSP, *const TAB = base + LY::TAB, *const YM = base + LY::YM;
     T *const MUF = base + LY::MUF, *const PKF = base + LY::PKF, *const ZM = base + LY::ZM, *const PKQ = base + LY::PKQ;
     T* const DUMP = base + LY::DUM;
@@ -110,6 +104,7 @@ __global__ void __launch_bounds__(64, (state_meas_waves<T>())) ukf_state_meas_ke
     uint32_t tsel = 0u;
 #pragma unroll
     for (int t = 0; t < D; ++t) tsel |= ((mbits >> (t / 3)) & 1u) << t;
+    // (not row_stage_state: two records at once, the covariances inflated on the way)
     MUF[l] = T(a.mu[f * S + ls]);
     ZM[l] = T(a.z[f * S + ls]);
     for (int i = l; i < PK; i += 16) {
@@ -129,7 +124,7 @@ __global__ void __launch_bounds__(64, (state_meas_waves<T>())) ukf_state_meas_ke
             const T q = PKQ[hi * (hi + 1) / 2 + lo];
             b = b || (selr && ((tsel >> c) & 1u) && !m_finite(q));
         }
-        bad = bank_row_any(b);
+        bad = row_any(b);
     }
     const bool do_u = live && mvalid && !bad;
 
@@ -141,11 +136,7 @@ __global__ void __launch_bounds__(64, (state_meas_waves<T>())) ukf_state_meas_ke
         T mu_r[S];
 #pragma unroll
         for (int s = 0; s < S; ++s) mu_r[s] = MUF[s];
-        T arow[D];
-        load_row<T, D>(PKF, l, arow);
-        const T rs = chol16<T, D, LS>(arow, FAC, l, ok1);
-        wsync();
-        sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);   // the scaled columns stay: C reads them
+        ok1 = row_factorise<T, D, LS>(PKF, FAC, RSP, l);   // the scaled columns stay: C reads them
         T col[D];
         load_column<T, D, LS>(FAC, l, T(1), col);
         sigma_pair<T, M>(mu_r, col, xp, xm);          // lanes >= D: the centre twice (their column is zero)
@@ -162,8 +153,8 @@ __global__ void __launch_bounds__(64, (state_meas_waves<T>())) ukf_state_meas_ke
         int it = 0;
         while (wave_any(active)) {
             T dp[D], dm[D];
-            sm_boxminus<T, M>(xp, ref, dp);
-            sm_boxminus<T, M>(xm, ref, dm);
+            row_boxminus<T, M>(xp, ref, dp);
+            row_boxminus<T, M>(xm, ref, dm);
 #pragma unroll
             for (int c = 0; c < D; ++c) dp[c] = ((tsel >> c) & 1u) ? fma(wm, dm[c], wp * dp[c]) : T(0);
             row_allreduce_n<T, D>(dp);
@@ -174,7 +165,7 @@ __global__ void __launch_bounds__(64, (state_meas_waves<T>())) ukf_state_meas_ke
                 m2 = fma(dp[c], dp[c], m2);
             }
             T nr[S];
-            sm_boxplus<T, M>(ref, dp, nr);
+            row_boxplus<T, M>(ref, dp, nr);
 #pragma unroll
             for (int s = 0; s < S; ++s) ref[s] = active ? nr[s] : ref[s];
             const bool more = m2 > a.mean_tol * a.mean_tol;
@@ -189,7 +180,7 @@ __global__ void __launch_bounds__(64, (state_meas_waves<T>())) ukf_state_meas_ke
     wsync();
     // ================================================================= 3. S = 1/2 sum dz dz^T + b Qz (identity outside the selection): row lr
     T srow[D];
-    sm_table_row<T, D, LS>(TAB, N, lr, srow);
+    row_table_row<T, D, LS>(TAB, N, lr, srow);
     {
         const bool selr = (tsel >> lr) & 1u;
 #pragma unroll
@@ -211,7 +202,7 @@ __global__ void __launch_bounds__(64, (state_meas_waves<T>())) ukf_state_meas_ke
             const T zv = ZM[s];
             zf[s] = ((tsel >> tz) & 1u) ? zv : ref[s];
         }
-        sm_boxminus<T, M>(zf, ref, nu);
+        row_boxminus<T, M>(zf, ref, nu);
 #pragma unroll
         for (int c = 0; c < D; ++c) nu[c] = ((tsel >> c) & 1u) ? nu[c] : T(0);
     }
@@ -235,11 +226,11 @@ __global__ void __launch_bounds__(64, (state_meas_waves<T>())) ukf_state_meas_ke
     bool ok2;
     T lndet;
     {
-        const T rs = chol16<T, D, LS>(srow, FAC, l, ok2);
+        const T rs = chol16<T, D, LS>(srow, FAC, l, ok2);   // (not row_factorise_row: the unscaled pivots are read in between)
         wsync();
         const T pv = FAC[lr * LS + lr];   // the pivots, unscaled: det S is their product (an unselected one is exactly 1)
         lndet = row_allreduce((l < D) ? m_log(pv) : T(0));
-        sm_scale_factor<T, D, LS>(FAC, RSP, l, rs);
+        row_scale_factor<T, D, LS>(FAC, RSP, l, rs);
     }
 #pragma unroll
     for (int k = 0; k < D; ++k) {
@@ -290,28 +281,8 @@ __global__ void __launch_bounds__(64, (state_meas_waves<T>())) ukf_state_meas_ke
     wsync();   // Y is dead
     UKFB_MARK("m_commit");
     // ================================================================= 7. commit: applyDelta(mu, Sigma~, delta)
-    bool ok3;
     T mnew[S];
-    {
-        const T rs = chol16<T, D, LS>(sg, FAC, l, ok3);
-        wsync();
-        T col[D], dpl[D], dmi[D], mu_r[S];
-        load_column<T, D, LS>(FAC, l, rs, col);
-#pragma unroll
-        for (int c = 0; c < D; ++c) {
-            dpl[c] = del[c] + col[c];
-            dmi[c] = del[c] - col[c];
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < S; ++s2) mu_r[s2] = MUF[s2];   // (reloaded: not kept live across the kernel)
-        sfence();
-        sm_boxplus<T, M>(mu_r, del, mnew);
-        sm_boxplus<T, M>(mu_r, dpl, xp);
-        sm_boxplus<T, M>(mu_r, dmi, xm);
-        sm_publish_deltas<T, M, LS>(TAB, DUMP, l, xp, xm, mnew);
-    }
-    wsync();
-    sm_table_row<T, D, LS>(TAB, 2 * D, lr, sg);
+    const bool ok3 = row_apply_delta<T, M, LS>(FAC, TAB, MUF, DUMP, l, lr, del, sg, mnew);
     const bool okc = ok1 && ok2 && (!accept || ok3);
     const bool good = do_u && okc && accept;
     uint32_t st = !fvalid ? ST_OK : (!live ? ST_UNINITIALISED : (!mvalid ? ST_INACTIVE : (bad ? ST_ERR_NONFINITE_MEAS : ST_OK)));
@@ -321,6 +292,7 @@ __global__ void __launch_bounds__(64, (state_meas_waves<T>())) ukf_state_meas_ke
 
     UKFB_MARK("m_store");
     // ---- the new state through LDS (the records are dead), then whole rows of the packed arrays
+    // (in place in every kernel: as a shared function the block spilled to scratch, which the build gate refuses)
     {
         T v = mnew[0];
 #pragma unroll

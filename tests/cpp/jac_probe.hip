@@ -9,7 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../slam-pose_estimation_amd/csrc/ukf_delayed.hpp"   // pulls in ukf_bank.hpp
+#include "../../slam-pose_estimation_amd/csrc/ukf_bank.hpp"
+#include "../../slam-pose_estimation_amd/csrc/ukf_delayed.hpp"
 
 enum { JACP_IN = 3, JACP_OUT = 9 };
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Build gate for EVERY shipped kernel instantiation (ukf_kernel16, the generic ukf_kernel, ukf_innovation_kernel, ukf_bank_*_kernel, ukf_smooth_kernel, ukf_forecast_kernel, ukf_lifecycle_*_kernel, ukf_state_meas_kernel, ukf_sensor_meas_kernel, ukf_sampled_kernel, ukf_sigma_points_kernel, ukf_predict_sampled_kernel, ukf_delayed_kernel, ukf_condition_kernel): no scratch and no AGPRs, and
+"""Build gate for EVERY shipped kernel instantiation (the name fragments of GATED below): no scratch and no AGPRs, and
 the tuned kernels keep the wavefronts per SIMD their design counts on (fp64: three, fp32: five) -- a register regression
 that costs a wavefront fails the build instead of showing up as a slower bench line.
 
@@ -29,6 +29,30 @@ def parse(text):
     return out
 
 
+# every kernel whose name holds one of these fragments is gated
+GATED = ("ukf_kernel", "ukf_innovation_kernel", "ukf_bank_", "ukf_smooth_kernel", "ukf_forecast_kernel", "ukf_lifecycle_",
+         "ukf_state_meas_kernel", "ukf_sensor_meas_kernel", "ukf_sampled_kernel", "ukf_sigma_points_kernel",
+         "ukf_predict_sampled_kernel", "ukf_delayed_kernel", "ukf_condition_kernel")
+
+# (name fragments, fragments that exclude, wavefronts per SIMD the kernel must keep, what the error calls it), checked in this
+# order.  The tuned kernels (the register side; LDS is checked by the layout's static_asserts): ukf_kernel16<double, ...> three
+# wavefronts per SIMD (<= 168 VGPRs), ukf_kernel16<float, ...> five (<= 96); --no-occupancy-floor lifts these two.  The feature
+# kernels are sized for two in either precision: that is their launch bound; in fp64 their LDS slices (15 ... 38 KB per
+# workgroup) admit one to two, in fp32 two to three.
+TUNED = "tuned"
+FLOORS = (
+    (("ukf_kernel16Id",), (), 3, "tuned fp64 kernels", TUNED),
+    (("ukf_kernel16I",), ("ukf_kernel16Id",), 5, "tuned fp32 kernels", TUNED),
+    (("ukf_state_meas_kernel",), (), 2, "state-measurement kernels", None),
+    (("ukf_sensor_meas_kernel",), (), 2, "sensor-measurement kernels", None),
+    (("ukf_sampled_kernel", "ukf_sigma_points_kernel"), (), 2, "sampled-update / sigma-point kernels", None),
+    (("ukf_predict_sampled_kernel",), (), 2, "sampled-prediction kernels", None),
+    (("ukf_delayed_kernel",), (), 2, "delayed-measurement kernels", None),
+    (("ukf_condition_kernel",), (), 2, "conditioning kernels", None),
+    (("ukf_forecast_kernel",), (), 2, "forecast kernels", None),
+)
+
+
 def main(paths):
     # --allow-agpr: diagnostic builds with the fp64 one-wavefront-per-filter kernels (make GENERIC_F64=1)
     allow_agpr = "--allow-agpr" in paths
@@ -36,10 +60,7 @@ def main(paths):
     bad, rows = [], []
     for p in paths:
         for k in parse(open(p).read()):
-            if "ukf_kernel" not in k["name"] and "ukf_innovation_kernel" not in k["name"] and "ukf_bank_" not in k["name"] \
-                    and "ukf_smooth_kernel" not in k["name"] and "ukf_forecast_kernel" not in k["name"] and "ukf_lifecycle_" not in k["name"] and "ukf_state_meas_kernel" not in k["name"] and "ukf_sensor_meas_kernel" not in k["name"] \
-                    and "ukf_sampled_kernel" not in k["name"] and "ukf_sigma_points_kernel" not in k["name"] and "ukf_predict_sampled_kernel" not in k["name"] \
-                    and "ukf_delayed_kernel" not in k["name"] and "ukf_condition_kernel" not in k["name"]:
+            if not any(frag in k["name"] for frag in GATED):
                 continue
             rows.append(k)
             if k.get("scratch", 0) or (k.get("agpr", 0) and not allow_agpr):
@@ -50,52 +71,15 @@ def main(paths):
     if bad:
         print("ERROR: kernels with scratch or AGPR spills (unsafe with this toolchain):", [b["name"] for b in bad])
         return 1
-    # occupancy floor of the tuned kernels (the register side; LDS is checked by the layout's static_asserts):
-    # ukf_kernel16<double, ...> three wavefronts per SIMD (<= 168 VGPRs), ukf_kernel16<float, ...> five (<= 96)
-    slow = [k for k in rows if "ukf_kernel16I" in k["name"] and
-            k.get("occupancy", 0) < (3 if "ukf_kernel16Id" in k["name"] else 5)]
-    if slow and "--no-occupancy-floor" not in sys.argv:
-        print("ERROR: tuned kernels below their occupancy floor (fp64: 3, fp32: 5 wavefronts per SIMD):",
-              [(k["name"], k.get("vgpr"), k.get("occupancy")) for k in slow])
-        return 1
-    # the state-measurement kernels are sized for two wavefronts per SIMD in either precision (their launch bound; fp64: 16 ...
-    # 26 KB of LDS per workgroup admit one to two, fp32 three)
-    low = [k for k in rows if "ukf_state_meas_kernel" in k["name"] and k.get("occupancy", 0) < 2]
-    if low:
-        print("ERROR: state-measurement kernels below two wavefronts per SIMD:", [(k["name"], k.get("vgpr")) for k in low])
-        return 1
-    # so are the sensor-frame measurement kernels (fp64: 21 ... 23 KB of LDS per workgroup, fp32 half of it)
-    low = [k for k in rows if "ukf_sensor_meas_kernel" in k["name"] and k.get("occupancy", 0) < 2]
-    if low:
-        print("ERROR: sensor-measurement kernels below two wavefronts per SIMD:", [(k["name"], k.get("vgpr")) for k in low])
-        return 1
-    # and the kernels of the user-defined measurement models: the sigma-point export and the sampled update (fp64: 23 ... 25 KB of
-    # LDS per workgroup for the update, 9 ... 10 KB for the export)
-    low = [k for k in rows if ("ukf_sampled_kernel" in k["name"] or "ukf_sigma_points_kernel" in k["name"]) and k.get("occupancy", 0) < 2]
-    if low:
-        print("ERROR: sampled-update / sigma-point kernels below two wavefronts per SIMD:", [(k["name"], k.get("vgpr")) for k in low])
-        return 1
-    # and the sampled prediction (its launch bound; fp64: 19.6 ... 21.4 KB of LDS per workgroup, fp32 half of it)
-    low = [k for k in rows if "ukf_predict_sampled_kernel" in k["name"] and k.get("occupancy", 0) < 2]
-    if low:
-        print("ERROR: sampled-prediction kernels below two wavefronts per SIMD:", [(k["name"], k.get("vgpr")) for k in low])
-        return 1
-    # the delayed-measurement kernels: two wavefronts per SIMD in either precision (their launch bound; fp64: 35 ... 38 KB of LDS
-    # per workgroup admit four workgroups a compute unit, one wavefront per SIMD resident, fp32 two)
-    low = [k for k in rows if "ukf_delayed_kernel" in k["name"] and k.get("occupancy", 0) < 2]
-    if low:
-        print("ERROR: delayed-measurement kernels below two wavefronts per SIMD:", [(k["name"], k.get("vgpr")) for k in low])
-        return 1
-    # the conditioning kernels (their launch bound; fp64: 15.5 ... 16.8 KB of LDS per workgroup, fp32 half of it)
-    low = [k for k in rows if "ukf_condition_kernel" in k["name"] and k.get("occupancy", 0) < 2]
-    if low:
-        print("ERROR: conditioning kernels below two wavefronts per SIMD:", [(k["name"], k.get("vgpr")) for k in low])
-        return 1
-    # and the forecast kernels (their launch bound; fp64: 21 ... 23 KB of LDS per workgroup, fp32 half of it)
-    low = [k for k in rows if "ukf_forecast_kernel" in k["name"] and k.get("occupancy", 0) < 2]
-    if low:
-        print("ERROR: forecast kernels below two wavefronts per SIMD:", [(k["name"], k.get("vgpr")) for k in low])
-        return 1
+    for frags, excluded, floor, what, kind in FLOORS:
+        if kind == TUNED and "--no-occupancy-floor" in sys.argv:
+            continue
+        low = [k for k in rows if any(frag in k["name"] for frag in frags) and not any(frag in k["name"] for frag in excluded)
+               and k.get("occupancy", 0) < floor]
+        if low:
+            print(f"ERROR: {what} below their floor of {floor} wavefronts per SIMD:",
+                  [(k["name"], k.get("vgpr"), k.get("occupancy")) for k in low])
+            return 1
     return 0
 
 
