@@ -199,6 +199,28 @@ public:
                                  z_pred, S, innov, maha, loglik, st.data()));
         return st;
     }
+    /** Bearing measurements (ukf_batch.h, "bearing measurements"): ukf->update(z, h, Q) with a direction on the sphere S^2 --
+     *  h(X) = d(X) / |d(X)| for one of the UKFB_BEARING_* models, the mean iterated on the sphere, a two-dimensional noise.
+     *  The arrays of ukfb_sensor_in with the header's meaning for bearings (z a direction, not necessarily of unit length; Q the
+     *  3 x 3 covariance of the direction noise, of which the tangent part enters); commit = false is read-only (only `out` is
+     *  written).  Stream-ordered. */
+    void integrateBearingMeasurementDev(int model_uniform, const ukfb_sensor_in& in, bool commit = true, const ukfb_sensor_out* out = NULL)
+    {
+        check(ukfb_update_bearing_dev(engine, model_uniform, &in, commit ? 1 : 0, out));
+    }
+    /** host arrays, shaped as for integrateSensorMeasurement; z_pred [N][3] the predicted unit vector, S [N][3][3] of rank 2,
+     *  innov [N][3] the sphere logarithm; returns the status */
+    std::vector<uint32_t> integrateBearingMeasurement(int model, const double* z, const double* Q, const double* mount_uniform = NULL,
+                                                      const double* point_uniform = NULL, const double* mount = NULL,
+                                                      const double* point = NULL, const int32_t* model_per_filter = NULL,
+                                                      bool commit = true, double* z_pred = NULL, double* S = NULL, double* innov = NULL,
+                                                      double* maha = NULL, double* loglik = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_update_bearing(engine, model, model_per_filter, z, Q, mount, mount_uniform, point, point_uniform, commit ? 1 : 0,
+                                  z_pred, S, innov, maha, loglik, st.data()));
+        return st;
+    }
     /** User-defined measurement models (ukf_batch.h, "user-defined measurement models"): ukf->update(z, h, Q) for an h of the
      *  caller's.  sigmaPointsDev exports every filter's sigma points, filter-major: X_out_dev [N][2 D + 1][S] (point 0 = mu,
      *  1 + 2 j = mu (+) L col j, 2 + 2 j = mu (+) (-L col j)), delta_out_dev [N][2 D + 1][D] the tangent offsets; either may be

@@ -880,6 +880,62 @@ int ukfb_update_sensor(ukfb_engine* e, int model, const int32_t* model_per_filte
                        const double* point /* or NULL */, const double* point_uniform /* or NULL */, int commit,
                        double* z_pred, double* S, double* innov, double* maha, double* loglik, uint32_t* status);
 
+/* ---- bearing measurements: directions on the sphere S^2 ------------------------------------------------------------------ */
+/* ukf->update(z, h, Q) for sensors that measure a DIRECTION: a camera pixel of a known landmark, a USBL or sonar bearing, a
+ * sun or star sensor, a magnetometer whose magnitude is not trusted.  The measurement is a unit vector in the sensor frame, a
+ * point of the manifold S^2 (ukfom: MTK::S2): its noise is two-dimensional, its mean is iterated on the sphere and its
+ * differences are sphere logarithms.  Conventions (q, R(q) x, MOUNT = r[3], qs[4], POINT = b[3]) as for the sensor-frame
+ * measurements above.  h(X) = d(X) / |d(X)| with
+ *   id  engine  d(X)
+ *   0   Pose    R(qs)^T (R(q)^T (b - p) - r)      the direction to a known point b
+ *   1   Pose    R(qs)^T R(q)^T b                  a nav-frame direction b (sun, field)
+ *   2   Orient  R(qs)^T R(q)^T b                  the same for OrientationState
+ * POSE_POINT reads r, qs, b; the NAV_DIRECTION models qs, b.  Entries a model does not read may be NaN and never meet
+ * arithmetic.  A negative per-filter id: no measurement for that filter (untouched, INACTIVE); so is an id of the other
+ * engine's model or beyond 2.  Such a UNIFORM id is UKFB_ERR_WRONG_MODEL.
+ * ukfb_sensor_in / ukfb_sensor_out are reused; what their fields mean HERE:
+ *   z_dev   [capacity][3]  the measured direction; it need not be normalised, the call uses z^ = z / |z|
+ *   Q_dev   [capacity][9] or ONE 3x3 with q_is_uniform: the covariance of the direction noise as a 3-vector in the sensor
+ *           frame, symmetric, the lower triangle is read.  Only its tangent part at the predicted direction enters: P Q P with
+ *           P = I - z-bar z-bar^T.  The caller never sees a tangent basis, and no result depends on one.
+ *   z_pred  [capacity][3]  z-bar, a unit vector
+ *   S       [capacity][9]  Sigma_z + P Q P: 3 x 3 of rank 2 in the ambient frame (S z-bar = 0), WITHOUT the z-bar z-bar^T term below
+ *   innov   [capacity][3]  nu = log_z-bar(z^), nu perpendicular to z-bar
+ *   maha    d^2 = nu^T S3^-1 nu;  loglik = -0.5 (d^2 + ln det S3 + 2 ln 2 pi)
+ * Sphere maps, for unit u, v and w perpendicular to u:
+ *   log_u(v) = theta t / |t|, t = v - (u.v) u, theta = atan2(|u x v|, u.v); 0 when t = 0 and u.v > 0.  At the exact antipode
+ *              (t = 0, u.v < 0) any tangent vector of length pi: the direction is unspecified, the result finite.
+ *   exp_u(w) = cos|w| u + sinc|w| w, renormalised.
+ * Per filter the steps are those of ukf::update with the measurement manifold S^2:
+ *   1. L = chol(Sigma), sigma points X_i, Z_i = h(X_i);
+ *   2. z-bar = the iterated mean from Z_0: m = 1/(2 D + 1) sum_i log_ref(Z_i), ref <- exp_ref(m), until |m| <= mean_tol or
+ *      mean_max_iter trips (WARN_MEAN_NOCONV); the step is applied before it is judged.  Unlike on R^m this really iterates;
+ *   3. w_i = log_z-bar(Z_i); Sigma_z = 1/2 sum w_i w_i^T (3 x 3, Sigma_z z-bar = 0); C = 1/2 sum (X_i (-) mu) w_i^T (D x 3);
+ *   4. S3 = Sigma_z + P Q P + z-bar z-bar^T: positive definite with a unit eigenvalue along z-bar; d^2, ln det S3 and
+ *      K = C S3^-1 equal the 2 x 2 quantities in ANY orthonormal tangent basis B (S2 = B^T (Sigma_z + Q) B, ...), because S3 is
+ *      block diagonal in (B, z-bar) and nu and the columns of C^T have no component along z-bar;
+ *   5. nu = log_z-bar(z^), d^2 and loglik as above;
+ *   6. the gate of ukfb_update_dev;
+ *   7. Sigma~ = Sigma - Y Y^T (Y = C Ls^-T, S3 = Ls Ls^T); (mu, Sigma) = applyDelta(mu, Sigma~, K nu).
+ * commit = 0, the status rules, NaN to the float outputs of a refused filter, "never changes a bit of another filter", stream
+ * ordering, no allocation at call time and the fp32 / wide_arithmetic behaviour are those of ukfb_update_sensor_dev.  In
+ * addition: ERR_NONFINITE_MEAS also covers |z|^2 zero or not finite (and here every entry of z and Q is judged); a sigma point
+ * whose |d|^2 is zero or not finite (a landmark exactly at the sensor, b = 0) makes S non-finite: ERR_CHOLESKY, the state is
+ * kept.  No new status bit. */
+enum ukfb_bearing_model {
+    UKFB_BEARING_NONE = -1,
+    UKFB_BEARING_POSE_POINT = 0,           /* Pose    d = R(qs)^T (R(q)^T (b - p) - r)   direction to a known point        */
+    UKFB_BEARING_POSE_NAV_DIRECTION = 1,   /* Pose    d = R(qs)^T R(q)^T b               a nav-frame direction (sun, field) */
+    UKFB_BEARING_ORIENT_NAV_DIRECTION = 2  /* Orient  d = R(qs)^T R(q)^T b                                                  */
+};
+/* out may be NULL with commit = 1 */
+int ukfb_update_bearing_dev(ukfb_engine* e, int model_uniform, const ukfb_sensor_in* in, int commit, const ukfb_sensor_out* out);
+/* host arrays of doubles, shaped as for ukfb_update_sensor.  Synchronises. */
+int ukfb_update_bearing(ukfb_engine* e, int model, const int32_t* model_per_filter /* or NULL */, const double* z, const double* Q,
+                        const double* mount /* or NULL */, const double* mount_uniform /* or NULL */,
+                        const double* point /* or NULL */, const double* point_uniform /* or NULL */, int commit,
+                        double* z_pred, double* S, double* innov, double* maha, double* loglik, uint32_t* status);
+
 /* ---- user-defined measurement models: sigma-point export, sampled update ------------------------------------------------- */
 /* ukf->update(z, h, Q) for an h the library does not know (four DVL beams, a camera pixel of a known landmark, range plus
  * range rate, two antennas at once, ...).  The library hands out the sigma points of every filter, the caller evaluates h on

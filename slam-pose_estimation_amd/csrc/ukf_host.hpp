@@ -431,6 +431,44 @@ constexpr int sensor_filter_scalars(int S, int D) {
 using SensorGeometry = RowGeometry;
 inline RowGeometry sensor_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(sensor_filter_scalars(S, D), capacity, compute_size); }
 
+// ---- bearing measurements (ukfb_update_bearing_dev) -----------------------------------------------------------------------
+// A direction on the sphere S^2 in the sensor frame, h = d / |d|: ids 0, 1 are the Pose engine's, 2 the OrientationState
+// engine's (UKFB_BEARING_*).  The input record is the sensor-frame measurements' (SENSOR_INPUT_*): every model reads all of z
+// and Q, qs and b; only POSE_POINT reads the lever arm r.
+constexpr int BEARING_MODELS = 3, BEARING_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
+constexpr bool bearing_model_ok(int engine_model, int64_t id) {
+    return engine_model == UKFB_MODEL_POSE ? (id == UKFB_BEARING_POSE_POINT || id == UKFB_BEARING_POSE_NAV_DIRECTION)
+                                           : id == UKFB_BEARING_ORIENT_NAV_DIRECTION;
+}
+constexpr bool bearing_reads_lever(int64_t id) { return id == UKFB_BEARING_POSE_POINT; }
+constexpr bool bearing_input_used(int64_t id, int i) {
+    return (id < 0 || id >= BEARING_MODELS || i < 0 || i >= SENSOR_INPUT_SCALARS) ? false
+         : (i >= SENSOR_INPUT_MOUNT && i < SENSOR_INPUT_MOUNT + 3) ? bearing_reads_lever(id) : true;
+}
+// per_filter_models: the ids come from a device array (checked per filter by the kernel: an id the engine's model does not have
+// marks the filter INACTIVE); otherwise the one id must be the engine model's
+inline Verdict check_bearing_args(int engine_model, bool per_filter_models, int model_uniform, const ukfb_sensor_in* in, int commit,
+                                  const ukfb_sensor_out* out) {
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    if (!in->z_dev || !in->Q_dev) return {UKFB_ERR_INVALID_ARG, "z_dev and Q_dev must not be NULL"};
+    if (in->q_is_uniform != 0 && in->q_is_uniform != 1) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
+    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    if (!per_filter_models && !bearing_model_ok(engine_model, model_uniform))
+        return {UKFB_ERR_WRONG_MODEL, "bearing model id not valid for this engine (Pose: 0, 1; OrientationState: 2)"};
+    if (commit == 0 && (!out || (!out->z_pred && !out->S && !out->innov && !out->maha && !out->loglik && !out->status)))
+        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
+    return {};
+}
+// LDS of one filter, in scalars of the compute type (ukf_bearing.hpp, BearingLayout): the regions of the sensor-frame kernel --
+// the factor with its reciprocal pivots, the delta table of the commit (2 D + 1 rows; the D x 3 half differences W and the
+// D x 3 solved cross-covariance Y alias it, four scalars a row), the state's record (mean padded to 16, packed covariance
+// padded to even), the input record (32) and the sink of lane-predicated stores (16); rounded up to a multiple of four.
+// The sphere side (the unit vectors, their logarithms, the 3 x 3 statistics) lives in registers.
+constexpr int bearing_filter_scalars(int S, int D) {
+    return S > 16 ? -1 : (D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 32 + 16 + 3) / 4 * 4;
+}
+inline RowGeometry bearing_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(bearing_filter_scalars(S, D), capacity, compute_size); }
+
 // ---- user-defined measurement models (ukfb_sigma_points_dev, ukfb_update_sampled_dev) --------------------------------------
 // The caller evaluates h on the exported sigma points; the update is finished from the samples Z_i = h(X_i), m = 1 ...
 // SAMPLED_MAX_M, one m for the call.

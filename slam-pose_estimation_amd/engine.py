@@ -66,6 +66,8 @@ EXPORTS = [
     "ukfb_update_state_dev", "ukfb_update_state", "ukfb_pose_update_body_states",
     # sensor-frame measurements: lever arms, ranges, landmark fixes, nav-frame vectors
     "ukfb_update_sensor_dev", "ukfb_update_sensor",
+    # bearing measurements: directions on the sphere S^2
+    "ukfb_update_bearing_dev", "ukfb_update_bearing",
     # user-defined measurement models: sigma-point export, the update finished from the caller's samples
     "ukfb_sigma_points_dev", "ukfb_update_sampled_dev", "ukfb_sigma_points", "ukfb_update_sampled",
     # user-defined process models: the prediction finished from the caller's propagated sigma points
@@ -97,6 +99,10 @@ SENSOR_NONE = -1
 SENSOR_POSE_POSITION, SENSOR_POSE_RANGE, SENSOR_POSE_POINT, SENSOR_POSE_VELOCITY, SENSOR_POSE_NAV_VELOCITY = 0, 1, 2, 3, 4
 SENSOR_ORIENT_VELOCITY, SENSOR_ORIENT_NAV_VECTOR, SENSOR_ORIENT_SPECIFIC_FORCE = 5, 6, 7
 SENSOR_MOUNT_IDENTITY = (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0)   # r = 0, qs = (0, 0, 0, 1)
+
+# models of ukfb_update_bearing_dev: 0, 1 the Pose engine's, 2 the OrientationState engine's
+BEARING_NONE = -1
+BEARING_POSE_POINT, BEARING_POSE_NAV_DIRECTION, BEARING_ORIENT_NAV_DIRECTION = 0, 1, 2
 
 # largest measurement dimension of ukfb_update_sampled_dev (UKFB_SAMPLED_MAX_M)
 SAMPLED_MAX_M = 6
@@ -770,6 +776,40 @@ class BatchUKF:
                                           _pd(mp), _pd(mu_), _pd(pp), _pd(pu), C.c_int(1 if commit else 0), _pd(o["z_pred"]),
                                           _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]),
                                           o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_update_sensor")
+        return o
+
+    # ---- bearing measurements: z [capacity, 3] a direction, Q [capacity, 9] (or 9 scalars), mount [capacity, 7], point [capacity, 3]
+    def update_bearing_dev(self, model: int, z_dev, Q_dev, q_is_uniform: bool = False, model_dev=None, mount_dev=None,
+                           mount=SENSOR_MOUNT_IDENTITY, point_dev=None, point=(0.0, 0.0, 0.0), commit: bool = True, z_pred=None,
+                           S=None, innov=None, maha=None, loglik=None, status=None):
+        """ukfom's update with a direction on the sphere S^2 (BEARING_* constants; model_dev int32 [capacity] = an id per
+        filter, negative: none).  z need not be normalised; Q is the 3 x 3 covariance of the direction noise in the sensor
+        frame, of which the tangent part at the predicted direction enters.  mount, point, commit and the keyword outputs as
+        for update_sensor_dev; z_pred is a unit vector, S = Sigma_z + P Q P (3 x 3, rank 2), innov the sphere logarithm.
+        Stream-ordered."""
+        ptr = lambda x: None if x is None else _devptr(x).value
+        sin = SensorIn(ptr(model_dev), ptr(z_dev), ptr(Q_dev), 1 if q_is_uniform else 0, ptr(mount_dev),
+                       (C.c_double * 7)(*[float(v) for v in mount]), ptr(point_dev), (C.c_double * 3)(*[float(v) for v in point]))
+        out = SensorOut(ptr(z_pred), ptr(S), ptr(innov), ptr(maha), ptr(loglik), ptr(status))
+        _chk(self._lib.ukfb_update_bearing_dev(self._h, C.c_int(int(model)), C.byref(sin), C.c_int(1 if commit else 0), C.byref(out)),
+             "ukfb_update_bearing_dev")
+
+    def update_bearing(self, model, z, Q, mount=SENSOR_MOUNT_IDENTITY, point=(0.0, 0.0, 0.0), commit: bool = True):
+        """Host arrays, shaped as for update_sensor.  Returns a dict of NumPy arrays: z_pred [n, 3], S [n, 3, 3], innov [n, 3],
+        maha [n], loglik [n], status [n]; synchronises"""
+        n = self.capacity
+        z = _f64(z, (n, 3)); Q = _f64(Q, (n, 3, 3))
+        per = None if np.isscalar(model) else np.ascontiguousarray(model, dtype=np.int32).reshape(n)
+        mount = _f64(mount); point = _f64(point)
+        mp, mu_ = (mount.reshape(n, 7), None) if mount.ndim == 2 else (None, mount.reshape(7))
+        pp, pu = (point.reshape(n, 3), None) if point.ndim == 2 else (None, point.reshape(3))
+        o = {"z_pred": np.empty((n, 3)), "S": np.empty((n, 3, 3)), "innov": np.empty((n, 3)), "maha": np.empty(n),
+             "loglik": np.empty(n), "status": np.empty(n, dtype=np.uint32)}
+        _chk(self._lib.ukfb_update_bearing(self._h, C.c_int(0 if per is not None else int(model)),
+                                           per.ctypes.data_as(C.POINTER(C.c_int32)) if per is not None else None, _pd(z), _pd(Q),
+                                           _pd(mp), _pd(mu_), _pd(pp), _pd(pu), C.c_int(1 if commit else 0), _pd(o["z_pred"]),
+                                           _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]),
+                                           o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_update_bearing")
         return o
 
     # ---- user-defined measurement models: X [capacity, 2 D + 1, S], delta [capacity, 2 D + 1, D], Z [capacity, 2 D + 1, m]

@@ -1,0 +1,230 @@
+"""NumPy float64 statement of the bearing measurements of include/ukf_batch.h ("bearing measurements"): the three direction
+models, the sphere S^2 as a measurement manifold for the oracle's own pieces (on.sigma_points, on.mean_sigma_points,
+on.cov_sigma_points, on.ukf_update, which are duck-typed on the manifold), and the status rules of the header.
+A helper, not collected; tests/test_bearing_reference.py pins it.
+
+The update is stated in the 2 x 2 BASIS FORM: S2 carries an explicit orthonormal tangent basis B(u) [3, 2]; boxminus returns
+B(u)^T log_u(v), boxplus is exp_u(B(u) d), the noise is Q2 = B^T Q B at the predicted direction.  S and nu are lifted to the
+ambient frame with B for the outputs.  The kernel works in the 3-dimensional embedded form without any basis; that the two
+agree, and that no result depends on the basis, is what tests/test_bearing_reference.py checks.
+
+Conventions as tests/sensor_meas_reference.py: mount = r[3] then qs[4] (x, y, z, w); point = b[3]."""
+import numpy as np
+
+import sensor_meas_reference as sr
+from oracle import ukf_numpy as on
+
+LN_2PI = float(np.log(2.0 * np.pi))
+
+POSE_POINT, POSE_NAV_DIRECTION, ORIENT_NAV_DIRECTION = 0, 1, 2
+POSE_IDS, ORIENT_IDS = (0, 1), (2,)
+NAMES = {0: "POSE_POINT", 1: "POSE_NAV_DIRECTION", 2: "ORIENT_NAV_DIRECTION"}
+READS_LEVER = (0,)
+
+
+def ids_of(man):
+    return POSE_IDS if man is on.POSE else ORIENT_IDS
+
+
+def unit(v):
+    return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+# ------------------------------------------------------------------------------------------------ the sphere
+def s2_log(u, v):
+    """log_u(v) [..., 3] for unit u, v: theta t / |t|, t = v - (u.v) u, theta = atan2(|u x v|, u.v); 0 where t = 0"""
+    u, v = np.broadcast_arrays(np.asarray(u, dtype=np.float64), np.asarray(v, dtype=np.float64))
+    c = np.sum(u * v, axis=-1, keepdims=True)
+    t = v - c * u
+    s = np.linalg.norm(np.cross(u, v), axis=-1, keepdims=True)
+    th = np.arctan2(s, c)
+    nt = np.linalg.norm(t, axis=-1, keepdims=True)
+    return np.where(nt > 0, th * t / np.where(nt > 0, nt, 1.0), 0.0)
+
+
+def s2_exp(u, w):
+    """exp_u(w) = cos|w| u + sinc|w| w, renormalised"""
+    u, w = np.broadcast_arrays(np.asarray(u, dtype=np.float64), np.asarray(w, dtype=np.float64))
+    th = np.linalg.norm(w, axis=-1, keepdims=True)
+    sinc = np.where(th > 1e-8, np.sin(th) / np.where(th > 0, th, 1.0), 1.0 - th * th / 6.0)
+    return unit(np.cos(th) * u + sinc * w)
+
+
+def basis_duff(u):
+    """an orthonormal basis [..., 3, 2] of the tangent plane at u (Duff et al., "Building an orthonormal basis, revisited")"""
+    u = np.asarray(u, dtype=np.float64)
+    s = np.where(u[..., 2] >= 0, 1.0, -1.0)
+    a = -1.0 / (s + u[..., 2])
+    b = u[..., 0] * u[..., 1] * a
+    e1 = np.stack([1.0 + s * u[..., 0] ** 2 * a, s * b, -s * u[..., 0]], axis=-1)
+    e2 = np.stack([b, s + u[..., 1] ** 2 * a, -u[..., 1]], axis=-1)
+    return np.stack([e1, e2], axis=-1)
+
+
+def basis_rotated(angle):
+    """basis_duff turned by `angle` in the tangent plane"""
+    c, s = np.cos(angle), np.sin(angle)
+    R = np.array([[c, -s], [s, c]])
+    return lambda u: basis_duff(u) @ R
+
+
+class S2:
+    """the unit sphere with a tangent basis, in the interface of oracle.ukf_numpy._Compound (D, boxplus, boxminus)"""
+    D = 2
+    S = 3
+
+    def __init__(self, basis=basis_duff):
+        self.basis = basis
+
+    def boxminus(self, x, y):
+        x, y = np.broadcast_arrays(np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64))
+        return np.einsum("...ij,...i->...j", self.basis(y), s2_log(y, x))
+
+    def boxplus(self, x, d, scale=1.0):
+        return s2_exp(x, np.einsum("...ij,...j->...i", self.basis(x), scale * np.asarray(d, dtype=np.float64)))
+
+
+# ------------------------------------------------------------------------------------------------ the models
+def direction(mid, X, mount, point):
+    """d(X) [..., 3] before it is normalised; mount [..., 7], point [..., 3] broadcast against X's leading axes"""
+    r, qs, b = mount[..., 0:3], mount[..., 3:7], point
+    if mid == POSE_POINT:
+        return sr.rot_t(qs, sr.rot_t(X[..., 3:7], b - X[..., 0:3]) - r)
+    q = X[..., 3:7] if mid == POSE_NAV_DIRECTION else X[..., 0:4]
+    return sr.rot_t(qs, sr.rot_t(q, np.broadcast_to(b, q.shape[:-1] + (3,))))
+
+
+def used_inputs(mid):
+    """(entries of mount [7], entries of point [3]) that model `mid` reads; every model reads all of z and Q"""
+    mm = np.ones(7, bool)
+    mm[0:3] = mid in READS_LEVER
+    return mm, np.ones(3, bool)
+
+
+def mean_steps(manz, Z, tol=on.MEAN_TOL, max_it=on.MEAN_MAX_IT):
+    """the iteration of on.mean_sigma_points once more, for what it does not return -> (trips [B]: steps whose norm exceeded
+    tol, norms [B, trips.max() + 1]: the norm of every step a filter made, NaN beyond its last)"""
+    B = Z.shape[0]
+    ref = Z[:, 0].copy()
+    active, it, norms = np.ones(B, bool), np.zeros(B, np.int64), []
+    while active.any():
+        md = manz.boxminus(Z, ref[:, None, :]).mean(axis=1)
+        nrm = np.sqrt(np.sum(md * md, axis=-1))
+        norms.append(np.where(active, nrm, np.nan))
+        ref = np.where(active[:, None], manz.boxplus(ref, md), ref)
+        big = nrm > tol
+        it = np.where(active & big, it + 1, it)
+        active = active & big & (it < max_it)
+    return it, np.stack(norms, axis=1)
+
+
+def update_bearing(man, mu, cov, models, z, Q, mount, point, gate_chi2=-1.0, initialised=None, tol=on.MEAN_TOL,
+                   max_it=on.MEAN_MAX_IT, basis=basis_duff):
+    """mu [B, S], cov [B, D, D], models an int or [B], z [B, 3], Q [B, 3, 3] (or [3, 3]), mount [B, 7] (or [7]), point [B, 3]
+    (or [3]) -> dict(mu, cov, z_pred [B, 3], S [B, 3, 3], innov [B, 3], maha [B], loglik [B], status [B]) and, for the tests'
+    own assertions, trips [B] (mean steps above tol), spread [B] (the largest sigma-point angle from z-bar), logdet [B] and
+    tol_margin [B] (the smallest relative distance of a mean step's norm from tol); NaN / 0 for filters that were not scored."""
+    B = mu.shape[0]
+    models = np.broadcast_to(np.asarray(models, dtype=np.int64), (B,))
+    z = np.asarray(z, dtype=np.float64)
+    Q = np.broadcast_to(np.asarray(Q, dtype=np.float64), (B, 3, 3))
+    mount = np.broadcast_to(np.asarray(mount, dtype=np.float64), (B, 7))
+    point = np.broadcast_to(np.asarray(point, dtype=np.float64), (B, 3))
+    init = np.ones(B, bool) if initialised is None else np.asarray(initialised, dtype=bool)
+    manz = S2(basis)
+    o = {"mu": mu.copy(), "cov": cov.copy(), "z_pred": np.full((B, 3), np.nan), "S": np.full((B, 3, 3), np.nan),
+         "innov": np.full((B, 3), np.nan), "maha": np.full(B, np.nan), "loglik": np.full(B, np.nan),
+         "status": np.zeros(B, dtype=np.uint32), "trips": np.zeros(B, np.int64), "spread": np.full(B, np.nan),
+         "logdet": np.full(B, np.nan), "tol_margin": np.full(B, np.nan)}
+    valid = np.isin(models, ids_of(man))
+    o["status"][~init] = on.ST_UNINITIALISED
+    o["status"][init & ~valid] = on.ST_INACTIVE
+    for mid in np.unique(models[init & valid]):
+        mid = int(mid)
+        idx = np.nonzero(init & valid & (models == mid))[0]
+        um, up = used_inputs(mid)
+        with np.errstate(over="ignore", invalid="ignore"):
+            zz = np.sum(z[idx] * z[idx], axis=1)
+        fin = (np.isfinite(z[idx]).all(axis=1) & np.isfinite(Q[idx]).all(axis=(1, 2)) & np.isfinite(mount[idx][:, um]).all(axis=1) &
+               np.isfinite(point[idx][:, up]).all(axis=1) & np.isfinite(zz) & (zz > 0))
+        o["status"][idx[~fin]] = on.ST_ERR_NONFINITE_MEAS
+        idx = idx[fin]
+        if idx.size == 0:
+            continue
+        zhat = unit(z[idx])
+        Ql = np.tril(Q[idx])
+        Q3 = Ql + np.swapaxes(np.tril(Q[idx], -1), 1, 2)   # symmetric from the lower triangle
+        # entries the model does not read never meet arithmetic
+        mt = np.where(um, mount[idx], sr.IDENTITY_MOUNT)[:, None, :]
+        pt = point[idx][:, None, :]
+        X, ok = on.sigma_points(man, mu[idx], np.where(_pd(cov[idx])[:, None, None], cov[idx], np.eye(man.D)))
+        ok = _pd(cov[idx])
+        d = direction(mid, X, mt, pt)
+        with np.errstate(over="ignore", invalid="ignore"):
+            d2n = np.sum(d * d, axis=-1)
+        degen = ~(np.isfinite(d2n) & (d2n > 0)).all(axis=1)   # a sigma point with |d|^2 zero or not finite: S is not finite
+        safe = np.array([1.0, 0.0, 0.0])
+
+        def hh(Xs, degen=degen, mt=mt, pt=pt, mid=mid):
+            dd = direction(mid, Xs, mt if Xs.ndim == 3 else mt[:, 0], pt if Xs.ndim == 3 else pt[:, 0])
+            sel = degen[:, None, None] if Xs.ndim == 3 else degen[:, None]
+            return unit(np.where(sel, safe, dd))
+        Z = hh(X)
+        mz, _ = on.mean_sigma_points(manz, Z, tol, max_it)
+        trips, steps = mean_steps(manz, Z, tol, max_it)
+        Bz = basis(mz)
+        Q2 = np.swapaxes(Bz, 1, 2) @ Q3 @ Bz
+        S = on.cov_sigma_points(manz, mz, Z) + Q2
+        _, ok_s = on.cholesky_lower(S)
+        ok_s &= ok & ~degen
+        eye = np.eye(2)
+        S_safe = np.where(ok_s[:, None, None], S, eye)
+        innov = manz.boxminus(zhat, mz)
+        d2 = np.einsum("bi,bij,bj->b", innov, np.linalg.inv(S_safe), innov)
+        logdet = np.linalg.slogdet(S_safe)[1]
+        # (a filter whose Sigma or S is not positive definite gets the identity: its result is discarded below)
+        m2, C2, s = on.ukf_update(man, manz, mu[idx], np.where(ok[:, None, None], cov[idx], np.eye(man.D)), zhat, hh,
+                                  np.where(ok_s[:, None, None], Q2, eye), tol, max_it, gate_chi2)
+        s = np.where(ok_s, s, s | on.ST_ERR_CHOLESKY).astype(np.uint32)
+        s = np.where((s & on.ST_ERR_CHOLESKY) != 0, s & ~np.uint32(on.ST_REJECTED_GATE), s).astype(np.uint32)
+        s = np.where(ok, s, s & ~np.uint32(on.ST_WARN_MEAN_NOCONV)).astype(np.uint32)   # no sigma points, no mean
+        commit = (s & (on.ST_ERR_CHOLESKY | on.ST_REJECTED_GATE)) == 0
+        scored = (s & on.ST_ERR_CHOLESKY) == 0
+        o["mu"][idx[commit]], o["cov"][idx[commit]] = m2[commit], C2[commit]
+        sc = idx[scored]
+        o["z_pred"][sc] = mz[scored]
+        o["S"][sc] = (Bz @ S @ np.swapaxes(Bz, 1, 2))[scored]
+        o["innov"][sc] = np.einsum("bij,bj->bi", Bz, innov)[scored]
+        o["maha"][sc] = d2[scored]
+        o["logdet"][sc] = logdet[scored]
+        o["loglik"][sc] = -0.5 * (d2[scored] + logdet[scored] + 2.0 * LN_2PI)
+        o["trips"][sc] = trips[scored]
+        o["spread"][sc] = np.max(np.linalg.norm(s2_log(mz[:, None, :], Z), axis=-1), axis=1)[scored]
+        o["tol_margin"][sc] = np.nanmin(np.abs(steps - tol) / tol, axis=1)[scored]
+        o["status"][idx] = s
+    return o
+
+
+def _pd(cov):
+    return on.cholesky_lower(cov)[1]
+
+
+# ------------------------------------------------------------------------------------------------ the tests' input family
+def make_inputs(man, mu, lo, hi, dtype=np.float64, seed=5):
+    """-> (mount [n, 7], point [n, 3], {id: z [n, 3]}, Q [n, 3, 3]) as an engine of storage `dtype` holds them: mounts
+    r ~ U(-1, 1)^3, qs = exp(U(-1, 1)^3); points lo ... hi metres from the body origin (OrientationState: a nav-frame vector of
+    that length); z = unit(h(mu) + 0.01 N(0, 1)) U(0.5, 2), so that the normalisation is exercised; Q = 0.01^2 (I + 0.3 A A^T)"""
+    n = mu.shape[0]
+    rng = np.random.default_rng(seed)
+    st = lambda x: np.asarray(x, dtype=np.float64).astype(dtype).astype(np.float64)   # noqa: E731
+    mount = np.concatenate([rng.uniform(-1.0, 1.0, (n, 3)), on.so3_exp(rng.uniform(-1.0, 1.0, (n, 3)))], axis=1)
+    away = unit(rng.standard_normal((n, 3))) * rng.uniform(lo, hi, (n, 1))
+    point = (mu[:, 0:3] + away) if man is on.POSE else away
+    mount, point = st(mount), st(point)
+    z = {}
+    for mid in ids_of(man):
+        mt = np.where(used_inputs(mid)[0], mount, sr.IDENTITY_MOUNT)
+        z[mid] = st(unit(unit(direction(mid, mu, mt, point)) + 0.01 * rng.standard_normal((n, 3))) * rng.uniform(0.5, 2.0, (n, 1)))
+    A = rng.standard_normal((n, 3, 3))
+    Q = st(0.01 ** 2 * (np.eye(3) + 0.3 * A @ np.swapaxes(A, 1, 2)))
+    return mount, point, z, Q
