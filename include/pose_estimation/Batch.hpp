@@ -221,6 +221,31 @@ public:
                                   z_pred, S, innov, maha, loglik, st.data()));
         return st;
     }
+    /** Sensor-frame association (ukf_batch.h, "sensor-frame association"): in.candidates samples per filter scored through a
+     *  UKFB_SENSOR_* model in one launch, the nearest candidate inside the gate chosen and, with commit, the update finished
+     *  with it.  in.point_per_candidate = 0: every candidate is a detection of the one point; 1: candidate k is a fix of its
+     *  own landmark or beacon in.point_dev [candidates][N][3].  commit = false is read-only (only `out` is written).
+     *  Stream-ordered. */
+    void associateSensorMeasurementDev(int model_uniform, const ukfb_associate_in& in, bool commit = true, const ukfb_associate_out* out = NULL)
+    {
+        check(ukfb_associate_sensor_dev(engine, model_uniform, &in, commit ? 1 : 0, out));
+    }
+    /** host arrays: z [candidates][N][3], Q [N][3][3]; mount / point as for integrateSensorMeasurement, with
+     *  point_per_candidate point [candidates][N][3]; z_pred [H][N][3], S [H][N][3][3] (H = candidates per hypothesis, else 1),
+     *  innov [candidates][N][3], maha / loglik [candidates][N], n_gated [N] or NULL; best [N] receives the chosen candidate
+     *  (-1: none); returns the status */
+    std::vector<uint32_t> associateSensorMeasurement(int model, int candidates, const double* z, const double* Q, int32_t* best,
+                                                     const double* mount_uniform = NULL, const double* point_uniform = NULL,
+                                                     const double* mount = NULL, const double* point = NULL,
+                                                     bool point_per_candidate = false, const int32_t* model_per_filter = NULL,
+                                                     bool commit = true, double* z_pred = NULL, double* S = NULL, double* innov = NULL,
+                                                     double* maha = NULL, double* loglik = NULL, int32_t* n_gated = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_associate_sensor(engine, model, model_per_filter, candidates, z, Q, mount, mount_uniform, point, point_uniform,
+                                    point_per_candidate ? 1 : 0, commit ? 1 : 0, z_pred, S, innov, maha, loglik, best, n_gated, st.data()));
+        return st;
+    }
     /** User-defined measurement models (ukf_batch.h, "user-defined measurement models"): ukf->update(z, h, Q) for an h of the
      *  caller's.  sigmaPointsDev exports every filter's sigma points, filter-major: X_out_dev [N][2 D + 1][S] (point 0 = mu,
      *  1 + 2 j = mu (+) L col j, 2 + 2 j = mu (+) (-L col j)), delta_out_dev [N][2 D + 1][D] the tangent offsets; either may be

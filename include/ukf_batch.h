@@ -936,6 +936,72 @@ int ukfb_update_bearing(ukfb_engine* e, int model, const int32_t* model_per_filt
                         const double* point /* or NULL */, const double* point_uniform /* or NULL */, int commit,
                         double* z_pred, double* S, double* innov, double* maha, double* loglik, uint32_t* status);
 
+/* ---- sensor-frame association: K candidates per filter in one launch ------------------------------------------------------ */
+/* The sensor-frame measurements above (model ids 0 ... 7 of enum ukfb_sensor_model, the same h, steps and conventions) scored
+ * against up to UKFB_ASSOCIATE_MAX_CANDIDATES candidate samples per filter, the nearest candidate inside the gate chosen, and
+ * with commit = 1 the update finished with it: which of several USBL or sonar returns belongs to this track, which map
+ * landmark a POSE_POINT fix refers to, which beacon a POSE_RANGE belongs to.  Two modes, one per call:
+ *   point_per_candidate = 0  SHARED-H: K detections z[k] against one hypothesis (the point is per filter or uniform, as in
+ *                            ukfb_sensor_in).  Steps 1 - 4 of ukfb_update_sensor_dev run once, step 5 per candidate.  H = 1.
+ *   point_per_candidate = 1  PER-HYPOTHESIS: candidate k pairs z[k] with the landmark or beacon b[k].  Step 1 runs once,
+ *                            steps 2 - 5 per candidate on the same sigma points.  H = candidates.  For a filter whose model
+ *                            does not read b the flag has no effect (its H hypotheses are equal) and the points are never read.
+ * A candidate is ABSENT when an entry among the first m of z[k] -- or, per-hypothesis, an entry of the b[k] its model reads --
+ * is not finite: it scores NaN and is never best.  This is how a ragged detection list is padded.  A candidate whose own S is
+ * not positive definite scores NaN and is never best.
+ *   best     the candidate with the smallest finite d^2, with cfg.gate_chi2 >= 0 only among those with d^2 <= gate_chi2 (the
+ *            update's own comparison); equal d^2: the lower index; -1: none (ukfb_innovation_dev's rule)
+ *   n_gated  the number of finite candidates inside the gate (all finite ones when the gate is off): above 1 the association
+ *            is ambiguous
+ * commit = 1: steps 6 - 7 run with the best candidate's nu (per-hypothesis: and its Y, Ls); mean, covariance and the engine's
+ * own status array are written.  commit = 0: READ-ONLY on the engine, bit for bit, like ukfb_innovation_dev.
+ * Status of THIS call (out->status, and with commit = 1 the engine's status array):
+ *   UNINITIALISED, INACTIVE, WARN_MEAN_NOCONV  as in ukfb_update_sensor_dev (per-hypothesis: any present candidate's mean);
+ *   ERR_NONFINITE_MEAS  a non-finite Q or mount entry the model reads, or EVERY candidate is absent;
+ *   ERR_CHOLESKY        Sigma fails, no present candidate has a positive-definite S, or the accepted update's Sigma~ fails;
+ *   REJECTED_GATE       some candidate is finite and none is inside the gate; the scores are still written.
+ * A filter with one of UNINITIALISED, INACTIVE, ERR_NONFINITE_MEAS, ERR_CHOLESKY keeps every bit, writes NaN to its float
+ * outputs (padding entries of innov: 0) and -1 / 0 to best / n_gated; no filter ever changes a bit of another.  Stream-ordered,
+ * no host synchronisation, no allocation at call time; the same kernel serves every lanes_per_filter setting; fp32 engines
+ * compute in fp32, with wide_arithmetic in fp64 (stored fp32).  A uniform id of the other engine's models is
+ * UKFB_ERR_WRONG_MODEL; candidates outside 1 ... 32 is UKFB_ERR_OUT_OF_RANGE and writes nothing.  Bearings on S^2, per-candidate
+ * Q or mount, weighted association and assignment across filters are not served.  Device groups: per shard through
+ * ukfb_group_shard. */
+#define UKFB_ASSOCIATE_MAX_CANDIDATES 32
+typedef struct ukfb_associate_in {   /* device pointers in engine precision; the *_uniform values are host doubles, by value */
+    const int32_t* model_dev;        /* [capacity] model id per filter, or NULL: the call's model_uniform serves every filter */
+    int            candidates;       /* K = 1 ... UKFB_ASSOCIATE_MAX_CANDIDATES                                               */
+    const void*    z_dev;            /* [candidates][capacity][3]  the slot layout of ukfb_innovation_dev                     */
+    const void*    Q_dev;            /* [capacity][9] row-major 3x3, or ONE 3x3 with q_is_uniform (as ukfb_sensor_in)         */
+    int            q_is_uniform;
+    const void*    mount_dev;        /* [capacity][7] r, then qs (x, y, z, w); NULL: mount_uniform serves every filter        */
+    double         mount_uniform[7];
+    const void*    point_dev;        /* point_per_candidate = 0: [capacity][3], or NULL: point_uniform serves every filter;
+                                        point_per_candidate = 1: [candidates][capacity][3], not NULL                          */
+    double         point_uniform[3];
+    int            point_per_candidate;   /* 0: shared-h mode; 1: per-hypothesis mode                                         */
+} ukfb_associate_in;
+typedef struct ukfb_associate_out {  /* device pointers, engine precision; any may be NULL.  H: see above                     */
+    void*     z_pred;   /* [H][capacity][3]           z-bar: first m entries (rest 0)                                         */
+    void*     S;        /* [H][capacity][9]           row-major 3x3, leading m x m block = S, rest 0                          */
+    void*     innov;    /* [candidates][capacity][3]  nu = z - z-bar, first m entries (rest 0)                                */
+    void*     maha;     /* [candidates][capacity]     d^2 = nu^T S^-1 nu                                                      */
+    void*     loglik;   /* [candidates][capacity]     -0.5 (d^2 + ln det S + m ln 2 pi)                                       */
+    int32_t*  best;     /* [capacity]                                                                                         */
+    int32_t*  n_gated;  /* [capacity]                                                                                         */
+    uint32_t* status;   /* [capacity]                 UKFB_ST_* of THIS call                                                  */
+} ukfb_associate_out;
+/* out may be NULL with commit = 1 */
+int ukfb_associate_sensor_dev(ukfb_engine* e, int model_uniform, const ukfb_associate_in* in, int commit, const ukfb_associate_out* out);
+/* host arrays of doubles: z [candidates][capacity][3], Q [capacity][3][3]; model_per_filter, mount, mount_uniform as for
+ * ukfb_update_sensor; point [capacity][3] (or, with point_per_candidate, [candidates][capacity][3]) or NULL, then point_uniform
+ * [3] (NULL: 0).  Outputs shaped as in ukfb_associate_out: any may be NULL.  Synchronises. */
+int ukfb_associate_sensor(ukfb_engine* e, int model, const int32_t* model_per_filter /* or NULL */, int candidates, const double* z,
+                          const double* Q, const double* mount /* or NULL */, const double* mount_uniform /* or NULL */,
+                          const double* point /* or NULL */, const double* point_uniform /* or NULL */, int point_per_candidate,
+                          int commit, double* z_pred, double* S, double* innov, double* maha, double* loglik, int32_t* best,
+                          int32_t* n_gated, uint32_t* status);
+
 /* ---- user-defined measurement models: sigma-point export, sampled update ------------------------------------------------- */
 /* ukf->update(z, h, Q) for an h the library does not know (four DVL beams, a camera pixel of a known landmark, range plus
  * range rate, two antennas at once, ...).  The library hands out the sigma points of every filter, the caller evaluates h on

@@ -469,6 +469,33 @@ constexpr int bearing_filter_scalars(int S, int D) {
 }
 inline RowGeometry bearing_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(bearing_filter_scalars(S, D), capacity, compute_size); }
 
+// ---- sensor-frame association (ukfb_associate_sensor_dev) -----------------------------------------------------------------
+// The sensor-frame models against K candidates per filter (ukf_associate.hpp): ids, inputs and the LDS map are the
+// sensor-frame measurements'.  H hypotheses per filter: K when every candidate brings its own point, else one.
+constexpr int ASSOCIATE_MAX_CANDIDATES = UKFB_ASSOCIATE_MAX_CANDIDATES;
+constexpr int associate_hypotheses(int candidates, int point_per_candidate) { return point_per_candidate ? candidates : 1; }
+// scalars of one output array of a call on `capacity` filters: z_pred / S hold H slots of 3 / 9 a filter, innov K slots of 3,
+// maha / loglik K slots of 1 (what the host-array form allocates and copies)
+constexpr int64_t associate_out_scalars(int slots, int64_t capacity, int per_filter) { return int64_t(slots) * capacity * per_filter; }
+// The candidate range is judged first and alone decides UKFB_ERR_OUT_OF_RANGE; then the NULL rules (point_per_candidate needs
+// point_dev: there is no uniform value for K points), then the uniform id, then "nothing to compute".
+inline Verdict check_associate_args(int engine_model, bool per_filter_models, int model_uniform, const ukfb_associate_in* in, int commit,
+                                    const ukfb_associate_out* out) {
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    if (in->candidates < 1 || in->candidates > ASSOCIATE_MAX_CANDIDATES) return {UKFB_ERR_OUT_OF_RANGE, "candidates must be 1 ... 32"};
+    if (!in->z_dev || !in->Q_dev) return {UKFB_ERR_INVALID_ARG, "z_dev and Q_dev must not be NULL"};
+    if (in->q_is_uniform != 0 && in->q_is_uniform != 1) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
+    if (in->point_per_candidate != 0 && in->point_per_candidate != 1) return {UKFB_ERR_INVALID_ARG, "point_per_candidate must be 0 or 1"};
+    if (in->point_per_candidate && !in->point_dev)
+        return {UKFB_ERR_INVALID_ARG, "point_per_candidate needs point_dev [candidates][capacity][3]"};
+    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    if (!per_filter_models && !sensor_model_ok(engine_model, model_uniform))
+        return {UKFB_ERR_WRONG_MODEL, "sensor model id not valid for this engine (Pose: 0 ... 4, OrientationState: 5 ... 7)"};
+    if (commit == 0 && (!out || (!out->z_pred && !out->S && !out->innov && !out->maha && !out->loglik && !out->best && !out->n_gated && !out->status)))
+        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
+    return {};
+}
+
 // ---- user-defined measurement models (ukfb_sigma_points_dev, ukfb_update_sampled_dev) --------------------------------------
 // The caller evaluates h on the exported sigma points; the update is finished from the samples Z_i = h(X_i), m = 1 ...
 // SAMPLED_MAX_M, one m for the call.

@@ -68,6 +68,8 @@ EXPORTS = [
     "ukfb_update_sensor_dev", "ukfb_update_sensor",
     # bearing measurements: directions on the sphere S^2
     "ukfb_update_bearing_dev", "ukfb_update_bearing",
+    # sensor-frame association: K candidates per filter scored in one launch, the nearest inside the gate committed
+    "ukfb_associate_sensor_dev", "ukfb_associate_sensor",
     # user-defined measurement models: sigma-point export, the update finished from the caller's samples
     "ukfb_sigma_points_dev", "ukfb_update_sampled_dev", "ukfb_sigma_points", "ukfb_update_sampled",
     # user-defined process models: the prediction finished from the caller's propagated sigma points
@@ -104,6 +106,9 @@ SENSOR_MOUNT_IDENTITY = (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0)   # r = 0, qs = (0, 
 BEARING_NONE = -1
 BEARING_POSE_POINT, BEARING_POSE_NAV_DIRECTION, BEARING_ORIENT_NAV_DIRECTION = 0, 1, 2
 
+# most candidates per filter of ukfb_associate_sensor_dev (UKFB_ASSOCIATE_MAX_CANDIDATES)
+ASSOCIATE_MAX_CANDIDATES = 32
+
 # largest measurement dimension of ukfb_update_sampled_dev (UKFB_SAMPLED_MAX_M)
 SAMPLED_MAX_M = 6
 
@@ -137,6 +142,20 @@ class SensorOut(C.Structure):
     """ukfb_sensor_out: device pointers in engine precision (status uint32), any may be NULL"""
     _fields_ = [("z_pred", C.c_void_p), ("S", C.c_void_p), ("innov", C.c_void_p), ("maha", C.c_void_p),
                 ("loglik", C.c_void_p), ("status", C.c_void_p)]
+
+
+class AssociateIn(C.Structure):
+    """ukfb_associate_in: ukfb_sensor_in with `candidates` slots of z ([candidates, capacity, 3]) and, with
+    point_per_candidate, of the point"""
+    _fields_ = [("model_dev", C.c_void_p), ("candidates", C.c_int), ("z_dev", C.c_void_p), ("Q_dev", C.c_void_p),
+                ("q_is_uniform", C.c_int), ("mount_dev", C.c_void_p), ("mount_uniform", C.c_double * 7), ("point_dev", C.c_void_p),
+                ("point_uniform", C.c_double * 3), ("point_per_candidate", C.c_int)]
+
+
+class AssociateOut(C.Structure):
+    """ukfb_associate_out: device pointers in engine precision (best, n_gated int32, status uint32), any may be NULL"""
+    _fields_ = [("z_pred", C.c_void_p), ("S", C.c_void_p), ("innov", C.c_void_p), ("maha", C.c_void_p),
+                ("loglik", C.c_void_p), ("best", C.c_void_p), ("n_gated", C.c_void_p), ("status", C.c_void_p)]
 
 
 class SampledIn(C.Structure):
@@ -810,6 +829,56 @@ class BatchUKF:
                                            _pd(mp), _pd(mu_), _pd(pp), _pd(pu), C.c_int(1 if commit else 0), _pd(o["z_pred"]),
                                            _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]),
                                            o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_update_bearing")
+        return o
+
+    # ---- sensor-frame association: z [candidates, capacity, 3]; the point [capacity, 3] or, per hypothesis, [candidates, capacity, 3]
+    def associate_sensor_dev(self, model: int, candidates: int, z_dev, Q_dev, q_is_uniform: bool = False, model_dev=None,
+                             mount_dev=None, mount=SENSOR_MOUNT_IDENTITY, point_dev=None, point=(0.0, 0.0, 0.0),
+                             point_per_candidate: bool = False, commit: bool = True, z_pred=None, S=None, innov=None, maha=None,
+                             loglik=None, best=None, n_gated=None, status=None):
+        """`candidates` samples per filter scored through a sensor-frame model (SENSOR_* constants) in one launch; the
+        candidate with the smallest d^2 inside the gate is `best` and, with commit=True, updates the filter.
+        point_per_candidate=False: every candidate is a detection of the one point (point_dev [capacity, 3] or the host
+        value `point`); True: candidate k is a fix of its own landmark or beacon point_dev [candidates, capacity, 3].
+        Keyword outputs (device buffers in engine precision; best, n_gated int32; status uint32 / int32): z_pred
+        [H, capacity, 3], S [H, capacity, 9] with H = candidates per hypothesis, else 1; innov [candidates, capacity, 3],
+        maha / loglik [candidates, capacity].  commit=False is read-only.  Stream-ordered."""
+        ptr = lambda x: None if x is None else _devptr(x).value
+        ain = AssociateIn(ptr(model_dev), int(candidates), ptr(z_dev), ptr(Q_dev), 1 if q_is_uniform else 0, ptr(mount_dev),
+                          (C.c_double * 7)(*[float(v) for v in mount]), ptr(point_dev), (C.c_double * 3)(*[float(v) for v in point]),
+                          1 if point_per_candidate else 0)
+        out = AssociateOut(ptr(z_pred), ptr(S), ptr(innov), ptr(maha), ptr(loglik), ptr(best), ptr(n_gated), ptr(status))
+        _chk(self._lib.ukfb_associate_sensor_dev(self._h, C.c_int(int(model)), C.byref(ain), C.c_int(1 if commit else 0), C.byref(out)),
+             "ukfb_associate_sensor_dev")
+
+    def associate_sensor(self, model, z, Q, mount=SENSOR_MOUNT_IDENTITY, point=(0.0, 0.0, 0.0), point_per_candidate: bool = False,
+                         commit: bool = True):
+        """Host arrays: z [candidates, capacity, 3], Q [capacity, 3, 3]; model an int or an int32 array [capacity]; mount [7]
+        or [capacity, 7]; point [3] or [capacity, 3], with point_per_candidate [candidates, capacity, 3].  Returns a dict of
+        NumPy arrays: z_pred [H, n, 3], S [H, n, 3, 3], innov [K, n, 3], maha / loglik [K, n], best / n_gated / status [n];
+        synchronises"""
+        n = self.capacity
+        z = _f64(z)
+        K = int(z.shape[0]) if z.ndim == 3 else 0
+        z = _f64(z, (K, n, 3)); Q = _f64(Q, (n, 3, 3))
+        H = K if point_per_candidate else 1
+        per = None if np.isscalar(model) else np.ascontiguousarray(model, dtype=np.int32).reshape(n)
+        mount = _f64(mount); point = _f64(point)
+        mp, mu_ = (mount.reshape(n, 7), None) if mount.ndim == 2 else (None, mount.reshape(7))
+        if point_per_candidate:
+            pp, pu = point.reshape(K, n, 3), None
+        else:
+            pp, pu = (point.reshape(n, 3), None) if point.ndim == 2 else (None, point.reshape(3))
+        o = {"z_pred": np.empty((H, n, 3)), "S": np.empty((H, n, 3, 3)), "innov": np.empty((K, n, 3)), "maha": np.empty((K, n)),
+             "loglik": np.empty((K, n)), "best": np.empty(n, dtype=np.int32), "n_gated": np.empty(n, dtype=np.int32),
+             "status": np.empty(n, dtype=np.uint32)}
+        pi = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        _chk(self._lib.ukfb_associate_sensor(self._h, C.c_int(0 if per is not None else int(model)),
+                                             pi(per) if per is not None else None, C.c_int(K), _pd(z), _pd(Q), _pd(mp), _pd(mu_),
+                                             _pd(pp), _pd(pu), C.c_int(1 if point_per_candidate else 0), C.c_int(1 if commit else 0),
+                                             _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]),
+                                             pi(o["best"]), pi(o["n_gated"]), o["status"].ctypes.data_as(C.POINTER(C.c_uint32))),
+             "ukfb_associate_sensor")
         return o
 
     # ---- user-defined measurement models: X [capacity, 2 D + 1, S], delta [capacity, 2 D + 1, D], Z [capacity, 2 D + 1, m]
