@@ -1,8 +1,5 @@
 // ukf_bank_api.hip -- C-ABI of the filter banks (include/ukf_batch.h, "filter banks"): argument checks (ukf_host.hpp), the
 // launch requests, and the host-array forms.
-#include <cmath>
-#include <vector>
-
 #include "ukf_api_common.hpp"
 #include "ukf_bank_req.hpp"
 
@@ -75,24 +72,15 @@ int ukfb_bank_combine(ukfb_engine* e, int hypotheses, const double* w, double* m
     if (!w || !mu) return ukfb::fail({UKFB_ERR_INVALID_ARG, "w and mu must not be NULL"});
     ukfb::DeviceScope scope(e->device);
     UKFB_HIP_TRY(scope.err);
-    const size_t n = size_t(e->cap), tracks = n / size_t(hypotheses), ts = e->tsize, S = size_t(e->S), PK = size_t(e->PK);
-    ukfb::DeviceBuffers buf;
-    void *w_d = nullptr, *mu_d = nullptr, *cov_d = nullptr;
-    uint32_t* st_d = nullptr;
-    UKFB_HIP_TRY(buf.take(&w_d, n * ts));
-    UKFB_HIP_TRY(buf.take(&mu_d, tracks * S * ts));
-    if (cov) UKFB_HIP_TRY(buf.take(&cov_d, tracks * PK * ts));
-    if (status) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&st_d), tracks * sizeof(uint32_t)));
-    if (const int rc = ukfb::upload_scalars(e, w_d, w, n)) return rc;
+    const size_t n = size_t(e->cap), tracks = n / size_t(hypotheses);
+    ukfb::HostStage stage(e);
+    const void* w_d = stage.in(w, n);
+    void* mu_d = stage.out(mu, tracks * size_t(e->S));
+    void* cov_d = stage.cov_out(cov, tracks);
+    uint32_t* st_d = stage.raw_out(status, tracks);
+    if (const int rc = stage.rc()) return rc;
     if (const int rc = ukfb_bank_combine_dev(e, hypotheses, w_d, mu_d, cov_d, st_d)) return rc;
-    if (const int rc = ukfb::download_scalars(e, mu_d, mu, tracks * S)) return rc;
-    if (cov) {
-        std::vector<double> packed(tracks * PK);
-        if (const int rc = ukfb::download_scalars(e, cov_d, packed.data(), tracks * PK)) return rc;
-        ukfb::unpack_symmetric(packed.data(), tracks, e->D, cov);
-    }
-    if (status) UKFB_HIP_TRY(hipMemcpyAsync(status, st_d, tracks * sizeof(uint32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    return ukfb_sync(e);   // (the temporaries are freed after the stream has drained)
+    return stage.finish();
 }
 
 int ukfb_bank_mix(ukfb_engine* e, int hypotheses, const double* w, const double* transition, double* w_pred, uint32_t* status) {
@@ -101,18 +89,14 @@ int ukfb_bank_mix(ukfb_engine* e, int hypotheses, const double* w, const double*
     if (const int rc = ukfb::fail(ukfb::check_bank_transition(transition, hypotheses))) return rc;
     ukfb::DeviceScope scope(e->device);
     UKFB_HIP_TRY(scope.err);
-    const size_t n = size_t(e->cap), tracks = n / size_t(hypotheses), ts = e->tsize;
-    ukfb::DeviceBuffers buf;
-    void *w_d = nullptr, *wp_d = nullptr;
-    uint32_t* st_d = nullptr;
-    UKFB_HIP_TRY(buf.take(&w_d, n * ts));
-    UKFB_HIP_TRY(buf.take(&wp_d, n * ts));
-    if (status) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&st_d), tracks * sizeof(uint32_t)));
-    if (const int rc = ukfb::upload_scalars(e, w_d, w, n)) return rc;
+    const size_t n = size_t(e->cap), tracks = n / size_t(hypotheses);
+    ukfb::HostStage stage(e);
+    const void* w_d = stage.in(w, n);
+    void* wp_d = stage.out(w_pred, n);
+    uint32_t* st_d = stage.raw_out(status, tracks);
+    if (const int rc = stage.rc()) return rc;
     if (const int rc = ukfb_bank_mix_dev(e, hypotheses, w_d, transition, wp_d, st_d)) return rc;
-    if (const int rc = ukfb::download_scalars(e, wp_d, w_pred, n)) return rc;
-    if (status) UKFB_HIP_TRY(hipMemcpyAsync(status, st_d, tracks * sizeof(uint32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    return ukfb_sync(e);
+    return stage.finish();
 }
 
 }  // extern "C"

@@ -1,7 +1,5 @@
 // ukf_delayed_api.hip -- C-ABI of the delayed-measurement update (include/ukf_batch.h, "late samples"): argument checks
 // (ukf_host.hpp), the device form, the lag helper and the host-array form.
-#include <vector>
-
 #include "ukf_api_common.hpp"
 #include "ukf_delayed_req.hpp"
 
@@ -23,19 +21,10 @@ __global__ void delayed_lag_kernel(const DelayedLagArgs a) {
 
 }  // namespace ukfb
 
-namespace {
-
-int entry(ukfb_engine* e) {
-    if (!e) return UKFB_ERR_INVALID_ARG;
-    return ukfb::refuse_poisoned(e);
-}
-
-}  // namespace
-
 extern "C" {
 
 int ukfb_update_delayed_dev(ukfb_engine* e, const ukfb_delayed_in* in, int commit, const ukfb_delayed_out* out) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_delayed_args(in, commit, out))) return rc;
     ukfb::DeviceScope scope(e->device);
     UKFB_HIP_TRY(scope.err);
@@ -47,7 +36,7 @@ int ukfb_update_delayed_dev(ukfb_engine* e, const ukfb_delayed_in* in, int commi
 }
 
 int ukfb_delayed_lag_dev(ukfb_engine* e, int steps, const int64_t* step_ts_us, const int64_t* sample_ts_us_dev, int32_t* lag_out_dev) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_delayed_lag_args(steps, step_ts_us, sample_ts_us_dev != nullptr, lag_out_dev != nullptr)))
         return rc;
     ukfb::DeviceScope scope(e->device);
@@ -68,7 +57,7 @@ int ukfb_update_delayed(ukfb_engine* e, int steps, const double* dt, const doubl
                         const double* in_b, int lag_uniform, const int32_t* lag, int meas_model, const int32_t* meas_model_per_filter,
                         const double* z, const double* Q, int commit, double* z_pred, double* S, double* innov, double* maha,
                         double* loglik, uint32_t* status, double* mu_out, double* cov_out) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     // (what the device call will see: a buffer for each input given and each output wanted)
     ukfb_delayed_in in{};
     in.steps = steps;
@@ -81,73 +70,32 @@ int ukfb_update_delayed(ukfb_engine* e, int steps, const double* dt, const doubl
     in.meas_model_uniform = meas_model;
     in.z_dev = z;
     in.Q_dev = Q;
-    ukfb_delayed_out wanted{z_pred, S, innov, maha, loglik, status, mu_out, cov_out};
+    const ukfb_delayed_out wanted{z_pred, S, innov, maha, loglik, status, mu_out, cov_out};
     if (const int rc = ukfb::fail(ukfb::check_delayed_args(&in, commit, &wanted))) return rc;
     ukfb::DeviceScope scope(e->device);
     UKFB_HIP_TRY(scope.err);
-    const size_t n = size_t(e->cap), ts = e->tsize, SS = size_t(e->S), PK = size_t(e->PK), recs = size_t(steps) * n;
-    ukfb::DeviceBuffers buf;
-    void *mu_d = nullptr, *cov_d = nullptr, *a_d = nullptr, *b_d = nullptr, *z_d = nullptr, *q_d = nullptr;
-    void *zp_d = nullptr, *s_d = nullptr, *inn_d = nullptr, *maha_d = nullptr, *ll_d = nullptr, *mo_d = nullptr, *co_d = nullptr;
-    int32_t *lag_d = nullptr, *model_d = nullptr;
-    uint32_t* st_d = nullptr;
-    UKFB_HIP_TRY(buf.take(&mu_d, recs * SS * ts));
-    UKFB_HIP_TRY(buf.take(&cov_d, recs * PK * ts));
-    if (in_a) UKFB_HIP_TRY(buf.take(&a_d, recs * 3 * ts));
-    if (in_b) UKFB_HIP_TRY(buf.take(&b_d, recs * 3 * ts));
-    UKFB_HIP_TRY(buf.take(&z_d, n * 3 * ts));
-    UKFB_HIP_TRY(buf.take(&q_d, n * 9 * ts));
-    if (lag) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&lag_d), n * sizeof(int32_t)));
-    if (meas_model_per_filter) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&model_d), n * sizeof(int32_t)));
-    if (z_pred) UKFB_HIP_TRY(buf.take(&zp_d, n * 4 * ts));
-    if (S) UKFB_HIP_TRY(buf.take(&s_d, n * 9 * ts));
-    if (innov) UKFB_HIP_TRY(buf.take(&inn_d, n * 3 * ts));
-    if (maha) UKFB_HIP_TRY(buf.take(&maha_d, n * ts));
-    if (loglik) UKFB_HIP_TRY(buf.take(&ll_d, n * ts));
-    if (status) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&st_d), n * sizeof(uint32_t)));
-    if (mu_out) UKFB_HIP_TRY(buf.take(&mo_d, n * SS * ts));
-    if (cov_out) UKFB_HIP_TRY(buf.take(&co_d, n * PK * ts));
-    std::vector<double> packed(recs * PK);
-    ukfb::pack_lower(cov_hist, recs, e->D, packed.data());
-    if (const int rc = ukfb::upload_scalars(e, mu_d, mu_hist, recs * SS)) return rc;
-    if (const int rc = ukfb::upload_scalars(e, cov_d, packed.data(), recs * PK)) return rc;
-    if (in_a)
-        if (const int rc = ukfb::upload_scalars(e, a_d, in_a, recs * 3)) return rc;
-    if (in_b)
-        if (const int rc = ukfb::upload_scalars(e, b_d, in_b, recs * 3)) return rc;
-    if (const int rc = ukfb::upload_scalars(e, z_d, z, n * 3)) return rc;
-    if (const int rc = ukfb::upload_scalars(e, q_d, Q, n * 9)) return rc;
-    if (lag_d) UKFB_HIP_TRY(hipMemcpyAsync(lag_d, lag, n * sizeof(int32_t), hipMemcpyHostToDevice, ukfb::main_stream(e)));
-    if (model_d) UKFB_HIP_TRY(hipMemcpyAsync(model_d, meas_model_per_filter, n * sizeof(int32_t), hipMemcpyHostToDevice, ukfb::main_stream(e)));
-    in.mu_hist_dev = mu_d;
-    in.cov_hist_dev = cov_d;
-    in.in_a_dev = a_d;
-    in.in_b_dev = b_d;
-    in.lag_dev = lag_d;
-    in.meas_model_dev = model_d;
-    in.z_dev = z_d;
-    in.Q_dev = q_d;
-    const ukfb_delayed_out out{zp_d, s_d, inn_d, maha_d, ll_d, st_d, mo_d, co_d};
+    const size_t n = size_t(e->cap), SS = size_t(e->S), recs = size_t(steps) * n;
+    ukfb::HostStage stage(e);
+    in.mu_hist_dev = stage.in(mu_hist, recs * SS);
+    in.cov_hist_dev = stage.cov_in(cov_hist, recs);
+    in.in_a_dev = stage.in(in_a, recs * 3);
+    in.in_b_dev = stage.in(in_b, recs * 3);
+    in.lag_dev = stage.raw_in(lag, n);
+    in.meas_model_dev = stage.raw_in(meas_model_per_filter, n);
+    in.z_dev = stage.in(z, n * 3);
+    in.Q_dev = stage.in(Q, n * 9);
+    ukfb_delayed_out out{};
+    out.z_pred = stage.out(z_pred, n * 4);
+    out.S = stage.out(S, n * 9);
+    out.innov = stage.out(innov, n * 3);
+    out.maha = stage.out(maha, n);
+    out.loglik = stage.out(loglik, n);
+    out.status = stage.raw_out(status, n);
+    out.mu_out = stage.out(mu_out, n * SS);
+    out.cov_out = stage.cov_out(cov_out, n);
+    if (const int rc = stage.rc()) return rc;
     if (const int rc = ukfb_update_delayed_dev(e, &in, commit, &out)) return rc;
-    if (z_pred)
-        if (const int rc = ukfb::download_scalars(e, zp_d, z_pred, n * 4)) return rc;
-    if (S)
-        if (const int rc = ukfb::download_scalars(e, s_d, S, n * 9)) return rc;
-    if (innov)
-        if (const int rc = ukfb::download_scalars(e, inn_d, innov, n * 3)) return rc;
-    if (maha)
-        if (const int rc = ukfb::download_scalars(e, maha_d, maha, n)) return rc;
-    if (loglik)
-        if (const int rc = ukfb::download_scalars(e, ll_d, loglik, n)) return rc;
-    if (mu_out)
-        if (const int rc = ukfb::download_scalars(e, mo_d, mu_out, n * SS)) return rc;
-    if (cov_out) {
-        std::vector<double> pk(n * PK);
-        if (const int rc = ukfb::download_scalars(e, co_d, pk.data(), n * PK)) return rc;
-        ukfb::unpack_symmetric(pk.data(), n, e->D, cov_out);
-    }
-    if (status) UKFB_HIP_TRY(hipMemcpyAsync(status, st_d, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    return ukfb_sync(e);   // (the temporaries are freed after the stream has drained)
+    return stage.finish();
 }
 
 }  // extern "C"

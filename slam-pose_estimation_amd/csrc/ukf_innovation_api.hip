@@ -1,8 +1,5 @@
 // ukf_innovation_api.hip -- C-ABI of the read-only innovation statistics (include/ukf_batch.h, "innovation statistics and
 // measurement association"): argument checks (ukf_host.hpp), the launch requests, and the host-array form.
-#include <cmath>
-#include <vector>
-
 #include "ukf_api_common.hpp"
 #include "ukf_innovation.hpp"
 #include "ukf_innovation_req.hpp"
@@ -62,30 +59,21 @@ int ukfb_innovation(ukfb_engine* e, int meas_model, int candidates, const double
         return rc;
     ukfb::DeviceScope scope(e->device);
     UKFB_HIP_TRY(scope.err);
-    const size_t n = size_t(e->cap), K = size_t(candidates), ts = e->tsize;
-    ukfb::DeviceBuffers buf;
-    void *z_d = nullptr, *Q_d = nullptr;
+    const size_t n = size_t(e->cap), K = size_t(candidates);
+    ukfb::HostStage stage(e);
+    const void* z_d = stage.in(z, K * n * 3);
+    const void* Q_d = stage.in(Q, n * 9);
     ukfb_innovation_out o{};
-    UKFB_HIP_TRY(buf.take(&z_d, K * n * 3 * ts));
-    UKFB_HIP_TRY(buf.take(&Q_d, n * 9 * ts));
-    if (z_pred) UKFB_HIP_TRY(buf.take(&o.z_pred, n * 4 * ts));
-    if (S) UKFB_HIP_TRY(buf.take(&o.S, n * 9 * ts));
-    if (innov) UKFB_HIP_TRY(buf.take(&o.innov, K * n * 3 * ts));
-    if (maha) UKFB_HIP_TRY(buf.take(&o.maha, K * n * ts));
-    if (loglik) UKFB_HIP_TRY(buf.take(&o.loglik, K * n * ts));
-    if (best) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&o.best), n * sizeof(int32_t)));
-    if (status) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&o.status), n * sizeof(uint32_t)));
-    if (const int rc = ukfb::upload_scalars(e, z_d, z, K * n * 3)) return rc;
-    if (const int rc = ukfb::upload_scalars(e, Q_d, Q, n * 9)) return rc;
+    o.z_pred = stage.out(z_pred, n * 4);
+    o.S = stage.out(S, n * 9);
+    o.innov = stage.out(innov, K * n * 3);
+    o.maha = stage.out(maha, K * n);
+    o.loglik = stage.out(loglik, K * n);
+    o.best = stage.raw_out(best, n);
+    o.status = stage.raw_out(status, n);
+    if (const int rc = stage.rc()) return rc;
     if (const int rc = ukfb_innovation_dev(e, meas_model, nullptr, candidates, z_d, Q_d, 0, &o)) return rc;
-    if (z_pred) if (const int rc = ukfb::download_scalars(e, o.z_pred, z_pred, n * 4)) return rc;
-    if (S) if (const int rc = ukfb::download_scalars(e, o.S, S, n * 9)) return rc;
-    if (innov) if (const int rc = ukfb::download_scalars(e, o.innov, innov, K * n * 3)) return rc;
-    if (maha) if (const int rc = ukfb::download_scalars(e, o.maha, maha, K * n)) return rc;
-    if (loglik) if (const int rc = ukfb::download_scalars(e, o.loglik, loglik, K * n)) return rc;
-    if (best) UKFB_HIP_TRY(hipMemcpyAsync(best, o.best, n * sizeof(int32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    if (status) UKFB_HIP_TRY(hipMemcpyAsync(status, o.status, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    return ukfb_sync(e);   // (the temporaries are freed after the stream has drained)
+    return stage.finish();
 }
 
 }  // extern "C"

@@ -1,16 +1,9 @@
 // ukf_lifecycle_api.hip -- C-ABI of the filter lifecycle (include/ukf_batch.h, "filter lifecycle"): argument checks and launch
 // geometry (ukf_host.hpp), the engine's lifecycle workspace, the launches of ukf_lifecycle.hpp, and the host-array forms.
-#include <vector>
-
 #include "ukf_api_common.hpp"
 #include "ukf_lifecycle.hpp"
 
 namespace {
-
-int entry(ukfb_engine* e) {
-    if (!e) return UKFB_ERR_INVALID_ARG;
-    return ukfb::refuse_poisoned(e);
-}
 
 ukfb::LifecycleArrays arrays_of(const ukfb_engine* e) {
     ukfb::LifecycleArrays a;
@@ -64,7 +57,7 @@ int workspace(ukfb_engine* e, ukfb::LifecycleWorkspace* ws) {
 extern "C" {
 
 int ukfb_gather_filters_dev(ukfb_engine* e, int64_t n, const int32_t* index_dev, const ukfb_filter_records* out) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_lifecycle_args(e->cap, n, out != nullptr, false, false, false, false, e->Rn_per_filter))) return rc;
     if (n == 0) return UKFB_OK;
     ukfb::DeviceScope scope(e->device);
@@ -80,7 +73,7 @@ int ukfb_gather_filters_dev(ukfb_engine* e, int64_t n, const int32_t* index_dev,
 }
 
 int ukfb_scatter_filters_dev(ukfb_engine* e, int64_t n, const int32_t* index_dev, const ukfb_filter_records* in) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_lifecycle_args(e->cap, n, in != nullptr, true, in && in->mu, in && in->cov_packed, in && in->noise,
                                                              e->Rn_per_filter)))
         return rc;
@@ -101,7 +94,7 @@ int ukfb_scatter_filters_dev(ukfb_engine* e, int64_t n, const int32_t* index_dev
 }
 
 int ukfb_retire_dev(ukfb_engine* e, const uint8_t* retire_mask_dev) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (!retire_mask_dev) return ukfb::fail({UKFB_ERR_INVALID_ARG, "retire_mask_dev must not be NULL"});
     ukfb::DeviceScope scope(e->device);
     UKFB_HIP_TRY(scope.err);
@@ -113,7 +106,7 @@ int ukfb_retire_dev(ukfb_engine* e, const uint8_t* retire_mask_dev) {
 }
 
 int ukfb_compact_dev(ukfb_engine* e, int group, int32_t* new_index_dev, int32_t* old_index_dev, int64_t* live_dev) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_compact_args(e->cap, group))) return rc;
     ukfb::DeviceScope scope(e->device);
     UKFB_HIP_TRY(scope.err);
@@ -139,89 +132,58 @@ int ukfb_compact_dev(ukfb_engine* e, int group, int32_t* new_index_dev, int32_t*
 }
 
 int ukfb_gather_filters(ukfb_engine* e, int64_t n, const int32_t* index, double* mu, double* cov, int64_t* last_ts_us, uint8_t* initialised) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_lifecycle_args(e->cap, n, true, false, false, false, false, e->Rn_per_filter))) return rc;
     if (n == 0) return UKFB_OK;
     ukfb::DeviceScope scope(e->device);
     UKFB_HIP_TRY(scope.err);
-    const size_t m = size_t(n), ts = e->tsize, S = size_t(e->S), PK = size_t(e->PK);
-    ukfb::DeviceBuffers buf;
-    int32_t* idx_d = nullptr;
+    const size_t m = size_t(n);
+    ukfb::HostStage stage(e);
+    const int32_t* idx_d = stage.raw_in(index, m);
     ukfb_filter_records rec{};
-    if (index) {
-        UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&idx_d), m * sizeof(int32_t)));
-        UKFB_HIP_TRY(hipMemcpyAsync(idx_d, index, m * sizeof(int32_t), hipMemcpyHostToDevice, ukfb::main_stream(e)));
-    }
-    if (mu) UKFB_HIP_TRY(buf.take(&rec.mu, m * S * ts));
-    if (cov) UKFB_HIP_TRY(buf.take(&rec.cov_packed, m * PK * ts));
-    if (last_ts_us) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&rec.last_ts_us), m * sizeof(int64_t)));
-    if (initialised) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&rec.initialised), m));
+    rec.mu = stage.out(mu, m * size_t(e->S));
+    rec.cov_packed = stage.cov_out(cov, m);
+    rec.last_ts_us = stage.raw_out(last_ts_us, m);
+    rec.initialised = stage.raw_out(initialised, m);
+    if (const int rc = stage.rc()) return rc;
     if (const int rc = ukfb_gather_filters_dev(e, n, idx_d, &rec)) return rc;
-    if (mu)
-        if (const int rc = ukfb::download_scalars(e, rec.mu, mu, m * S)) return rc;
-    if (cov) {
-        std::vector<double> packed(m * PK);
-        if (const int rc = ukfb::download_scalars(e, rec.cov_packed, packed.data(), m * PK)) return rc;
-        ukfb::unpack_symmetric(packed.data(), m, e->D, cov);
-    }
-    if (last_ts_us) UKFB_HIP_TRY(hipMemcpyAsync(last_ts_us, rec.last_ts_us, m * sizeof(int64_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    if (initialised) UKFB_HIP_TRY(hipMemcpyAsync(initialised, rec.initialised, m, hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    return ukfb_sync(e);   // (the temporaries are freed after the stream has drained)
+    return stage.finish();
 }
 
 int ukfb_scatter_filters(ukfb_engine* e, int64_t n, const int32_t* index, const double* mu, const double* cov, const int64_t* last_ts_us,
                          const uint8_t* initialised, uint32_t* status) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_lifecycle_args(e->cap, n, true, true, mu != nullptr, cov != nullptr, false, e->Rn_per_filter))) return rc;
     if (n == 0) return UKFB_OK;
     ukfb::DeviceScope scope(e->device);
     UKFB_HIP_TRY(scope.err);
-    const size_t m = size_t(n), ts = e->tsize, S = size_t(e->S), PK = size_t(e->PK);
-    ukfb::DeviceBuffers buf;
-    int32_t* idx_d = nullptr;
+    const size_t m = size_t(n);
+    ukfb::HostStage stage(e);
+    const int32_t* idx_d = stage.raw_in(index, m);
     ukfb_filter_records rec{};
-    hipStream_t s = ukfb::main_stream(e);
-    if (index) {
-        UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&idx_d), m * sizeof(int32_t)));
-        UKFB_HIP_TRY(hipMemcpyAsync(idx_d, index, m * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    }
-    UKFB_HIP_TRY(buf.take(&rec.mu, m * S * ts));
-    UKFB_HIP_TRY(buf.take(&rec.cov_packed, m * PK * ts));
-    if (last_ts_us) {
-        UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&rec.last_ts_us), m * sizeof(int64_t)));
-        UKFB_HIP_TRY(hipMemcpyAsync(rec.last_ts_us, last_ts_us, m * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    }
-    if (initialised) {
-        UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&rec.initialised), m));
-        UKFB_HIP_TRY(hipMemcpyAsync(rec.initialised, initialised, m, hipMemcpyHostToDevice, s));
-    }
-    if (status) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&rec.status), m * sizeof(uint32_t)));
-    std::vector<double> packed(m * PK);
-    ukfb::pack_lower(cov, m, e->D, packed.data());
-    if (const int rc = ukfb::upload_scalars(e, rec.mu, mu, m * S)) return rc;
-    if (const int rc = ukfb::upload_scalars(e, rec.cov_packed, packed.data(), m * PK)) return rc;
+    rec.mu = stage.in(mu, m * size_t(e->S));
+    rec.cov_packed = stage.cov_in(cov, m);
+    rec.last_ts_us = stage.raw_in(last_ts_us, m);
+    rec.initialised = stage.raw_in(initialised, m);
+    rec.status = stage.raw_out(status, m);
+    if (const int rc = stage.rc()) return rc;
     if (const int rc = ukfb_scatter_filters_dev(e, n, idx_d, &rec)) return rc;
-    if (status) UKFB_HIP_TRY(hipMemcpyAsync(status, rec.status, m * sizeof(uint32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    return ukfb_sync(e);
+    return stage.finish();
 }
 
 int ukfb_compact(ukfb_engine* e, int group, int32_t* new_index, int32_t* old_index, int64_t* live) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_compact_args(e->cap, group))) return rc;
     ukfb::DeviceScope scope(e->device);
     UKFB_HIP_TRY(scope.err);
-    const size_t bytes = size_t(e->cap) * sizeof(int32_t);
-    ukfb::DeviceBuffers buf;
-    int32_t *new_d = nullptr, *old_d = nullptr;
-    int64_t* live_d = nullptr;
-    if (new_index) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&new_d), bytes));
-    if (old_index) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&old_d), bytes));
-    if (live) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&live_d), sizeof(int64_t)));
+    const size_t n = size_t(e->cap);
+    ukfb::HostStage stage(e);
+    int32_t* new_d = stage.raw_out(new_index, n);
+    int32_t* old_d = stage.raw_out(old_index, n);
+    int64_t* live_d = stage.raw_out(live, 1);
+    if (const int rc = stage.rc()) return rc;
     if (const int rc = ukfb_compact_dev(e, group, new_d, old_d, live_d)) return rc;
-    if (new_index) UKFB_HIP_TRY(hipMemcpyAsync(new_index, new_d, bytes, hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    if (old_index) UKFB_HIP_TRY(hipMemcpyAsync(old_index, old_d, bytes, hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    if (live) UKFB_HIP_TRY(hipMemcpyAsync(live, live_d, sizeof(int64_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    return ukfb_sync(e);
+    return stage.finish();
 }
 
 }  // extern "C"

@@ -1,16 +1,9 @@
 // ukf_smooth_api.hip -- C-ABI of the fixed-interval smoother (include/ukf_batch.h, "fixed-interval smoothing"): argument
 // checks and the chunking of a window into launches (ukf_host.hpp), the history push, and the host-array form.
-#include <vector>
-
 #include "ukf_api_common.hpp"
 #include "ukf_smooth_req.hpp"
 
 namespace {
-
-int entry(ukfb_engine* e) {
-    if (!e) return UKFB_ERR_INVALID_ARG;
-    return ukfb::refuse_poisoned(e);
-}
 
 // The chain's covariance between the launches of a window that has no covariance output: one record [capacity][PK], created
 // the first time the engine records a history (or, for a caller that fills its rings itself, the first time such a window
@@ -27,7 +20,7 @@ int ensure_chain_workspace(ukfb_engine* e) {
 extern "C" {
 
 int ukfb_history_push_dev(ukfb_engine* e, int slots, int slot, void* mu_hist_dev, void* cov_hist_dev) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_history_args(slots, slot, mu_hist_dev != nullptr, cov_hist_dev != nullptr))) return rc;
     ukfb::DeviceScope scope(e->device);
     UKFB_HIP_TRY(scope.err);
@@ -43,7 +36,7 @@ int ukfb_history_push_dev(ukfb_engine* e, int slots, int slot, void* mu_hist_dev
 int ukfb_smooth_dev(ukfb_engine* e, int steps, const double* dt, int slots, int first_slot, const void* mu_hist_dev,
                     const void* cov_hist_dev, const void* in_a_dev, const void* in_b_dev, void* mu_out_dev, void* cov_out_dev,
                     uint32_t* status_dev) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_smooth_args(steps, slots, first_slot, dt != nullptr, mu_hist_dev != nullptr,
                                                           cov_hist_dev != nullptr, mu_out_dev != nullptr)))
         return rc;
@@ -77,33 +70,20 @@ int ukfb_smooth_dev(ukfb_engine* e, int steps, const double* dt, int slots, int 
 
 int ukfb_smooth(ukfb_engine* e, int steps, const double* dt, double* mu, double* cov, const double* in_a, const double* in_b,
                 uint32_t* status) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_smooth_args(steps, steps, 0, dt != nullptr, mu != nullptr, cov != nullptr, mu != nullptr))) return rc;
     ukfb::DeviceScope scope(e->device);
     UKFB_HIP_TRY(scope.err);
-    const size_t n = size_t(e->cap), ts = e->tsize, S = size_t(e->S), PK = size_t(e->PK), recs = size_t(steps) * n;
-    ukfb::DeviceBuffers buf;
-    void *mu_d = nullptr, *cov_d = nullptr, *a_d = nullptr, *b_d = nullptr;
-    uint32_t* st_d = nullptr;
-    UKFB_HIP_TRY(buf.take(&mu_d, recs * S * ts));
-    UKFB_HIP_TRY(buf.take(&cov_d, recs * PK * ts));
-    if (in_a) UKFB_HIP_TRY(buf.take(&a_d, recs * 3 * ts));
-    if (in_b) UKFB_HIP_TRY(buf.take(&b_d, recs * 3 * ts));
-    if (status) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&st_d), n * sizeof(uint32_t)));
-    std::vector<double> packed(recs * PK);
-    ukfb::pack_lower(cov, recs, e->D, packed.data());
-    if (const int rc = ukfb::upload_scalars(e, mu_d, mu, recs * S)) return rc;
-    if (const int rc = ukfb::upload_scalars(e, cov_d, packed.data(), recs * PK)) return rc;
-    if (in_a)
-        if (const int rc = ukfb::upload_scalars(e, a_d, in_a, recs * 3)) return rc;
-    if (in_b)
-        if (const int rc = ukfb::upload_scalars(e, b_d, in_b, recs * 3)) return rc;
+    const size_t n = size_t(e->cap), recs = size_t(steps) * n;
+    ukfb::HostStage stage(e);
+    void* mu_d = stage.inout(mu, recs * size_t(e->S));
+    void* cov_d = stage.cov_inout(cov, recs);
+    const void* a_d = stage.in(in_a, recs * 3);
+    const void* b_d = stage.in(in_b, recs * 3);
+    uint32_t* st_d = stage.raw_out(status, n);
+    if (const int rc = stage.rc()) return rc;
     if (const int rc = ukfb_smooth_dev(e, steps, dt, steps, 0, mu_d, cov_d, a_d, b_d, mu_d, cov_d, st_d)) return rc;   // in place
-    if (const int rc = ukfb::download_scalars(e, mu_d, mu, recs * S)) return rc;
-    if (const int rc = ukfb::download_scalars(e, cov_d, packed.data(), recs * PK)) return rc;
-    ukfb::unpack_symmetric(packed.data(), recs, e->D, cov);
-    if (status) UKFB_HIP_TRY(hipMemcpyAsync(status, st_d, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    return ukfb_sync(e);   // (the temporaries are freed after the stream has drained)
+    return stage.finish();
 }
 
 }  // extern "C"

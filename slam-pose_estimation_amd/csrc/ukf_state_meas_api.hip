@@ -5,21 +5,12 @@
 #include "ukf_api_common.hpp"
 #include "ukf_state_meas_req.hpp"
 
-namespace {
-
-int entry(ukfb_engine* e) {
-    if (!e) return UKFB_ERR_INVALID_ARG;
-    return ukfb::refuse_poisoned(e);
-}
-
-}  // namespace
-
 extern "C" {
 
 int ukfb_update_state_dev(ukfb_engine* e, uint32_t block_mask_uniform, const int32_t* block_mask_dev, const void* z_dev,
                           const void* Qz_packed_dev, double state_inflation, double meas_inflation, int commit,
                           const ukfb_state_meas_out* out) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_state_meas_args(e->model, block_mask_dev != nullptr, block_mask_uniform, z_dev != nullptr,
                                                               Qz_packed_dev != nullptr, state_inflation, meas_inflation, commit, out)))
         return rc;
@@ -39,7 +30,7 @@ int ukfb_update_state_dev(ukfb_engine* e, uint32_t block_mask_uniform, const int
 
 int ukfb_update_state(ukfb_engine* e, uint32_t block_mask, const int32_t* block_mask_per_filter, const double* z, const double* Qz,
                       double state_inflation, double meas_inflation, int commit, double* maha, double* loglik, uint32_t* status) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     // (the outputs the device call will see: a buffer for each one the caller wants)
     ukfb_state_meas_out wanted{maha, loglik, status};
     if (const int rc = ukfb::fail(ukfb::check_state_meas_args(e->model, block_mask_per_filter != nullptr, block_mask, z != nullptr,
@@ -47,34 +38,22 @@ int ukfb_update_state(ukfb_engine* e, uint32_t block_mask, const int32_t* block_
         return rc;
     ukfb::DeviceScope scope(e->device);
     UKFB_HIP_TRY(scope.err);
-    const size_t n = size_t(e->cap), ts = e->tsize, S = size_t(e->S), PK = size_t(e->PK);
-    ukfb::DeviceBuffers buf;
-    void *z_d = nullptr, *q_d = nullptr, *maha_d = nullptr, *ll_d = nullptr;
-    int32_t* mask_d = nullptr;
-    uint32_t* st_d = nullptr;
-    UKFB_HIP_TRY(buf.take(&z_d, n * S * ts));
-    UKFB_HIP_TRY(buf.take(&q_d, n * PK * ts));
-    if (block_mask_per_filter) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&mask_d), n * sizeof(int32_t)));
-    if (maha) UKFB_HIP_TRY(buf.take(&maha_d, n * ts));
-    if (loglik) UKFB_HIP_TRY(buf.take(&ll_d, n * ts));
-    if (status) UKFB_HIP_TRY(buf.take(reinterpret_cast<void**>(&st_d), n * sizeof(uint32_t)));
-    std::vector<double> packed(n * PK);
-    ukfb::pack_lower(Qz, n, e->D, packed.data());
-    if (const int rc = ukfb::upload_scalars(e, z_d, z, n * S)) return rc;
-    if (const int rc = ukfb::upload_scalars(e, q_d, packed.data(), n * PK)) return rc;
-    if (mask_d) UKFB_HIP_TRY(hipMemcpyAsync(mask_d, block_mask_per_filter, n * sizeof(int32_t), hipMemcpyHostToDevice, ukfb::main_stream(e)));
-    const ukfb_state_meas_out out{maha_d, ll_d, st_d};
+    const size_t n = size_t(e->cap);
+    ukfb::HostStage stage(e);
+    const int32_t* mask_d = stage.raw_in(block_mask_per_filter, n);
+    const void* z_d = stage.in(z, n * size_t(e->S));
+    const void* q_d = stage.cov_in(Qz, n);
+    ukfb_state_meas_out out{};
+    out.maha = stage.out(maha, n);
+    out.loglik = stage.out(loglik, n);
+    out.status = stage.raw_out(status, n);
+    if (const int rc = stage.rc()) return rc;
     if (const int rc = ukfb_update_state_dev(e, block_mask, mask_d, z_d, q_d, state_inflation, meas_inflation, commit, &out)) return rc;
-    if (maha)
-        if (const int rc = ukfb::download_scalars(e, maha_d, maha, n)) return rc;
-    if (loglik)
-        if (const int rc = ukfb::download_scalars(e, ll_d, loglik, n)) return rc;
-    if (status) UKFB_HIP_TRY(hipMemcpyAsync(status, st_d, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
-    return ukfb_sync(e);   // (the temporaries are freed after the stream has drained)
+    return stage.finish();
 }
 
 int ukfb_pose_update_body_states(ukfb_engine* e, uint32_t block_mask, const double* records, const uint8_t* active) {
-    if (const int rc = entry(e)) return rc;
+    if (const int rc = ukfb::entry(e)) return rc;
     if (e->model != UKFB_MODEL_POSE) return ukfb::fail({UKFB_ERR_WRONG_MODEL, "Pose engines only"});
     if (!records) return ukfb::fail({UKFB_ERR_INVALID_ARG, "records must not be NULL"});
     if (!ukfb::state_meas_mask_ok(ukfb::state_meas_blocks(e->model), int64_t(block_mask)))

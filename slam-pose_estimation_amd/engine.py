@@ -260,6 +260,32 @@ def _devptr(x):
     return C.c_void_p(int(x))
 
 
+def _ptr(x):
+    """The address behind _devptr as a plain int, or None: what a pointer field of a ctypes Structure takes."""
+    return None if x is None else _devptr(x).value
+
+
+def _typed_pointer(ctype):
+    return lambda a: a.ctypes.data_as(C.POINTER(ctype)) if a is not None else None
+
+
+# the ctypes pointer of a NumPy array of that element type, None for None (as _pd for doubles)
+_pi32, _pu32, _pu8, _pi64 = (_typed_pointer(t) for t in (C.c_int32, C.c_uint32, C.c_uint8, C.c_int64))
+
+
+def _int_or_i32(x, n):
+    """An argument that is one int for the batch or an int32 array [n] -> (the int or 0, the array or None)."""
+    if np.isscalar(x):
+        return int(x), None
+    return 0, np.ascontiguousarray(x, dtype=np.int32).reshape(n)
+
+
+def _per_or_uniform(a, n, width):
+    """A host value [width] for the batch or an array [n, width] per filter (mount, point) -> (per-filter, uniform), one None."""
+    a = _f64(a)
+    return (a.reshape(n, width), None) if a.ndim == 2 else (None, a.reshape(width))
+
+
 def _torch_current_stream(device: int):
     """hipStream_t of torch's current stream on `device` (0 = the default stream), or None when torch is not in use."""
     import sys
@@ -354,15 +380,14 @@ class BatchUKF:
         mu = np.empty((count, self.S))
         cov = np.empty((count, self.D, self.D)) if with_cov else None
         init = np.empty(count, dtype=np.uint8)
-        _chk(self._lib.ukfb_get_state(self._h, C.c_int64(first), C.c_int64(count), _pd(mu), _pd(cov),
-                                      init.ctypes.data_as(C.POINTER(C.c_uint8))), "ukfb_get_state")
+        _chk(self._lib.ukfb_get_state(self._h, C.c_int64(first), C.c_int64(count), _pd(mu), _pd(cov), _pu8(init)),
+             "ukfb_get_state")
         return (mu, cov, init.astype(bool)) if with_cov else (mu, init.astype(bool))
 
     def status(self, first: int = 0, count: Optional[int] = None):
         count = self.capacity - first if count is None else count
         st = np.empty(count, dtype=np.uint32)
-        _chk(self._lib.ukfb_get_status(self._h, C.c_int64(first), C.c_int64(count),
-                                       st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_get_status")
+        _chk(self._lib.ukfb_get_status(self._h, C.c_int64(first), C.c_int64(count), _pu32(st)), "ukfb_get_status")
         return st
 
     def status_summary(self) -> int:
@@ -372,14 +397,12 @@ class BatchUKF:
 
     def set_last_measurement_time(self, t_us, first: int = 0):
         t = np.ascontiguousarray(t_us, dtype=np.int64)
-        _chk(self._lib.ukfb_set_last_measurement_time(self._h, C.c_int64(first), C.c_int64(t.size),
-                                                      t.ctypes.data_as(C.POINTER(C.c_int64))), "set_last_time")
+        _chk(self._lib.ukfb_set_last_measurement_time(self._h, C.c_int64(first), C.c_int64(t.size), _pi64(t)), "set_last_time")
 
     def last_measurement_time(self, first: int = 0, count: Optional[int] = None):
         count = self.capacity - first if count is None else count
         t = np.empty(count, dtype=np.int64)
-        _chk(self._lib.ukfb_get_last_measurement_time(self._h, C.c_int64(first), C.c_int64(count),
-                                                      t.ctypes.data_as(C.POINTER(C.c_int64))), "get_last_time")
+        _chk(self._lib.ukfb_get_last_measurement_time(self._h, C.c_int64(first), C.c_int64(count), _pi64(t)), "get_last_time")
         return t
 
     def device_views(self):
@@ -458,8 +481,7 @@ class BatchUKF:
 
     def predict_timestamps(self, ts_us):
         t = np.ascontiguousarray(ts_us, dtype=np.int64).reshape(self.capacity)
-        _chk(self._lib.ukfb_predict_timestamps(self._h, t.ctypes.data_as(C.POINTER(C.c_int64))),
-             "ukfb_predict_timestamps")
+        _chk(self._lib.ukfb_predict_timestamps(self._h, _pi64(t)), "ukfb_predict_timestamps")
 
     def predict_dt_dev(self, dt_dev):
         _chk(self._lib.ukfb_predict_dt_dev(self._h, _devptr(dt_dev)), "ukfb_predict_dt_dev")
@@ -472,13 +494,10 @@ class BatchUKF:
         z = _f64(z, (self.capacity, 3)); Q = _f64(Q, (self.capacity, 3, 3))
         if np.isscalar(meas_model):
             act = np.ascontiguousarray(active, dtype=np.uint8) if active is not None else None
-            _chk(self._lib.ukfb_update(self._h, C.c_int(int(meas_model)), _pd(z), _pd(Q),
-                                       act.ctypes.data_as(C.POINTER(C.c_uint8)) if act is not None else None),
-                 "ukfb_update")
+            _chk(self._lib.ukfb_update(self._h, C.c_int(int(meas_model)), _pd(z), _pd(Q), _pu8(act)), "ukfb_update")
         else:
             m = np.ascontiguousarray(meas_model, dtype=np.int32).reshape(self.capacity)
-            _chk(self._lib.ukfb_update_mixed(self._h, m.ctypes.data_as(C.POINTER(C.c_int32)), _pd(z), _pd(Q)),
-                 "ukfb_update_mixed")
+            _chk(self._lib.ukfb_update_mixed(self._h, _pi32(m), _pd(z), _pd(Q)), "ukfb_update_mixed")
 
     def update_dev(self, meas_model_uniform: int, z_dev, Q_dev, meas_model_dev=None):
         _chk(self._lib.ukfb_update_dev(self._h, C.c_int(meas_model_uniform), _devptr(meas_model_dev), _devptr(z_dev),
@@ -489,8 +508,7 @@ class BatchUKF:
                        meas_model_dev=None, z_pred=None, S=None, innov=None, maha=None, loglik=None, best=None, status=None):
         """z_dev [candidates][capacity][3], Q_dev [capacity][9] (or 9 scalars with q_is_uniform); the keyword outputs are
         device buffers in engine precision (best int32, status uint32), None = not wanted.  Stream-ordered."""
-        ptr = lambda x: None if x is None else _devptr(x).value
-        out = InnovationOut(ptr(z_pred), ptr(S), ptr(innov), ptr(maha), ptr(loglik), ptr(best), ptr(status))
+        out = InnovationOut(_ptr(z_pred), _ptr(S), _ptr(innov), _ptr(maha), _ptr(loglik), _ptr(best), _ptr(status))
         _chk(self._lib.ukfb_innovation_dev(self._h, C.c_int(meas_model_uniform), _devptr(meas_model_dev), C.c_int(candidates),
                                            _devptr(z_dev), _devptr(Q_dev), C.c_int(1 if q_is_uniform else 0), C.byref(out)),
              "ukfb_innovation_dev")
@@ -511,10 +529,9 @@ class BatchUKF:
         K = z.shape[0]
         o = {"z_pred": np.empty((n, 4)), "S": np.empty((n, 3, 3)), "innov": np.empty((K, n, 3)), "maha": np.empty((K, n)),
              "loglik": np.empty((K, n)), "best": np.empty(n, dtype=np.int32), "status": np.empty(n, dtype=np.uint32)}
-        _chk(self._lib.ukfb_innovation(self._h, C.c_int(int(meas_model)), C.c_int(K), _pd(z), _pd(Q), _pd(o["z_pred"]), _pd(o["S"]),
-                                       _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]),
-                                       o["best"].ctypes.data_as(C.POINTER(C.c_int32)),
-                                       o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_innovation")
+        _chk(self._lib.ukfb_innovation(self._h, C.c_int(int(meas_model)), C.c_int(K), _pd(z), _pd(Q), _pd(o["z_pred"]),
+                                       _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]), _pi32(o["best"]),
+                                       _pu32(o["status"])), "ukfb_innovation")
         return o
 
     # ---- filter banks: capacity / M tracks of M hypotheses, track-major (hypothesis j of track t = filter t * M + j)
@@ -549,8 +566,7 @@ class BatchUKF:
         w = _f64(w, (self.capacity,))
         T = self.capacity // max(int(hypotheses), 1)
         mu, cov, st = np.empty((T, self.S)), np.empty((T, self.D, self.D)), np.empty(T, dtype=np.uint32)
-        _chk(self._lib.ukfb_bank_combine(self._h, C.c_int(hypotheses), _pd(w), _pd(mu), _pd(cov),
-                                         st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_bank_combine")
+        _chk(self._lib.ukfb_bank_combine(self._h, C.c_int(hypotheses), _pd(w), _pd(mu), _pd(cov), _pu32(st)), "ukfb_bank_combine")
         return mu, cov, st
 
     def bank_mix(self, hypotheses: int, w, transition):
@@ -559,8 +575,7 @@ class BatchUKF:
         P = _f64(transition, (hypotheses, hypotheses))
         T = self.capacity // max(int(hypotheses), 1)
         wp, st = np.empty(self.capacity), np.empty(T, dtype=np.uint32)
-        _chk(self._lib.ukfb_bank_mix(self._h, C.c_int(hypotheses), _pd(w), _pd(P), _pd(wp),
-                                     st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_bank_mix")
+        _chk(self._lib.ukfb_bank_mix(self._h, C.c_int(hypotheses), _pd(w), _pd(P), _pd(wp), _pu32(st)), "ukfb_bank_mix")
         return wp, st
 
     # ---- fixed-interval smoothing: history rings [slots, capacity, S] / [slots, capacity, PK] in engine precision
@@ -594,8 +609,7 @@ class BatchUKF:
         a = _f64(in_a, (steps, n, 3)) if in_a is not None else None
         b = _f64(in_b, (steps, n, 3)) if in_b is not None else None
         st = np.zeros(n, dtype=np.uint32)
-        _chk(self._lib.ukfb_smooth(self._h, C.c_int(steps), _pd(d), _pd(mu), _pd(cov), _pd(a), _pd(b),
-                                   st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_smooth")
+        _chk(self._lib.ukfb_smooth(self._h, C.c_int(steps), _pd(d), _pd(mu), _pd(cov), _pd(a), _pd(b), _pu32(st)), "ukfb_smooth")
         return mu, cov, st
 
     # ---- forecast: rings [slots, capacity, S] / [slots, capacity, PK] in engine precision, the history's format
@@ -605,7 +619,7 @@ class BatchUKF:
             raise UkfbError("forecast: exactly one of dt and ts_us")
         d = np.ascontiguousarray(dt, dtype=np.float64).reshape(-1) if dt is not None else None
         t = np.ascontiguousarray(ts_us, dtype=np.int64).reshape(-1) if ts_us is not None else None
-        return d, t, (d.size if d is not None else t.size), (t.ctypes.data_as(C.POINTER(C.c_int64)) if t is not None else None)
+        return d, t, (d.size if d is not None else t.size), _pi64(t)
 
     def forecast_dev(self, slots: int, first_slot: int, mu_out, cov_out=None, status=None, dt=None, ts_us=None, start_mu=None,
                      start_cov=None, in_a_dev=None, in_b_dev=None):
@@ -637,7 +651,7 @@ class BatchUKF:
         cov = np.zeros((steps, n, self.D, self.D)) if with_cov else None
         st = np.zeros(n, dtype=np.uint32)
         _chk(self._lib.ukfb_forecast(self._h, C.c_int(steps), _pd(d), tp, _pd(sm), _pd(sc), _pd(a), _pd(b), _pd(mu), _pd(cov),
-                                     st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_forecast")
+                                     _pu32(st)), "ukfb_forecast")
         return mu, cov, st
 
     # ---- filter lifecycle: records [n, S] / [n, PK] / int64 [n] / uint8 [n] / [n, 3] / [n, 3] / [n, D, D] / uint32 [n] on the device
@@ -697,9 +711,8 @@ class BatchUKF:
         n = (idx.size if idx is not None else self.capacity) if n is None else n
         mu, cov = np.zeros((n, self.S)), np.zeros((n, self.D, self.D))
         ts, init = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.uint8)
-        _chk(self._lib.ukfb_gather_filters(self._h, C.c_int64(n), idx.ctypes.data_as(C.POINTER(C.c_int32)) if idx is not None else None,
-                                           _pd(mu), _pd(cov), ts.ctypes.data_as(C.POINTER(C.c_int64)),
-                                           init.ctypes.data_as(C.POINTER(C.c_uint8))), "ukfb_gather_filters")
+        _chk(self._lib.ukfb_gather_filters(self._h, C.c_int64(n), _pi32(idx), _pd(mu), _pd(cov), _pi64(ts), _pu8(init)),
+             "ukfb_gather_filters")
         return mu, cov, ts, init.astype(bool)
 
     def scatter_filters(self, index, mu, cov, last_ts_us=None, initialised=None):
@@ -713,18 +726,15 @@ class BatchUKF:
         if idx is not None and idx.size != n:
             raise UkfbError("scatter_filters: one index per record")
         st = np.zeros(n, dtype=np.uint32)
-        _chk(self._lib.ukfb_scatter_filters(self._h, C.c_int64(n), idx.ctypes.data_as(C.POINTER(C.c_int32)) if idx is not None else None,
-                                            _pd(mu), _pd(cov), ts.ctypes.data_as(C.POINTER(C.c_int64)) if ts is not None else None,
-                                            init.ctypes.data_as(C.POINTER(C.c_uint8)) if init is not None else None,
-                                            st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_scatter_filters")
+        _chk(self._lib.ukfb_scatter_filters(self._h, C.c_int64(n), _pi32(idx), _pd(mu), _pd(cov), _pi64(ts), _pu8(init), _pu32(st)),
+             "ukfb_scatter_filters")
         return st
 
     def compact(self, group: int = 1):
         """Host form -> (new_index int32 [capacity], old_index int32 [capacity], live); synchronises"""
         new, old = np.zeros(self.capacity, dtype=np.int32), np.zeros(self.capacity, dtype=np.int32)
         live = C.c_int64(0)
-        _chk(self._lib.ukfb_compact(self._h, C.c_int(group), new.ctypes.data_as(C.POINTER(C.c_int32)),
-                                    old.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(live)), "ukfb_compact")
+        _chk(self._lib.ukfb_compact(self._h, C.c_int(group), _pi32(new), _pi32(old), C.byref(live)), "ukfb_compact")
         return new, old, int(live.value)
 
     # ---- joint state-block measurements: z in the state's own layout [capacity, S], Qz the packed lower triangle [capacity, PK]
@@ -735,8 +745,7 @@ class BatchUKF:
         bank_combine_dev is a valid (z_dev, Qz_packed_dev) as it lies.  The update runs on state_inflation * Sigma and
         meas_inflation * Qz (1 / w, 1 / (1 - w): covariance intersection).  commit=False is read-only: only the keyword
         outputs (device buffers [capacity] in engine precision, status uint32 / int32) are written.  Stream-ordered."""
-        ptr = lambda x: None if x is None else _devptr(x).value
-        out = StateMeasOut(ptr(maha), ptr(loglik), ptr(status))
+        out = StateMeasOut(_ptr(maha), _ptr(loglik), _ptr(status))
         _chk(self._lib.ukfb_update_state_dev(self._h, C.c_uint32(int(block_mask)), _devptr(block_mask_dev), _devptr(z_dev),
                                              _devptr(Qz_packed_dev), C.c_double(state_inflation), C.c_double(meas_inflation),
                                              C.c_int(1 if commit else 0), C.byref(out)), "ukfb_update_state_dev")
@@ -746,12 +755,11 @@ class BatchUKF:
         (maha [capacity], loglik [capacity], status [capacity]); synchronises"""
         n = self.capacity
         z = _f64(z, (n, self.S)); Qz = _f64(Qz, (n, self.D, self.D))
-        per = None if np.isscalar(block_mask) else np.ascontiguousarray(block_mask, dtype=np.int32).reshape(n)
+        mask, per = _int_or_i32(block_mask, n)
         maha, ll, st = np.empty(n), np.empty(n), np.empty(n, dtype=np.uint32)
-        _chk(self._lib.ukfb_update_state(self._h, C.c_uint32(0 if per is not None else int(block_mask)),
-                                         per.ctypes.data_as(C.POINTER(C.c_int32)) if per is not None else None, _pd(z), _pd(Qz),
-                                         C.c_double(state_inflation), C.c_double(meas_inflation), C.c_int(1 if commit else 0),
-                                         _pd(maha), _pd(ll), st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_update_state")
+        _chk(self._lib.ukfb_update_state(self._h, C.c_uint32(mask), _pi32(per), _pd(z), _pd(Qz), C.c_double(state_inflation),
+                                         C.c_double(meas_inflation), C.c_int(1 if commit else 0), _pd(maha), _pd(ll), _pu32(st)),
+             "ukfb_update_state")
         return maha, ll, st
 
     def update_body_states(self, block_mask: int, records, active=None):
@@ -759,8 +767,7 @@ class BatchUKF:
         of the blocks `block_mask` selects; active uint8 [capacity] or None.  Synchronises."""
         rec = _f64(records, (self.capacity, BODY_STATE_SCALARS))
         act = np.ascontiguousarray(active, dtype=np.uint8).reshape(self.capacity) if active is not None else None
-        _chk(self._lib.ukfb_pose_update_body_states(self._h, C.c_uint32(int(block_mask)), _pd(rec),
-                                                    act.ctypes.data_as(C.POINTER(C.c_uint8)) if act is not None else None),
+        _chk(self._lib.ukfb_pose_update_body_states(self._h, C.c_uint32(int(block_mask)), _pd(rec), _pu8(act)),
              "ukfb_pose_update_body_states")
 
     # ---- sensor-frame measurements: z [capacity, 3], Q [capacity, 9] (or 9 scalars), mount [capacity, 7], point [capacity, 3]
@@ -771,31 +778,31 @@ class BatchUKF:
         negative: none).  mount = r[3] then qs[4] (x, y, z, w), point = b[3]: host values for the whole batch, or device
         arrays per filter (mount_dev / point_dev).  commit=False is read-only: only the keyword outputs (device buffers in
         engine precision, status uint32 / int32) are written.  Stream-ordered."""
-        ptr = lambda x: None if x is None else _devptr(x).value
-        sin = SensorIn(ptr(model_dev), ptr(z_dev), ptr(Q_dev), 1 if q_is_uniform else 0, ptr(mount_dev),
-                       (C.c_double * 7)(*[float(v) for v in mount]), ptr(point_dev), (C.c_double * 3)(*[float(v) for v in point]))
-        out = SensorOut(ptr(z_pred), ptr(S), ptr(innov), ptr(maha), ptr(loglik), ptr(status))
+        sin = SensorIn(_ptr(model_dev), _ptr(z_dev), _ptr(Q_dev), 1 if q_is_uniform else 0, _ptr(mount_dev),
+                       (C.c_double * 7)(*[float(v) for v in mount]), _ptr(point_dev), (C.c_double * 3)(*[float(v) for v in point]))
+        out = SensorOut(_ptr(z_pred), _ptr(S), _ptr(innov), _ptr(maha), _ptr(loglik), _ptr(status))
         _chk(self._lib.ukfb_update_sensor_dev(self._h, C.c_int(int(model)), C.byref(sin), C.c_int(1 if commit else 0), C.byref(out)),
              "ukfb_update_sensor_dev")
+
+    def _update_sensor_frame(self, fn: str, model, z, Q, mount, point, commit):
+        """ukfb_update_sensor and ukfb_update_bearing: one signature, one shape of arguments and results"""
+        n = self.capacity
+        z = _f64(z, (n, 3)); Q = _f64(Q, (n, 3, 3))
+        uniform, per = _int_or_i32(model, n)
+        mp, mu_ = _per_or_uniform(mount, n, 7)
+        pp, pu = _per_or_uniform(point, n, 3)
+        o = {"z_pred": np.empty((n, 3)), "S": np.empty((n, 3, 3)), "innov": np.empty((n, 3)), "maha": np.empty(n),
+             "loglik": np.empty(n), "status": np.empty(n, dtype=np.uint32)}
+        _chk(getattr(self._lib, fn)(self._h, C.c_int(uniform), _pi32(per), _pd(z), _pd(Q), _pd(mp), _pd(mu_), _pd(pp), _pd(pu),
+                                    C.c_int(1 if commit else 0), _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]),
+                                    _pd(o["loglik"]), _pu32(o["status"])), fn)
+        return o
 
     def update_sensor(self, model, z, Q, mount=SENSOR_MOUNT_IDENTITY, point=(0.0, 0.0, 0.0), commit: bool = True):
         """Host arrays: z [capacity, 3], Q [capacity, 3, 3]; model an int or an int32 array [capacity]; mount [7] or
         [capacity, 7], point [3] or [capacity, 3].  Returns a dict of NumPy arrays: z_pred [n, 3], S [n, 3, 3], innov [n, 3],
         maha [n], loglik [n], status [n]; synchronises"""
-        n = self.capacity
-        z = _f64(z, (n, 3)); Q = _f64(Q, (n, 3, 3))
-        per = None if np.isscalar(model) else np.ascontiguousarray(model, dtype=np.int32).reshape(n)
-        mount = _f64(mount); point = _f64(point)
-        mp, mu_ = (mount.reshape(n, 7), None) if mount.ndim == 2 else (None, mount.reshape(7))
-        pp, pu = (point.reshape(n, 3), None) if point.ndim == 2 else (None, point.reshape(3))
-        o = {"z_pred": np.empty((n, 3)), "S": np.empty((n, 3, 3)), "innov": np.empty((n, 3)), "maha": np.empty(n),
-             "loglik": np.empty(n), "status": np.empty(n, dtype=np.uint32)}
-        _chk(self._lib.ukfb_update_sensor(self._h, C.c_int(0 if per is not None else int(model)),
-                                          per.ctypes.data_as(C.POINTER(C.c_int32)) if per is not None else None, _pd(z), _pd(Q),
-                                          _pd(mp), _pd(mu_), _pd(pp), _pd(pu), C.c_int(1 if commit else 0), _pd(o["z_pred"]),
-                                          _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]),
-                                          o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_update_sensor")
-        return o
+        return self._update_sensor_frame("ukfb_update_sensor", model, z, Q, mount, point, commit)
 
     # ---- bearing measurements: z [capacity, 3] a direction, Q [capacity, 9] (or 9 scalars), mount [capacity, 7], point [capacity, 3]
     def update_bearing_dev(self, model: int, z_dev, Q_dev, q_is_uniform: bool = False, model_dev=None, mount_dev=None,
@@ -806,30 +813,16 @@ class BatchUKF:
         frame, of which the tangent part at the predicted direction enters.  mount, point, commit and the keyword outputs as
         for update_sensor_dev; z_pred is a unit vector, S = Sigma_z + P Q P (3 x 3, rank 2), innov the sphere logarithm.
         Stream-ordered."""
-        ptr = lambda x: None if x is None else _devptr(x).value
-        sin = SensorIn(ptr(model_dev), ptr(z_dev), ptr(Q_dev), 1 if q_is_uniform else 0, ptr(mount_dev),
-                       (C.c_double * 7)(*[float(v) for v in mount]), ptr(point_dev), (C.c_double * 3)(*[float(v) for v in point]))
-        out = SensorOut(ptr(z_pred), ptr(S), ptr(innov), ptr(maha), ptr(loglik), ptr(status))
+        sin = SensorIn(_ptr(model_dev), _ptr(z_dev), _ptr(Q_dev), 1 if q_is_uniform else 0, _ptr(mount_dev),
+                       (C.c_double * 7)(*[float(v) for v in mount]), _ptr(point_dev), (C.c_double * 3)(*[float(v) for v in point]))
+        out = SensorOut(_ptr(z_pred), _ptr(S), _ptr(innov), _ptr(maha), _ptr(loglik), _ptr(status))
         _chk(self._lib.ukfb_update_bearing_dev(self._h, C.c_int(int(model)), C.byref(sin), C.c_int(1 if commit else 0), C.byref(out)),
              "ukfb_update_bearing_dev")
 
     def update_bearing(self, model, z, Q, mount=SENSOR_MOUNT_IDENTITY, point=(0.0, 0.0, 0.0), commit: bool = True):
         """Host arrays, shaped as for update_sensor.  Returns a dict of NumPy arrays: z_pred [n, 3], S [n, 3, 3], innov [n, 3],
         maha [n], loglik [n], status [n]; synchronises"""
-        n = self.capacity
-        z = _f64(z, (n, 3)); Q = _f64(Q, (n, 3, 3))
-        per = None if np.isscalar(model) else np.ascontiguousarray(model, dtype=np.int32).reshape(n)
-        mount = _f64(mount); point = _f64(point)
-        mp, mu_ = (mount.reshape(n, 7), None) if mount.ndim == 2 else (None, mount.reshape(7))
-        pp, pu = (point.reshape(n, 3), None) if point.ndim == 2 else (None, point.reshape(3))
-        o = {"z_pred": np.empty((n, 3)), "S": np.empty((n, 3, 3)), "innov": np.empty((n, 3)), "maha": np.empty(n),
-             "loglik": np.empty(n), "status": np.empty(n, dtype=np.uint32)}
-        _chk(self._lib.ukfb_update_bearing(self._h, C.c_int(0 if per is not None else int(model)),
-                                           per.ctypes.data_as(C.POINTER(C.c_int32)) if per is not None else None, _pd(z), _pd(Q),
-                                           _pd(mp), _pd(mu_), _pd(pp), _pd(pu), C.c_int(1 if commit else 0), _pd(o["z_pred"]),
-                                           _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]),
-                                           o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_update_bearing")
-        return o
+        return self._update_sensor_frame("ukfb_update_bearing", model, z, Q, mount, point, commit)
 
     # ---- sensor-frame association: z [candidates, capacity, 3]; the point [capacity, 3] or, per hypothesis, [candidates, capacity, 3]
     def associate_sensor_dev(self, model: int, candidates: int, z_dev, Q_dev, q_is_uniform: bool = False, model_dev=None,
@@ -843,11 +836,10 @@ class BatchUKF:
         Keyword outputs (device buffers in engine precision; best, n_gated int32; status uint32 / int32): z_pred
         [H, capacity, 3], S [H, capacity, 9] with H = candidates per hypothesis, else 1; innov [candidates, capacity, 3],
         maha / loglik [candidates, capacity].  commit=False is read-only.  Stream-ordered."""
-        ptr = lambda x: None if x is None else _devptr(x).value
-        ain = AssociateIn(ptr(model_dev), int(candidates), ptr(z_dev), ptr(Q_dev), 1 if q_is_uniform else 0, ptr(mount_dev),
-                          (C.c_double * 7)(*[float(v) for v in mount]), ptr(point_dev), (C.c_double * 3)(*[float(v) for v in point]),
+        ain = AssociateIn(_ptr(model_dev), int(candidates), _ptr(z_dev), _ptr(Q_dev), 1 if q_is_uniform else 0, _ptr(mount_dev),
+                          (C.c_double * 7)(*[float(v) for v in mount]), _ptr(point_dev), (C.c_double * 3)(*[float(v) for v in point]),
                           1 if point_per_candidate else 0)
-        out = AssociateOut(ptr(z_pred), ptr(S), ptr(innov), ptr(maha), ptr(loglik), ptr(best), ptr(n_gated), ptr(status))
+        out = AssociateOut(_ptr(z_pred), _ptr(S), _ptr(innov), _ptr(maha), _ptr(loglik), _ptr(best), _ptr(n_gated), _ptr(status))
         _chk(self._lib.ukfb_associate_sensor_dev(self._h, C.c_int(int(model)), C.byref(ain), C.c_int(1 if commit else 0), C.byref(out)),
              "ukfb_associate_sensor_dev")
 
@@ -862,23 +854,17 @@ class BatchUKF:
         K = int(z.shape[0]) if z.ndim == 3 else 0
         z = _f64(z, (K, n, 3)); Q = _f64(Q, (n, 3, 3))
         H = K if point_per_candidate else 1
-        per = None if np.isscalar(model) else np.ascontiguousarray(model, dtype=np.int32).reshape(n)
-        mount = _f64(mount); point = _f64(point)
-        mp, mu_ = (mount.reshape(n, 7), None) if mount.ndim == 2 else (None, mount.reshape(7))
-        if point_per_candidate:
-            pp, pu = point.reshape(K, n, 3), None
-        else:
-            pp, pu = (point.reshape(n, 3), None) if point.ndim == 2 else (None, point.reshape(3))
+        uniform, per = _int_or_i32(model, n)
+        mp, mu_ = _per_or_uniform(mount, n, 7)
+        pp, pu = (_f64(point, (K, n, 3)), None) if point_per_candidate else _per_or_uniform(point, n, 3)
         o = {"z_pred": np.empty((H, n, 3)), "S": np.empty((H, n, 3, 3)), "innov": np.empty((K, n, 3)), "maha": np.empty((K, n)),
              "loglik": np.empty((K, n)), "best": np.empty(n, dtype=np.int32), "n_gated": np.empty(n, dtype=np.int32),
              "status": np.empty(n, dtype=np.uint32)}
-        pi = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        _chk(self._lib.ukfb_associate_sensor(self._h, C.c_int(0 if per is not None else int(model)),
-                                             pi(per) if per is not None else None, C.c_int(K), _pd(z), _pd(Q), _pd(mp), _pd(mu_),
-                                             _pd(pp), _pd(pu), C.c_int(1 if point_per_candidate else 0), C.c_int(1 if commit else 0),
-                                             _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]),
-                                             pi(o["best"]), pi(o["n_gated"]), o["status"].ctypes.data_as(C.POINTER(C.c_uint32))),
-             "ukfb_associate_sensor")
+        _chk(self._lib.ukfb_associate_sensor(self._h, C.c_int(uniform), _pi32(per), C.c_int(K), _pd(z), _pd(Q), _pd(mp), _pd(mu_),
+                                             _pd(pp), _pd(pu), C.c_int(1 if point_per_candidate else 0),
+                                             C.c_int(1 if commit else 0), _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]),
+                                             _pd(o["maha"]), _pd(o["loglik"]), _pi32(o["best"]), _pi32(o["n_gated"]),
+                                             _pu32(o["status"])), "ukfb_associate_sensor")
         return o
 
     # ---- user-defined measurement models: X [capacity, 2 D + 1, S], delta [capacity, 2 D + 1, D], Z [capacity, 2 D + 1, m]
@@ -896,9 +882,8 @@ class BatchUKF:
         [capacity] or None.  The state must not change between the export and this call.  z and Z may be written relative to
         any per-filter origin (fp32 engines: one near the values).  commit=False is read-only: only the keyword outputs
         (device buffers in engine precision, status uint32 / int32) are written.  Stream-ordered."""
-        ptr = lambda x: None if x is None else _devptr(x).value
-        sin = SampledIn(int(m), ptr(Z_dev), ptr(z_dev), ptr(Q_dev), 1 if q_is_uniform else 0, ptr(active_dev))
-        out = SampledOut(ptr(z_pred), ptr(S), ptr(innov), ptr(maha), ptr(loglik), ptr(status))
+        sin = SampledIn(int(m), _ptr(Z_dev), _ptr(z_dev), _ptr(Q_dev), 1 if q_is_uniform else 0, _ptr(active_dev))
+        out = SampledOut(_ptr(z_pred), _ptr(S), _ptr(innov), _ptr(maha), _ptr(loglik), _ptr(status))
         _chk(self._lib.ukfb_update_sampled_dev(self._h, C.byref(sin), C.c_int(1 if commit else 0), C.byref(out)),
              "ukfb_update_sampled_dev")
 
@@ -906,7 +891,7 @@ class BatchUKF:
         """Host form -> (X [capacity, 2 D + 1, S], delta [capacity, 2 D + 1, D], status [capacity]); synchronises"""
         n, pts = self.capacity, 2 * self.D + 1
         X, delta, st = np.empty((n, pts, self.S)), np.empty((n, pts, self.D)), np.empty(n, dtype=np.uint32)
-        _chk(self._lib.ukfb_sigma_points(self._h, _pd(X), _pd(delta), st.ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_sigma_points")
+        _chk(self._lib.ukfb_sigma_points(self._h, _pd(X), _pd(delta), _pu32(st)), "ukfb_sigma_points")
         return X, delta, st
 
     def update_sampled(self, Z, z, Q, active=None, commit: bool = True):
@@ -922,10 +907,9 @@ class BatchUKF:
         act = np.ascontiguousarray(active, dtype=np.uint8).reshape(n) if active is not None else None
         o = {"z_pred": np.empty((n, m)), "S": np.empty((n, m, m)), "innov": np.empty((n, m)), "maha": np.empty(n),
              "loglik": np.empty(n), "status": np.empty(n, dtype=np.uint32)}
-        _chk(self._lib.ukfb_update_sampled(self._h, C.c_int(m), _pd(Z), _pd(z), _pd(Q), C.c_int(1 if uniform else 0),
-                                           act.ctypes.data_as(C.POINTER(C.c_uint8)) if act is not None else None,
-                                           C.c_int(1 if commit else 0), _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]),
-                                           _pd(o["loglik"]), o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_update_sampled")
+        _chk(self._lib.ukfb_update_sampled(self._h, C.c_int(m), _pd(Z), _pd(z), _pd(Q), C.c_int(1 if uniform else 0), _pu8(act),
+                                           C.c_int(1 if commit else 0), _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]),
+                                           _pd(o["maha"]), _pd(o["loglik"]), _pu32(o["status"])), "ukfb_update_sampled")
         return o
 
     # ---- user-defined process models: XX [capacity, 2 D + 1, S] = f(X) of sigma_points_dev's X, R [capacity, D, D]
@@ -936,9 +920,8 @@ class BatchUKF:
         is read); active_dev uint8 [capacity] or None.  Times, noise tables and latches are not touched.  commit=False is
         read-only: only the keyword outputs (device buffers in engine precision: mu [capacity, S], cov_packed [capacity, PK];
         status uint32 / int32) are written.  Stream-ordered, nothing is allocated."""
-        ptr = lambda x: None if x is None else _devptr(x).value
-        pin = PredictSampledIn(ptr(XX), ptr(R), 1 if r_is_uniform else 0, ptr(active_dev))
-        out = PredictSampledOut(ptr(mu), ptr(cov_packed), ptr(status))
+        pin = PredictSampledIn(_ptr(XX), _ptr(R), 1 if r_is_uniform else 0, _ptr(active_dev))
+        out = PredictSampledOut(_ptr(mu), _ptr(cov_packed), _ptr(status))
         _chk(self._lib.ukfb_predict_sampled_dev(self._h, C.byref(pin), C.c_int(1 if commit else 0), C.byref(out)),
              "ukfb_predict_sampled_dev")
 
@@ -951,10 +934,9 @@ class BatchUKF:
         R = R.reshape(D, D) if uniform else R.reshape(n, D, D)
         act = np.ascontiguousarray(active, dtype=np.uint8).reshape(n) if active is not None else None
         o = {"mu": np.empty((n, S)), "cov": np.empty((n, D, D)), "status": np.empty(n, dtype=np.uint32)}
-        _chk(self._lib.ukfb_predict_sampled(self._h, _pd(XX), _pd(R), C.c_int(1 if uniform else 0),
-                                            act.ctypes.data_as(C.POINTER(C.c_uint8)) if act is not None else None,
-                                            C.c_int(1 if commit else 0), _pd(o["mu"]), _pd(o["cov"]),
-                                            o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_predict_sampled")
+        _chk(self._lib.ukfb_predict_sampled(self._h, _pd(XX), _pd(R), C.c_int(1 if uniform else 0), _pu8(act),
+                                            C.c_int(1 if commit else 0), _pd(o["mu"]), _pd(o["cov"]), _pu32(o["status"])),
+             "ukfb_predict_sampled")
         return o
 
     # ---- covariance conditioning: var_floor [D], eig_floor in (0, 1)
@@ -967,9 +949,8 @@ class BatchUKF:
         keeps every bit.  renormalize_quaternion also brings the stored quaternion back to unit length.  commit=False is
         read-only: only the keyword outputs (device buffers in engine precision: eig_min / eig_max [capacity], mu [capacity, S],
         cov_packed [capacity, PK]; status uint32 / int32) are written.  Stream-ordered, nothing is allocated."""
-        ptr = lambda x: None if x is None else _devptr(x).value
-        cin = ConditionIn(ptr(var_floor_dev), float(eig_floor), ptr(select_dev), 1 if renormalize_quaternion else 0)
-        out = ConditionOut(ptr(eig_min), ptr(eig_max), ptr(mu), ptr(cov_packed), ptr(status))
+        cin = ConditionIn(_ptr(var_floor_dev), float(eig_floor), _ptr(select_dev), 1 if renormalize_quaternion else 0)
+        out = ConditionOut(_ptr(eig_min), _ptr(eig_max), _ptr(mu), _ptr(cov_packed), _ptr(status))
         _chk(self._lib.ukfb_condition_dev(self._h, C.byref(cin), C.c_int(1 if commit else 0), C.byref(out)), "ukfb_condition_dev")
 
     def condition(self, var_floor, eig_floor: float, select=None, renormalize_quaternion: bool = False, commit: bool = True):
@@ -980,11 +961,9 @@ class BatchUKF:
         sel = np.ascontiguousarray(select, dtype=np.uint8).reshape(n) if select is not None else None
         o = {"eig_min": np.empty(n), "eig_max": np.empty(n), "mu": np.empty((n, S)), "cov": np.empty((n, D, D)),
              "status": np.empty(n, dtype=np.uint32)}
-        _chk(self._lib.ukfb_condition(self._h, _pd(v), C.c_double(float(eig_floor)),
-                                      sel.ctypes.data_as(C.POINTER(C.c_uint8)) if sel is not None else None,
+        _chk(self._lib.ukfb_condition(self._h, _pd(v), C.c_double(float(eig_floor)), _pu8(sel),
                                       C.c_int(1 if renormalize_quaternion else 0), C.c_int(1 if commit else 0), _pd(o["eig_min"]),
-                                      _pd(o["eig_max"]), _pd(o["mu"]), _pd(o["cov"]),
-                                      o["status"].ctypes.data_as(C.POINTER(C.c_uint32))), "ukfb_condition")
+                                      _pd(o["eig_max"]), _pd(o["mu"]), _pd(o["cov"]), _pu32(o["status"])), "ukfb_condition")
         return o
 
     # ---- late samples: the window of smooth_dev with the engine's own state as its last step
@@ -998,13 +977,11 @@ class BatchUKF:
         outputs (device buffers in engine precision, status uint32 / int32; mu_out [capacity, S] / cov_out [capacity, PK] = the
         corrected present state) are written.  Stream-ordered, nothing is allocated."""
         d = np.ascontiguousarray(dt, dtype=np.float64).reshape(-1)
-        ptr = lambda x: None if x is None else _devptr(x).value
-        per = lambda x: (0, ptr(x)) if hasattr(x, "data_ptr") else (int(x), None)
+        per = lambda x: (0, _ptr(x)) if hasattr(x, "data_ptr") else (int(x), None)
         (lag_u, lag_p), (mod_u, mod_p) = per(lag), per(meas_model)
-        din = DelayedIn(d.size + 1, d.ctypes.data_as(C.POINTER(C.c_double)) if d.size else None, int(slots), int(first_slot),
-                        ptr(mu_hist), ptr(cov_hist), ptr(in_a_dev), ptr(in_b_dev), lag_u, lag_p, mod_u, mod_p, ptr(z_dev), ptr(Q_dev),
-                        1 if q_is_uniform else 0)
-        out = DelayedOut(ptr(z_pred), ptr(S), ptr(innov), ptr(maha), ptr(loglik), ptr(status), ptr(mu_out), ptr(cov_out))
+        din = DelayedIn(d.size + 1, _pd(d) if d.size else None, int(slots), int(first_slot), _ptr(mu_hist), _ptr(cov_hist),
+                        _ptr(in_a_dev), _ptr(in_b_dev), lag_u, lag_p, mod_u, mod_p, _ptr(z_dev), _ptr(Q_dev), 1 if q_is_uniform else 0)
+        out = DelayedOut(_ptr(z_pred), _ptr(S), _ptr(innov), _ptr(maha), _ptr(loglik), _ptr(status), _ptr(mu_out), _ptr(cov_out))
         _chk(self._lib.ukfb_update_delayed_dev(self._h, C.byref(din), C.c_int(1 if commit else 0), C.byref(out)),
              "ukfb_update_delayed_dev")
 
@@ -1019,17 +996,14 @@ class BatchUKF:
         a = _f64(in_a, (steps, n, 3)) if in_a is not None else None
         b = _f64(in_b, (steps, n, 3)) if in_b is not None else None
         z = _f64(z, (n, 3)); Q = _f64(Q, (n, 3, 3))
-        i32 = lambda x: None if np.isscalar(x) else np.ascontiguousarray(x, dtype=np.int32).reshape(n)
-        lag_p, mod_p = i32(lag), i32(meas_model)
-        ip = lambda x: x.ctypes.data_as(C.POINTER(C.c_int32)) if x is not None else None
+        (lag_u, lag_p), (mod_u, mod_p) = _int_or_i32(lag, n), _int_or_i32(meas_model, n)
         o = {"z_pred": np.empty((n, 4)), "S": np.empty((n, 3, 3)), "innov": np.empty((n, 3)), "maha": np.empty(n),
              "loglik": np.empty(n), "status": np.empty(n, dtype=np.uint32), "mu_out": np.empty((n, self.S)),
              "cov_out": np.empty((n, self.D, self.D))}
-        _chk(self._lib.ukfb_update_delayed(self._h, C.c_int(steps), _pd(d) if d.size else None, _pd(mu_hist), _pd(cov_hist), _pd(a),
-                                           _pd(b), C.c_int(0 if lag_p is not None else int(lag)), ip(lag_p),
-                                           C.c_int(0 if mod_p is not None else int(meas_model)), ip(mod_p), _pd(z), _pd(Q),
-                                           C.c_int(1 if commit else 0), _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]),
-                                           _pd(o["loglik"]), o["status"].ctypes.data_as(C.POINTER(C.c_uint32)), _pd(o["mu_out"]),
+        _chk(self._lib.ukfb_update_delayed(self._h, C.c_int(steps), _pd(d) if d.size else None, _pd(mu_hist), _pd(cov_hist),
+                                           _pd(a), _pd(b), C.c_int(lag_u), _pi32(lag_p), C.c_int(mod_u), _pi32(mod_p), _pd(z), _pd(Q),
+                                           C.c_int(1 if commit else 0), _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]),
+                                           _pd(o["maha"]), _pd(o["loglik"]), _pu32(o["status"]), _pd(o["mu_out"]),
                                            _pd(o["cov_out"])), "ukfb_update_delayed")
         return o
 
@@ -1038,8 +1012,8 @@ class BatchUKF:
         lag_out_dev int32 [capacity]: the step nearest each sample (ties: the older), 0 for a sample newer than the present,
         len(step_ts_us) (out of the window) for one older than the first step by more than half a step.  Stream-ordered."""
         ts = np.ascontiguousarray(step_ts_us, dtype=np.int64).reshape(-1)
-        _chk(self._lib.ukfb_delayed_lag_dev(self._h, C.c_int(ts.size), ts.ctypes.data_as(C.POINTER(C.c_int64)),
-                                            _devptr(sample_ts_us_dev), _devptr(lag_out_dev)), "ukfb_delayed_lag_dev")
+        _chk(self._lib.ukfb_delayed_lag_dev(self._h, C.c_int(ts.size), _pi64(ts), _devptr(sample_ts_us_dev), _devptr(lag_out_dev)),
+             "ukfb_delayed_lag_dev")
 
     # ---- fused cycle
     def cycle(self, dt: float, meas_model: int, z, Q):
@@ -1058,8 +1032,7 @@ class BatchUKF:
     def update_uniform_q(self, meas_model: int, z, Q9, active=None):
         z = _f64(z, (self.capacity, 3)); Q9 = _f64(Q9, (9,))
         a = None if active is None else np.ascontiguousarray(active, dtype=np.uint8).reshape(self.capacity)
-        _chk(self._lib.ukfb_update_uniform_q(self._h, C.c_int(meas_model), _pd(z), _pd(Q9),
-                                             a.ctypes.data_as(C.POINTER(C.c_uint8)) if a is not None else None), "ukfb_update_uniform_q")
+        _chk(self._lib.ukfb_update_uniform_q(self._h, C.c_int(meas_model), _pd(z), _pd(Q9), _pu8(a)), "ukfb_update_uniform_q")
 
     def cycle_dev(self, dt: float, meas_model_uniform: int, z_dev, Q_dev, meas_model_dev=None):
         _chk(self._lib.ukfb_cycle_dev(self._h, C.c_double(dt), C.c_int(meas_model_uniform), _devptr(meas_model_dev),
@@ -1088,9 +1061,9 @@ class BatchUKF:
         m = np.ascontiguousarray(meas_model, dtype=np.int32).reshape(-1)
         if d.size != m.size:
             raise ValueError("dt and meas_model need one entry per cycle")
-        _chk(self._lib.ukfb_cycle_schedule_dev(self._h, C.c_int(d.size), _pd(d), m.ctypes.data_as(C.POINTER(C.c_int32)),
-                                               C.c_int(slots), C.c_int(first_slot), _devptr(in_a_dev), _devptr(in_b_dev),
-                                               _devptr(z_dev), _devptr(Q_dev)), "ukfb_cycle_schedule_dev")
+        _chk(self._lib.ukfb_cycle_schedule_dev(self._h, C.c_int(d.size), _pd(d), _pi32(m), C.c_int(slots), C.c_int(first_slot),
+                                               _devptr(in_a_dev), _devptr(in_b_dev), _devptr(z_dev), _devptr(Q_dev)),
+             "ukfb_cycle_schedule_dev")
 
     def cycle_multi(self, dt: float, meas_model: int, z, Q, in_a=None, in_b=None):
         """Host arrays, one input set per cycle: z [cycles, capacity, 3], Q [cycles, capacity, 3, 3], in_a / in_b
@@ -1109,9 +1082,7 @@ class BatchUKF:
         t = np.ascontiguousarray(ts_us, dtype=np.int64).reshape(self.capacity)
         m = np.ascontiguousarray(meas_model, dtype=np.int32).reshape(self.capacity)
         z = _f64(z, (self.capacity, 3)); Q = _f64(Q, (self.capacity, 3, 3))
-        _chk(self._lib.ukfb_cycle_timestamps(self._h, t.ctypes.data_as(C.POINTER(C.c_int64)),
-                                             m.ctypes.data_as(C.POINTER(C.c_int32)), _pd(z), _pd(Q)),
-             "ukfb_cycle_timestamps")
+        _chk(self._lib.ukfb_cycle_timestamps(self._h, _pi64(t), _pi32(m), _pd(z), _pd(Q)), "ukfb_cycle_timestamps")
 
     def process_events(self, filter_index, ts_us, meas_model, z, Q):
         """Time-ordered asynchronous measurement stream (any arrival order).  Returns (status_or, rounds)."""
@@ -1121,9 +1092,7 @@ class BatchUKF:
         m = np.ascontiguousarray(meas_model, dtype=np.int32).reshape(n)
         z = _f64(z, (n, 3)); Q = _f64(Q, (n, 3, 3))
         st, rounds = C.c_uint32(0), C.c_int64(0)
-        _chk(self._lib.ukfb_process_events(self._h, C.c_int64(n), f.ctypes.data_as(C.POINTER(C.c_int64)),
-                                           t.ctypes.data_as(C.POINTER(C.c_int64)),
-                                           m.ctypes.data_as(C.POINTER(C.c_int32)), _pd(z), _pd(Q), C.byref(st),
+        _chk(self._lib.ukfb_process_events(self._h, C.c_int64(n), _pi64(f), _pi64(t), _pi32(m), _pd(z), _pd(Q), C.byref(st),
                                            C.byref(rounds)), "ukfb_process_events")
         return int(st.value), int(rounds.value)
 
@@ -1149,8 +1118,7 @@ class BatchUKF:
         items = C.c_int64(0)
         cap = int(self.capacity) + 16
         out = np.empty(cap, dtype=np.int32)
-        _chk(self._lib.ukfb_last_model_groups(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), C.c_int64(cap), C.byref(items)),
-             "ukfb_last_model_groups")
+        _chk(self._lib.ukfb_last_model_groups(self._h, _pi32(out), C.c_int64(cap), C.byref(items)), "ukfb_last_model_groups")
         return out[:int(items.value)].copy()
 
     def timer_begin(self):
@@ -1267,15 +1235,14 @@ class UKFGroup:
     def state(self, first: int = 0, count: Optional[int] = None):
         count = self.total - first if count is None else count
         mu = np.empty((count, self.S)); cov = np.empty((count, self.D, self.D)); init = np.empty(count, dtype=np.uint8)
-        _chk(self._lib.ukfb_group_get_state(self._g, C.c_int64(first), C.c_int64(count), _pd(mu), _pd(cov),
-                                            init.ctypes.data_as(C.POINTER(C.c_uint8))), "ukfb_group_get_state")
+        _chk(self._lib.ukfb_group_get_state(self._g, C.c_int64(first), C.c_int64(count), _pd(mu), _pd(cov), _pu8(init)),
+             "ukfb_group_get_state")
         return mu, cov, init.astype(bool)
 
     def status(self, first: int = 0, count: Optional[int] = None):
         count = self.total - first if count is None else count
         st = np.empty(count, dtype=np.uint32)
-        _chk(self._lib.ukfb_group_get_status(self._g, C.c_int64(first), C.c_int64(count), st.ctypes.data_as(C.POINTER(C.c_uint32))),
-             "ukfb_group_get_status")
+        _chk(self._lib.ukfb_group_get_status(self._g, C.c_int64(first), C.c_int64(count), _pu32(st)), "ukfb_group_get_status")
         return st
 
     def status_summary(self) -> int:
@@ -1340,8 +1307,7 @@ class UKFGroup:
         t = np.ascontiguousarray(ts_us, dtype=np.int64).reshape(self.total)
         m = np.ascontiguousarray(meas_model, dtype=np.int32).reshape(self.total)
         z = _f64(z, (self.total, 3)); Q = _f64(Q, (self.total, 3, 3))
-        _chk(self._lib.ukfb_group_cycle_timestamps(self._g, t.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                   m.ctypes.data_as(C.POINTER(C.c_int32)), _pd(z), _pd(Q)), "ukfb_group_cycle_timestamps")
+        _chk(self._lib.ukfb_group_cycle_timestamps(self._g, _pi64(t), _pi32(m), _pd(z), _pd(Q)), "ukfb_group_cycle_timestamps")
 
     def process_events(self, filter_index, ts_us, meas_model, z, Q):
         """Time-ordered asynchronous stream over the sharded batch (filter indices in batch numbering, any arrival order).
@@ -1352,9 +1318,8 @@ class UKFGroup:
         m = np.ascontiguousarray(meas_model, dtype=np.int32).reshape(n)
         z = _f64(z, (n, 3)); Q = _f64(Q, (n, 3, 3))
         st, rounds = C.c_uint32(0), C.c_int64(0)
-        _chk(self._lib.ukfb_group_process_events(self._g, C.c_int64(n), f.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                 t.ctypes.data_as(C.POINTER(C.c_int64)), m.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                 _pd(z), _pd(Q), C.byref(st), C.byref(rounds)), "ukfb_group_process_events")
+        _chk(self._lib.ukfb_group_process_events(self._g, C.c_int64(n), _pi64(f), _pi64(t), _pi32(m), _pd(z), _pd(Q), C.byref(st),
+                                                 C.byref(rounds)), "ukfb_group_process_events")
         return int(st.value), int(rounds.value)
 
     def sync(self):
