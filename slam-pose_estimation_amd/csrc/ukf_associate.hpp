@@ -2,7 +2,7 @@
 // candidate samples per filter in one launch, the nearest candidate inside the gate chosen by ukfb_innovation_dev's rule and,
 // with commit = 1, the update finished with it.  Definitions: include/ukf_batch.h ("sensor-frame association"), DESIGN.md 4.26.
 //
-// Layout, LDS map (SensorLayout) and device functions are the sensor kernel's: one filter per 16-lane DPP row, lane l < D owns
+// Layout, LDS map (sensor_map) and device functions are the sensor kernel's: one filter per 16-lane DPP row, lane l < D owns
 // the sigma pair of factor column l, lane D the centre; h is sensor_h itself, S, its factor and the solves are the same
 // statements in the same order.  What differs:
 //  * step 1 (chol(Sigma), the sigma pair in registers) runs once and stays resident over the candidate loop;
@@ -73,8 +73,8 @@ UKFB_DEV void assoc_measure(const T (&xp)[M::S], const T (&xm)[M::S], int id, in
                             bool need_sens, bool active, T mean_tol, int mean_max_it, const T* FAC, const T* INP, T* WT, T* DUMP, int l,
                             int lr, AssocHyp<T>& hy) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1;
-    using LY = SensorLayout<M>;
-    constexpr int LS = LY::LS, ZS = LY::ZS;
+    constexpr SensorMap LY = sensor_map(S, D);
+    constexpr int LS = LY.LS, ZS = LY.ZS;
     using TH = double;
     // ---- 2. Z = h(X) on the lane's pair, relative to Z_0
     T zp[3], zm[3];
@@ -196,18 +196,20 @@ template <class T> UKFB_DEV T assoc_pick3(T v0, T v1, T v2, int l) { return (l =
 template <class T, class M, class TS, bool HYP>
 __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_associate_kernel(const AssociateArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2;
-    using LY = SensorLayout<M>;
-    constexpr int LS = LY::LS, ZS = LY::ZS, Q = MT<M>::Q;
+    constexpr SensorMap LY = sensor_map(S, D);
+    constexpr int LS = LY.LS, ZS = LY.ZS, Q = MT<M>::Q;
+    static_assert(row_fits(M::S, M::D), "a filter fits one row");
+    static_assert(2 * D * ZS <= LY.MUF - LY.TAB && SENSOR_INPUT_SCALARS <= LY.DUM - LY.INP, "W, Y and the input record fit their regions");
     extern __shared__ __attribute__((aligned(16))) unsigned char asc_smem[];
 
     const RowCoords<M> rc(a.n, threadIdx.x);
     const int l = rc.l, lr = rc.lr, ls = rc.ls;
     const bool fvalid = rc.fvalid;
     const int64_t f = rc.f;
-    T* const base = row_slice<T, LY::PF>(asc_smem, rc.g);
-    T *const FAC = base + LY::FAC, *const RSP = base + LY::RSP, *const TAB = base + LY::TAB, *const WT = base + LY::WT;
-    T *const YM = base + LY::YM, *const MUF = base + LY::MUF, *const PKF = base + LY::PKF, *const INP = base + LY::INP;
-    T* const DUMP = base + LY::DUM;
+    T* const base = row_slice<T, LY.PF>(asc_smem, rc.g);
+    T *const FAC = base + LY.FAC, *const RSP = base + LY.RSP, *const TAB = base + LY.TAB, *const WT = base + LY.WT;
+    T *const YM = base + LY.YM, *const MUF = base + LY.MUF, *const PKF = base + LY.PKF, *const INP = base + LY.INP;
+    T* const DUMP = base + LY.DUM;
 
     // ---- the row's filter, model and records: Q, mount and (shared-h mode) the point; the candidates are streamed below
     const bool live = fvalid && a.initialised[f] != 0;

@@ -11,7 +11,7 @@ namespace ukfb {
 
 template <class TS, class M, class TC> static int launch_associate_typed(ukfb_engine* e, const AssociateReq& r) {
     using MC = typename M::template rebind<TC>;
-    const SensorGeometry geo = sensor_geometry(MC::S, MC::D, e->cap, sizeof(TC));   // the sensor kernel's LDS map
+    const RowGeometry geo = sensor_geometry(MC::S, MC::D, e->cap, sizeof(TC));   // the sensor kernel's LDS map
     if (geo.grid == 0) return UKFB_OK;
     AssociateArgs<TC, TS> a{};
     a.n = e->cap;

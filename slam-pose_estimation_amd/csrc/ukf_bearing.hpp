@@ -2,7 +2,7 @@
 // in the sensor frame; the mean is iterated on the sphere, the differences are sphere logarithms, the noise is two-dimensional.
 // Definitions: include/ukf_batch.h ("bearing measurements"), DESIGN.md 4.25.
 //
-// Layout and LDS map: the sensor-frame kernel's (ukf_sensor_meas.hpp: SensorArgs, SensorLayout, sensor_solve3) on ukf_row.hpp --
+// Layout and LDS map: the sensor-frame kernel's (ukf_sensor_meas.hpp: SensorArgs, sensor_map, sensor_solve3) on ukf_row.hpp --
 // one filter per 16-lane DPP row, four per wavefront, one wavefront per workgroup.
 //  * lane l < D owns the sigma pair of factor column l and evaluates h on both points; lane D owns the centre.
 //  * the sphere side lives in registers and in fp64 in every mode: the lane's two unit vectors, the reference of the mean
@@ -22,17 +22,13 @@
 //    wave-mates (the mean iteration runs while any row is active; a converged row keeps its reference bit for bit).
 //  * commit = 0: the kernel gets NULL for the state's output pointers -- it has nothing through which it could store.
 //  * TS (storage) / T (compute) as in ukf_kernel16: TS = float with T = double is the wide-arithmetic mode.
-// LDS per filter: bearing_filter_scalars (ukf_host.hpp).
+// LDS per filter: sensor_map (ukf_host.hpp).
 #pragma once
 
 #include "ukf_row.hpp"
 #include "ukf_sensor_meas.hpp"
 
 namespace ukfb {
-
-template <class M> struct BearingLayout : SensorLayout<M> {
-    static_assert(SensorLayout<M>::PF == bearing_filter_scalars(M::S, M::D), "LDS accounting of ukf_host.hpp");
-};
 
 // What h reads beside the sigma point: the (neutralised) lever arm, the inverse of qs, the point, 1 / |q|^2 of the mean's
 // orientation (every sigma point's orientation is the mean's times a unit exponential)
@@ -98,18 +94,20 @@ UKFB_DEV void s2_exp(const double (&u)[3], const double (&w)[3], double (&r)[3])
 template <class T, class M, class TS>
 __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_bearing_kernel(const SensorArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
-    using LY = BearingLayout<M>;
-    constexpr int LS = LY::LS, ZS = LY::ZS, Q = MT<M>::Q;
+    constexpr SensorMap LY = sensor_map(S, D);
+    constexpr int LS = LY.LS, ZS = LY.ZS, Q = MT<M>::Q;
+    static_assert(row_fits(M::S, M::D), "a filter fits one row");
+    static_assert(2 * D * ZS <= LY.MUF - LY.TAB && SENSOR_INPUT_SCALARS <= LY.DUM - LY.INP, "W, Y and the input record fit their regions");
     extern __shared__ __attribute__((aligned(16))) unsigned char bea_smem[];
 
     const RowCoords<M> rc(a.n, threadIdx.x);
     const int l = rc.l, lr = rc.lr, ls = rc.ls;
     const bool fvalid = rc.fvalid;
     const int64_t f = rc.f;
-    T* const base = row_slice<T, LY::PF>(bea_smem, rc.g);
-    T *const FAC = base + LY::FAC, *const RSP = base + LY::RSP, *const TAB = base + LY::TAB, *const WT = base + LY::WT;
-    T *const YM = base + LY::YM, *const MUF = base + LY::MUF, *const PKF = base + LY::PKF, *const INP = base + LY::INP;
-    T* const DUMP = base + LY::DUM;
+    T* const base = row_slice<T, LY.PF>(bea_smem, rc.g);
+    T *const FAC = base + LY.FAC, *const RSP = base + LY.RSP, *const TAB = base + LY.TAB, *const WT = base + LY.WT;
+    T *const YM = base + LY.YM, *const MUF = base + LY.MUF, *const PKF = base + LY.PKF, *const INP = base + LY.INP;
+    T* const DUMP = base + LY.DUM;
 
     // ---- the row's filter, model and records
     const bool live = fvalid && a.initialised[f] != 0;

@@ -25,7 +25,7 @@
 //    wave-mates.
 //  * commit = 0: the kernel gets NULL for the state's output pointers -- it has nothing through which it could store.
 //  * TS (storage) / T (compute) as in ukf_kernel16: TS = float with T = double is the wide-arithmetic mode.
-// Global stores are plain vector stores.  LDS per filter: condition_filter_scalars (ukf_host.hpp).
+// Global stores are plain vector stores.  LDS per filter: condition_map (ukf_host.hpp).
 #pragma once
 
 #include "ukf_row.hpp"
@@ -51,21 +51,6 @@ template <class T, class TS> struct ConditionArgs {
     TS* mu_o;                    // [n][S] or null
     TS* cov_packed;              // [n][PK] or null
     uint32_t* status;            // [n] or null
-};
-
-template <class M> struct ConditionLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS;
-    static constexpr int PKE = (PK + 1) / 2 * 2;
-    static constexpr int ROW = 0;                         // D * LS: the rows of M J of a step (the row phase's exchange)
-    static constexpr int VPB = ROW + D * LS;              // D * LS: V as every row published it
-    static constexpr int LAM = VPB + D * LS;              // 16: the eigenvalues
-    static constexpr int SDV = LAM + 16;                  // 16: s_t = sqrt(d_t)
-    static constexpr int MUF = SDV + 16;                  // the state: mean (16), Sigma packed (PKE)
-    static constexpr int PKF = MUF + 16;
-    static constexpr int DUM = PKF + PKE;                 // 16: sink of lane-predicated stores
-    static constexpr int PF = (DUM + 16 + CONDITION_SLICE_PAD + 3) / 4 * 4;
-    static_assert(PF == condition_filter_scalars(S, D), "LDS accounting of ukf_host.hpp");
-    static_assert(LS >= D && S <= 16 && D + 1 <= 16, "a filter fits one row");
 };
 
 template <class T> struct CondNum;
@@ -141,9 +126,10 @@ template <int R, class T, int D, int LS> UKFB_DEV void cond_jacobi_step(T (&Mr)[
 template <class T, class M, class TS>
 __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_condition_kernel(const ConditionArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, Q = MT<M>::Q;
-    using LY = ConditionLayout<M>;
+    constexpr ConditionMap LY = condition_map(S, D);   // the LDS slice (ukf_host.hpp)
     using SC = CondSchedule<D>;
-    constexpr int LS = LY::LS;
+    constexpr int LS = LY.LS;
+    static_assert(row_fits(M::S, M::D), "a filter fits one row");
     extern __shared__ __attribute__((aligned(16))) unsigned char cnd_smem[];
 
     // (RowCoords' statements in place: built on it, this kernel left the spread of the parent's own runs -- profiles/row_toolkit_rates.txt)
@@ -154,9 +140,9 @@ __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_condition_kernel(c
     const int n_wg = int(n_here < ROW_FILTERS_PER_GROUP ? n_here : int64_t(ROW_FILTERS_PER_GROUP));
     const bool fvalid = g < n_wg;
     const int64_t f = wg0 + (fvalid ? g : (n_wg - 1));   // rows beyond the batch repeat its last filter and store nothing
-    T* const base = reinterpret_cast<T*>(cnd_smem) + g * LY::PF;
-    T *const ROWS = base + LY::ROW, *const VPB = base + LY::VPB, *const LAM = base + LY::LAM, *const SDV = base + LY::SDV;
-    T *const MUF = base + LY::MUF, *const PKF = base + LY::PKF, *const DUMP = base + LY::DUM;
+    T* const base = reinterpret_cast<T*>(cnd_smem) + g * LY.PF;
+    T *const ROWS = base + LY.ROW, *const VPB = base + LY.VPB, *const LAM = base + LY.LAM, *const SDV = base + LY.SDV;
+    T *const MUF = base + LY.MUF, *const PKF = base + LY.PKF, *const DUMP = base + LY.DUM;
 
     // ---- the row's filter: the state to LDS, the lower triangle judged on the way; the floor judged where it lies
     const bool live = fvalid && a.initialised[f] != 0;

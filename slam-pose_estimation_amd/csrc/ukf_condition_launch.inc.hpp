@@ -10,7 +10,7 @@ namespace ukfb {
 
 template <class TS, class M, class TC> static int launch_condition_typed(ukfb_engine* e, const ConditionReq& r) {
     using MC = typename M::template rebind<TC>;
-    const SampledGeometry geo = condition_geometry(MC::S, MC::D, e->cap, sizeof(TC));
+    const RowGeometry geo = condition_geometry(MC::S, MC::D, e->cap, sizeof(TC));
     if (geo.grid == 0) return UKFB_OK;
     ConditionArgs<TC, TS> a{};
     a.n = e->cap;

@@ -26,12 +26,12 @@
 //  * commit = 0: the kernel gets NULL for the engine's state pointers -- it has nothing through which it could store there.
 //  * TS (storage) / T (compute) as in ukf_kernel16: TS = float with T = double is the wide-arithmetic mode.  Plain fp32 holds the
 //    1e-4 gate without any fp64 piece (tests/test_delayed_reference.py: the all-float32 evaluation is 2e-6 from the float64 one).
-// LDS per filter: delayed_filter_scalars (ukf_host.hpp) -- the smoother's slice and the rows of M behind it.
+// LDS per filter: delayed_map (ukf_host.hpp) -- the smoother's slice and the rows of M behind it.
 #pragma once
 
 #include "ukf_row.hpp"
 #include "ukf_bank.hpp"          // bank_jrinv_coeff
-#include "ukf_smooth.hpp"        // SmoothLayout: the slice is the smoother's, widened
+#include "ukf_smooth.hpp"
 #include "ukf_sensor_meas.hpp"   // sensor_solve3
 
 namespace ukfb {
@@ -76,16 +76,6 @@ template <class T, class TS> struct DelayedArgs {
     double dt[SMOOTH_MAX_BACK];  // dt[k]: time step of the prediction redone by backward step k (step n - 1 - k -> n - k)
 };
 
-template <class M> struct DelayedLayout {
-    using SL = SmoothLayout<M>;
-    static constexpr int S = M::S, D = M::D, LS = ROW_LS, ZS = 4;
-    static constexpr int MOP = SL::PF;                    // D * LS: the operator M, row l at MOP + l * LS
-    static constexpr int WT = SL::TAB, YM = SL::TAB + D * ZS, YN = SL::TAB + 2 * D * ZS;   // D x 3 matrices in the dead delta table
-    static constexpr int PF = (MOP + D * LS + 3) / 4 * 4;
-    static_assert(PF == delayed_filter_scalars(S, D), "LDS accounting of ukf_host.hpp");
-    static_assert(3 * D * ZS <= (2 * D + 1) * LS, "W, Y_s and Y_n fit the delta table");
-};
-
 // (a, b) of Jr(phi) = I - a [phi]x + b [phi]x^2 as functions of t = theta^2 (see the head of the file)
 template <class T> UKFB_DEV void delayed_jr_coeffs(T t, T& a, T& b) {
     T ch, sh;
@@ -113,8 +103,9 @@ template <class T> UKFB_DEV void delayed_rot_matrix(const T (&p)[3], T t, T ca, 
 
 // What a row derives from its lane index (the smoother's SmoothRow over the wider slice, and the rows of M)
 template <class T, class M, class TS> struct DelayedRow {
-    using LY = DelayedLayout<M>;
-    using SL = SmoothLayout<M>;
+    static constexpr DelayedMap LY = delayed_map(M::S, M::D);   // the LDS slice (ukf_host.hpp): the smoother's, widened
+    static_assert(row_fits(M::S, M::D), "a filter fits one row");
+    static_assert(3 * M::D * LY.ZS <= LY.CSM - LY.TAB, "W, Y_s and Y_n fit the delta table");
     int l, lr, ls;
     bool fvalid, live;
     int64_t f;
@@ -131,10 +122,10 @@ template <class T, class M, class TS> struct DelayedRow {
         fvalid = g < n_wg;
         f = wg0 + (fvalid ? g : (n_wg - 1));   // rows beyond the batch repeat its last filter and store nothing
         live = fvalid && a.initialised[f] != 0;
-        T* const base = reinterpret_cast<T*>(smem) + g * LY::PF;
-        FAC = base + SL::FAC; RSP = base + SL::RSP; TAB = base + SL::TAB; GM = base + SL::GM; MM = base + SL::MM;
-        CSM = base + SL::CSM; CSP = base + SL::CSP; MUF = base + SL::MUF; PKF = base + SL::PKF; ROT = base + SL::ROT;
-        DUMP = base + SL::DUM; SMR = base + SL::SMR; MUP = base + SL::MUP; MOP = base + LY::MOP;
+        T* const base = reinterpret_cast<T*>(smem) + g * LY.PF;
+        FAC = base + LY.FAC; RSP = base + LY.RSP; TAB = base + LY.TAB; GM = base + LY.GM; MM = base + LY.MM;
+        CSM = base + LY.CSM; CSP = base + LY.CSP; MUF = base + LY.MUF; PKF = base + LY.PKF; ROT = base + LY.ROT;
+        DUMP = base + LY.DUM; SMR = base + LY.SMR; MUP = base + LY.MUP; MOP = base + LY.MOP;
         Rn = a.Rn + f * a.Rn_stride;
         Racc = a.Racc + f * a.Rn_stride;
     }
@@ -169,8 +160,8 @@ template <class T, class M, class TS> struct DelayedSample {
 template <class T, class M, class TS>
 __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_delayed_kernel(const DelayedArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
-    using LY = DelayedLayout<M>;
-    constexpr int LS = LY::LS, ZS = LY::ZS, Q = MT<M>::Q, RT = MT<M>::RT;
+    constexpr DelayedMap LY = delayed_map(S, D);
+    constexpr int LS = LY.LS, ZS = LY.ZS, Q = MT<M>::Q, RT = MT<M>::RT;
     extern __shared__ __attribute__((aligned(16))) unsigned char delayed_smem[];
     uint32_t st = ST_OK;
     bool chain_ok = true;
@@ -536,9 +527,9 @@ __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_delayed_kernel(con
     const DelayedSample<T, M, TS> smp(a, f, live);
     const int midc = smp.midc, m = smp.m;
     const bool so3 = smp.so3, do_u = smp.do_u;
-    T* const WT = TAB + (LY::WT - LY::SL::TAB);
-    T* const YM = TAB + (LY::YM - LY::SL::TAB);
-    T* const YN = TAB + (LY::YN - LY::SL::TAB);
+    T* const WT = TAB + (LY.WT - LY.TAB);
+    T* const YM = TAB + (LY.YM - LY.TAB);
+    T* const YN = TAB + (LY.YN - LY.TAB);
     // the engine's present state into the (dead) filtered-record region
     MUF[l] = T(a.mu[f * S + ls]);
     for (int i = l; i < PK; i += 16) PKF[i] = T(a.cov[f * PK + i]);

@@ -11,7 +11,7 @@ namespace ukfb {
 template <class TS, class M, class TC> static int launch_delayed_typed(ukfb_engine* e, const DelayedReq& r) {
     using MC = typename M::template rebind<TC>;
     constexpr int D = MC::D;
-    const DelayedGeometry geo = delayed_geometry(MC::S, D, e->cap, sizeof(TC));
+    const RowGeometry geo = delayed_geometry(MC::S, D, e->cap, sizeof(TC));
     if (geo.grid == 0) return UKFB_OK;
     DelayedArgs<TC, TS> a{};
     a.n = e->cap;

@@ -15,7 +15,7 @@
 //  * a filter that fails, is gated or is uninitialised rides along: every select is per row, no row's bits depend on its
 //    wave-mates (the mean iteration runs while any row is active; a converged row keeps its reference).
 //  * TS (storage) / T (compute) as in ukf_kernel16: TS = float with T = double is the wide-arithmetic mode.
-// LDS per filter: forecast_filter_scalars (ukf_host.hpp) -- the factor region (Sigma's factor, then the rows of Sigma^-), the
+// LDS per filter: forecast_map (ukf_host.hpp) -- the factor region (Sigma's factor, then the rows of Sigma^-), the
 // delta table, the chain record, the rotation matrix, a sink.
 #pragma once
 
@@ -48,24 +48,11 @@ template <class T, class TS> struct ForecastArgs {
     int64_t ts_us[FORECAST_MAX_STEPS];  // ts_us[c]: its stamp (ts form)
 };
 
-template <class M> struct ForecastLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS;
-    static constexpr int PKE = (PK + 1) / 2 * 2;
-    static constexpr int FAC = 0;                         // D * LS factor columns (later the rows of Sigma^-), then 16 reciprocal pivots
-    static constexpr int RSP = FAC + D * LS;
-    static constexpr int TAB = RSP + 16;                  // (2 D + 1) * LS delta table
-    static constexpr int CSM = TAB + (2 * D + 1) * LS;    // chain mean (16), chain covariance (PKE)
-    static constexpr int CSP = CSM + 16;
-    static constexpr int ROT = CSP + PKE;                 // 9 (+ 1)
-    static constexpr int DUM = ROT + 10;                  // 16: sink of lane-predicated stores
-    static constexpr int PF = (DUM + 16 + FORECAST_SLICE_PAD + 3) / 4 * 4;
-    static_assert(PF == forecast_filter_scalars(S, D), "LDS accounting of ukf_host.hpp");
-    static_assert(LS >= D && S <= 16 && D + 1 <= 16, "a filter fits one row");
-};
-
-// What a row derives from its lane index (public members in this order: the step loop binds them by name)
+// What a row derives from its lane index; its LDS slice is forecast_map's (ukf_host.hpp).  Public members in this order: the step
+// loop binds them by name
 template <class T, class M, class TS> struct ForecastRow {
-    using LY = ForecastLayout<M>;
+    static constexpr ForecastMap LY = forecast_map(M::S, M::D);
+    static_assert(row_fits(M::S, M::D), "a filter fits one row");
     int l, lr, ls;       // lane of the row; clamped to a row of the matrices / an entry of the mean
     bool fvalid, live;   // the row has a filter of the batch; ... that is initialised: the row stores
     int64_t f;           // rows beyond the batch repeat its last filter and store nothing
@@ -75,9 +62,9 @@ template <class T, class M, class TS> struct ForecastRow {
         const RowCoords<M> rc(a.n, lane);
         l = rc.l; lr = rc.lr; ls = rc.ls; fvalid = rc.fvalid; f = rc.f;
         live = fvalid && a.initialised[f] != 0;
-        T* const base = row_slice<T, LY::PF>(smem, rc.g);
-        FAC = base + LY::FAC; RSP = base + LY::RSP; TAB = base + LY::TAB; CSM = base + LY::CSM; CSP = base + LY::CSP;
-        ROT = base + LY::ROT; DUMP = base + LY::DUM;
+        T* const base = row_slice<T, LY.PF>(smem, rc.g);
+        FAC = base + LY.FAC; RSP = base + LY.RSP; TAB = base + LY.TAB; CSM = base + LY.CSM; CSP = base + LY.CSP;
+        ROT = base + LY.ROT; DUMP = base + LY.DUM;
         Rn = a.Rn + f * a.Rn_stride;
         Racc = a.Racc + f * a.Rn_stride;
     }
@@ -87,8 +74,8 @@ template <class T, class M, class TS> struct ForecastRow {
 template <class T, class M, class TS>
 __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_forecast_kernel(const ForecastArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
-    using LY = ForecastLayout<M>;
-    constexpr int LS = LY::LS;
+    constexpr ForecastMap LY = forecast_map(S, D);
+    constexpr int LS = LY.LS;
     extern __shared__ __attribute__((aligned(16))) unsigned char forecast_smem[];
     uint32_t st = ST_OK;
     int slot = a.first_slot;

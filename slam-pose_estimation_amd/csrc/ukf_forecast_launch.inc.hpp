@@ -11,7 +11,7 @@ namespace ukfb {
 template <class TS, class M, class TC> static int launch_forecast_typed(ukfb_engine* e, const ForecastReq& r) {
     using MC = typename M::template rebind<TC>;
     constexpr int S = MC::S, D = MC::D;
-    const ForecastGeometry geo = forecast_geometry(S, D, e->cap, sizeof(TC));
+    const RowGeometry geo = forecast_geometry(S, D, e->cap, sizeof(TC));
     if (geo.grid == 0) return UKFB_OK;
     ForecastArgs<TC, TS> a{};
     a.n = e->cap;

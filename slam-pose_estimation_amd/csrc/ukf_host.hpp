@@ -28,6 +28,12 @@ struct Verdict {   // a return code and, unless UKFB_OK, the text ukfb_last_erro
     int rc = UKFB_OK;
     const char* msg = nullptr;
 };
+// two clauses many checks have: a flag is 0 or 1; a call that commits nothing needs somewhere to write
+constexpr bool zero_or_one(int v) { return v == 0 || v == 1; }
+inline Verdict nothing_to_compute(int commit, bool has_output) {
+    if (commit == 0 && !has_output) return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
+    return {};
+}
 
 // ---- configuration ------------------------------------------------------------------------------------------------------
 // generic_f64: the fp64 one-wavefront-per-filter layouts are built (make GENERIC_F64=1)
@@ -46,8 +52,8 @@ inline Verdict check_config(int precision, bool generic_f64, ukfb_config& c) {
     if (!layout_supported(precision, c.lanes_per_filter, generic_f64))
         return {UKFB_ERR_INVALID_ARG, "lanes_per_filter 32 / 64 in fp64 is a diagnostic build option (make GENERIC_F64=1)"};
     if (c.mean_max_iter < 1) return {UKFB_ERR_INVALID_ARG, "mean_max_iter must be >= 1"};
-    if (c.wide_arithmetic != 0 && c.wide_arithmetic != 1) return {UKFB_ERR_INVALID_ARG, "wide_arithmetic must be 0 or 1"};
-    if (c.full_update_check != 0 && c.full_update_check != 1) return {UKFB_ERR_INVALID_ARG, "full_update_check must be 0 or 1"};
+    if (!zero_or_one(c.wide_arithmetic)) return {UKFB_ERR_INVALID_ARG, "wide_arithmetic must be 0 or 1"};
+    if (!zero_or_one(c.full_update_check)) return {UKFB_ERR_INVALID_ARG, "full_update_check must be 0 or 1"};
     if (c.wide_arithmetic && precision == UKFB_F32 && c.lanes_per_filter != 16)
         return {UKFB_ERR_INVALID_ARG, "wide_arithmetic runs on the tuned layout only (lanes_per_filter 16)"};
     return {};
@@ -212,6 +218,33 @@ struct RowGeometry {
 inline RowGeometry row_geometry(int filter_scalars, int64_t capacity, size_t compute_size) {
     return {(capacity + ROW_FILTERS_PER_GROUP - 1) / ROW_FILTERS_PER_GROUP, int(size_t(ROW_FILTERS_PER_GROUP) * filter_scalars * compute_size)};
 }
+// A filter's slice is described once: a *_map(S, D) below lists its regions in their order, as offsets in scalars of the compute
+// type.  The kernel reads the map as a constexpr object, the host sizes the launch from its PF (*_filter_scalars: -1 where a
+// filter does not fit a row).  Every scalar a kernel reads is one it wrote: the pads are never read.
+constexpr bool row_fits(int S, int D) { return ROW_LS >= D && S <= 16 && D + 1 <= 16; }   // a filter fits one row: every kernel asserts it
+struct RowSlice {   // bump counter over a slice
+    int used = 0;
+    constexpr int take(int n) {
+        const int at = used;
+        used += n;
+        return at;
+    }
+    // rounded up to a multiple of four, so that every filter's slice starts 16-byte aligned in either precision
+    constexpr int size() const { return (used + 3) / 4 * 4; }
+    // the recurring regions
+    constexpr void factor(int D, int& fac, int& rsp) {   // D * ROW_LS factor columns, then 16 reciprocal pivots
+        fac = take(D * ROW_LS);
+        rsp = take(16);
+    }
+    constexpr int table(int D) { return take((2 * D + 1) * ROW_LS); }   // the delta table of 2 D + 1 rows
+    constexpr void record(int D, int& mean, int& packed) {   // a mean padded to 16, then a packed covariance padded to even
+        mean = take(16);
+        packed = take((D * (D + 1) / 2 + 1) / 2 * 2);
+    }
+    constexpr int rotation() { return take(10); }         // a rotation matrix: 9 (+ 1)
+    constexpr int sink() { return take(16); }             // the sink of lane-predicated stores
+    constexpr int rows(int D) { return take(D * ROW_LS); }   // D parked rows
+};
 
 // ---- filter banks (ukfb_bank_weights_dev, ukfb_bank_combine_dev, ukfb_bank_mix_dev) ---------------------------------------
 // An engine of `capacity` filters read as capacity / M tracks of M hypotheses, track-major (hypothesis j of track t = filter
@@ -262,7 +295,7 @@ inline BankGeometry bank_geometry(int S, int D, int hypotheses, int64_t capacity
 // A window of `steps` consecutive slots of a ring of `slots`, oldest first: step c lives in slot (first_slot + c) % slots.  The
 // backward pass has steps - 1 steps; a launch covers at most SMOOTH_MAX_BACK of them (their dt travel in the kernel arguments)
 // and the next launch starts from the smoothed record the previous one stored.
-constexpr int SMOOTH_MAX_BACK = 32, SMOOTH_LS = ROW_LS, SMOOTH_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
+constexpr int SMOOTH_MAX_BACK = 32;
 inline Verdict check_history_args(int slots, int slot, bool has_mu_hist, bool has_cov_hist) {
     if (slots < 1 || slot < 0 || slot >= slots) return {UKFB_ERR_INVALID_ARG, "slots >= 1, 0 <= slot < slots"};
     if (!has_mu_hist || !has_cov_hist) return {UKFB_ERR_INVALID_ARG, "mu_hist and cov_hist must not be NULL"};
@@ -290,21 +323,33 @@ struct SmoothPlan {
         return {top, int((int64_t(first_slot) + top) % slots), std::min(SMOOTH_MAX_BACK, top), top - 1, k == 0};
     }
 };
-// LDS of one filter, in scalars of the compute type (ukf_smooth.hpp, SmoothLayout): the factor region with its reciprocal
-// pivots, the delta table of 2 D + 1 rows (G and M alias it), the chain record and the filtered record (mean padded to 16,
-// packed covariance padded to even), the rotation matrix (9 + 1 pad), the sink of
-// lane-predicated stores (16), and what is parked across the solves (the rows of Sigma^-, mu^- padded to 16).  Every scalar the kernel reads is one it wrote: the pads are never read.
-constexpr int smooth_filter_scalars(int S, int D) {
-    return S > 16 ? -1 : 2 * D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 2 * (16 + (D * (D + 1) / 2 + 1) / 2 * 2) + 10 + 16 + 16;
+struct SmoothMap {
+    int LS, FAC, RSP, TAB, GM, MM, CSM, CSP, MUF, PKF, ROT, DUM, SMR, MUP, PF;
+};
+constexpr SmoothMap smooth_map(int, int D) {
+    RowSlice s;
+    SmoothMap m{};
+    m.LS = ROW_LS;
+    s.factor(D, m.FAC, m.RSP);
+    m.TAB = s.table(D);   // G (D * LS) and M (D * LS) alias it
+    m.GM = m.TAB; m.MM = m.TAB + D * m.LS;
+    s.record(D, m.CSM, m.CSP);   // the chain's record
+    s.record(D, m.MUF, m.PKF);   // the filtered record
+    m.ROT = s.rotation();
+    m.DUM = s.sink();
+    m.SMR = s.rows(D);     // the rows of Sigma^-, parked between its factorisation and M
+    m.MUP = s.take(16);    // mu^-, parked across the solves
+    m.PF = s.size();
+    return m;
 }
-using SmoothGeometry = RowGeometry;
+constexpr int smooth_filter_scalars(int S, int D) { return S > 16 ? -1 : smooth_map(S, D).PF; }
 inline RowGeometry smooth_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(smooth_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- forecast (ukfb_forecast_dev) -------------------------------------------------------------------------------------------
 // `steps` predictions chained from a start record into a window of a ring of `slots`: step c lives in slot
 // (first_slot + c) % slots.  One launch: the time steps (or stamps) of all steps travel in the kernel arguments, so a call
 // covers at most FORECAST_MAX_STEPS of them and a longer horizon is chained by the caller.
-constexpr int FORECAST_MAX_STEPS = UKFB_FORECAST_MAX_STEPS, FORECAST_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
+constexpr int FORECAST_MAX_STEPS = UKFB_FORECAST_MAX_STEPS;
 inline Verdict check_forecast_args(int steps, int slots, int first_slot, bool has_dt, bool has_ts, bool has_start_mu, bool has_start_cov,
                                    bool has_mu_out) {
     if (slots < 1 || steps < 1) return {UKFB_ERR_INVALID_ARG, "steps >= 1, slots >= 1"};
@@ -316,23 +361,29 @@ inline Verdict check_forecast_args(int steps, int slots, int first_slot, bool ha
         return {UKFB_ERR_OUT_OF_RANGE, "steps <= min(slots, 32): chain a longer horizon from the last slot of the call before"};
     return {};
 }
-// LDS of one filter, in scalars of the compute type (ukf_forecast.hpp, ForecastLayout): the factor region with its reciprocal
-// pivots (the rows of Sigma^- are parked in it while the noise is added), the delta table of 2 D + 1 rows, the chain record (mean
-// padded to 16, packed covariance padded to even), the rotation matrix (9 + 1 pad), the sink of lane-predicated stores (16) and a
-// pad of four that keeps the four slices of a workgroup on different banks in either precision; rounded up to a multiple of
-// four.  Every scalar the kernel reads is one it wrote: the pads are never read.
-constexpr int FORECAST_SLICE_PAD = 4;
-constexpr int forecast_filter_scalars(int S, int D) {
-    return S > 16 ? -1
-                  : (D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 10 + 16 + FORECAST_SLICE_PAD + 3) / 4 * 4;
+constexpr int FORECAST_SLICE_PAD = 4;   // keeps the four slices of a workgroup on different banks in either precision
+struct ForecastMap {
+    int LS, FAC, RSP, TAB, CSM, CSP, ROT, DUM, PF;
+};
+constexpr ForecastMap forecast_map(int, int D) {
+    RowSlice s;
+    ForecastMap m{};
+    m.LS = ROW_LS;
+    s.factor(D, m.FAC, m.RSP);   // (the rows of Sigma^- are parked in the columns while the noise is added)
+    m.TAB = s.table(D);
+    s.record(D, m.CSM, m.CSP);   // the chain's record
+    m.ROT = s.rotation();
+    m.DUM = s.sink();
+    s.take(FORECAST_SLICE_PAD);
+    m.PF = s.size();
+    return m;
 }
-using ForecastGeometry = RowGeometry;
+constexpr int forecast_filter_scalars(int S, int D) { return S > 16 ? -1 : forecast_map(S, D).PF; }
 inline RowGeometry forecast_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(forecast_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- joint state-block measurements (ukfb_update_state_dev) --------------------------------------------------------------
 // A measurement is a sub-manifold of the state: the compound of the blocks a mask selects, in state order.  Every block but the
 // OrientationState's gravity has three tangent dimensions, so tangent dimension t belongs to block t / 3 in both models.
-constexpr int STATE_MEAS_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
 constexpr int state_meas_blocks(int engine_model) { return engine_model == UKFB_MODEL_POSE ? 4 : 5; }
 constexpr bool state_meas_mask_ok(int blocks, int64_t mask) { return mask > 0 && (mask >> blocks) == 0; }
 // tangent dimensions of a mask (D: 12 / 13; the last block of OrientationState has one)
@@ -346,24 +397,30 @@ inline int state_meas_dim(int D, uint32_t mask) {
 inline Verdict check_state_meas_args(int engine_model, bool per_filter_masks, uint32_t mask_uniform, bool has_z, bool has_Qz,
                                      double state_inflation, double meas_inflation, int commit, const ukfb_state_meas_out* out) {
     if (!has_z || !has_Qz) return {UKFB_ERR_INVALID_ARG, "z and Qz must not be NULL"};
-    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    if (!zero_or_one(commit)) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
     if (!(std::isfinite(state_inflation) && state_inflation >= 1.0) || !(std::isfinite(meas_inflation) && meas_inflation >= 1.0))
         return {UKFB_ERR_INVALID_ARG, "state_inflation and meas_inflation must be finite and >= 1"};
     if (!per_filter_masks && !state_meas_mask_ok(state_meas_blocks(engine_model), int64_t(mask_uniform)))
         return {UKFB_ERR_INVALID_ARG, "block_mask must select at least one block and none beyond the model's (Pose: 4, OrientationState: 5)"};
-    if (commit == 0 && (!out || (!out->maha && !out->loglik && !out->status)))
-        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
-    return {};
+    return nothing_to_compute(commit, out && (out->maha || out->loglik || out->status));
 }
-// LDS of one filter, in scalars of the compute type (ukf_state_meas.hpp, StateMeasLayout): the factor region with its reciprocal
-// pivots, the delta table of 2 D + 1 rows (the solved cross-covariance aliases it), the state's and the measurement's record
-// (mean padded to 16, packed covariance padded to even) and the sink of lane-predicated stores (16); rounded up to a multiple
-// of four so that every filter's slice starts 16-byte aligned in either precision.  Every scalar the kernel reads is one it
-// wrote: the pads are never read.
-constexpr int state_meas_filter_scalars(int S, int D) {
-    return S > 16 ? -1 : (D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 2 * (16 + (D * (D + 1) / 2 + 1) / 2 * 2) + 16 + 3) / 4 * 4;
+struct StateMeasMap {
+    int LS, FAC, RSP, TAB, YM, MUF, PKF, ZM, PKQ, DUM, PF;
+};
+constexpr StateMeasMap state_meas_map(int, int D) {
+    RowSlice s;
+    StateMeasMap m{};
+    m.LS = ROW_LS;
+    s.factor(D, m.FAC, m.RSP);
+    m.TAB = s.table(D);   // the solved cross-covariance Y (D * LS) aliases it
+    m.YM = m.TAB;
+    s.record(D, m.MUF, m.PKF);   // the state: mean, a Sigma packed
+    s.record(D, m.ZM, m.PKQ);    // the measurement: mean, b Qz packed
+    m.DUM = s.sink();
+    m.PF = s.size();
+    return m;
 }
-using StateMeasGeometry = RowGeometry;
+constexpr int state_meas_filter_scalars(int S, int D) { return S > 16 ? -1 : state_meas_map(S, D).PF; }
 inline RowGeometry state_meas_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(state_meas_filter_scalars(S, D), capacity, compute_size); }
 // A base::samples::RigidBodyState record (49 scalars: position, orientation x y z w, velocity, angular velocity, then the four
 // 3 x 3 covariances in that order) as a Pose measurement: z = the record's first 13 scalars as they are, Qz = the four blocks
@@ -379,7 +436,7 @@ inline void body_state_to_measurement(const double* rec, double* z, double* Qz) 
 // ---- sensor-frame measurements (ukfb_update_sensor_dev) -------------------------------------------------------------------
 // Measurement models with a mount (lever arm r, sensor -> body rotation qs) and / or a nav-frame point b: ids 0 ... 4 are the
 // Pose engine's, 5 ... 7 the OrientationState engine's (UKFB_SENSOR_*).  Bit id of each set: the model reads that input.
-constexpr int SENSOR_MODELS = 8, SENSOR_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
+constexpr int SENSOR_MODELS = 8;
 constexpr unsigned SENSOR_READS_LEVER = 0x2fu;      // POSE_POSITION, POSE_RANGE, POSE_POINT, POSE_VELOCITY, ORIENT_VELOCITY
 constexpr unsigned SENSOR_READS_ROTATION = 0x6cu;   // POSE_POINT, POSE_VELOCITY, ORIENT_VELOCITY, ORIENT_NAV_VECTOR
 constexpr unsigned SENSOR_READS_POINT = 0x46u;      // POSE_RANGE, POSE_POINT, ORIENT_NAV_VECTOR
@@ -408,34 +465,66 @@ constexpr bool sensor_input_used(int64_t id, int i) {
 constexpr double sensor_input_neutral(int i) { return i == SENSOR_INPUT_MOUNT + 6 ? 1.0 : 0.0; }
 // per_filter_models: the ids come from a device array (checked per filter by the kernel: an id the engine's model does not have
 // marks the filter INACTIVE); otherwise the one id must be the engine model's
+// The clauses the sensor-frame update, the bearing update and the association share, in their order; what only the
+// association has (K candidates, a point per candidate) is neutral in the other two.  The candidate range is judged first and
+// alone decides UKFB_ERR_OUT_OF_RANGE; then the NULL rules (point_per_candidate needs point_dev: there is no uniform value for K
+// points), then the uniform id, then "nothing to compute".
+struct SensorCall {
+    int candidates;
+    bool has_z, has_Q;
+    int q_is_uniform, point_per_candidate;
+    bool has_point;
+};
+inline Verdict check_sensor_call(const SensorCall& c, int commit, bool model_ok, const char* wrong_model, bool has_output) {
+    if (c.candidates < 1 || c.candidates > UKFB_ASSOCIATE_MAX_CANDIDATES) return {UKFB_ERR_OUT_OF_RANGE, "candidates must be 1 ... 32"};
+    if (!c.has_z || !c.has_Q) return {UKFB_ERR_INVALID_ARG, "z_dev and Q_dev must not be NULL"};
+    if (!zero_or_one(c.q_is_uniform)) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
+    if (!zero_or_one(c.point_per_candidate)) return {UKFB_ERR_INVALID_ARG, "point_per_candidate must be 0 or 1"};
+    if (c.point_per_candidate && !c.has_point)
+        return {UKFB_ERR_INVALID_ARG, "point_per_candidate needs point_dev [candidates][capacity][3]"};
+    if (!zero_or_one(commit)) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    if (!model_ok) return {UKFB_ERR_WRONG_MODEL, wrong_model};
+    return nothing_to_compute(commit, has_output);
+}
+template <class Out> bool meas_has_output(const Out* out) {   // ukfb_sensor_out, ukfb_sampled_out: the same six
+    return out && (out->z_pred || out->S || out->innov || out->maha || out->loglik || out->status);
+}
+// the sensor-frame and the bearing update: one candidate, no point per candidate
+inline SensorCall sensor_call(const ukfb_sensor_in* in) {
+    return {/*candidates*/ 1, in->z_dev != nullptr, in->Q_dev != nullptr, in->q_is_uniform, /*point_per_candidate*/ 0, /*has_point*/ true};
+}
 inline Verdict check_sensor_args(int engine_model, bool per_filter_models, int model_uniform, const ukfb_sensor_in* in, int commit,
                                  const ukfb_sensor_out* out) {
     if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
-    if (!in->z_dev || !in->Q_dev) return {UKFB_ERR_INVALID_ARG, "z_dev and Q_dev must not be NULL"};
-    if (in->q_is_uniform != 0 && in->q_is_uniform != 1) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
-    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
-    if (!per_filter_models && !sensor_model_ok(engine_model, model_uniform))
-        return {UKFB_ERR_WRONG_MODEL, "sensor model id not valid for this engine (Pose: 0 ... 4, OrientationState: 5 ... 7)"};
-    if (commit == 0 && (!out || (!out->z_pred && !out->S && !out->innov && !out->maha && !out->loglik && !out->status)))
-        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
-    return {};
+    return check_sensor_call(sensor_call(in), commit,
+                             per_filter_models || sensor_model_ok(engine_model, model_uniform),
+                             "sensor model id not valid for this engine (Pose: 0 ... 4, OrientationState: 5 ... 7)", meas_has_output(out));
 }
-// LDS of one filter, in scalars of the compute type (ukf_sensor_meas.hpp, SensorLayout): the factor region with its reciprocal
-// pivots, the delta table of the commit (2 D + 1 rows; the D x 3 half differences W and the D x 3 solved cross-covariance Y
-// alias it, four scalars a row), the state's record (mean padded to 16, packed covariance padded to even), the input record
-// (32) and the sink of lane-predicated stores (16); rounded up to a multiple of four so that every filter's slice starts
-// 16-byte aligned in either precision.  Every scalar the kernel reads is one it wrote: the pads are never read.
-constexpr int sensor_filter_scalars(int S, int D) {
-    return S > 16 ? -1 : (D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 32 + 16 + 3) / 4 * 4;
+struct SensorMap {
+    int LS, ZS, FAC, RSP, TAB, WT, YM, MUF, PKF, INP, DUM, PF;
+};
+constexpr SensorMap sensor_map(int, int D) {
+    RowSlice s;
+    SensorMap m{};
+    m.LS = ROW_LS;
+    m.ZS = 4;   // row stride of the D x 3 matrices
+    s.factor(D, m.FAC, m.RSP);
+    m.TAB = s.table(D);   // the commit's; the half differences W and the solved cross-covariance Y (D * ZS each) alias it
+    m.WT = m.TAB; m.YM = m.TAB + D * m.ZS;
+    s.record(D, m.MUF, m.PKF);   // the state: mean, Sigma packed
+    m.INP = s.take(32);          // z, Q, mount, point (SENSOR_INPUT_*), ten pads
+    m.DUM = s.sink();
+    m.PF = s.size();
+    return m;
 }
-using SensorGeometry = RowGeometry;
+constexpr int sensor_filter_scalars(int S, int D) { return S > 16 ? -1 : sensor_map(S, D).PF; }
 inline RowGeometry sensor_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(sensor_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- bearing measurements (ukfb_update_bearing_dev) -----------------------------------------------------------------------
 // A direction on the sphere S^2 in the sensor frame, h = d / |d|: ids 0, 1 are the Pose engine's, 2 the OrientationState
 // engine's (UKFB_BEARING_*).  The input record is the sensor-frame measurements' (SENSOR_INPUT_*): every model reads all of z
 // and Q, qs and b; only POSE_POINT reads the lever arm r.
-constexpr int BEARING_MODELS = 3, BEARING_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
+constexpr int BEARING_MODELS = 3;
 constexpr bool bearing_model_ok(int engine_model, int64_t id) {
     return engine_model == UKFB_MODEL_POSE ? (id == UKFB_BEARING_POSE_POINT || id == UKFB_BEARING_POSE_NAV_DIRECTION)
                                            : id == UKFB_BEARING_ORIENT_NAV_DIRECTION;
@@ -450,24 +539,14 @@ constexpr bool bearing_input_used(int64_t id, int i) {
 inline Verdict check_bearing_args(int engine_model, bool per_filter_models, int model_uniform, const ukfb_sensor_in* in, int commit,
                                   const ukfb_sensor_out* out) {
     if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
-    if (!in->z_dev || !in->Q_dev) return {UKFB_ERR_INVALID_ARG, "z_dev and Q_dev must not be NULL"};
-    if (in->q_is_uniform != 0 && in->q_is_uniform != 1) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
-    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
-    if (!per_filter_models && !bearing_model_ok(engine_model, model_uniform))
-        return {UKFB_ERR_WRONG_MODEL, "bearing model id not valid for this engine (Pose: 0, 1; OrientationState: 2)"};
-    if (commit == 0 && (!out || (!out->z_pred && !out->S && !out->innov && !out->maha && !out->loglik && !out->status)))
-        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
-    return {};
+    return check_sensor_call(sensor_call(in), commit,
+                             per_filter_models || bearing_model_ok(engine_model, model_uniform),
+                             "bearing model id not valid for this engine (Pose: 0, 1; OrientationState: 2)", meas_has_output(out));
 }
-// LDS of one filter, in scalars of the compute type (ukf_bearing.hpp, BearingLayout): the regions of the sensor-frame kernel --
-// the factor with its reciprocal pivots, the delta table of the commit (2 D + 1 rows; the D x 3 half differences W and the
-// D x 3 solved cross-covariance Y alias it, four scalars a row), the state's record (mean padded to 16, packed covariance
-// padded to even), the input record (32) and the sink of lane-predicated stores (16); rounded up to a multiple of four.
-// The sphere side (the unit vectors, their logarithms, the 3 x 3 statistics) lives in registers.
-constexpr int bearing_filter_scalars(int S, int D) {
-    return S > 16 ? -1 : (D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 32 + 16 + 3) / 4 * 4;
-}
-inline RowGeometry bearing_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(bearing_filter_scalars(S, D), capacity, compute_size); }
+// No map of its own: the slice is the sensor-frame kernel's (sensor_map).  The sphere side (the unit vectors, their logarithms,
+// the 3 x 3 statistics) lives in registers.
+constexpr int bearing_filter_scalars(int S, int D) { return sensor_filter_scalars(S, D); }
+inline RowGeometry bearing_geometry(int S, int D, int64_t capacity, size_t compute_size) { return sensor_geometry(S, D, capacity, compute_size); }
 
 // ---- sensor-frame association (ukfb_associate_sensor_dev) -----------------------------------------------------------------
 // The sensor-frame models against K candidates per filter (ukf_associate.hpp): ids, inputs and the LDS map are the
@@ -477,29 +556,20 @@ constexpr int associate_hypotheses(int candidates, int point_per_candidate) { re
 // scalars of one output array of a call on `capacity` filters: z_pred / S hold H slots of 3 / 9 a filter, innov K slots of 3,
 // maha / loglik K slots of 1 (what the host-array form allocates and copies)
 constexpr int64_t associate_out_scalars(int slots, int64_t capacity, int per_filter) { return int64_t(slots) * capacity * per_filter; }
-// The candidate range is judged first and alone decides UKFB_ERR_OUT_OF_RANGE; then the NULL rules (point_per_candidate needs
-// point_dev: there is no uniform value for K points), then the uniform id, then "nothing to compute".
+// (the clauses and their order: check_sensor_call)
 inline Verdict check_associate_args(int engine_model, bool per_filter_models, int model_uniform, const ukfb_associate_in* in, int commit,
                                     const ukfb_associate_out* out) {
     if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
-    if (in->candidates < 1 || in->candidates > ASSOCIATE_MAX_CANDIDATES) return {UKFB_ERR_OUT_OF_RANGE, "candidates must be 1 ... 32"};
-    if (!in->z_dev || !in->Q_dev) return {UKFB_ERR_INVALID_ARG, "z_dev and Q_dev must not be NULL"};
-    if (in->q_is_uniform != 0 && in->q_is_uniform != 1) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
-    if (in->point_per_candidate != 0 && in->point_per_candidate != 1) return {UKFB_ERR_INVALID_ARG, "point_per_candidate must be 0 or 1"};
-    if (in->point_per_candidate && !in->point_dev)
-        return {UKFB_ERR_INVALID_ARG, "point_per_candidate needs point_dev [candidates][capacity][3]"};
-    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
-    if (!per_filter_models && !sensor_model_ok(engine_model, model_uniform))
-        return {UKFB_ERR_WRONG_MODEL, "sensor model id not valid for this engine (Pose: 0 ... 4, OrientationState: 5 ... 7)"};
-    if (commit == 0 && (!out || (!out->z_pred && !out->S && !out->innov && !out->maha && !out->loglik && !out->best && !out->n_gated && !out->status)))
-        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
-    return {};
+    return check_sensor_call({in->candidates, in->z_dev != nullptr, in->Q_dev != nullptr, in->q_is_uniform, in->point_per_candidate, in->point_dev != nullptr},
+                             commit, per_filter_models || sensor_model_ok(engine_model, model_uniform),
+                             "sensor model id not valid for this engine (Pose: 0 ... 4, OrientationState: 5 ... 7)",
+                             out && (out->z_pred || out->S || out->innov || out->maha || out->loglik || out->best || out->n_gated || out->status));
 }
 
 // ---- user-defined measurement models (ukfb_sigma_points_dev, ukfb_update_sampled_dev) --------------------------------------
 // The caller evaluates h on the exported sigma points; the update is finished from the samples Z_i = h(X_i), m = 1 ...
 // SAMPLED_MAX_M, one m for the call.
-constexpr int SAMPLED_MAX_M = UKFB_SAMPLED_MAX_M, SAMPLED_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
+constexpr int SAMPLED_MAX_M = UKFB_SAMPLED_MAX_M;
 // The record of one filter's inputs and of S as the kernel keeps them: z (SAMPLED_MAX_M), Q row-major m x m (up to
 // SAMPLED_MAX_M^2), then S row-major with row stride SAMPLED_MAX_M, z-bar and nu (SAMPLED_MAX_M each; parked for the outputs)
 constexpr int SAMPLED_INPUT_Z = 0, SAMPLED_INPUT_Q = SAMPLED_MAX_M, SAMPLED_INPUT_S = SAMPLED_INPUT_Q + SAMPLED_MAX_M * SAMPLED_MAX_M;
@@ -516,27 +586,45 @@ inline Verdict check_sigma_points_args(bool has_X, bool has_delta) {
 inline Verdict check_sampled_args(const ukfb_sampled_in* in, int commit, const ukfb_sampled_out* out) {
     if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
     if (!in->Z_dev || !in->z_dev || !in->Q_dev) return {UKFB_ERR_INVALID_ARG, "Z_dev, z_dev and Q_dev must not be NULL"};
-    if (in->q_is_uniform != 0 && in->q_is_uniform != 1) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
-    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
-    if (commit == 0 && (!out || (!out->z_pred && !out->S && !out->innov && !out->maha && !out->loglik && !out->status)))
-        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
+    if (!zero_or_one(in->q_is_uniform)) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
+    if (!zero_or_one(commit)) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    if (const Verdict v = nothing_to_compute(commit, meas_has_output(out)); v.rc != UKFB_OK) return v;
     if (!sampled_m_ok(in->m)) return {UKFB_ERR_OUT_OF_RANGE, "m must be 1 ... 6 (UKFB_SAMPLED_MAX_M)"};
     return {};
 }
-// LDS of one filter of the update, in scalars of the compute type (ukf_sampled.hpp, SampledLayout): the factor region with its
-// reciprocal pivots, the delta table of the commit (2 D + 1 rows; the D x 6 half differences W, the D x 6 solved
-// cross-covariance Y and the staged samples, (2 D + 1) x 6 at most, alias it), the state's record (mean padded to 16, packed
-// covariance padded to even), the input record with S, z-bar and nu behind it (SAMPLED_INPUT_REGION) and the sink of lane-predicated stores
-// (16); rounded up to a multiple of four so that every filter's slice starts 16-byte aligned in either precision.  Every scalar
-// the kernel reads is one it wrote: the pads are never read.
-constexpr int sampled_filter_scalars(int S, int D) {
-    return S > 16 ? -1 : (D * SMOOTH_LS + 16 + (2 * D + 1) * SMOOTH_LS + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + SAMPLED_INPUT_REGION + 16 + 3) / 4 * 4;
+struct SampledMap {   // the update
+    int LS, ZS, MM, FAC, RSP, TAB, WT, YM, ZST, MUF, PKF, INP, DUM, PF;
+};
+constexpr SampledMap sampled_map(int, int D) {
+    RowSlice s;
+    SampledMap m{};
+    m.LS = ROW_LS;
+    m.MM = SAMPLED_MAX_M;
+    m.ZS = m.MM;   // row stride of the D x 6 matrices and of nothing else
+    s.factor(D, m.FAC, m.RSP);
+    m.TAB = s.table(D);   // the commit's; W, Y (D * ZS each) and the staged samples ((2 D + 1) * m, stride m) alias it
+    m.WT = m.TAB; m.YM = m.TAB + D * m.ZS; m.ZST = m.TAB + 2 * D * m.ZS;
+    s.record(D, m.MUF, m.PKF);              // the state: mean, Sigma packed
+    m.INP = s.take(SAMPLED_INPUT_REGION);   // z, Q, S, z-bar, nu (SAMPLED_INPUT_*), pads
+    m.DUM = s.sink();
+    m.PF = s.size();
+    return m;
 }
-// and of the export (SigmaPointsLayout): the factor region with its reciprocal pivots, the state's record and the sink
-constexpr int sigma_points_filter_scalars(int S, int D) {
-    return S > 16 ? -1 : (D * SMOOTH_LS + 16 + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 16 + 3) / 4 * 4;
+struct SigmaPointsMap {   // the export
+    int LS, FAC, RSP, MUF, PKF, DUM, PF;
+};
+constexpr SigmaPointsMap sigma_points_map(int, int D) {
+    RowSlice s;
+    SigmaPointsMap m{};
+    m.LS = ROW_LS;
+    s.factor(D, m.FAC, m.RSP);
+    s.record(D, m.MUF, m.PKF);   // the state: mean, Sigma packed
+    m.DUM = s.sink();
+    m.PF = s.size();
+    return m;
 }
-using SampledGeometry = RowGeometry;
+constexpr int sampled_filter_scalars(int S, int D) { return S > 16 ? -1 : sampled_map(S, D).PF; }
+constexpr int sigma_points_filter_scalars(int S, int D) { return S > 16 ? -1 : sigma_points_map(S, D).PF; }
 inline RowGeometry sampled_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(sampled_filter_scalars(S, D), capacity, compute_size); }
 inline RowGeometry sigma_points_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(sigma_points_filter_scalars(S, D), capacity, compute_size); }
 
@@ -546,27 +634,32 @@ inline RowGeometry sigma_points_geometry(int S, int D, int64_t capacity, size_t 
 inline Verdict check_predict_sampled_args(const ukfb_predict_sampled_in* in, int commit, const ukfb_predict_sampled_out* out) {
     if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
     if (!in->XX_dev || !in->R_dev) return {UKFB_ERR_INVALID_ARG, "XX_dev and R_dev must not be NULL"};
-    if (in->r_is_uniform != 0 && in->r_is_uniform != 1) return {UKFB_ERR_INVALID_ARG, "r_is_uniform must be 0 or 1"};
-    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
-    if (commit == 0 && (!out || (!out->mu && !out->cov_packed && !out->status)))
-        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
-    return {};
+    if (!zero_or_one(in->r_is_uniform)) return {UKFB_ERR_INVALID_ARG, "r_is_uniform must be 0 or 1"};
+    if (!zero_or_one(commit)) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    return nothing_to_compute(commit, out && (out->mu || out->cov_packed || out->status));
 }
-// LDS of one filter, in scalars of the compute type (ukf_predict_sampled.hpp, PredictSampledLayout): the D rows of Sigma^- (stride
-// SMOOTH_LS; parked while R is added), the delta table of 2 D + 1 rows (the staged samples, (2 D + 1) S scalars, alias it), the
-// predicted record (mean padded to 16 -- XX_0 waits there until the mean is formed --, packed covariance padded to even) and the
-// sink of lane-predicated stores (16); rounded up to a multiple of four so that every filter's slice starts 16-byte aligned in
-// either precision.  No factor, no reciprocal pivots, no rotation matrix: the kernel factorises nothing.  Every scalar the kernel
-// reads is one it wrote: the pads are never read.
-constexpr int predict_sampled_filter_scalars(int S, int D) {
-    return S > 16 ? -1 : (D * SMOOTH_LS + (2 * D + 1) * SMOOTH_LS + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 16 + 3) / 4 * 4;
+struct PredictSampledMap {   // no factor, no reciprocal pivots, no rotation matrix: the kernel factorises nothing
+    int LS, SMR, TAB, STG, CSM, CSP, DUM, PF;
+};
+constexpr PredictSampledMap predict_sampled_map(int, int D) {
+    RowSlice s;
+    PredictSampledMap m{};
+    m.LS = ROW_LS;
+    m.SMR = s.rows(D);    // the rows of Sigma^-, parked while R is added
+    m.TAB = s.table(D);   // the staged samples ((2 D + 1) * S) alias it
+    m.STG = m.TAB;
+    s.record(D, m.CSM, m.CSP);   // the predicted record: mean (XX_0 until the mean is formed), Sigma^- packed
+    m.DUM = s.sink();
+    m.PF = s.size();
+    return m;
 }
+constexpr int predict_sampled_filter_scalars(int S, int D) { return S > 16 ? -1 : predict_sampled_map(S, D).PF; }
 inline RowGeometry predict_sampled_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(predict_sampled_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- covariance conditioning (ukfb_condition_dev) ----------------------------------------------------------------------------
 // Eigenvalue repair of the covariance in its correlation scaling by cyclic Jacobi, round-robin ordering.  The launch is the
 // sampled update's: four filters per workgroup, one wavefront.
-constexpr int CONDITION_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP, CONDITION_MAX_SWEEPS = 12, CONDITION_SLICE_PAD = 4;
+constexpr int CONDITION_MAX_SWEEPS = 12, CONDITION_SLICE_PAD = 4;
 // players of the round-robin schedule (D rounded up to even; the odd D is padded with a decoupled unit row), pairs per step and
 // steps per sweep; the first pair of a step is the one that holds the last player: where that player is the padding, the pair is
 // the identity and is dropped
@@ -578,12 +671,10 @@ inline Verdict check_condition_args(const ukfb_condition_in* in, int commit, con
     if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
     if (!in->var_floor_dev) return {UKFB_ERR_INVALID_ARG, "var_floor_dev must not be NULL"};
     if (!(in->eig_floor > 0.0 && in->eig_floor < 1.0)) return {UKFB_ERR_INVALID_ARG, "eig_floor must lie in (0, 1)"};   // (NaN fails both)
-    if (in->renormalize_quaternion != 0 && in->renormalize_quaternion != 1)
+    if (!zero_or_one(in->renormalize_quaternion))
         return {UKFB_ERR_INVALID_ARG, "renormalize_quaternion must be 0 or 1"};
-    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
-    if (commit == 0 && (!out || (!out->eig_min && !out->eig_max && !out->mu && !out->cov_packed && !out->status)))
-        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
-    return {};
+    if (!zero_or_one(commit)) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    return nothing_to_compute(commit, out && (out->eig_min || out->eig_max || out->mu || out->cov_packed || out->status));
 }
 // the host form's floor: every entry finite and > 0
 inline Verdict check_condition_floor(const double* var_floor, int D) {
@@ -593,20 +684,30 @@ inline Verdict check_condition_floor(const double* var_floor, int D) {
             return {UKFB_ERR_INVALID_ARG, "every entry of var_floor must be finite and > 0"};
     return {};
 }
-// LDS of one filter, in scalars of the compute type (ukf_condition.hpp, ConditionLayout): the D parked rows of the row phase and
-// the D published rows of V (stride SMOOTH_LS each), the eigenvalues (16), the sigmas s_t (16), the state's record (mean padded
-// to 16, packed covariance padded to even), the sink of lane-predicated stores (16) and CONDITION_SLICE_PAD scalars that keep the
-// four slices of a workgroup off each other's banks in either precision; rounded up to a multiple of four so that every filter's
-// slice starts 16-byte aligned.  Every scalar the kernel reads is one it wrote: the pads are never read.
-constexpr int condition_filter_scalars(int S, int D) {
-    return S > 16 ? -1 : (2 * D * SMOOTH_LS + 16 + 16 + 16 + (D * (D + 1) / 2 + 1) / 2 * 2 + 16 + CONDITION_SLICE_PAD + 3) / 4 * 4;
+struct ConditionMap {
+    int LS, ROW, VPB, LAM, SDV, MUF, PKF, DUM, PF;
+};
+constexpr ConditionMap condition_map(int, int D) {
+    RowSlice s;
+    ConditionMap m{};
+    m.LS = ROW_LS;
+    m.ROW = s.rows(D);    // the rows of M J of a step (the row phase's exchange)
+    m.VPB = s.rows(D);    // V as every row published it
+    m.LAM = s.take(16);   // the eigenvalues
+    m.SDV = s.take(16);   // s_t = sqrt(d_t)
+    s.record(D, m.MUF, m.PKF);   // the state: mean, Sigma packed
+    m.DUM = s.sink();
+    s.take(CONDITION_SLICE_PAD);   // keeps the four slices of a workgroup off each other's banks in either precision
+    m.PF = s.size();
+    return m;
 }
+constexpr int condition_filter_scalars(int S, int D) { return S > 16 ? -1 : condition_map(S, D).PF; }
 inline RowGeometry condition_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(condition_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- late samples (ukfb_update_delayed_dev, ukfb_delayed_lag_dev) -----------------------------------------------------------
 // The smoother's window with the engine's own state as its last step: the chain runs at most steps - 1 <= SMOOTH_MAX_BACK
 // backward steps, all in one launch (their dt travel in the kernel arguments), so steps <= DELAYED_MAX_STEPS.
-constexpr int DELAYED_MAX_STEPS = UKFB_DELAYED_MAX_STEPS, DELAYED_FILTERS_PER_GROUP = ROW_FILTERS_PER_GROUP;
+constexpr int DELAYED_MAX_STEPS = UKFB_DELAYED_MAX_STEPS;
 static_assert(DELAYED_MAX_STEPS == SMOOTH_MAX_BACK + 1, "one launch covers the longest window");
 inline Verdict check_delayed_args(const ukfb_delayed_in* in, int commit, const ukfb_delayed_out* out) {
     if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
@@ -615,11 +716,12 @@ inline Verdict check_delayed_args(const ukfb_delayed_in* in, int commit, const u
     if (in->steps > 1 && !in->dt) return {UKFB_ERR_INVALID_ARG, "dt must not be NULL for a window of more than one step"};
     if (!in->mu_hist_dev || !in->cov_hist_dev) return {UKFB_ERR_INVALID_ARG, "mu_hist_dev and cov_hist_dev must not be NULL"};
     if (!in->z_dev || !in->Q_dev) return {UKFB_ERR_INVALID_ARG, "z_dev and Q_dev must not be NULL"};
-    if (in->q_is_uniform != 0 && in->q_is_uniform != 1) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
-    if (commit != 0 && commit != 1) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
-    if (commit == 0 && (!out || (!out->z_pred && !out->S && !out->innov && !out->maha && !out->loglik && !out->status && !out->mu_out &&
-                                 !out->cov_out)))
-        return {UKFB_ERR_INVALID_ARG, "commit = 0 with every output NULL: nothing to compute"};
+    if (!zero_or_one(in->q_is_uniform)) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
+    if (!zero_or_one(commit)) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    if (const Verdict v = nothing_to_compute(commit, out && (out->z_pred || out->S || out->innov || out->maha || out->loglik || out->status ||
+                                                             out->mu_out || out->cov_out));
+        v.rc != UKFB_OK)
+        return v;
     if (in->steps > std::min(in->slots, DELAYED_MAX_STEPS))
         return {UKFB_ERR_OUT_OF_RANGE, "steps <= min(slots, 33): a sample older than that is out of the window"};
     return {};
@@ -651,13 +753,19 @@ UKFB_HD int32_t delayed_lag_of(int steps, const int64_t* step_ts_us, int64_t t) 
     }
     return int32_t(n - best);
 }
-// LDS of one filter, in scalars of the compute type (ukf_delayed.hpp, DelayedLayout): the smoother's slice and behind it the D
-// rows (stride SMOOTH_LS) of the operator M; rounded up to a multiple of four so that every filter's slice starts 16-byte
-// aligned in either precision.  Every scalar the kernel reads is one it wrote.
-constexpr int delayed_filter_scalars(int S, int D) {
-    return S > 16 ? -1 : (smooth_filter_scalars(S, D) + D * SMOOTH_LS + 3) / 4 * 4;
+struct DelayedMap : SmoothMap {   // the smoother's slice, widened
+    int ZS, WT, YM, YN, MOP;
+};
+constexpr DelayedMap delayed_map(int S, int D) {
+    DelayedMap m{smooth_map(S, D), 0, 0, 0, 0, 0};
+    RowSlice s{m.PF};
+    m.ZS = 4;   // row stride of the D x 3 matrices W, Y_s and Y_n in the dead delta table
+    m.WT = m.TAB; m.YM = m.TAB + D * m.ZS; m.YN = m.TAB + 2 * D * m.ZS;
+    m.MOP = s.rows(D);   // the operator M, row l at MOP + l * LS
+    m.PF = s.size();
+    return m;
 }
-using DelayedGeometry = RowGeometry;
+constexpr int delayed_filter_scalars(int S, int D) { return S > 16 ? -1 : delayed_map(S, D).PF; }
 inline RowGeometry delayed_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(delayed_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- packed covariances of the host-array forms ---------------------------------------------------------------------------

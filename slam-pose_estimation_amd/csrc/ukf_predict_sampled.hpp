@@ -21,7 +21,7 @@
 //    wave-mates (the mean iteration runs while any row is active; a converged row keeps its reference).
 //  * commit = 0: the kernel gets NULL for the state's output pointers -- it has nothing through which it could store.
 //  * TS (storage) / T (compute) as in ukf_kernel16: TS = float with T = double is the wide-arithmetic mode.
-// LDS per filter: predict_sampled_filter_scalars (ukf_host.hpp).
+// LDS per filter: predict_sampled_map (ukf_host.hpp).
 #pragma once
 
 #include "ukf_row.hpp"
@@ -45,27 +45,14 @@ template <class T, class TS> struct PredictSampledArgs {
     uint32_t* status;            // [n] or null
 };
 
-template <class M> struct PredictSampledLayout {
-    static constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2, LS = ROW_LS;
-    static constexpr int PKE = (PK + 1) / 2 * 2;
-    static constexpr int SMR = 0;                         // D * LS: the rows of Sigma^-
-    static constexpr int TAB = SMR + D * LS;              // (2 D + 1) * LS delta table; the staged samples (N * S) alias it
-    static constexpr int STG = TAB;
-    static constexpr int CSM = TAB + N * LS;              // the predicted record: mean (16; XX_0 until the mean is formed),
-    static constexpr int CSP = CSM + 16;                  // Sigma^- packed (PKE)
-    static constexpr int DUM = CSP + PKE;                 // 16: sink of lane-predicated stores
-    static constexpr int PF = (DUM + 16 + 3) / 4 * 4;
-    static_assert(PF == predict_sampled_filter_scalars(S, D), "LDS accounting of ukf_host.hpp");
-    static_assert(LS >= D && S <= 16 && D + 1 <= 16, "a filter fits one row");
-    static_assert(N * S <= N * LS, "the staged samples fit the table they alias");
-};
-
 // (the second bound: wavefronts per SIMD the register allocator must leave room for)
 template <class T, class M, class TS>
 __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_predict_sampled_kernel(const PredictSampledArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2, Q = MT<M>::Q;
-    using LY = PredictSampledLayout<M>;
-    constexpr int LS = LY::LS;
+    constexpr PredictSampledMap LY = predict_sampled_map(S, D);   // the LDS slice (ukf_host.hpp)
+    constexpr int LS = LY.LS;
+    static_assert(row_fits(M::S, M::D), "a filter fits one row");
+    static_assert(N * S <= LY.CSM - LY.STG, "the staged samples fit the table they alias");
     extern __shared__ __attribute__((aligned(16))) unsigned char psm_smem[];
 
     // (RowCoords' statements in place: built on it, this kernel left the spread of the parent's own runs -- profiles/row_toolkit_rates.txt)
@@ -76,9 +63,9 @@ __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_predict_sampled_ke
     const int n_wg = int(n_here < ROW_FILTERS_PER_GROUP ? n_here : int64_t(ROW_FILTERS_PER_GROUP));
     const bool fvalid = g < n_wg;
     const int64_t f = wg0 + (fvalid ? g : (n_wg - 1));   // rows beyond the batch repeat its last filter and store nothing
-    T* const base = reinterpret_cast<T*>(psm_smem) + g * LY::PF;
-    T *const SMR = base + LY::SMR, *const TAB = base + LY::TAB, *const STG = base + LY::STG, *const CSM = base + LY::CSM;
-    T *const CSP = base + LY::CSP, *const DUMP = base + LY::DUM;
+    T* const base = reinterpret_cast<T*>(psm_smem) + g * LY.PF;
+    T *const SMR = base + LY.SMR, *const TAB = base + LY.TAB, *const STG = base + LY.STG, *const CSM = base + LY.CSM;
+    T *const CSP = base + LY.CSP, *const DUMP = base + LY.DUM;
     const TS* const Rf = a.R + f * a.R_stride;
 
     // ---- the row's filter and its record: the samples to LDS, judged on the way; the lower triangle of R is judged where it

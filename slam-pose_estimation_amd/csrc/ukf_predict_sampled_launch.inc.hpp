@@ -10,7 +10,7 @@ namespace ukfb {
 
 template <class TS, class M, class TC> static int launch_predict_sampled_typed(ukfb_engine* e, const PredictSampledReq& r) {
     using MC = typename M::template rebind<TC>;
-    const SampledGeometry geo = predict_sampled_geometry(MC::S, MC::D, e->cap, sizeof(TC));
+    const RowGeometry geo = predict_sampled_geometry(MC::S, MC::D, e->cap, sizeof(TC));
     if (geo.grid == 0) return UKFB_OK;
     PredictSampledArgs<TC, TS> a{};
     a.n = e->cap;

@@ -26,7 +26,7 @@
 //    wave-mates (the mean iteration runs while any row is active; a converged row keeps its reference).
 //  * commit = 0: the kernel gets NULL for the state's output pointers -- it has nothing through which it could store.
 //  * TS (storage) / T (compute) as in ukf_kernel16: TS = float with T = double is the wide-arithmetic mode.
-// LDS per filter: sampled_filter_scalars, sigma_points_filter_scalars (ukf_host.hpp).
+// LDS per filter: sampled_map, sigma_points_map (ukf_host.hpp).
 #pragma once
 
 #include "ukf_row.hpp"
@@ -68,53 +68,21 @@ template <class T, class TS> struct SampledArgs {
     uint32_t* status;            // [n] or null
 };
 
-template <class M> struct SigmaPointsLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS;
-    static constexpr int PKE = (PK + 1) / 2 * 2;
-    static constexpr int FAC = 0;                         // D * LS factor columns, then 16 reciprocal pivots
-    static constexpr int RSP = FAC + D * LS;
-    static constexpr int MUF = RSP + 16;                  // the state: mean (16), Sigma packed (PKE)
-    static constexpr int PKF = MUF + 16;
-    static constexpr int DUM = PKF + PKE;                 // 16: sink of lane-predicated stores
-    static constexpr int PF = (DUM + 16 + 3) / 4 * 4;
-    static_assert(PF == sigma_points_filter_scalars(S, D), "LDS accounting of ukf_host.hpp");
-    static_assert(LS >= D && S <= 16 && D + 1 <= 16, "a filter fits one row");
-};
-
-template <class M> struct SampledLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS, MM = SAMPLED_MAX_M;
-    static constexpr int PKE = (PK + 1) / 2 * 2;
-    static constexpr int ZS = MM;                         // row stride of the D x 6 matrices and of nothing else
-    static constexpr int FAC = 0;                         // D * LS factor columns, then 16 reciprocal pivots
-    static constexpr int RSP = FAC + D * LS;
-    static constexpr int TAB = RSP + 16;                  // (2 D + 1) * LS delta table of the commit; W, Y (D * ZS each) and the
-    static constexpr int WT = TAB, YM = TAB + D * ZS;     // staged samples ((2 D + 1) * m, stride m) alias it
-    static constexpr int ZST = TAB + 2 * D * ZS;
-    static constexpr int MUF = TAB + (2 * D + 1) * LS;    // the state: mean (16), Sigma packed (PKE)
-    static constexpr int PKF = MUF + 16;
-    static constexpr int INP = PKF + PKE;                 // z, Q, S, z-bar, nu (SAMPLED_INPUT_*), pads
-    static constexpr int DUM = INP + SAMPLED_INPUT_REGION;   // 16: sink of lane-predicated stores
-    static constexpr int PF = (DUM + 16 + 3) / 4 * 4;
-    static_assert(PF == sampled_filter_scalars(S, D), "LDS accounting of ukf_host.hpp");
-    static_assert(LS >= D && S <= 16 && D + 1 <= 16, "a filter fits one row");
-    static_assert(2 * D * ZS + (2 * D + 1) * MM <= (2 * D + 1) * LS, "W, Y and the staged samples fit the table they alias");
-    static_assert(SAMPLED_INPUT_SCALARS <= SAMPLED_INPUT_REGION && MM * (MM + 1) / 2 == 21, "the input record fits its region");
-};
-
 // ---------------------------------------------------------------------------------------------------------------- the export
 template <class T, class M, class TS>
 __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_sigma_points_kernel(const SigmaPointsArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
-    using LY = SigmaPointsLayout<M>;
-    constexpr int LS = LY::LS;
+    constexpr SigmaPointsMap LY = sigma_points_map(S, D);   // the LDS slice (ukf_host.hpp)
+    constexpr int LS = LY.LS;
+    static_assert(row_fits(M::S, M::D), "a filter fits one row");
     extern __shared__ __attribute__((aligned(16))) unsigned char sgp_smem[];
 
     const RowCoords<M> rc(a.n, threadIdx.x);
     const int l = rc.l, ls = rc.ls;
     const bool fvalid = rc.fvalid;
     const int64_t f = rc.f;
-    T* const base = row_slice<T, LY::PF>(sgp_smem, rc.g);
-    T *const FAC = base + LY::FAC, *const RSP = base + LY::RSP, *const MUF = base + LY::MUF, *const PKF = base + LY::PKF;
+    T* const base = row_slice<T, LY.PF>(sgp_smem, rc.g);
+    T *const FAC = base + LY.FAC, *const RSP = base + LY.RSP, *const MUF = base + LY.MUF, *const PKF = base + LY.PKF;
 
     const bool live = fvalid && a.initialised[f] != 0;
     row_stage_state<T, PK>(MUF, PKF, a.mu, a.cov, f * S, f * PK, l, ls);
@@ -183,8 +151,11 @@ template <class T> UKFB_DEV void sampled_solve6(T (&c)[SAMPLED_MAX_M], const T (
 template <class T, class M, class TS>
 __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_sampled_kernel(const SampledArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
-    using LY = SampledLayout<M>;
-    constexpr int LS = LY::LS, ZS = LY::ZS, MM = LY::MM;
+    constexpr SampledMap LY = sampled_map(S, D);   // the LDS slice (ukf_host.hpp)
+    constexpr int LS = LY.LS, ZS = LY.ZS, MM = LY.MM;
+    static_assert(row_fits(M::S, M::D), "a filter fits one row");
+    static_assert(LY.ZST - LY.TAB + N * MM <= LY.MUF - LY.TAB, "W, Y and the staged samples fit the table they alias");
+    static_assert(SAMPLED_INPUT_SCALARS <= LY.DUM - LY.INP && MM * (MM + 1) / 2 == 21, "the input record fits its region");
     extern __shared__ __attribute__((aligned(16))) unsigned char smp_smem[];
 
     // (RowCoords' statements in place: built on it, this kernel left the spread of the parent's own runs -- profiles/row_toolkit_rates.txt)
@@ -195,10 +166,10 @@ __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_sampled_kernel(con
     const int n_wg = int(n_here < ROW_FILTERS_PER_GROUP ? n_here : int64_t(ROW_FILTERS_PER_GROUP));
     const bool fvalid = g < n_wg;
     const int64_t f = wg0 + (fvalid ? g : (n_wg - 1));   // rows beyond the batch repeat its last filter and store nothing
-    T* const base = reinterpret_cast<T*>(smp_smem) + g * LY::PF;
-    T *const FAC = base + LY::FAC, *const RSP = base + LY::RSP, *const TAB = base + LY::TAB, *const WT = base + LY::WT;
-    T *const YM = base + LY::YM, *const ZST = base + LY::ZST, *const MUF = base + LY::MUF, *const PKF = base + LY::PKF;
-    T *const INP = base + LY::INP, *const DUMP = base + LY::DUM;
+    T* const base = reinterpret_cast<T*>(smp_smem) + g * LY.PF;
+    T *const FAC = base + LY.FAC, *const RSP = base + LY.RSP, *const TAB = base + LY.TAB, *const WT = base + LY.WT;
+    T *const YM = base + LY.YM, *const ZST = base + LY.ZST, *const MUF = base + LY.MUF, *const PKF = base + LY.PKF;
+    T *const INP = base + LY.INP, *const DUMP = base + LY.DUM;
     const int m = a.m, mm = m * m;   // wave-uniform
 
     // ---- the row's filter and records: the state, z and Q (a lane takes entries l, l + 16, l + 32), the samples

@@ -11,7 +11,7 @@ namespace ukfb {
 
 template <class TS, class M, class TC> static int launch_sigma_points_typed(ukfb_engine* e, const SigmaPointsReq& r) {
     using MC = typename M::template rebind<TC>;
-    const SampledGeometry geo = sigma_points_geometry(MC::S, MC::D, e->cap, sizeof(TC));
+    const RowGeometry geo = sigma_points_geometry(MC::S, MC::D, e->cap, sizeof(TC));
     if (geo.grid == 0) return UKFB_OK;
     SigmaPointsArgs<TC, TS> a{};
     a.n = e->cap;
@@ -27,7 +27,7 @@ template <class TS, class M, class TC> static int launch_sigma_points_typed(ukfb
 
 template <class TS, class M, class TC> static int launch_sampled_typed(ukfb_engine* e, const SampledReq& r) {
     using MC = typename M::template rebind<TC>;
-    const SampledGeometry geo = sampled_geometry(MC::S, MC::D, e->cap, sizeof(TC));
+    const RowGeometry geo = sampled_geometry(MC::S, MC::D, e->cap, sizeof(TC));
     if (geo.grid == 0) return UKFB_OK;
     SampledArgs<TC, TS> a{};
     a.n = e->cap;

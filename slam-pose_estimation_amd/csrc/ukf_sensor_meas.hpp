@@ -24,7 +24,7 @@
 //    wave-mates (the mean iteration runs while any row is active; a converged row keeps its reference).
 //  * commit = 0: the kernel gets NULL for the state's output pointers -- it has nothing through which it could store.
 //  * TS (storage) / T (compute) as in ukf_kernel16: TS = float with T = double is the wide-arithmetic mode.
-// LDS per filter: sensor_filter_scalars (ukf_host.hpp).
+// LDS per filter: sensor_map (ukf_host.hpp).
 #pragma once
 
 #include "ukf_row.hpp"
@@ -59,23 +59,6 @@ template <class T, class TS> struct SensorArgs {
     uint32_t* status;            // [n] or null
 };
 
-template <class M> struct SensorLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS;
-    static constexpr int PKE = (PK + 1) / 2 * 2;
-    static constexpr int ZS = 4;                          // row stride of the D x 3 matrices
-    static constexpr int FAC = 0;                         // D * LS factor columns, then 16 reciprocal pivots
-    static constexpr int RSP = FAC + D * LS;
-    static constexpr int TAB = RSP + 16;                  // (2 D + 1) * LS delta table of the commit; W and Y (D * ZS each) alias it
-    static constexpr int WT = TAB, YM = TAB + D * ZS;
-    static constexpr int MUF = TAB + (2 * D + 1) * LS;    // the state: mean (16), Sigma packed (PKE)
-    static constexpr int PKF = MUF + 16;
-    static constexpr int INP = PKF + PKE;                 // 32: z, Q, mount, point (SENSOR_INPUT_*), ten pads
-    static constexpr int DUM = INP + 32;                  // 16: sink of lane-predicated stores
-    static constexpr int PF = (DUM + 16 + 3) / 4 * 4;
-    static_assert(PF == sensor_filter_scalars(S, D), "LDS accounting of ukf_host.hpp");
-    static_assert(LS >= D && S <= 16 && D + 1 <= 16, "a filter fits one row");
-    static_assert(2 * D * ZS <= (2 * D + 1) * LS && SENSOR_INPUT_SCALARS <= 32, "W, Y and the input record fit their regions");
-};
 
 // What h reads beside the sigma point: the (neutralised) mount and point, the inverse of qs, 1 / |q|^2 of the mean's
 // orientation (every sigma point's orientation is the mean's times a unit exponential) and, OrientationState, the gyro sample
@@ -151,8 +134,10 @@ template <class T> UKFB_DEV void sensor_solve3(T (&c)[3], T l10, T l20, T l21, c
 template <class T, class M, class TS>
 __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_sensor_meas_kernel(const SensorArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
-    using LY = SensorLayout<M>;
-    constexpr int LS = LY::LS, ZS = LY::ZS, Q = MT<M>::Q;
+    constexpr SensorMap LY = sensor_map(S, D);
+    constexpr int LS = LY.LS, ZS = LY.ZS, Q = MT<M>::Q;
+    static_assert(row_fits(M::S, M::D), "a filter fits one row");
+    static_assert(2 * D * ZS <= LY.MUF - LY.TAB && SENSOR_INPUT_SCALARS <= LY.DUM - LY.INP, "W, Y and the input record fit their regions");
     extern __shared__ __attribute__((aligned(16))) unsigned char sen_smem[];
 
     // (RowCoords' statements in place: built on it, this kernel left the spread of the parent's own runs -- profiles/row_toolkit_rates.txt)
@@ -163,10 +148,10 @@ __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_sensor_meas_kernel
     const int n_wg = int(n_here < ROW_FILTERS_PER_GROUP ? n_here : int64_t(ROW_FILTERS_PER_GROUP));
     const bool fvalid = g < n_wg;
     const int64_t f = wg0 + (fvalid ? g : (n_wg - 1));   // rows beyond the batch repeat its last filter and store nothing
-    T* const base = reinterpret_cast<T*>(sen_smem) + g * LY::PF;
-    T *const FAC = base + LY::FAC, *const RSP = base + LY::RSP, *const TAB = base + LY::TAB, *const WT = base + LY::WT;
-    T *const YM = base + LY::YM, *const MUF = base + LY::MUF, *const PKF = base + LY::PKF, *const INP = base + LY::INP;
-    T* const DUMP = base + LY::DUM;
+    T* const base = reinterpret_cast<T*>(sen_smem) + g * LY.PF;
+    T *const FAC = base + LY.FAC, *const RSP = base + LY.RSP, *const TAB = base + LY.TAB, *const WT = base + LY.WT;
+    T *const YM = base + LY.YM, *const MUF = base + LY.MUF, *const PKF = base + LY.PKF, *const INP = base + LY.INP;
+    T* const DUMP = base + LY.DUM;
 
     // ---- the row's filter, model and records
     const bool live = fvalid && a.initialised[f] != 0;

@@ -10,7 +10,7 @@ namespace ukfb {
 
 template <class TS, class M, class TC> static int launch_sensor_meas_typed(ukfb_engine* e, const SensorReq& r) {
     using MC = typename M::template rebind<TC>;
-    const SensorGeometry geo = sensor_geometry(MC::S, MC::D, e->cap, sizeof(TC));
+    const RowGeometry geo = sensor_geometry(MC::S, MC::D, e->cap, sizeof(TC));
     if (geo.grid == 0) return UKFB_OK;
     SensorArgs<TC, TS> a{};
     a.n = e->cap;

@@ -21,7 +21,7 @@
 //  * a filter that fails, is gated or is uninitialised rides along: every select is per row, no row's bits depend on its
 //    wave-mates (the mean iteration runs while any row is active; a converged row keeps its reference).
 //  * TS (storage) / T (compute) as in ukf_kernel16: TS = float with T = double is the wide-arithmetic mode.
-// LDS per filter: smooth_filter_scalars (ukf_host.hpp) -- the factor region (Sigma's, then Sigma^-'s, then Sigma~'s), the delta
+// LDS per filter: smooth_map (ukf_host.hpp) -- the factor region (Sigma's, then Sigma^-'s, then Sigma~'s), the delta
 // table (aliased by G and M once C and Sigma^- are formed), the chain record, the filtered record, the rotation matrix, a sink.
 #pragma once
 
@@ -57,30 +57,11 @@ template <class T, class TS> struct SmoothArgs {
     double dt[SMOOTH_MAX_BACK];  // dt[k]: time step of the prediction redone by backward step k of this launch
 };
 
-template <class M> struct SmoothLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS;
-    static constexpr int PKE = (PK + 1) / 2 * 2;
-    static constexpr int FAC = 0;                         // D * LS factor columns, then 16 reciprocal pivots
-    static constexpr int RSP = FAC + D * LS;
-    static constexpr int TAB = RSP + 16;                  // (2 D + 1) * LS delta table; G (D * LS) and M (D * LS) alias it
-    static constexpr int GM = TAB, MM = TAB + D * LS;
-    static constexpr int CSM = TAB + (2 * D + 1) * LS;    // chain mean (16), chain covariance (PKE)
-    static constexpr int CSP = CSM + 16;
-    static constexpr int MUF = CSP + PKE;                 // filtered mean (16), filtered covariance (PKE)
-    static constexpr int PKF = MUF + 16;
-    static constexpr int ROT = PKF + PKE;                 // 9 (+ 1)
-    static constexpr int DUM = ROT + 10;                  // 16: sink of lane-predicated stores
-    static constexpr int SMR = DUM + 16;                  // D * LS rows of Sigma^-, parked between its factorisation and M
-    static constexpr int MUP = SMR + D * LS;              // 16: mu^-, parked across the solves
-    static constexpr int PF = MUP + 16;
-    static_assert(PF == smooth_filter_scalars(S, D), "LDS accounting of ukf_host.hpp");
-    static_assert(LS >= D && S <= 16 && D + 1 <= 16, "a filter fits one row");
-};
-
-// What a row derives from its lane index: its filter, its predicates and its LDS slice (public members in this order: the step
-// loop binds them by name)
+// What a row derives from its lane index: its filter, its predicates and its LDS slice (smooth_map, ukf_host.hpp; public members
+// in this order: the step loop binds them by name)
 template <class T, class M, class TS> struct SmoothRow {
-    using LY = SmoothLayout<M>;
+    static constexpr SmoothMap LY = smooth_map(M::S, M::D);
+    static_assert(row_fits(M::S, M::D), "a filter fits one row");
     int l, lr, ls;          // lane of the row; clamped to a row of the matrices / an entry of the mean
     bool fvalid, live, wr;  // the row has a filter of the batch; ... that is initialised; = both: the row stores
     int64_t f;              // rows beyond the batch repeat its last filter and store nothing
@@ -91,10 +72,10 @@ template <class T, class M, class TS> struct SmoothRow {
         l = rc.l; lr = rc.lr; ls = rc.ls; fvalid = rc.fvalid; f = rc.f;
         live = fvalid && a.initialised[f] != 0;
         wr = live;
-        T* const base = row_slice<T, LY::PF>(smem, rc.g);
-        FAC = base + LY::FAC; RSP = base + LY::RSP; TAB = base + LY::TAB; GM = base + LY::GM; MM = base + LY::MM;
-        CSM = base + LY::CSM; CSP = base + LY::CSP; MUF = base + LY::MUF; PKF = base + LY::PKF; ROT = base + LY::ROT;
-        DUMP = base + LY::DUM; SMR = base + LY::SMR; MUP = base + LY::MUP;
+        T* const base = row_slice<T, LY.PF>(smem, rc.g);
+        FAC = base + LY.FAC; RSP = base + LY.RSP; TAB = base + LY.TAB; GM = base + LY.GM; MM = base + LY.MM;
+        CSM = base + LY.CSM; CSP = base + LY.CSP; MUF = base + LY.MUF; PKF = base + LY.PKF; ROT = base + LY.ROT;
+        DUMP = base + LY.DUM; SMR = base + LY.SMR; MUP = base + LY.MUP;
         Rn = a.Rn + f * a.Rn_stride;
         Racc = a.Racc + f * a.Rn_stride;
     }
@@ -103,8 +84,8 @@ template <class T, class M, class TS> struct SmoothRow {
 template <class T, class M, class TS>
 __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_smooth_kernel(const SmoothArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
-    using LY = SmoothLayout<M>;
-    constexpr int LS = LY::LS, Q = MT<M>::Q, RT = MT<M>::RT;
+    constexpr SmoothMap LY = smooth_map(S, D);
+    constexpr int LS = LY.LS, Q = MT<M>::Q, RT = MT<M>::RT;
     extern __shared__ __attribute__((aligned(16))) unsigned char smooth_smem[];
     uint32_t st = ST_OK;
     int slot = a.top_slot;

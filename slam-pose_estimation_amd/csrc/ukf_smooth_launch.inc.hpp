@@ -11,7 +11,7 @@ namespace ukfb {
 template <class TS, class M, class TC> static int launch_smooth_typed(ukfb_engine* e, const SmoothReq& r) {
     using MC = typename M::template rebind<TC>;
     constexpr int S = MC::S, D = MC::D, PK = D * (D + 1) / 2;
-    const SmoothGeometry geo = smooth_geometry(S, D, e->cap, sizeof(TC));
+    const RowGeometry geo = smooth_geometry(S, D, e->cap, sizeof(TC));
     if (geo.grid == 0) return UKFB_OK;
     const SmoothLaunch& p = r.part;
     SmoothArgs<TC, TS> a{};

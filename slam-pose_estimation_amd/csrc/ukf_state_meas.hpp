@@ -16,7 +16,7 @@
 //    wave-mates (the mean iteration runs while any row is active; a converged row keeps its reference).
 //  * commit = 0: the kernel gets NULL for the state's output pointers -- it has nothing through which it could store.
 //  * TS (storage) / T (compute) as in ukf_kernel16: TS = float with T = double is the wide-arithmetic mode.
-// LDS per filter: state_meas_filter_scalars (ukf_host.hpp).
+// LDS per filter: state_meas_map (ukf_host.hpp).
 #pragma once
 
 #include "ukf_row.hpp"
@@ -44,24 +44,6 @@ template <class T, class TS> struct StateMeasArgs {
     uint32_t* status;            // [n] or null
 };
 
-template <class M> struct StateMeasLayout {
-    static constexpr int S = M::S, D = M::D, PK = D * (D + 1) / 2, LS = ROW_LS;
-    static constexpr int PKE = (PK + 1) / 2 * 2;
-    static constexpr int FAC = 0;                         // D * LS factor columns, then 16 reciprocal pivots
-    static constexpr int RSP = FAC + D * LS;
-    static constexpr int TAB = RSP + 16;                  // (2 D + 1) * LS delta table; Y (D * LS) aliases it
-    static constexpr int YM = TAB;
-    static constexpr int MUF = TAB + (2 * D + 1) * LS;    // the state: mean (16), a Sigma packed (PKE)
-    static constexpr int PKF = MUF + 16;
-    static constexpr int ZM = PKF + PKE;                  // the measurement: mean (16), b Qz packed (PKE)
-    static constexpr int PKQ = ZM + 16;
-    static constexpr int DUM = PKQ + PKE;                 // 16: sink of lane-predicated stores
-    static constexpr int PF = (DUM + 16 + 3) / 4 * 4;
-    static_assert(PF == state_meas_filter_scalars(S, D), "LDS accounting of ukf_host.hpp");
-    static_assert(LS >= D && S <= 16 && D + 1 <= 16, "a filter fits one row");
-    static_assert(state_meas_blocks(M::MODEL) == (D + 2) / 3, "tangent dimension t belongs to block t / 3");
-};
-
 // row_publish_deltas with the unselected columns zeroed (tsel: bit t = tangent dimension t is measured)
 template <class T, class M, int LS>
 UKFB_DEV void stm_publish_deltas(T* TAB, T* DUMP, int l, uint32_t tsel, const T (&xp)[M::S], const T (&xm)[M::S], const T (&ref)[M::S]) {
@@ -83,18 +65,20 @@ UKFB_DEV void stm_publish_deltas(T* TAB, T* DUMP, int l, uint32_t tsel, const T 
 template <class T, class M, class TS>
 __global__ void __launch_bounds__(64, ROW_WAVES_PER_SIMD) ukf_state_meas_kernel(const StateMeasArgs<T, TS> a) {
     constexpr int S = M::S, D = M::D, N = 2 * D + 1, PK = D * (D + 1) / 2;
-    using LY = StateMeasLayout<M>;
-    constexpr int LS = LY::LS, Q = MT<M>::Q, RT = MT<M>::RT, NB = (D + 2) / 3;
+    constexpr StateMeasMap LY = state_meas_map(S, D);   // the LDS slice (ukf_host.hpp)
+    constexpr int LS = LY.LS, Q = MT<M>::Q, RT = MT<M>::RT, NB = (D + 2) / 3;
+    static_assert(row_fits(M::S, M::D), "a filter fits one row");
+    static_assert(state_meas_blocks(M::MODEL) == NB, "tangent dimension t belongs to block t / 3");
     extern __shared__ __attribute__((aligned(16))) unsigned char stm_smem[];
 
     const RowCoords<M> rc(a.n, threadIdx.x);
     const int l = rc.l, lr = rc.lr, ls = rc.ls;
     const bool fvalid = rc.fvalid;
     const int64_t f = rc.f;
-    T* const base = row_slice<T, LY::PF>(stm_smem, rc.g);
-    T *const FAC = base + LY::FAC, *const RSP = base + LY::RSP, *const TAB = base + LY::TAB, *const YM = base + LY::YM;
-    T *const MUF = base + LY::MUF, *const PKF = base + LY::PKF, *const ZM = base + LY::ZM, *const PKQ = base + LY::PKQ;
-    T* const DUMP = base + LY::DUM;
+    T* const base = row_slice<T, LY.PF>(stm_smem, rc.g);
+    T *const FAC = base + LY.FAC, *const RSP = base + LY.RSP, *const TAB = base + LY.TAB, *const YM = base + LY.YM;
+    T *const MUF = base + LY.MUF, *const PKF = base + LY.PKF, *const ZM = base + LY.ZM, *const PKQ = base + LY.PKQ;
+    T* const DUMP = base + LY.DUM;
 
     // ---- the row's filter, mask and records
     const bool live = fvalid && a.initialised[f] != 0;

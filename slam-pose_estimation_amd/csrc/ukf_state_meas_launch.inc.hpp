@@ -10,7 +10,7 @@ namespace ukfb {
 
 template <class TS, class M, class TC> static int launch_state_meas_typed(ukfb_engine* e, const StateMeasReq& r) {
     using MC = typename M::template rebind<TC>;
-    const StateMeasGeometry geo = state_meas_geometry(MC::S, MC::D, e->cap, sizeof(TC));
+    const RowGeometry geo = state_meas_geometry(MC::S, MC::D, e->cap, sizeof(TC));
     if (geo.grid == 0) return UKFB_OK;
     StateMeasArgs<TC, TS> a{};
     a.n = e->cap;

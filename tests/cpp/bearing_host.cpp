@@ -27,7 +27,7 @@ int main() {
     st_only.status = &word;
     // ids per engine
     EXPECT(UKFB_BEARING_NONE == -1 && UKFB_BEARING_POSE_POINT == 0 && UKFB_BEARING_POSE_NAV_DIRECTION == 1);
-    EXPECT(UKFB_BEARING_ORIENT_NAV_DIRECTION == 2 && BEARING_MODELS == 3 && BEARING_FILTERS_PER_GROUP == 4);
+    EXPECT(UKFB_BEARING_ORIENT_NAV_DIRECTION == 2 && BEARING_MODELS == 3 && ROW_FILTERS_PER_GROUP == 4);
     for (int64_t id = -3; id <= 12; ++id) {
         EXPECT(bearing_model_ok(UKFB_MODEL_POSE, id) == (id == 0 || id == 1));
         EXPECT(bearing_model_ok(UKFB_MODEL_ORIENT, id) == (id == 2));
@@ -96,10 +96,10 @@ int main() {
     for (const auto& m : models) {
         const int PK = m.D * (m.D + 1) / 2;
         const int sc = bearing_filter_scalars(m.S, m.D);
-        const int floor_sc = m.D * SMOOTH_LS + (2 * m.D + 1) * SMOOTH_LS + m.S + PK + SENSOR_INPUT_SCALARS;
+        const int floor_sc = m.D * ROW_LS + (2 * m.D + 1) * ROW_LS + m.S + PK + SENSOR_INPUT_SCALARS;
         EXPECT(sc >= floor_sc && sc <= floor_sc * 115 / 100 && sc % 4 == 0);
         EXPECT(sc == sensor_filter_scalars(m.S, m.D));
-        EXPECT(2 * m.D * 4 <= (2 * m.D + 1) * SMOOTH_LS);   // W and Y (D x 3, stride 4) fit the table they alias
+        EXPECT(2 * m.D * 4 <= (2 * m.D + 1) * ROW_LS);   // W and Y (D x 3, stride 4) fit the table they alias
         for (size_t bytes : {size_t(4), size_t(8)}) {
             const RowGeometry g = bearing_geometry(m.S, m.D, 1022, bytes);
             EXPECT(g.grid == 256 && g.lds_bytes == int(4 * sc * bytes));

@@ -96,7 +96,7 @@ int main() {
     EXPECT(condition_players(13) == 14 && condition_steps(13) == 13 && condition_pairs_per_step(13) == 7 && condition_first_pair(13) == 1);
     EXPECT(condition_steps(12) * (condition_pairs_per_step(12) - condition_first_pair(12)) == 12 * 11 / 2);
     EXPECT(condition_steps(13) * (condition_pairs_per_step(13) - condition_first_pair(13)) == 13 * 12 / 2);
-    EXPECT(CONDITION_MAX_SWEEPS == 12 && CONDITION_FILTERS_PER_GROUP == 4);
+    EXPECT(CONDITION_MAX_SWEEPS == 12 && ROW_FILTERS_PER_GROUP == 4);
     // LDS by hand.  Pose (S 13, D 12): 2 * 12 * 14 rows + 3 * 16 + 78 packed + 16 sink + 4 pad = 482 -> 484;
     // OrientationState (S 14, D 13): 2 * 13 * 14 + 48 + 92 (91 padded to even) + 16 + 4 = 524
     EXPECT(condition_filter_scalars(13, 12) == (336 + 48 + 78 + 16 + 4 + 3) / 4 * 4 && condition_filter_scalars(13, 12) == 484);
@@ -111,10 +111,10 @@ int main() {
         for (size_t bytes : {size_t(4), size_t(8)}) {
             EXPECT((sc * int(bytes)) % 16 == 0);
             EXPECT((sc * int(bytes) / 4) % 32 != 0);   // the four slices start on different banks
-            EXPECT((SMOOTH_LS * int(bytes)) % 8 == 0); // the parked rows start 8-byte aligned
+            EXPECT((ROW_LS * int(bytes)) % 8 == 0); // the parked rows start 8-byte aligned
             const struct { int64_t n, grid; } cases[] = {{0, 0}, {1, 1}, {3, 1}, {4, 1}, {5, 2}, {1022, 256}, {1048576, 262144}};
             for (const auto& c : cases) {
-                const SampledGeometry g = condition_geometry(m.S, m.D, c.n, bytes);
+                const RowGeometry g = condition_geometry(m.S, m.D, c.n, bytes);
                 EXPECT(g.grid == c.grid && g.lds_bytes == int(4 * sc * bytes) && g.lds_bytes <= 65536 && g.lds_bytes % 16 == 0);
             }
         }

@@ -81,8 +81,8 @@ int main() {
     // 160 KiB of a compute unit at least four times in fp64
     for (const int* sd : {(const int[]){13, 12}, (const int[]){14, 13}}) {
         const int S = sd[0], D = sd[1], pf = delayed_filter_scalars(S, D);
-        EXPECT(pf % 4 == 0 && pf >= smooth_filter_scalars(S, D) + D * SMOOTH_LS && pf < smooth_filter_scalars(S, D) + D * SMOOTH_LS + 4);
-        const DelayedGeometry g8 = delayed_geometry(S, D, 1022, 8), g4 = delayed_geometry(S, D, 1022, 4);
+        EXPECT(pf % 4 == 0 && pf >= smooth_filter_scalars(S, D) + D * ROW_LS && pf < smooth_filter_scalars(S, D) + D * ROW_LS + 4);
+        const RowGeometry g8 = delayed_geometry(S, D, 1022, 8), g4 = delayed_geometry(S, D, 1022, 4);
         EXPECT(g8.grid == 256 && g4.grid == 256);
         EXPECT(g8.lds_bytes == 4 * pf * 8 && g4.lds_bytes == 4 * pf * 4);
         EXPECT(4 * g8.lds_bytes <= 160 * 1024);

@@ -70,19 +70,19 @@ int main() {
     struct { int S, D; } models[2] = {{13, 12}, {14, 13}};
     for (const auto& m : models) {
         const int N = 2 * m.D + 1, sc = predict_sampled_filter_scalars(m.S, m.D);
-        EXPECT(N * m.S <= N * SMOOTH_LS);   // the staged samples fit the table they alias (equality for OrientationState)
+        EXPECT(N * m.S <= N * ROW_LS);   // the staged samples fit the table they alias (equality for OrientationState)
         EXPECT(sc % 4 == 0 && sc < forecast_filter_scalars(m.S, m.D) && sc < sampled_filter_scalars(m.S, m.D));
         for (size_t bytes : {size_t(4), size_t(8)}) {
             EXPECT((sc * int(bytes)) % 16 == 0);
             EXPECT((sc * int(bytes) / 4) % 32 != 0);   // the four slices start on different banks
             const struct { int64_t n, grid; } cases[] = {{0, 0}, {1, 1}, {4, 1}, {5, 2}, {1022, 256}};
             for (const auto& c : cases) {
-                const SampledGeometry g = predict_sampled_geometry(m.S, m.D, c.n, bytes);
+                const RowGeometry g = predict_sampled_geometry(m.S, m.D, c.n, bytes);
                 EXPECT(g.grid == c.grid && g.lds_bytes == int(4 * sc * bytes) && g.lds_bytes <= 65536 && g.lds_bytes % 16 == 0);
             }
         }
     }
-    EXPECT(14 * 27 == 27 * SMOOTH_LS);
+    EXPECT(14 * 27 == 27 * ROW_LS);
     EXPECT(predict_sampled_geometry(13, 12, 1022, 8).lds_bytes == 20096 && predict_sampled_geometry(14, 13, 1022, 4).lds_bytes == 10944);
     std::printf("OK: %d failure(s)\n", failures);
     return failures ? 1 : 0;

@@ -27,7 +27,7 @@ int main() {
     ukfb_sampled_out st_only{};
     st_only.status = &word;
     // the range of m: checked on the host, nothing is launched outside it
-    EXPECT(UKFB_SAMPLED_MAX_M == 6 && SAMPLED_MAX_M == 6 && SAMPLED_FILTERS_PER_GROUP == 4);
+    EXPECT(UKFB_SAMPLED_MAX_M == 6 && SAMPLED_MAX_M == 6 && ROW_FILTERS_PER_GROUP == 4);
     for (int m = -3; m <= 12; ++m) {
         ukfb_sampled_in v = in;
         v.m = m;
@@ -92,12 +92,12 @@ int main() {
         // the update: the sensor kernel's slice with the larger input record; W, Y (D x 6) and the staged samples ((2 D + 1) x 6)
         // fit the commit's table they alias
         EXPECT(sc == sensor_filter_scalars(m.S, m.D) + (SAMPLED_INPUT_REGION - 32) && sc % 4 == 0);
-        EXPECT(2 * m.D * SAMPLED_MAX_M + N * SAMPLED_MAX_M <= N * SMOOTH_LS);
+        EXPECT(2 * m.D * SAMPLED_MAX_M + N * SAMPLED_MAX_M <= N * ROW_LS);
         // the export: one D x 14 matrix, one record, and no more than 15 % on top
-        const int floor_se = m.D * SMOOTH_LS + m.S + PK;
+        const int floor_se = m.D * ROW_LS + m.S + PK;
         EXPECT(se >= floor_se && se <= floor_se * 115 / 100 + 32 && se % 4 == 0 && se < sc);
         for (size_t bytes : {size_t(4), size_t(8)}) {
-            const SampledGeometry g = sampled_geometry(m.S, m.D, 1022, bytes), x = sigma_points_geometry(m.S, m.D, 1022, bytes);
+            const RowGeometry g = sampled_geometry(m.S, m.D, 1022, bytes), x = sigma_points_geometry(m.S, m.D, 1022, bytes);
             EXPECT(g.grid == 256 && g.lds_bytes == int(4 * sc * bytes) && x.grid == 256 && x.lds_bytes == int(4 * se * bytes));
             EXPECT(g.lds_bytes <= 65536 && g.lds_bytes % 16 == 0 && (sc * int(bytes)) % 16 == 0 && (se * int(bytes)) % 16 == 0);
             EXPECT((sc * int(bytes) / 4) % 32 != 0 && (se * int(bytes) / 4) % 32 != 0);   // the four slices start on different banks

@@ -103,12 +103,12 @@ int main() {
         const int PK = m.D * (m.D + 1) / 2;
         const int sc = sensor_filter_scalars(m.S, m.D);
         // one D x 14 matrix, the commit's delta table, one record, the inputs, and no more than 15 % on top
-        const int floor_sc = m.D * SMOOTH_LS + (2 * m.D + 1) * SMOOTH_LS + m.S + PK + SENSOR_INPUT_SCALARS;
+        const int floor_sc = m.D * ROW_LS + (2 * m.D + 1) * ROW_LS + m.S + PK + SENSOR_INPUT_SCALARS;
         EXPECT(sc >= floor_sc && sc <= floor_sc * 115 / 100 && sc % 4 == 0);
         EXPECT(sc < state_meas_filter_scalars(m.S, m.D));
-        EXPECT(2 * m.D * 4 <= (2 * m.D + 1) * SMOOTH_LS);   // W and Y (D x 3, stride 4) fit the table they alias
+        EXPECT(2 * m.D * 4 <= (2 * m.D + 1) * ROW_LS);   // W and Y (D x 3, stride 4) fit the table they alias
         for (size_t bytes : {size_t(4), size_t(8)}) {
-            const SensorGeometry g = sensor_geometry(m.S, m.D, 1022, bytes);
+            const RowGeometry g = sensor_geometry(m.S, m.D, 1022, bytes);
             EXPECT(g.grid == 256 && g.lds_bytes == int(4 * sc * bytes));
             EXPECT(g.lds_bytes <= 65536 && g.lds_bytes % 16 == 0 && (sc * int(bytes)) % 16 == 0);
             EXPECT((sc * int(bytes) / 4) % 32 != 0);   // the four slices start on different banks

@@ -67,11 +67,11 @@ int main() {
         const int PK = m.D * (m.D + 1) / 2;
         const int sc = state_meas_filter_scalars(m.S, m.D);
         // one D x 14 matrix, the delta table, two records, and no more than 15 % on top
-        const int floor_sc = m.D * SMOOTH_LS + (2 * m.D + 1) * SMOOTH_LS + 2 * (m.S + PK);
+        const int floor_sc = m.D * ROW_LS + (2 * m.D + 1) * ROW_LS + 2 * (m.S + PK);
         EXPECT(sc >= floor_sc && sc <= floor_sc * 115 / 100 && sc % 4 == 0);
         EXPECT(sc < smooth_filter_scalars(m.S, m.D));
         for (size_t bytes : {size_t(4), size_t(8)}) {
-            const StateMeasGeometry g = state_meas_geometry(m.S, m.D, 1022, bytes);
+            const RowGeometry g = state_meas_geometry(m.S, m.D, 1022, bytes);
             EXPECT(g.grid == 256 && g.lds_bytes == int(4 * sc * bytes));
             EXPECT(g.lds_bytes <= 65536 && g.lds_bytes % 16 == 0 && (sc * int(bytes)) % 16 == 0);
             EXPECT((sc * int(bytes) / 4) % 32 != 0);   // the four slices start on different banks
