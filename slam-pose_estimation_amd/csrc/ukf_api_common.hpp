@@ -1,7 +1,9 @@
-// ukf_api_common.hpp -- the host plumbing the feature C-ABI files share (every ukf_*_api.hip: the Makefile's FEATURES): the
-// error macro, the argument verdict, the entry check with the poisoned-engine refusal, and HostStage, the one place where the
-// host-array forms allocate their temporaries and copy to and from the device.  Not for ukf_batch.hip / ukf_group.hip: their
-// HIP_TRY knows the timed-out wait and their fail has another signature.
+// ukf_api_common.hpp -- the host plumbing every host translation unit shares (the Makefile's HOST_TUS and every ukf_*_api.hip):
+// the error macro and the device scope, the argument verdict, the entry check with the poisoned-engine refusal, the owner of a
+// temporary device buffer, the bounded waits, the transfers between host doubles and the engine's arrays, and HostStage, the
+// one place where the host-array forms allocate their temporaries and copy to and from the device.  What is only declared
+// here is defined once, in namespace ukfb: the error channel, the waits, the transfers and launch in ukf_runtime.hip,
+// build_model_buckets in ukf_buckets.hip, rebuild_racc in ukf_batch.hip.
 #pragma once
 
 #include <algorithm>
@@ -9,7 +11,7 @@
 
 #include "ukf_engine.hpp"
 
-#define UKFB_HIP_TRY(expr)                         \
+#define HIP_TRY(expr)                              \
     do {                                           \
         const hipError_t _e = (expr);              \
         if (_e != hipSuccess) {                    \
@@ -18,8 +20,26 @@
         }                                          \
     } while (0)
 
+// the engine's device for the rest of the enclosing scope, the caller's device again afterwards (ukfb::DeviceScope)
+#define ON_DEVICE(dev)                                     \
+    ukfb::DeviceScope device_scope_(dev);                  \
+    HIP_TRY(device_scope_.err)
+
+// Waits for the engine's stream with the bounded polling wait (ukfb::engine_wait).  A wait that gives up POISONS the engine:
+// work of unknown state is still queued, so every later call fails fast with UKFB_ERR_HIP, and ukfb_destroy neither waits
+// again nor frees device memory that a kernel in flight may still touch (the process is expected to exit non-zero).
+#define ENGINE_SYNC(e)                                     \
+    do {                                                   \
+        const int _rc = ukfb::engine_wait(e);              \
+        if (_rc) return _rc;                               \
+    } while (0)
+
 namespace ukfb {
 
+inline int fail(int code, const char* msg) {
+    set_error_text(msg);
+    return code;
+}
 inline int fail(const ukfb::Verdict& v) {
     if (v.rc != UKFB_OK) set_error_text(v.msg ? v.msg : "invalid argument");
     return v.rc;
@@ -27,7 +47,7 @@ inline int fail(const ukfb::Verdict& v) {
 
 // UKFB_OK, or the refusal of an engine one of whose bounded waits gave up (every entry point decides where it asks)
 inline int refuse_poisoned(const ukfb_engine* e) {
-    if (e->poisoned) return fail({UKFB_ERR_HIP, "engine poisoned by an earlier wait that timed out (UKFB_WAIT_TIMEOUT_S)"});
+    if (e->poisoned) return fail(UKFB_ERR_HIP, "engine poisoned by an earlier wait that timed out (UKFB_WAIT_TIMEOUT_S)");
     return UKFB_OK;
 }
 
@@ -36,6 +56,49 @@ inline int entry(ukfb_engine* e) {
     if (!e) return UKFB_ERR_INVALID_ARG;
     return refuse_poisoned(e);
 }
+
+struct DevTmp {   // device scratch that is released on every exit path
+    void* p = nullptr;
+    DevTmp() = default;
+    DevTmp(DevTmp&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevTmp(const DevTmp&) = delete;
+    DevTmp& operator=(const DevTmp&) = delete;
+    ~DevTmp() { if (p) (void)hipFree(p); }
+};
+
+// The bounded polling waits (ukfb::wait_polling, ukf_host.hpp) on a stream or an event of the engine: UKFB_OK, or UKFB_ERR_HIP
+// with the text written -- `what` and the HIP error, or "timed out ..." after a wait that gave up, which also poisons the engine.
+int wait_stream(ukfb_engine* e, hipStream_t s, const char* what);
+int wait_event(ukfb_engine* e, hipEvent_t ev, const char* what);
+int engine_wait(ukfb_engine* e);   // refuses a poisoned engine, then waits for the engine's stream
+
+bool range_ok(const ukfb_engine* e, int64_t first, int64_t count);
+int check_meas_model(const ukfb_engine* e, int m);
+
+// host doubles <-> a device array in engine precision (elem_offset scalars into it); every one of them waits for the stream
+int upload(ukfb_engine* e, void* dst_dev, size_t elem_offset, const double* src, size_t n);
+int download(ukfb_engine* e, const void* src_dev, size_t elem_offset, double* dst, size_t n);
+int upload_on_copy_stream(ukfb_engine* e, void* dst_dev, const double* src, size_t n);
+int ensure_scratch(ukfb_engine* e, size_t bytes);
+int fill_scalar(ukfb_engine* e, void* dst_dev, size_t n, double value);
+
+template <class P> int upload_raw(ukfb_engine* e, P* dst_dev, const P* src, size_t n) {
+    if (n == 0) return UKFB_OK;
+    HIP_TRY(hipMemcpyAsync(dst_dev, src, n * sizeof(P), hipMemcpyHostToDevice, ukfb::main_stream(e)));
+    ENGINE_SYNC(e);
+    return UKFB_OK;
+}
+
+template <class P> int download_raw(ukfb_engine* e, const P* src_dev, P* dst, size_t n) {
+    if (n == 0) return UKFB_OK;
+    HIP_TRY(hipMemcpyAsync(dst, src_dev, n * sizeof(P), hipMemcpyDeviceToHost, ukfb::main_stream(e)));
+    ENGINE_SYNC(e);
+    return UKFB_OK;
+}
+
+int launch(ukfb_engine* e, const ukfb::LaunchReq& r);
+int build_model_buckets(ukfb_engine* e, const int32_t* meas_dev, int64_t* items);
+int rebuild_racc(ukfb_engine* e);
 
 // mount and point of a sensor-frame form (ukfb_sensor_in, ukfb_associate_in): r = 0, qs the identity and b = 0, unless the
 // caller says otherwise
@@ -51,16 +114,13 @@ inline void set_mount_point_uniform(In* in, const double* mount_uniform, const d
 // and noted for finish(), which downloads the outputs in the order they were described and drains the stream.  A NULL host
 // pointer gives a NULL device pointer and allocates nothing.  The first failure is latched (rc()): every later method then
 // does nothing and returns NULL, so a form asks once before its device call and once through finish().  Everything is freed
-// when the stage goes out of scope, on every path (hipFree waits for the device).  The copies go through the host in engine
-// precision: the host-array forms are a convenience, not a hot path.
+// when the stage goes out of scope, on every path (hipFree waits for the device).  The scalars cross with upload / download,
+// as every other host array of the engine does.
 class HostStage {
 public:
     explicit HostStage(ukfb_engine* e) : e_(e) {}
     HostStage(const HostStage&) = delete;
     HostStage& operator=(const HostStage&) = delete;
-    ~HostStage() {
-        for (void* p : bufs_) (void)hipFree(p);
-    }
 
     int rc() const { return rc_; }
 
@@ -91,12 +151,12 @@ public:
         if (rc_) return rc_;
         for (const Download& j : downloads_) {
             if (j.D < 0) {
-                UKFB_HIP_TRY(hipMemcpyAsync(j.host, j.dev, j.n, hipMemcpyDeviceToHost, main_stream(e_)));
+                HIP_TRY(hipMemcpyAsync(j.host, j.dev, j.n, hipMemcpyDeviceToHost, main_stream(e_)));
             } else if (j.D == 0) {
-                if (const int rc = download_scalars(j.dev, static_cast<double*>(j.host), j.n)) return rc;
+                if (const int rc = download(e_, j.dev, 0, static_cast<double*>(j.host), j.n)) return rc;
             } else {
                 std::vector<double> packed(j.n * size_t(e_->PK));
-                if (const int rc = download_scalars(j.dev, packed.data(), packed.size())) return rc;
+                if (const int rc = download(e_, j.dev, 0, packed.data(), packed.size())) return rc;
                 unpack_symmetric(packed.data(), j.n, j.D, static_cast<double*>(j.host));
             }
         }
@@ -113,22 +173,22 @@ private:
 
     void* take(size_t bytes) {   // (a zero-sized array still gets a buffer: the device forms refuse NULL for a required one)
         if (rc_) return nullptr;
-        void* p = nullptr;
-        rc_ = alloc(&p, bytes ? bytes : 1);
+        DevTmp buf;
+        rc_ = alloc(&buf.p, bytes ? bytes : 1);
         if (rc_) return nullptr;
-        bufs_.push_back(p);
-        return p;
+        bufs_.push_back(std::move(buf));
+        return bufs_.back().p;
     }
     int alloc(void** p, size_t bytes) {
-        UKFB_HIP_TRY(hipMalloc(p, bytes));
+        HIP_TRY(hipMalloc(p, bytes));
         return UKFB_OK;
     }
     int copy_in(void* dst, const void* src, size_t bytes) {
-        UKFB_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, main_stream(e_)));
+        HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, main_stream(e_)));
         return UKFB_OK;
     }
     int zero(void* dst, size_t bytes) {
-        UKFB_HIP_TRY(hipMemsetAsync(dst, 0, bytes, main_stream(e_)));
+        HIP_TRY(hipMemsetAsync(dst, 0, bytes, main_stream(e_)));
         return UKFB_OK;
     }
 
@@ -141,9 +201,9 @@ private:
         if (src && D) {
             std::vector<double> packed(n);
             pack_lower(src, count, D, packed.data());
-            rc_ = upload_scalars(d, packed.data(), n);
+            rc_ = upload(e_, d, 0, packed.data(), n);
         } else if (src) {
-            rc_ = upload_scalars(d, src, n);
+            rc_ = upload(e_, d, 0, src, n);
         }
         if (zeroed && !rc_) rc_ = zero(d, n * e_->tsize);
         if (rc_) return nullptr;
@@ -151,31 +211,9 @@ private:
         return d;
     }
 
-    int upload_scalars(void* dst, const double* src, size_t n) {
-        if (e_->prec == UKFB_F64) {
-            UKFB_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyHostToDevice, main_stream(e_)));
-            return ukfb_sync(e_);
-        }
-        std::vector<float> tmp(n);
-        for (size_t i = 0; i < n; ++i) tmp[i] = float(src[i]);
-        UKFB_HIP_TRY(hipMemcpyAsync(dst, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice, main_stream(e_)));
-        return ukfb_sync(e_);
-    }
-    int download_scalars(const void* src, double* dst, size_t n) {
-        if (e_->prec == UKFB_F64) {
-            UKFB_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToHost, main_stream(e_)));
-            return ukfb_sync(e_);
-        }
-        std::vector<float> tmp(n);
-        UKFB_HIP_TRY(hipMemcpyAsync(tmp.data(), src, n * sizeof(float), hipMemcpyDeviceToHost, main_stream(e_)));
-        if (const int rc = ukfb_sync(e_)) return rc;
-        for (size_t i = 0; i < n; ++i) dst[i] = double(tmp[i]);
-        return UKFB_OK;
-    }
-
     ukfb_engine* e_;
     int rc_ = UKFB_OK;
-    std::vector<void*> bufs_;
+    std::vector<DevTmp> bufs_;
     std::vector<Download> downloads_;
 };
 

@@ -8,8 +8,7 @@ extern "C" {
 int ukfb_associate_sensor_dev(ukfb_engine* e, int model_uniform, const ukfb_associate_in* in, int commit, const ukfb_associate_out* out) {
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_associate_args(e->model, in && in->model_dev, model_uniform, in, commit, out))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::AssociateReq r;
     r.model_uniform = model_uniform;
     r.in = *in;
@@ -35,8 +34,7 @@ int ukfb_associate_sensor(ukfb_engine* e, int model, const int32_t* model_per_fi
     ukfb::set_mount_point_uniform(&in, mount_uniform, point_uniform);
     const ukfb_associate_out wanted{z_pred, S, innov, maha, loglik, best, n_gated, status};
     if (const int rc = ukfb::fail(ukfb::check_associate_args(e->model, model_per_filter != nullptr, model, &in, commit, &wanted))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const int K = candidates, H = ukfb::associate_hypotheses(candidates, point_per_candidate);
     const size_t n = size_t(e->cap);
     const size_t nz = size_t(ukfb::associate_out_scalars(K, e->cap, 3)), nk = size_t(ukfb::associate_out_scalars(K, e->cap, 1));

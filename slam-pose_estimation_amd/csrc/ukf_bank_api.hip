@@ -23,8 +23,7 @@ int ukfb_bank_weights_dev(ukfb_engine* e, int hypotheses, const void* logw_in_de
                           void* w_out_dev, uint32_t* status_dev) {
     if (const int rc = entry(e, hypotheses)) return rc;
     if (!logw_out_dev) return ukfb::fail({UKFB_ERR_INVALID_ARG, "logw_out must not be NULL"});
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::BankWeightsReq r;
     r.hypotheses = hypotheses;
     r.logw_in_dev = logw_in_dev;
@@ -39,8 +38,7 @@ int ukfb_bank_combine_dev(ukfb_engine* e, int hypotheses, const void* w_dev, voi
                           uint32_t* status_dev) {
     if (const int rc = entry(e, hypotheses)) return rc;
     if (!w_dev || !mu_out_dev) return ukfb::fail({UKFB_ERR_INVALID_ARG, "w and mu_out must not be NULL"});
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::BankReq r;
     r.hypotheses = hypotheses;
     r.w_dev = w_dev;
@@ -55,8 +53,7 @@ int ukfb_bank_mix_dev(ukfb_engine* e, int hypotheses, const void* w_dev, const d
     if (const int rc = entry(e, hypotheses)) return rc;
     if (!w_dev || !w_pred_out_dev) return ukfb::fail({UKFB_ERR_INVALID_ARG, "w and w_pred_out must not be NULL"});
     if (const int rc = ukfb::fail(ukfb::check_bank_transition(transition, hypotheses))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::BankReq r;
     r.hypotheses = hypotheses;
     r.mix = true;
@@ -70,8 +67,7 @@ int ukfb_bank_mix_dev(ukfb_engine* e, int hypotheses, const void* w_dev, const d
 int ukfb_bank_combine(ukfb_engine* e, int hypotheses, const double* w, double* mu, double* cov, uint32_t* status) {
     if (const int rc = entry(e, hypotheses)) return rc;
     if (!w || !mu) return ukfb::fail({UKFB_ERR_INVALID_ARG, "w and mu must not be NULL"});
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t n = size_t(e->cap), tracks = n / size_t(hypotheses);
     ukfb::HostStage stage(e);
     const void* w_d = stage.in(w, n);
@@ -87,8 +83,7 @@ int ukfb_bank_mix(ukfb_engine* e, int hypotheses, const double* w, const double*
     if (const int rc = entry(e, hypotheses)) return rc;
     if (!w || !w_pred) return ukfb::fail({UKFB_ERR_INVALID_ARG, "w and w_pred must not be NULL"});
     if (const int rc = ukfb::fail(ukfb::check_bank_transition(transition, hypotheses))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t n = size_t(e->cap), tracks = n / size_t(hypotheses);
     ukfb::HostStage stage(e);
     const void* w_d = stage.in(w, n);

@@ -8,8 +8,7 @@ extern "C" {
 int ukfb_update_bearing_dev(ukfb_engine* e, int model_uniform, const ukfb_sensor_in* in, int commit, const ukfb_sensor_out* out) {
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_bearing_args(e->model, in && in->model_dev, model_uniform, in, commit, out))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::BearingReq r;
     r.model_uniform = model_uniform;
     r.in = *in;
@@ -33,8 +32,7 @@ int ukfb_update_bearing(ukfb_engine* e, int model, const int32_t* model_per_filt
     ukfb::set_mount_point_uniform(&in, mount_uniform, point_uniform);
     const ukfb_sensor_out wanted{z_pred, S, innov, maha, loglik, status};
     if (const int rc = ukfb::fail(ukfb::check_bearing_args(e->model, model_per_filter != nullptr, model, &in, commit, &wanted))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t n = size_t(e->cap);
     ukfb::HostStage stage(e);
     in.model_dev = stage.raw_in(model_per_filter, n);

@@ -8,8 +8,7 @@ extern "C" {
 int ukfb_condition_dev(ukfb_engine* e, const ukfb_condition_in* in, int commit, const ukfb_condition_out* out) {
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_condition_args(in, commit, out))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::ConditionReq r;
     r.in = *in;
     r.commit = commit != 0;
@@ -29,8 +28,7 @@ int ukfb_condition(ukfb_engine* e, const double* var_floor, double eig_floor, co
     const ukfb_condition_out wanted{eig_min, eig_max, mu, cov, status};
     if (const int rc = ukfb::fail(ukfb::check_condition_args(&in, commit, &wanted))) return rc;
     if (const int rc = ukfb::fail(ukfb::check_condition_floor(var_floor, e->D))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t n = size_t(e->cap);
     ukfb::HostStage stage(e);
     in.var_floor_dev = stage.in(var_floor, size_t(e->D));

@@ -26,8 +26,7 @@ extern "C" {
 int ukfb_update_delayed_dev(ukfb_engine* e, const ukfb_delayed_in* in, int commit, const ukfb_delayed_out* out) {
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_delayed_args(in, commit, out))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::DelayedReq r;
     r.in = *in;   // (in->dt is copied into the kernel arguments: nothing of the caller's is read after the call returns)
     r.commit = commit != 0;
@@ -39,8 +38,7 @@ int ukfb_delayed_lag_dev(ukfb_engine* e, int steps, const int64_t* step_ts_us, c
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_delayed_lag_args(steps, step_ts_us, sample_ts_us_dev != nullptr, lag_out_dev != nullptr)))
         return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     if (e->cap == 0) return UKFB_OK;
     ukfb::DelayedLagArgs a{};
     a.n = e->cap;
@@ -72,8 +70,7 @@ int ukfb_update_delayed(ukfb_engine* e, int steps, const double* dt, const doubl
     in.Q_dev = Q;
     const ukfb_delayed_out wanted{z_pred, S, innov, maha, loglik, status, mu_out, cov_out};
     if (const int rc = ukfb::fail(ukfb::check_delayed_args(&in, commit, &wanted))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t n = size_t(e->cap), SS = size_t(e->S), recs = size_t(steps) * n;
     ukfb::HostStage stage(e);
     in.mu_hist_dev = stage.in(mu_hist, recs * SS);

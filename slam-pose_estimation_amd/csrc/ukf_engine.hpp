@@ -1,5 +1,5 @@
 // ukf_engine.hpp -- host-side state of one batched UKF engine and the launch request that the
-// C-ABI (ukf_batch.hip) hands to the per-(precision, model) translation units.
+// C-ABI (ukfb::launch, ukf_runtime.hip) hands to the per-(precision, model) translation units.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -12,8 +12,7 @@ int ukfb_forecast_dev(ukfb_engine* e, int steps, const double* dt, const int64_t
     if (const int rc = ukfb::fail(ukfb::check_forecast_args(steps, slots, first_slot, dt != nullptr, ts_us != nullptr, start_mu_dev != nullptr,
                                                             start_cov_dev != nullptr, mu_out_dev != nullptr)))
         return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::ForecastReq r;
     r.steps = steps;
     r.slots = slots;
@@ -36,8 +35,7 @@ int ukfb_forecast(ukfb_engine* e, int steps, const double* dt, const int64_t* ts
     if (const int rc = ukfb::fail(ukfb::check_forecast_args(steps, steps, 0, dt != nullptr, ts_us != nullptr, start_mu != nullptr,
                                                             start_cov != nullptr, mu != nullptr)))
         return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t n = size_t(e->cap), S = size_t(e->S), recs = size_t(steps) * n;
     ukfb::HostStage stage(e);
     const void* smu_d = stage.in(start_mu, n * S);

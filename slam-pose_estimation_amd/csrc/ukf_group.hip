@@ -19,7 +19,7 @@
 
 #include <rccl/rccl.h>
 
-#include "ukf_engine.hpp"
+#include "ukf_api_common.hpp"
 
 namespace {
 
@@ -77,10 +77,7 @@ struct ukfb_group {
 
 namespace {
 
-int gfail(int code, const std::string& msg) {
-    ukfb::set_error_text(msg);   // one error channel: ukfb_last_error()
-    return code;
-}
+int gfail(int code, const std::string& msg) { return ukfb::fail(code, msg.c_str()); }   // one error channel: ukfb_last_error()
 
 // call(shard) -> rc on every shard in turn; the first failure ends it (the engine has left its text in ukfb_last_error())
 template <class F> int each_shard(ukfb_group* g, F&& call) {

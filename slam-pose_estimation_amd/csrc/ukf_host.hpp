@@ -7,7 +7,10 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <cstdlib>
+#include <thread>
 #include <vector>
 
 #include "../../include/ukf_batch.h"
@@ -768,6 +771,40 @@ constexpr DelayedMap delayed_map(int S, int D) {
 constexpr int delayed_filter_scalars(int S, int D) { return S > 16 ? -1 : delayed_map(S, D).PF; }
 inline RowGeometry delayed_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(delayed_filter_scalars(S, D), capacity, compute_size); }
 
+// ---- bounded waits ----------------------------------------------------------------------------------------------------------
+// Waiting by polling: hipEventSynchronize / hipStreamSynchronize sleep on an interrupt and were measured to
+// wake up to ~55 ms late on a loaded host (1 run in 5), which is longer than the work being waited for.
+// The wait is bounded: after a short spin the poll backs off to 50 us sleeps, and gives up
+// after UKFB_WAIT_TIMEOUT_S seconds (default 120) so that a kernel that never finishes cannot pin a host core
+// forever; the caller reports UKFB_ERR_HIP with "timed out".
+constexpr int WAIT_SPINS = 20000;
+constexpr double WAIT_TIMEOUT_DEFAULT_S = 120.0;
+// the value of UKFB_WAIT_TIMEOUT_S (NULL: unset); anything that is not a positive number is the default
+inline double wait_timeout_seconds(const char* s) {
+    const double v = s ? std::atof(s) : 0.0;
+    return v > 0.0 ? v : WAIT_TIMEOUT_DEFAULT_S;
+}
+template <class R> struct Waited {
+    R result;       // the query's last answer: its ready value, or an error (returned at once)
+    bool gave_up;   // still `not_ready` when the timeout ran out
+};
+template <class Query, class R> Waited<R> wait_polling(Query&& query, R not_ready, int spins, double timeout_s) {
+    R r;
+    for (int spin = 0; spin < spins; ++spin)
+        if ((r = query()) != not_ready) return {r, false};
+    const auto t0 = std::chrono::steady_clock::now();
+    while ((r = query()) == not_ready) {
+        std::this_thread::sleep_for(std::chrono::microseconds(50));
+        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_s) return {r, true};
+    }
+    return {r, false};
+}
+
+// ---- host doubles <-> engine precision ------------------------------------------------------------------------------------
+// fp32 engines: arrays of at least this many scalars cross PCIe as doubles and are narrowed / widened on the device, smaller
+// ones in a host loop (upload / download, ukf_runtime.hip)
+constexpr size_t DEVICE_CONVERT_MIN = 16384;
+
 // ---- packed covariances of the host-array forms ---------------------------------------------------------------------------
 // `count` row-major D x D matrices <-> their lower triangles, row by row (entry (r, c), c <= r, at r (r + 1) / 2 + c of D (D + 1) / 2).
 // pack_lower reads the lower triangle only; unpack_symmetric writes both triangles.
@@ -809,7 +846,7 @@ struct CyclePlan {
 };
 
 // ---- workspace sizing ---------------------------------------------------------------------------------------------------
-// model-class buckets (ukf_batch.hip): blocks of BK_BLOCK filters for the count and scatter kernels
+// model-class buckets (ukf_buckets.hip): blocks of BK_BLOCK filters for the count and scatter kernels
 constexpr int BK_THREADS = 256, BK_PER_THREAD = 4, BK_BLOCK = BK_THREADS * BK_PER_THREAD;
 constexpr int BUCKET_INLINE_BLOCKS = 2048;   // up to 2 M filters: every scatter block sums 3 x 2048 counts at most
 constexpr int64_t BUCKET_MIN_FILTERS = 16384;

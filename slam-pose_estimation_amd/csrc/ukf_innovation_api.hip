@@ -13,8 +13,7 @@ int ukfb_innovation_dev(ukfb_engine* e, int meas_model_uniform, const int32_t* m
                                                               z_dev != nullptr, Q_dev != nullptr, out)))
         return rc;
     if (const int rc = ukfb::refuse_poisoned(e)) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::InnovReq r;
     r.meas_uniform = meas_model_uniform;
     r.meas_dev = meas_model_dev;
@@ -33,8 +32,7 @@ int ukfb_select_candidates_dev(ukfb_engine* e, int candidates, const int32_t* be
                                                           best_dev != nullptr, z_dev != nullptr, z_sel_dev != nullptr)))
         return rc;
     if (const int rc = ukfb::refuse_poisoned(e)) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     if (e->cap == 0) return UKFB_OK;
     const dim3 gd((unsigned)((e->cap + 255) / 256)), bd(256);
     if (e->prec == UKFB_F64)
@@ -45,7 +43,7 @@ int ukfb_select_candidates_dev(ukfb_engine* e, int candidates, const int32_t* be
         hipLaunchKernelGGL(ukfb::select_candidates_kernel<float>, gd, bd, 0, ukfb::main_stream(e), e->cap, candidates, best_dev,
                            meas_model_uniform, meas_model_dev, static_cast<const float*>(z_dev), static_cast<float*>(z_sel_dev),
                            meas_model_sel_dev);
-    UKFB_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return UKFB_OK;
 }
 
@@ -57,8 +55,7 @@ int ukfb_innovation(ukfb_engine* e, int meas_model, int candidates, const double
     asked.best = best; asked.status = status;
     if (const int rc = ukfb::fail(ukfb::check_innovation_args(e->model, false, meas_model, candidates, z != nullptr, Q != nullptr, &asked)))
         return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t n = size_t(e->cap), K = size_t(candidates);
     ukfb::HostStage stage(e);
     const void* z_d = stage.in(z, K * n * 3);

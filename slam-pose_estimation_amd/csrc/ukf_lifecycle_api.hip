@@ -33,7 +33,7 @@ int workspace(ukfb_engine* e, ukfb::LifecycleWorkspace* ws) {
     const ukfb::LifecycleGeometry geo = ukfb::lifecycle_geometry(e->cap, 1);
     if (!e->lifecycle_ws) {
         void* p = nullptr;
-        UKFB_HIP_TRY(hipMalloc(&p, geo.ws_words * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&p, geo.ws_words * sizeof(uint32_t)));
         const hipError_t err = hipMemsetAsync(static_cast<uint32_t*>(p) + geo.owner_off, 0xff, size_t(e->cap) * sizeof(uint32_t), ukfb::main_stream(e));
         if (err != hipSuccess) {
             (void)hipFree(p);
@@ -60,8 +60,7 @@ int ukfb_gather_filters_dev(ukfb_engine* e, int64_t n, const int32_t* index_dev,
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_lifecycle_args(e->cap, n, out != nullptr, false, false, false, false, e->Rn_per_filter))) return rc;
     if (n == 0) return UKFB_OK;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::LifecycleWorkspace ws;   // (gather needs none of it; the first lifecycle call of an engine creates it whichever it is)
     if (const int rc = workspace(e, &ws)) return rc;
     const dim3 grid(unsigned(ukfb::lifecycle_record_blocks(n))), block(ukfb::LC_THREADS);
@@ -78,8 +77,7 @@ int ukfb_scatter_filters_dev(ukfb_engine* e, int64_t n, const int32_t* index_dev
                                                              e->Rn_per_filter)))
         return rc;
     if (n == 0) return UKFB_OK;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::LifecycleWorkspace ws;
     if (const int rc = workspace(e, &ws)) return rc;
     hipStream_t s = ukfb::main_stream(e);
@@ -96,8 +94,7 @@ int ukfb_scatter_filters_dev(ukfb_engine* e, int64_t n, const int32_t* index_dev
 int ukfb_retire_dev(ukfb_engine* e, const uint8_t* retire_mask_dev) {
     if (const int rc = ukfb::entry(e)) return rc;
     if (!retire_mask_dev) return ukfb::fail({UKFB_ERR_INVALID_ARG, "retire_mask_dev must not be NULL"});
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::LifecycleWorkspace ws;
     if (const int rc = workspace(e, &ws)) return rc;
     hipLaunchKernelGGL(ukfb::ukf_lifecycle_retire_kernel, dim3(unsigned(ukfb::lifecycle_item_blocks(e->cap))), dim3(ukfb::LC_THREADS), 0, ukfb::main_stream(e),
@@ -108,8 +105,7 @@ int ukfb_retire_dev(ukfb_engine* e, const uint8_t* retire_mask_dev) {
 int ukfb_compact_dev(ukfb_engine* e, int group, int32_t* new_index_dev, int32_t* old_index_dev, int64_t* live_dev) {
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_compact_args(e->cap, group))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::LifecycleWorkspace ws;
     if (const int rc = workspace(e, &ws)) return rc;
     const ukfb::LifecycleGeometry geo = ukfb::lifecycle_geometry(e->cap, group);
@@ -135,8 +131,7 @@ int ukfb_gather_filters(ukfb_engine* e, int64_t n, const int32_t* index, double*
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_lifecycle_args(e->cap, n, true, false, false, false, false, e->Rn_per_filter))) return rc;
     if (n == 0) return UKFB_OK;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t m = size_t(n);
     ukfb::HostStage stage(e);
     const int32_t* idx_d = stage.raw_in(index, m);
@@ -155,8 +150,7 @@ int ukfb_scatter_filters(ukfb_engine* e, int64_t n, const int32_t* index, const 
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_lifecycle_args(e->cap, n, true, true, mu != nullptr, cov != nullptr, false, e->Rn_per_filter))) return rc;
     if (n == 0) return UKFB_OK;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t m = size_t(n);
     ukfb::HostStage stage(e);
     const int32_t* idx_d = stage.raw_in(index, m);
@@ -174,8 +168,7 @@ int ukfb_scatter_filters(ukfb_engine* e, int64_t n, const int32_t* index, const 
 int ukfb_compact(ukfb_engine* e, int group, int32_t* new_index, int32_t* old_index, int64_t* live) {
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_compact_args(e->cap, group))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t n = size_t(e->cap);
     ukfb::HostStage stage(e);
     int32_t* new_d = stage.raw_out(new_index, n);

@@ -8,8 +8,7 @@ extern "C" {
 int ukfb_predict_sampled_dev(ukfb_engine* e, const ukfb_predict_sampled_in* in, int commit, const ukfb_predict_sampled_out* out) {
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_predict_sampled_args(in, commit, out))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::PredictSampledReq r;
     r.in = *in;
     r.commit = commit != 0;
@@ -28,8 +27,7 @@ int ukfb_predict_sampled(ukfb_engine* e, const double* XX, const double* R, int 
     in.active_dev = active;
     const ukfb_predict_sampled_out wanted{mu, cov, status};
     if (const int rc = ukfb::fail(ukfb::check_predict_sampled_args(&in, commit, &wanted))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t n = size_t(e->cap), S = size_t(e->S), D = size_t(e->D), pts = size_t(ukfb::sampled_points(e->D));
     ukfb::HostStage stage(e);
     in.XX_dev = stage.in(XX, n * pts * S);

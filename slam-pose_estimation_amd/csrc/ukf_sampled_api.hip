@@ -8,8 +8,7 @@ extern "C" {
 int ukfb_sigma_points_dev(ukfb_engine* e, void* X_out_dev, void* delta_out_dev, uint32_t* status_dev) {
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_sigma_points_args(X_out_dev != nullptr, delta_out_dev != nullptr))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::SigmaPointsReq r;
     r.X = X_out_dev;
     r.delta = delta_out_dev;
@@ -20,8 +19,7 @@ int ukfb_sigma_points_dev(ukfb_engine* e, void* X_out_dev, void* delta_out_dev, 
 int ukfb_update_sampled_dev(ukfb_engine* e, const ukfb_sampled_in* in, int commit, const ukfb_sampled_out* out) {
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_sampled_args(in, commit, out))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::SampledReq r;
     r.in = *in;
     r.commit = commit != 0;
@@ -32,8 +30,7 @@ int ukfb_update_sampled_dev(ukfb_engine* e, const ukfb_sampled_in* in, int commi
 int ukfb_sigma_points(ukfb_engine* e, double* X, double* delta, uint32_t* status) {
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_sigma_points_args(X != nullptr, delta != nullptr))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t n = size_t(e->cap), pts = size_t(ukfb::sampled_points(e->D));
     ukfb::HostStage stage(e);
     void* x_d = stage.out(X, n * pts * size_t(e->S));
@@ -58,8 +55,7 @@ int ukfb_update_sampled(ukfb_engine* e, int m, const double* Z, const double* z,
     in.active_dev = active;
     const ukfb_sampled_out wanted{z_pred, S, innov, maha, loglik, status};
     if (const int rc = ukfb::fail(ukfb::check_sampled_args(&in, commit, &wanted))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t n = size_t(e->cap), mz = size_t(m), pts = size_t(ukfb::sampled_points(e->D));
     ukfb::HostStage stage(e);
     in.Z_dev = stage.in(Z, n * pts * mz);

@@ -11,7 +11,7 @@ namespace {
 int ensure_chain_workspace(ukfb_engine* e) {
     if (e->smooth_chain) return UKFB_OK;
     const size_t bytes = size_t(e->cap) * size_t(e->PK) * e->tsize;
-    UKFB_HIP_TRY(hipMalloc(&e->smooth_chain, bytes ? bytes : 1));
+    HIP_TRY(hipMalloc(&e->smooth_chain, bytes ? bytes : 1));
     return UKFB_OK;
 }
 
@@ -22,14 +22,13 @@ extern "C" {
 int ukfb_history_push_dev(ukfb_engine* e, int slots, int slot, void* mu_hist_dev, void* cov_hist_dev) {
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_history_args(slots, slot, mu_hist_dev != nullptr, cov_hist_dev != nullptr))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t mu_bytes = size_t(e->cap) * size_t(e->S) * e->tsize, cov_bytes = size_t(e->cap) * size_t(e->PK) * e->tsize;
     if (e->cap == 0) return UKFB_OK;
     if (const int rc = ensure_chain_workspace(e)) return rc;   // (the first push of an engine: ukfb_smooth_dev then never allocates)
     hipStream_t s = ukfb::main_stream(e);   // joins the second half of a split launch first
-    UKFB_HIP_TRY(hipMemcpyAsync(static_cast<char*>(mu_hist_dev) + size_t(slot) * mu_bytes, e->mu, mu_bytes, hipMemcpyDeviceToDevice, s));
-    UKFB_HIP_TRY(hipMemcpyAsync(static_cast<char*>(cov_hist_dev) + size_t(slot) * cov_bytes, e->cov, cov_bytes, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(static_cast<char*>(mu_hist_dev) + size_t(slot) * mu_bytes, e->mu, mu_bytes, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(static_cast<char*>(cov_hist_dev) + size_t(slot) * cov_bytes, e->cov, cov_bytes, hipMemcpyDeviceToDevice, s));
     return UKFB_OK;
 }
 
@@ -40,8 +39,7 @@ int ukfb_smooth_dev(ukfb_engine* e, int steps, const double* dt, int slots, int 
     if (const int rc = ukfb::fail(ukfb::check_smooth_args(steps, slots, first_slot, dt != nullptr, mu_hist_dev != nullptr,
                                                           cov_hist_dev != nullptr, mu_out_dev != nullptr)))
         return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const ukfb::SmoothPlan plan(steps, slots, first_slot);
     const size_t cov_rec = size_t(e->cap) * size_t(e->PK) * e->tsize;
     // without a covariance output the chain's covariance crosses a launch boundary through the engine's workspace
@@ -72,8 +70,7 @@ int ukfb_smooth(ukfb_engine* e, int steps, const double* dt, double* mu, double*
                 uint32_t* status) {
     if (const int rc = ukfb::entry(e)) return rc;
     if (const int rc = ukfb::fail(ukfb::check_smooth_args(steps, steps, 0, dt != nullptr, mu != nullptr, cov != nullptr, mu != nullptr))) return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t n = size_t(e->cap), recs = size_t(steps) * n;
     ukfb::HostStage stage(e);
     void* mu_d = stage.inout(mu, recs * size_t(e->S));

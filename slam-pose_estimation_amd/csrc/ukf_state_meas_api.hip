@@ -14,8 +14,7 @@ int ukfb_update_state_dev(ukfb_engine* e, uint32_t block_mask_uniform, const int
     if (const int rc = ukfb::fail(ukfb::check_state_meas_args(e->model, block_mask_dev != nullptr, block_mask_uniform, z_dev != nullptr,
                                                               Qz_packed_dev != nullptr, state_inflation, meas_inflation, commit, out)))
         return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     ukfb::StateMeasReq r;
     r.mask_uniform = block_mask_uniform;
     r.mask_dev = block_mask_dev;
@@ -36,8 +35,7 @@ int ukfb_update_state(ukfb_engine* e, uint32_t block_mask, const int32_t* block_
     if (const int rc = ukfb::fail(ukfb::check_state_meas_args(e->model, block_mask_per_filter != nullptr, block_mask, z != nullptr,
                                                               Qz != nullptr, state_inflation, meas_inflation, commit, &wanted)))
         return rc;
-    ukfb::DeviceScope scope(e->device);
-    UKFB_HIP_TRY(scope.err);
+    ON_DEVICE(e->device);
     const size_t n = size_t(e->cap);
     ukfb::HostStage stage(e);
     const int32_t* mask_d = stage.raw_in(block_mask_per_filter, n);

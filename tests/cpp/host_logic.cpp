@@ -1,6 +1,7 @@
 // host_logic.cpp -- the engine's host decisions (slam-pose_estimation_amd/csrc/ukf_host.hpp) on the CPU, built with g++ under
 // ASan / UBSan (make host_asan; run by tests/test_host_logic.py).  Argument: a file of process-noise cases written by that test
 // from synth.py, one per line: name model D expected(0/1) then D*D values.  Prints one line per failed check, exits 1 if any.
+#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -494,6 +495,53 @@ void kernel_levels() {
     p.gate = true;
     CHECK(ukfb::kernel_level(UKFB_MODEL_POSE, p) == 0, "gate on");
 }
+
+// ---- bounded waits: the polling loop against scripted queries, and the UKFB_WAIT_TIMEOUT_S parser -----------------------------
+void waits() {
+    enum Answer { READY = 0, NOT_READY = 7, BROKEN = 3 };
+    int queries = 0;
+    // ready_at: the number of the first query (from 1) that no longer answers NOT_READY; 0: never
+    auto scripted = [&queries](int ready_at, Answer then) {
+        queries = 0;
+        return [&queries, ready_at, then] { return ++queries >= ready_at && ready_at > 0 ? then : NOT_READY; };
+    };
+    {
+        const ukfb::Waited<Answer> w = ukfb::wait_polling(scripted(1, READY), NOT_READY, 100, 5.0);
+        CHECK(!w.gave_up && w.result == READY && queries == 1, "ready at the first poll: gave_up %d result %d queries %d", w.gave_up,
+              w.result, queries);
+    }
+    for (int k : {1, 7, 99}) {   // ready after k polls inside the spin: exactly k + 1 queries
+        const ukfb::Waited<Answer> w = ukfb::wait_polling(scripted(k + 1, READY), NOT_READY, 100, 5.0);
+        CHECK(!w.gave_up && w.result == READY && queries == k + 1, "k %d: gave_up %d result %d queries %d", k, w.gave_up, w.result,
+              queries);
+    }
+    {   // ready only after the spin phase has ended (10 spins, then the sleeping polls)
+        const ukfb::Waited<Answer> w = ukfb::wait_polling(scripted(25, READY), NOT_READY, 10, 5.0);
+        CHECK(!w.gave_up && w.result == READY && queries == 25, "past the spin: gave_up %d result %d queries %d", w.gave_up, w.result,
+              queries);
+    }
+    {   // an error is returned at once, in the spin and past it
+        const ukfb::Waited<Answer> w = ukfb::wait_polling(scripted(1, BROKEN), NOT_READY, 100, 5.0);
+        CHECK(!w.gave_up && w.result == BROKEN && queries == 1, "error: gave_up %d result %d queries %d", w.gave_up, w.result, queries);
+        const ukfb::Waited<Answer> v = ukfb::wait_polling(scripted(12, BROKEN), NOT_READY, 10, 5.0);
+        CHECK(!v.gave_up && v.result == BROKEN && queries == 12, "late error: gave_up %d result %d queries %d", v.gave_up, v.result,
+              queries);
+    }
+    {   // never ready: gives up, no sooner than the timeout and no later than the timeout plus 1 s
+        const double timeout = 0.05;
+        const auto t0 = std::chrono::steady_clock::now();
+        const ukfb::Waited<Answer> w = ukfb::wait_polling(scripted(0, READY), NOT_READY, 100, timeout);
+        const double took = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        CHECK(w.gave_up && w.result == NOT_READY, "never ready: gave_up %d result %d", w.gave_up, w.result);
+        CHECK(took >= timeout && took <= timeout + 1.0, "never ready: took %.4f s", took);
+        CHECK(queries > 100, "never ready: %d queries", queries);
+    }
+    CHECK(ukfb::wait_timeout_seconds(nullptr) == 120.0, "unset");
+    CHECK(ukfb::wait_timeout_seconds("0") == 120.0, "0");
+    CHECK(ukfb::wait_timeout_seconds("-3") == 120.0, "-3");
+    CHECK(ukfb::wait_timeout_seconds("abc") == 120.0, "abc");
+    CHECK(ukfb::wait_timeout_seconds("7.5") == 7.5, "7.5");
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -508,6 +556,7 @@ int main(int argc, char** argv) {
     models();
     packing();
     kernel_levels();
+    waits();
     std::printf("%s: %d failure(s)\n", failures ? "FAILED" : "OK", failures);
     return failures ? 1 : 0;
 }

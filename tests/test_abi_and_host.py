@@ -197,3 +197,23 @@ def test_group_entry_points_without_a_gpu(spe):
         with pytest.raises(spe.UkfbError) as ei:
             spe.UKFGroup(spe.MODEL_POSE, spe.F64, 64, [0, 0])
         assert "no usable HIP device" in str(ei.value)
+
+
+def test_last_error_is_one_channel_across_translation_units(spe):
+    """ukfb_last_error() lives in one translation unit and the entry points that write its text in others: the text of an
+    argument error comes back whichever file raised it (no GPU needed, nothing is launched)."""
+    import ctypes as C
+    import torch
+    lib = spe.load_library()
+    out = C.c_void_p(None)
+    rc = lib.ukfb_create(C.byref(out), 7, spe.F64, C.c_int64(8), 0, None)   # no such model: refused before any device is asked
+    assert rc == 1 and not out.value
+    assert lib.ukfb_last_error() == b"ukfb_create: bad argument"
+    devs = (C.c_int * 1)(0)
+    rc = lib.ukfb_group_create(C.byref(out), spe.MODEL_POSE, spe.F64, C.c_int64(0), devs, 1)   # fewer filters than shards
+    assert rc == 1 and not out.value
+    assert lib.ukfb_last_error() == b"ukfb_group_create: need devices and at least one filter per shard"
+    if not torch.cuda.is_available():
+        rc = lib.ukfb_create(C.byref(out), spe.MODEL_POSE, spe.F64, C.c_int64(8), 0, None)
+        assert rc == 2 and not out.value
+        assert lib.ukfb_last_error() == b"ukfb_create: no usable HIP device (the engine has no CPU fallback)"

@@ -11,6 +11,10 @@ NaN row and a non-zero status cross the staging path too, every other filter is 
 full group of four filters per wavefront and a partial one; the banks: capacity 6 with 2 hypotheses; windows of 3 steps;
 sampled update m = 2; 2 candidates, the association with either point_per_candidate setting; gather / scatter: 3 of 5.
 
+Capacity N_BIG, Pose, either precision: the sensor-frame update with every output and the conditioning (a covariance output)
+once more, where the [n][9] arrays (and mean and covariance) are long enough for an fp32 engine to convert them on the device
+while the [n][3] and [n] arrays of the same call still convert on the host.
+
 Each form runs twice, for either model and either precision.
   full  every optional input is given per filter and every output is requested, through the Python wrapper.  The optional
         per-filter inputs repeat what the second run's defaults and uniform values say (ids, mount, point, lag, activity,
@@ -42,6 +46,10 @@ HYP, N_BANK = 2, 6
 STEPS, DT = 3, 0.01
 K = 2          # candidates
 M = 2          # sampled measurement dimension
+# A capacity just past the point where [n][9] arrays hold the 16 384 scalars (ukfb::DEVICE_CONVERT_MIN) from which upload / download
+# convert on the device (fp32 engines), while [n][7], [n][3] and [n] stay below: 1 822 * 9 = 16 398, 1 822 * 7 = 12 754.  Not a
+# multiple of four: the last wavefront is a partial group.
+N_BIG = 1822
 ITEMS = np.array([4, DEAD, 0], dtype=np.int32)   # gather / scatter: 3 of 5, the uninitialised filter among them
 ACC_COV = 0.01 * np.eye(3)
 ST_UNINIT = 1 << 7
@@ -115,9 +123,8 @@ class Ctx:
     def engine(self):
         spe, n = self.spe, self.n
         e = tsm.new_engine(spe, self.model, n, self.prec, 0)
-        for i in range(n):
-            if i != DEAD:
-                e.initialize(self.mu0[i:i + 1], self.cov0[i:i + 1], first=i)
+        for lo, hi in ((0, DEAD), (DEAD + 1, n)):   # every filter but DEAD
+            e.initialize(self.mu0[lo:hi], self.cov0[lo:hi], first=lo)
         if self.model == "pose":
             e.set_acceleration(self.acc, ACC_COV)
         else:
@@ -573,3 +580,22 @@ def test_host_form_is_device_form(spe, form, model, prec):
         eh.close(); ed.close()
     if same_end:
         assert_same_engines(f"{form}: bare run against full run", ends[True], ends[False])
+
+
+@pytest.mark.parametrize("prec", [0, 1], ids=["f64", "f32"])
+def test_host_form_is_device_form_across_the_conversion_threshold(spe, prec):
+    """update_sensor with every output (z, mount, point, innov, maha, loglik below the threshold; Q, S above it) and condition (its
+    covariance output staged through cov_out, above it) at capacity N_BIG: bit for bit the device form"""
+    assert N_BIG * 7 < 16384 <= N_BIG * 9 < 16384 + 2 * 9 and N_BIG % 4 != 0
+    c = ctx(spe, "pose", prec, N_BIG)
+    for name, fn in (("update_sensor", form_update_sensor), ("condition", form_condition)):
+        eh, ed = c.engine(), c.engine()
+        before = snap(eh)
+        assert_same_engines(f"{name}: twins", before, snap(ed))
+        fn(c, eh, ed, True)
+        ed.sync()
+        torch.cuda.synchronize()
+        end = snap(eh)
+        assert_same_engines(f"{name}: host against device engine", end, snap(ed))
+        assert not all(np.array_equal(x, y, equal_nan=True) for x, y in zip(before, end)), f"{name} committed nothing"
+        eh.close(); ed.close()

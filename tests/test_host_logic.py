@@ -1,6 +1,6 @@
 """The engine's host decisions on the CPU: slam-pose_estimation_amd/csrc/ukf_host.hpp (configuration checks, process-noise
 classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, workspace sizing, packed
-covariances, the kernel level of a launch) compiled with g++ under ASan / UBSan and driven by tests/cpp/host_logic.cpp."""
+covariances, the kernel level of a launch, the bounded polling wait and its timeout setting) compiled with g++ under ASan / UBSan and driven by tests/cpp/host_logic.cpp."""
 import os
 import subprocess
 

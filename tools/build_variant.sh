@@ -25,7 +25,7 @@ obj=$out/obj_$name
 mkdir -p $obj
 pids=""
 common="-O3 --offload-arch=gfx950 -std=c++17 -fPIC -fno-slp-vectorize -DUKFB_GENERIC_F64=0"
-for tu in ukf_batch ukf_group; do
+for tu in $(make -s --no-print-directory -C $src host_tus); do   # the host translation units, as the Makefile lists them
   /opt/rocm/bin/hipcc $common "$@" -c $src/$tu.hip -o $obj/$tu.o 2> $obj/$tu.remarks &
   pids="$pids $!"
 done
