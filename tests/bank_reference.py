@@ -101,3 +101,27 @@ def weights(logw_in, loglik, M=None):
         e = np.exp(d)
         s = e.sum(axis=1, keepdims=True)
         return d - np.log(s), e / s, dead
+
+
+def make_tracks(spe, onp, model, T, M, spread=0.33, seed=7):
+    """T tracks of M hypotheses: a synthetic initial state and M tangent steps of about its own sigma, the rotation part spread
+    up to `spread` rad (the prototype's construction)."""
+    man = onp.POSE if model == "pose" else onp.ORIENT
+    mu0, cov0 = (spe.synth.pose_initial if model == "pose" else spe.synth.orient_initial)(T * M)
+    rng = np.random.default_rng(seed)
+    base = mu0[::M]
+    sig = np.sqrt(np.einsum("tii->ti", cov0[::M]))
+    step = rng.standard_normal((T, M, man.D)) * sig[:, None, :]
+    ro = rot_offset(man)
+    step[:, :, ro:ro + 3] = rng.uniform(-1, 1, (T, M, 3)) * spread / np.sqrt(3.0)
+    mu = man.boxplus(base[:, None, :], step)
+    cov = cov0.reshape(T, M, man.D, man.D).copy()
+    w = rng.uniform(0.05, 1.0, (T, M))
+    w /= w.sum(axis=1, keepdims=True)
+    return man, mu, cov, w
+
+
+def transition(M, seed=11):
+    rng = np.random.default_rng(seed)
+    P = 0.6 * np.eye(M) + 0.4 * rng.uniform(0.1, 1.0, (M, M))
+    return P / P.sum(axis=1, keepdims=True)

@@ -137,7 +137,7 @@ def ref_chol(A, prec):
         return None if L is None else np.array([[float(x) for x in r] for r in L])
 
 
-def scaled(A):
+def unit_diagonal(A):
     d = 1.0 / np.sqrt(np.abs(np.diagonal(A, axis1=-2, axis2=-1)))
     return A * d[..., :, None] * d[..., None, :]
 
@@ -149,9 +149,9 @@ def lambda_min_H(A, prec):
     makes a classification harder."""
     D = A.shape[0]
     if prec == F32:
-        return float(np.linalg.eigvalsh(scaled(A))[0])
+        return float(np.linalg.eigvalsh(unit_diagonal(A))[0])
     mp = _mp()
-    est = float(np.linalg.eigvalsh(scaled(A))[0])
+    est = float(np.linalg.eigvalsh(unit_diagonal(A))[0])
     tol = 1e-2 * abs(est) + 1e-3 * margin(prec, D)
     with mp.workdps(40):
         a = _mp_rows(A)
@@ -169,7 +169,7 @@ def classify(A, prec):
     D = A.shape[0]
     m = margin(prec, D)
     if prec == F32:
-        lam = float(np.linalg.eigvalsh(scaled(A))[0])
+        lam = float(np.linalg.eigvalsh(unit_diagonal(A))[0])
         return 1 if lam >= m else (-1 if lam <= -m else 0)
     mp = _mp()
     with mp.workdps(40):
@@ -234,11 +234,11 @@ def _unit_diag_with_lmin(rng, D, kappa, target=None):
     lam = 10.0 ** (-np.log10(kappa) * np.sort(rng.uniform(0, 1, D)))
     lam[0], lam[-1] = 1.0, 1.0 / kappa
     q = _orth(rng, D)
-    H = scaled((q * lam) @ q.T)
+    H = unit_diagonal((q * lam) @ q.T)
     if target is not None:
         for _ in range(3):
             w, v = np.linalg.eigh(H)
-            H = scaled(H + (target - w[0]) * np.outer(v[:, 0], v[:, 0]))
+            H = unit_diagonal(H + (target - w[0]) * np.outer(v[:, 0], v[:, 0]))
     return H
 
 

@@ -6,15 +6,7 @@
 #include <vector>
 
 #include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
-
-static int failures = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
-            ++failures;                                                     \
-        }                                                                   \
-    } while (0)
+#include "expect.hpp"
 
 int main() {
     using namespace ukfb;
@@ -68,6 +60,5 @@ int main() {
             EXPECT(bank_track_scalars(14, 13, m) >= m * (14 + 91 + 13 + 1) + 14 + 91);
             EXPECT(bank_geometry(13, 12, m, tracks * m, 4).lds_bytes * 2 <= g.lds_bytes);
         }
-    std::printf("OK: %d failure(s)\n", failures);
-    return failures ? 1 : 0;
+    return finish();
 }

@@ -6,15 +6,7 @@
 #include <limits>
 
 #include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
-
-static int failures = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
-            ++failures;                                                     \
-        }                                                                   \
-    } while (0)
+#include "expect.hpp"
 
 int main() {
     using namespace ukfb;
@@ -120,6 +112,5 @@ int main() {
         }
     }
     EXPECT(condition_geometry(13, 12, 1022, 8).lds_bytes == 15488 && condition_geometry(14, 13, 1022, 4).lds_bytes == 8384);
-    std::printf("OK: %d failure(s)\n", failures);
-    return failures ? 1 : 0;
+    return finish();
 }

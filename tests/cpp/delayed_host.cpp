@@ -5,15 +5,7 @@
 #include <vector>
 
 #include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
-
-static int failures = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
-            ++failures;                                                     \
-        }                                                                   \
-    } while (0)
+#include "expect.hpp"
 
 // the rule as include/ukf_batch.h words it, written independently of delayed_lag_of
 static int lag_by_the_words(const std::vector<int64_t>& ts, int64_t t) {
@@ -111,6 +103,5 @@ int main() {
     for (int64_t x = -1500; x <= 6500; x += 7) EXPECT(delayed_lag_of(5, ts.data(), x) == lag_by_the_words(ts, x));
     const std::vector<int64_t> one = {1000};
     EXPECT(delayed_lag_of(1, one.data(), 1000) == 0 && delayed_lag_of(1, one.data(), 2000) == 0 && delayed_lag_of(1, one.data(), 999) == 1);
-    std::printf("OK: %d failure(s)\n", failures);
-    return failures ? 1 : 0;
+    return finish();
 }

@@ -3,15 +3,7 @@
 #include <cstdio>
 
 #include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
-
-static int failures = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
-            ++failures;                                                     \
-        }                                                                   \
-    } while (0)
+#include "expect.hpp"
 
 int main() {
     using namespace ukfb;
@@ -67,6 +59,5 @@ int main() {
     }
     EXPECT(forecast_filter_scalars(13, 12) == 660 && forecast_filter_scalars(14, 13) == 716);
     EXPECT(forecast_filter_scalars(17, 16) == -1);
-    std::printf("OK: %d failure(s)\n", failures);
-    return failures ? 1 : 0;
+    return finish();
 }

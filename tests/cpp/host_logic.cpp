@@ -10,9 +10,10 @@
 #include <vector>
 
 #include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
+#include "expect.hpp"
 
 namespace {
-int failures = 0;
+// EXPECT with a message: the shared counter of expect.hpp
 #define CHECK(cond, ...)                                                             \
     do {                                                                             \
         if (!(cond)) {                                                               \
@@ -557,6 +558,5 @@ int main(int argc, char** argv) {
     packing();
     kernel_levels();
     waits();
-    std::printf("%s: %d failure(s)\n", failures ? "FAILED" : "OK", failures);
-    return failures ? 1 : 0;
+    return finish();
 }

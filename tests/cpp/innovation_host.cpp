@@ -3,15 +3,7 @@
 #include <cstdio>
 
 #include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
-
-static int failures = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
-            ++failures;                                                     \
-        }                                                                   \
-    } while (0)
+#include "expect.hpp"
 
 int main() {
     using namespace ukfb;
@@ -50,6 +42,5 @@ int main() {
     }
     // the order of the checks: a bad candidate count is reported before a wrong model
     EXPECT(check_innovation_args(UKFB_MODEL_POSE, false, 9, 0, true, true, &only_best).rc == UKFB_ERR_INVALID_ARG);
-    std::printf("OK: %d failure(s)\n", failures);
-    return failures ? 1 : 0;
+    return finish();
 }

@@ -4,15 +4,7 @@
 #include <cstdio>
 
 #include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
-
-static int failures = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
-            ++failures;                                                     \
-        }                                                                   \
-    } while (0)
+#include "expect.hpp"
 
 int main() {
     using namespace ukfb;
@@ -84,6 +76,5 @@ int main() {
     }
     EXPECT(14 * 27 == 27 * ROW_LS);
     EXPECT(predict_sampled_geometry(13, 12, 1022, 8).lds_bytes == 20096 && predict_sampled_geometry(14, 13, 1022, 4).lds_bytes == 10944);
-    std::printf("OK: %d failure(s)\n", failures);
-    return failures ? 1 : 0;
+    return finish();
 }

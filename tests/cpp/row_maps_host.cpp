@@ -5,15 +5,7 @@
 #include <initializer_list>
 
 #include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
-
-static int failures = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
-            ++failures;                                                     \
-        }                                                                   \
-    } while (0)
+#include "expect.hpp"
 
 struct Region {
     int at, size;   // offset from the map, size as the kernel uses the region
@@ -140,6 +132,5 @@ int main() {
     EXPECT(sensor_filter_scalars(17, 16) == -1 && bearing_filter_scalars(17, 16) == -1 && sampled_filter_scalars(17, 16) == -1);
     EXPECT(sigma_points_filter_scalars(17, 16) == -1 && predict_sampled_filter_scalars(17, 16) == -1);
     EXPECT(condition_filter_scalars(17, 16) == -1 && delayed_filter_scalars(17, 16) == -1);
-    std::printf("OK: %d failure(s)\n", failures);
-    return failures ? 1 : 0;
+    return finish();
 }

@@ -4,15 +4,7 @@
 #include <cstdio>
 
 #include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
-
-static int failures = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
-            ++failures;                                                     \
-        }                                                                   \
-    } while (0)
+#include "expect.hpp"
 
 int main() {
     using namespace ukfb;
@@ -108,6 +100,5 @@ int main() {
     EXPECT(sampled_filter_scalars(13, 12) == 740 && sampled_filter_scalars(14, 13) == 796);
     EXPECT(sigma_points_filter_scalars(13, 12) == 296 && sigma_points_filter_scalars(14, 13) == 324);
     EXPECT(sampled_filter_scalars(17, 16) == -1 && sigma_points_filter_scalars(17, 16) == -1);
-    std::printf("OK: %d failure(s)\n", failures);
-    return failures ? 1 : 0;
+    return finish();
 }

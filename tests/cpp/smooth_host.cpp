@@ -4,15 +4,7 @@
 #include <vector>
 
 #include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
-
-static int failures = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
-            ++failures;                                                     \
-        }                                                                   \
-    } while (0)
+#include "expect.hpp"
 
 int main() {
     using namespace ukfb;
@@ -83,6 +75,5 @@ int main() {
     // the shape tests/test_gpu_smooth.py pushes behind: 16 384 filters on an engine with a second stream run as split launches
     EXPECT(split_launch(false, false, true, true, 16384, 262144) && SPLIT_MIN_FILTERS <= 16384);
     EXPECT(!split_launch(false, false, false, true, 16384, 262144) && !split_launch(false, false, true, false, 16384, 262144));
-    std::printf("OK: %d failure(s)\n", failures);
-    return failures ? 1 : 0;
+    return finish();
 }

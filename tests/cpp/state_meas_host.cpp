@@ -7,15 +7,7 @@
 #include <vector>
 
 #include "../../slam-pose_estimation_amd/csrc/ukf_host.hpp"
-
-static int failures = 0;
-#define EXPECT(cond)                                                        \
-    do {                                                                    \
-        if (!(cond)) {                                                      \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
-            ++failures;                                                     \
-        }                                                                   \
-    } while (0)
+#include "expect.hpp"
 
 int main() {
     using namespace ukfb;
@@ -92,6 +84,5 @@ int main() {
                 EXPECT(Qz[size_t(r * 12 + c)] == want);
             }
     }
-    std::printf("OK: %d failure(s)\n", failures);
-    return failures ? 1 : 0;
+    return finish();
 }

@@ -162,7 +162,7 @@ ACC_COV = 0.01 * np.eye(3)
 
 def cycled_state(spe, model, n, prec=0, cycles=2):
     """synth.pose_initial / orient_initial after `cycles` real cycles by the C++ oracle (prec 0: fp64, 1: the float oracle with
-    the state rounded to float at every cycle): what cycled_engine of tests/test_gpu_state_meas.py / test_gpu_sensor_meas.py
+    the state rounded to float at every cycle): what cycled_engine of tests/engine_support.py
     downloads from an engine, without one"""
     from oracle import capi, ukf_numpy as on
     sy = spe.synth

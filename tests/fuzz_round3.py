@@ -26,7 +26,7 @@ def mad(a, b):
     return float(np.max(np.abs(np.asarray(a) - np.asarray(b)))) if np.size(a) else 0.0
 
 
-def dev(x, tdt):
+def dev_rows(x, tdt):
     return torch.from_numpy(np.ascontiguousarray(x.reshape(x.shape[0], -1))).to("cuda", tdt)
 
 
@@ -44,7 +44,7 @@ def bucket_scenario(rng, k):
     models = np.where(cls == 0, -1, np.where(cls == 2, 3, lin)).astype(np.int32)
     zz = s.pose_measurement_for_model(mu, np.maximum(models, 0), z - mu[:, :3])
     use_acc = rng.random() < 0.7
-    a_t, z_t, Q_t = dev(acc, tdt), dev(zz, tdt), dev(Q, tdt)
+    a_t, z_t, Q_t = dev_rows(acc, tdt), dev_rows(zz, tdt), dev_rows(Q, tdt)
     m_t = torch.from_numpy(models).cuda()
     torch.cuda.synchronize()
     dt = float(rng.choice([0.005, 0.01, 0.05]))
@@ -97,7 +97,7 @@ def split_scenario(rng, k):
         mu, cov = s.pose_initial(n)
         ring = [s.pose_cycle_inputs(n, c, mu[:, :3]) for c in range(3)]       # acc, z, Q
         zi, Qi, model = 1, 2, spe.MEAS_POS3
-    dring = [tuple(dev(x, tdt) for x in r) for r in ring]
+    dring = [tuple(dev_rows(x, tdt) for x in r) for r in ring]
     z_ring = torch.stack([d[zi] for d in dring]).contiguous()
     Q_ring = torch.stack([d[Qi] for d in dring]).contiguous()
     torch.cuda.synchronize()

@@ -75,3 +75,24 @@ def update_state(man, mu, cov, masks, z, Qz, a=1.0, b=1.0, gate_chi2=-1.0, initi
         ll[idx] = np.where(scored, -0.5 * (d2 + logdet + manz.D * LN_2PI), np.nan)
         st[idx] = s
     return mu_o, cov_o, maha, ll, st
+
+
+def full_mask(model):
+    return 15 if model == "pose" else 31
+
+
+def make_inputs(man, mu, cov, dtype, seed=11):
+    """the joint measurement the tests update with: z = mu (+) L xi, Qz = Sigma + (L A)(L A)^T, as the engine stores them"""
+    n = mu.shape[0]
+    rng = np.random.default_rng(seed)
+    L = np.linalg.cholesky(cov)
+    z = man.boxplus(mu, np.einsum("bij,bj->bi", L, rng.standard_normal((n, man.D))))
+    LA = L @ (0.3 * rng.standard_normal((n, man.D, man.D)))
+    Qz = cov + LA @ np.swapaxes(LA, 1, 2)
+    Qz = 0.5 * (Qz + np.swapaxes(Qz, 1, 2))
+    return z.astype(dtype).astype(np.float64), Qz.astype(dtype).astype(np.float64)
+
+
+def cycling_masks(model, n):
+    """every mask of the model, 0 included, so that four wave-mates always differ"""
+    return (np.arange(n) % (full_mask(model) + 1)).astype(np.int32)

@@ -8,6 +8,7 @@ import pytest
 import associate_reference as ar
 import feature_scaled_parity as fsp
 import sensor_meas_reference as sr
+from engine_support import man_of, same
 from oracle import ukf_numpy as on
 
 N = 48
@@ -15,12 +16,8 @@ ST_NONFINITE, ST_CHOLESKY, ST_NOCONV, ST_UNINIT, ST_INACTIVE, ST_REJECTED = 1 <<
 FLOATS = ("z_pred", "S", "innov", "maha", "loglik")
 
 
-def man_of(model):
-    return on.POSE if model == "pose" else on.ORIENT
-
-
 def inputs(spe, model, n=N, seed=5):
-    """the batch of tests/test_gpu_associate.py on the oracle's cycled state: tests/test_gpu_sensor_meas.make_inputs, and
+    """the batch of tests/test_gpu_associate.py on the oracle's cycled state: tests/sensor_meas_cases.make_inputs, and
     OrientationState's nav-frame vectors of length 1 ... 3 (acase of that file)"""
     mu, cov = fsp.cycled_state(spe, model, n)
     rng = np.random.default_rng(seed)
@@ -36,10 +33,6 @@ def inputs(spe, model, n=N, seed=5):
         z[mid] = zz
     Q = np.broadcast_to(0.05 ** 2 * np.eye(3), (n, 3, 3)).copy()
     return mu, cov, mount, point, gyro, z, Q
-
-
-def same(a, b, keys):
-    return all(np.array_equal(a[k], b[k], equal_nan=True) for k in keys)
 
 
 @pytest.mark.parametrize("model", ["pose", "orient"])

@@ -6,27 +6,9 @@ import pytest
 import bank_reference as br
 
 
-def make_tracks(spe, onp, model, T, M, spread=0.33, seed=7):
-    """T tracks of M hypotheses: a synthetic initial state and M tangent steps of about its own sigma, the rotation part spread
-    up to `spread` rad (the prototype's construction)."""
-    man = onp.POSE if model == "pose" else onp.ORIENT
-    mu0, cov0 = (spe.synth.pose_initial if model == "pose" else spe.synth.orient_initial)(T * M)
-    rng = np.random.default_rng(seed)
-    base = mu0[::M]
-    sig = np.sqrt(np.einsum("tii->ti", cov0[::M]))
-    step = rng.standard_normal((T, M, man.D)) * sig[:, None, :]
-    ro = br.rot_offset(man)
-    step[:, :, ro:ro + 3] = rng.uniform(-1, 1, (T, M, 3)) * spread / np.sqrt(3.0)
-    mu = man.boxplus(base[:, None, :], step)
-    cov = cov0.reshape(T, M, man.D, man.D).copy()
-    w = rng.uniform(0.05, 1.0, (T, M))
-    w /= w.sum(axis=1, keepdims=True)
-    return man, mu, cov, w
-
-
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_closed_form_transport_against_central_differences(spe, onp, model):
-    man, mu, cov, w = make_tracks(spe, onp, model, 64, 4)
+    man, mu, cov, w = br.make_tracks(spe, onp, model, 64, 4)
     mean, _, conv = br.mixture(man, mu, cov, w)
     assert conv.all()
     D, ro, h = man.D, br.rot_offset(man), 1e-5
@@ -45,7 +27,7 @@ def test_closed_form_transport_against_central_differences(spe, onp, model):
 
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_vector_blocks_are_textbook_moment_matching(spe, onp, model):
-    man, mu, cov, w = make_tracks(spe, onp, model, 64, 4)
+    man, mu, cov, w = br.make_tracks(spe, onp, model, 64, 4)
     mean, C, _ = br.mixture(man, mu, cov, w)
     for kind, so, to, n in man.fields:
         if kind == "so3":
@@ -59,7 +41,7 @@ def test_vector_blocks_are_textbook_moment_matching(spe, onp, model):
 
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_one_hot_identical_and_permuted_hypotheses(spe, onp, model):
-    man, mu, cov, w = make_tracks(spe, onp, model, 32, 4)
+    man, mu, cov, w = br.make_tracks(spe, onp, model, 32, 4)
     for j in range(4):
         oh = np.zeros_like(w); oh[:, j] = 1.0
         mean, C, _ = br.mixture(man, mu, cov, oh)
@@ -79,7 +61,7 @@ def test_one_hot_identical_and_permuted_hypotheses(spe, onp, model):
 
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_mixture_covariance_is_symmetric_positive_definite_and_transport_matters(spe, onp, model):
-    man, mu, cov, w = make_tracks(spe, onp, model, 512, 4)
+    man, mu, cov, w = br.make_tracks(spe, onp, model, 512, 4)
     mean, C, conv = br.mixture(man, mu, cov, w)
     assert conv.all()
     assert np.abs(C - np.swapaxes(C, 1, 2)).max() <= 1e-15

@@ -5,8 +5,8 @@ stand-alone program), and a NULL engine is refused before anything touches a dev
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
+
+from host_support import header_text, run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("ukfb_update_bearing_dev", "ukfb_update_bearing")
@@ -14,7 +14,7 @@ NAMES = ("ukfb_update_bearing_dev", "ukfb_update_bearing")
 
 def test_symbols_and_bindings(spe):
     lib = spe.load_library()
-    header = open(os.path.join(ROOT, "include", "ukf_batch.h")).read()
+    header = header_text()
     for name in NAMES:
         assert name in spe.engine.EXPORTS and hasattr(lib, name) and ("int " + name + "(") in header
     for method in ("update_bearing_dev", "update_bearing"):
@@ -46,14 +46,4 @@ def test_null_engine_is_refused(spe):
 
 
 def test_host_decisions_under_sanitizers(tmp_path):
-    gxx = shutil.which("g++")
-    assert gxx, "g++ is needed for the host-side checks"
-    exe = tmp_path / "bearing_host_asan"
-    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "bearing_host.cpp"), "-o", str(exe)], check=True, timeout=300)
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "OK: 0 failure(s)" in out.stdout
-    for marker in ("AddressSanitizer", "LeakSanitizer", "runtime error", "UndefinedBehaviorSanitizer"):
-        assert marker not in out.stderr + out.stdout, out.stderr
+    run_sanitized("bearing_host.cpp", tmp_path)

@@ -9,6 +9,7 @@ import pytest
 
 import bearing_reference as br
 import slam_pose_estimation_amd as spe
+from engine_support import scaled
 from oracle import ukf_numpy as on
 
 N = 1022
@@ -56,10 +57,6 @@ def batch(name):
             mu, cov = cycled("orient")
             _BATCH[name] = (on.ORIENT, mu, cov) + br.make_inputs(on.ORIENT, mu, 15.0, 80.0)
     return _BATCH[name]
-
-
-def scaled(a, b):
-    return float(np.max(np.abs(a - b) / (1.0 + np.abs(b))))
 
 
 # ------------------------------------------------------------------------------------------------ (a) no basis shows

@@ -8,15 +8,12 @@ import numpy as np
 import pytest
 
 import condition_reference as cr
+from engine_support import man_of
 from oracle import ukf_numpy as on
-from test_sensor_meas_reference import states
+from sensor_meas_cases import states
 
 N = 256
 EPS = 1e-10
-
-
-def man_of(model):
-    return on.POSE if model == "pose" else on.ORIENT
 
 
 def batch(model, eps=EPS, dtype=np.float64):

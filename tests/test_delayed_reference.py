@@ -6,14 +6,11 @@ import pytest
 
 import delayed_reference as dr
 import smoother_reference as sr
+from engine_support import scaled
 
 ACC_COV = 0.01 * np.eye(3)
 PV = [0, 1, 2, 6, 7, 8]          # tangent indices of (p, v) in PoseWithVelocity
 PVS = [0, 1, 2, 7, 8, 9]         # ... and the stored ones
-
-
-def scaled(x, ref):
-    return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref))))
 
 
 # ------------------------------------------------------------------------------------------------ the linear (p, v) system

@@ -1,9 +1,9 @@
 """tests/feature_f32.py and tests/feature_scaled_parity.py pinned on the CPU (no GPU anywhere in this file).
 
 The inputs are the GPU files' own families -- states after two real cycles with z = mu (+) L xi and Qz = Sigma + (L A)(L A)^T,
-mounts and points of tests/test_gpu_sensor_meas.make_inputs, the recorded window of tests/test_gpu_smooth.record (6 and 12
-steps, per-filter noise, latched inputs), the tracks of tests/test_bank_reference.make_tracks, the predicted state and clutter
-of tests/test_gpu_innovation -- with the C++ oracle in the engine's place (feature_scaled_parity.cycled_state /
+mounts and points of tests/sensor_meas_cases.make_inputs, the recorded window of tests/test_gpu_smooth.record (6 and 12
+steps, per-filter noise, latched inputs), the tracks of tests/bank_reference.make_tracks, the predicted state and clutter
+of tests/innovation_reference -- with the C++ oracle in the engine's place (feature_scaled_parity.cycled_state /
 recorded_window / predicted_state), 203 filters (scaled_parity.SPREAD_N), as an fp64 engine holds them and rounded to float32
 as an fp32 engine does.
 
@@ -35,24 +35,18 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bank_reference as br  # noqa: E402
 import feature_f32 as ff  # noqa: E402
 import feature_scaled_parity as fsp  # noqa: E402
+import innovation_reference as ir  # noqa: E402
 import scaled_parity as sp  # noqa: E402
+import sensor_meas_cases as smc  # noqa: E402
 import sensor_meas_reference as ser  # noqa: E402
 import smoother_reference as smo  # noqa: E402
 import state_meas_reference as smr  # noqa: E402
-import test_gpu_bank as gb  # noqa: E402
-import test_gpu_innovation as gi  # noqa: E402
-import test_gpu_sensor_meas as gse  # noqa: E402
-import test_gpu_state_meas as gsm  # noqa: E402
+from engine_support import man_of  # noqa: E402
 from oracle import ukf_numpy as on  # noqa: E402
-from test_bank_reference import make_tracks  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = sp.SPREAD_N
 MODELS = ("pose", "orient")
-
-
-def man_of(model):
-    return on.POSE if model == "pose" else on.ORIENT
 
 
 def rel(x, ref):
@@ -87,9 +81,9 @@ class Call:
 def state_meas_calls(spe, model, prec):
     mu, cov = fsp.cycled_state(spe, model, N, prec)
     man = man_of(model)
-    z, Qz = gsm.make_inputs(model, mu, cov, np.float32 if prec else np.float64)
-    full = gsm.full_mask(model)
-    masks = [full] + ([3] if model == "pose" else []) + [1 << b for b in range(len(man.fields))] + [gsm.cycling_masks(model, N)]
+    z, Qz = smr.make_inputs(man, mu, cov, np.float32 if prec else np.float64)
+    full = smr.full_mask(model)
+    masks = [full] + ([3] if model == "pose" else []) + [1 << b for b in range(len(man.fields))] + [smr.cycling_masks(model, N)]
     out = []
     for m in masks:
         for a, b in ((1.0, 1.0),) + (((1.0 / 0.3, 1.0 / 0.7),) if np.isscalar(m) and m == full else ()):
@@ -104,9 +98,9 @@ def state_meas_calls(spe, model, prec):
 def sensor_meas_calls(spe, model, prec):
     mu, cov = fsp.cycled_state(spe, model, N, prec)
     man = man_of(model)
-    mount, point, gyro, zs, Q = gse.make_inputs(model, mu, np.float32 if prec else np.float64)
+    mount, point, gyro, zs, Q = smc.make_inputs(model, mu, np.float32 if prec else np.float64)
     out = []
-    for mid in gse.ids_of(model):
+    for mid in ser.ids_of(man):
         ref = ser.update_sensor(man, mu, cov, mid, zs[mid], Q, mount, point, gyro)
         assert (ref["status"] == 0).all()
         m = ser.meas_dim(mid)
@@ -116,9 +110,9 @@ def sensor_meas_calls(spe, model, prec):
         c.ev = lambda p, c=c, ev=ev: (lambda o: (o["mu"], o["cov"]))(c._cache.setdefault(("o", p), ev(p)))
         c.ev_meas = lambda p, c=c, ev=ev, pick=pick: pick(c._cache.setdefault(("o", p), ev(p)))
         out.append(c)
-    per = gse.cycling_ids(model, N)
+    per = smc.cycling_ids(model, N)
     z = np.zeros((N, 3))
-    for mid in gse.ids_of(model):
+    for mid in ser.ids_of(man):
         z[per == mid] = zs[mid][per == mid]
     ref = ser.update_sensor(man, mu, cov, per, z, Q, mount, point, gyro)
     out.append(Call(f"sensor_meas/{model}/per-filter-ids", model, (ref["mu"], ref["cov"]),
@@ -145,10 +139,10 @@ def bank_calls(spe, model, prec):
     man = man_of(model)
     out = []
     for M, cap in ((2, None), (3, None), (4, None), (8, None), (4, 1)):
-        _, mu, cov, w = make_tracks(spe, on, model, N, M, seed=7)
+        _, mu, cov, w = br.make_tracks(spe, on, model, N, M, seed=7)
         mu, cov = r(mu), r(cov)
         w = r(r(w) / r(w).sum(axis=1, keepdims=True))
-        Pk = r(gb.transition(M))
+        Pk = r(br.transition(M))
         kw = {} if cap is None else {"max_it": cap}
         ref = br.mixture(man, mu, cov, w, **kw)
         out.append(Call(f"combine/{model}/M={M}/cap={cap}", model, ref[:2], lambda p, a=(mu, cov, w), kw=kw: ff.mixture(model, *a, p, **kw)))
@@ -161,14 +155,14 @@ def innovation_calls(spe, model, prec):
     mu, cov, Q = fsp.predicted_state(spe, model, N, prec)
     r = sp.f32r if prec else (lambda x: x)
     out = []
-    for mid in (gi.POSE_MODELS if model == "pose" else [9]):
-        z = r(gi.clutter(on, spe, model, mid, mu))
+    for mid in (ir.POSE_MODELS if model == "pose" else [9]):
+        z = r(ir.clutter(on, spe, model, mid, mu))
         for uq in (False, True):
             Qh = np.broadcast_to(Q[0], Q.shape).copy() if uq else Q
-            m, manz, mz, S, ok, conv = gi.reference(on, model, mid, mu, cov, Qh)
+            m, manz, mz, S, ok, conv = ir.reference(on, model, mid, mu, cov, Qh)
             assert ok.all() and conv.all()
             so3 = model == "pose" and mid == 3
-            nu, _, _ = gi.reference_scores(on, so3, m, manz, mz, S, z)
+            nu, _, _ = ir.reference_scores(on, so3, m, manz, mz, S, z)
             out.append(Call(f"innovation/{model}/model={mid}/uniform_q={int(uq)}", model, None, None, (mz, S, nu),
                             lambda p, mid=mid, Qh=Qh, z=z: ff.innovation_stats(model, mid, mu, cov, Qh, z, p), so3))
     return out
@@ -238,11 +232,11 @@ def degenerate_spread(spe):
         Qz[:, t0:t0 + 3, t0:t0 + 3] = Q3
         todo.append((f"state block {block} = model {mid}", "pose", mu, cov, mid, z3, Q3,
                      lambda z=z, Qz=Qz, block=block, mu=mu, cov=cov: ff.state_meas("pose", mu, cov, 1 << block, z, Qz, prec="f32")))
-    ident = np.array(gse.spe_identity())
+    ident = np.array(smc.spe_identity())
     for model, sid, mid in (("pose", ser.POSE_POSITION, spe.MEAS_POS3), ("pose", ser.POSE_VELOCITY, spe.MEAS_VEL3),
                             ("orient", ser.ORIENT_VELOCITY, spe.MEAS_ORIENT_BODYVEL3)):
         mu, cov = fsp.cycled_state(spe, model, N, 1)
-        _, _, gyro, _, Q = gse.make_inputs(model, mu, np.float32)
+        _, _, gyro, _, Q = smc.make_inputs(model, mu, np.float32)
         rng = np.random.default_rng(23)
         z = sp.f32r(ser.h(sid, mu, ident, np.zeros(3), gyro) + 0.05 * rng.standard_normal((N, 3)))
         todo.append((f"{ser.NAMES[sid]} r=0 qs=1 = model {mid}", model, mu, cov, mid, z, Q,

@@ -4,8 +4,8 @@ ukf_host.hpp (check_forecast_args, forecast_filter_scalars, forecast_geometry) h
 device."""
 import ctypes as C
 import os
-import shutil
-import subprocess
+
+from host_support import header_text, run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("ukfb_forecast_dev", "ukfb_forecast")
@@ -13,7 +13,7 @@ NAMES = ("ukfb_forecast_dev", "ukfb_forecast")
 
 def test_symbols_and_bindings(spe):
     lib = spe.load_library()
-    header = open(os.path.join(ROOT, "include", "ukf_batch.h")).read()
+    header = header_text()
     for name in NAMES:
         assert name in spe.engine.EXPORTS and hasattr(lib, name) and ("int " + name + "(") in header
     for method in ("forecast_dev", "forecast"):
@@ -35,14 +35,4 @@ def test_null_engine_is_refused(spe):
 
 
 def test_host_decisions_under_sanitizers(tmp_path):
-    gxx = shutil.which("g++")
-    assert gxx, "g++ is needed for the host-side checks"
-    exe = tmp_path / "forecast_host_asan"
-    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "forecast_host.cpp"), "-o", str(exe)], check=True, timeout=300)
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "OK: 0 failure(s)" in out.stdout
-    for marker in ("AddressSanitizer", "LeakSanitizer", "runtime error", "UndefinedBehaviorSanitizer"):
-        assert marker not in out.stderr + out.stdout, out.stderr
+    run_sanitized("forecast_host.cpp", tmp_path)

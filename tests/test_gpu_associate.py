@@ -1,7 +1,7 @@
 """Sensor-frame association on the device (ukfb_associate_sensor_dev / ukfb_associate_sensor, include/ukf_batch.h).
 
-States, inputs, engines, the three precision modes and their tolerances are those of tests/test_gpu_sensor_meas.py (imported:
-PRECS, case, engine_of, cycled_engine, make_inputs), but for the length of OrientationState's nav-frame vectors (acase below).  Candidates are the constructed maps of
+States, inputs, engines, the three precision modes and their tolerances are those of tests/test_gpu_sensor_meas.py (tests/sensor_meas_cases.py:
+PRECS, case, engine_of, make_inputs), but for the length of OrientationState's nav-frame vectors (acase below).  Candidates are the constructed maps of
 tests/associate_reference.constructed_candidates -- the true candidate of filter i at index i % K, clutter at least 6 sigma
 away -- whose separation tests/test_associate_reference.py asserts on the inputs, so that no decision here hinges on rounding.
 The reference is tests/associate_reference.py on the state AS DOWNLOADED and the inputs AS STORED.  Parity bound:
@@ -16,9 +16,10 @@ import torch
 import associate_reference as ar
 import feature_f32 as ff
 import feature_scaled_parity as fsp
+import sensor_meas_cases as smc
 import sensor_meas_reference as sr
-import test_gpu_sensor_meas as tsm
-from test_gpu_sensor_meas import PRECS, case, engine_of, ids_of, man_of, same_snap, scaled, snapshot, stored
+from engine_support import cycled_engine, man_of, same_snapshot, scaled, snapshot, stored, tdt
+from sensor_meas_cases import PRECS, case, cycling_ids, engine_of
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +33,7 @@ FILL = -7.0
 def run(e, ids, z, Q, mount, point, hyp=False, commit=True, q_uniform=False):
     """-> dict(mu, cov, z_pred [H, n, 3], S [H, n, 3, 3], innov [K, n, 3], maha, loglik [K, n], best, n_gated, status [n])
     after associate_sensor_dev; mount [7] / point [3]: uniform; hyp: point is [K, n, 3]"""
-    n, dt, K = e.capacity, tsm.tdt(e), int(np.shape(z)[0])
+    n, dt, K = e.capacity, tdt(e), int(np.shape(z)[0])
     H = K if hyp else 1
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dt)   # noqa: E731
     zd = dev(z)
@@ -46,7 +47,7 @@ def run(e, ids, z, Q, mount, point, hyp=False, commit=True, q_uniform=False):
          "best": full((n,), -9, torch.int32), "n_gated": full((n,), -9, torch.int32), "status": full((n,), -1, torch.int32)}
     torch.cuda.synchronize()
     e.associate_sensor_dev(int(ids) if idd is None else 0, K, zd, qd, q_is_uniform=q_uniform, model_dev=idd, mount_dev=md,
-                           mount=mount if md is None else tsm.spe_identity(), point_dev=pd, point=point if pd is None else (0.0, 0.0, 0.0),
+                           mount=mount if md is None else smc.spe_identity(), point_dev=pd, point=point if pd is None else (0.0, 0.0, 0.0),
                            point_per_candidate=hyp, commit=commit, **o)
     e.sync()
     torch.cuda.synchronize()
@@ -61,7 +62,7 @@ def run(e, ids, z, Q, mount, point, hyp=False, commit=True, q_uniform=False):
 _ACASE = {}
 
 
-def acase(spe, model, pname, n=tsm.N):
+def acase(spe, model, pname, n=smc.N):
     """The sensor test's case (state after two cycles as downloaded, inputs as stored).  PoseWithVelocity: as it is, landmarks
     and beacons 15 ... 80 m away.  OrientationState: the nav-frame vectors of ORIENT_NAV_VECTOR get the length of catalogue
     entries, 1 ... 3 (a field vector, a star direction), instead of that file's 15 ... 80.  Why: at 15 ... 80 the S of that
@@ -76,7 +77,7 @@ def acase(spe, model, pname, n=tsm.N):
         return c0
     key = (pname, n)
     if key not in _ACASE:
-        c = tsm.Case()
+        c = smc.Case()
         c.__dict__.update(c0.__dict__)
         rng = np.random.default_rng(29)
         c.point = stored(c0.point / np.linalg.norm(c0.point, axis=1, keepdims=True) * rng.uniform(1.0, 3.0, (n, 1)), c.dtype)
@@ -94,11 +95,11 @@ def reference(c, ids, zs, pts, hyp, gate=-1.0, **kw):
 
 def constructed(c, ids, K, hyp):
     """-> (z [K, n, 3], points, truth) for the case's batch, as the engine stores them"""
-    z_true = c.z[int(ids)] if np.isscalar(ids) else tsm.mixed_z(c, ids)
+    z_true = c.z[int(ids)] if np.isscalar(ids) else smc.mixed_z(c, ids)
     return ar.constructed_candidates(man_of(c.model), c.mu, c.cov, ids, z_true, c.Q, c.mount, c.point, c.gyro, K, hyp, c.dtype)
 
 
-def same(a, b, keys=("mu", "cov") + FLOATS + INTS, rows=None):
+def same_candidates(a, b, keys=("mu", "cov") + FLOATS + INTS, rows=None):
     """bit equality; rows: a selection of filters (the second axis of the per-candidate and per-hypothesis outputs)"""
     rows = slice(None) if rows is None else rows
     part = lambda o, k: o[k][:, rows] if k in FLOATS else o[k][rows]   # noqa: E731
@@ -139,7 +140,7 @@ def check_parity(name, c, got, ref, ids, zs, pts, hyp, tol=None, state=True):
             both = [ff.sensor_meas(c.model, c.mu, c.cov, idv, zb, c.Q, c.mount, pb, c.gyro, keep=keep, prec=p) for p in ("f32", "f64")]
             return tuple((o["mu"], o["cov"]) for o in both)
         fsp.judge_state("associate/" + name, c.model, c.pname, got["mu"], got["cov"], ref["mu"], ref["cov"], f32=st32)
-    dims = np.array([sr.meas_dim(int(i)) if i in ids_of(c.model) else 0 for i in idv])
+    dims = np.array([sr.meas_dim(int(i)) if i in sr.ids_of(man_of(c.model)) else 0 for i in idv])
     every = ~np.isnan(ref["maha"]).any(axis=0)
     for m in (1, 3):
         sel = every & (dims == m)
@@ -153,10 +154,6 @@ def check_parity(name, c, got, ref, ids, zs, pts, hyp, tol=None, state=True):
             fsp.judge_meas(f"associate/{name}/m={m}/h={hx}", c.pname, *pick(got), *pick(ref), f32=lambda: (one("f32"), one("f64")))
 
 
-def cycling_ids(model, n):
-    return tsm.cycling_ids(model, n)
-
-
 # ------------------------------------------------------------------------------------------------------------------ parity
 @pytest.mark.parametrize("hyp", [False, True], ids=["shared", "per-hypothesis"])
 @pytest.mark.parametrize("model", ["pose", "orient"])
@@ -167,7 +164,7 @@ def test_parity(spe, model, pname, hyp):
     ids = cycling_ids(model, c.n)
     zs, pts, truth = constructed(c, ids, K4, hyp)
     ref = reference(c, ids, zs, pts, hyp)
-    live = np.isin(ids, ids_of(model))
+    live = np.isin(ids, sr.ids_of(man_of(model)))
     assert np.array_equal(ref["status"], np.where(live, 0, ST_INACTIVE)) and np.array_equal(ref["best"], np.where(live, truth, -1))
     e = engine_of(spe, c)
     got = run(e, ids, zs, c.Q, c.mount, pts, hyp)
@@ -177,7 +174,7 @@ def test_parity(spe, model, pname, hyp):
     assert np.array_equal(got["mu"][~live], c.mu[~live]) and np.array_equal(got["cov"][~live], c.cov[~live])
     assert not np.array_equal(got["mu"][live], c.mu[live])
     check_parity(f"{model}/{pname}/{'hyp' if hyp else 'shared'}", c, got, ref, ids, zs, pts, hyp)
-    for mid in ids_of(model):
+    for mid in sr.ids_of(man_of(model)):
         m, rows = sr.meas_dim(mid), ids == mid
         assert (got["z_pred"][:, rows, m:] == 0).all() and (got["innov"][:, rows, m:] == 0).all()
         assert (got["S"][:, rows, m:, :] == 0).all() and (got["S"][:, rows, :, m:] == 0).all()
@@ -195,11 +192,11 @@ def test_agreement_with_update_sensor_fp64(spe, model, hyp):
     zs, pts, truth = constructed(c, ids, K4, hyp)
     e, twin = engine_of(spe, c), engine_of(spe, c)
     got = run(e, ids, zs, c.Q, c.mount, pts, hyp)
-    live = np.isin(ids, ids_of(model))
+    live = np.isin(ids, sr.ids_of(man_of(model)))
     assert np.array_equal(got["best"], np.where(live, truth, -1))
     bits = True
     for k in range(K4):
-        one = tsm.run(twin, ids, zs[k], c.Q, c.mount, pts[k] if hyp else pts, commit=False)
+        one = smc.run(twin, ids, zs[k], c.Q, c.mount, pts[k] if hyp else pts, commit=False)
         hx = k if hyp else 0
         pairs = {"maha": (got["maha"][k], one["maha"]), "loglik": (got["loglik"][k], one["loglik"]), "innov": (got["innov"][k][live], one["innov"][live]),
                  "z_pred": (got["z_pred"][hx], one["z_pred"]), "S": (got["S"][hx], one["S"])}
@@ -210,7 +207,7 @@ def test_agreement_with_update_sensor_fp64(spe, model, hyp):
             assert d <= c.tol, (k, key, d)
     rows = np.arange(c.n)
     sel = np.maximum(got["best"], 0)
-    fin = tsm.run(twin, np.where(got["best"] >= 0, ids, -1).astype(np.int32), zs[sel, rows], c.Q, c.mount, pts[sel, rows] if hyp else pts)
+    fin = smc.run(twin, np.where(got["best"] >= 0, ids, -1).astype(np.int32), zs[sel, rows], c.Q, c.mount, pts[sel, rows] if hyp else pts)
     e.close(); twin.close()
     em, ec = scaled(got["mu"], fin["mu"]), scaled(got["cov"], fin["cov"])
     bits_state = np.array_equal(got["mu"], fin["mu"]) and np.array_equal(got["cov"], fin["cov"])
@@ -225,11 +222,11 @@ def test_one_candidate_is_the_sensor_update(spe, model, pname):
     """K = 1 in either mode: every output of ukfb_update_sensor_dev, within tolerance"""
     c = acase(spe, model, pname)
     ids = cycling_ids(model, c.n)
-    z = tsm.mixed_z(c, ids)
+    z = smc.mixed_z(c, ids)
     twin = engine_of(spe, c)
-    one = tsm.run(twin, ids, z, c.Q, c.mount, c.point)
+    one = smc.run(twin, ids, z, c.Q, c.mount, c.point)
     twin.close()
-    live = np.isin(ids, ids_of(model))
+    live = np.isin(ids, sr.ids_of(man_of(model)))
     for hyp in (False, True):
         e = engine_of(spe, c)
         got = run(e, ids, z[None], c.Q, c.mount, c.point[None] if hyp else c.point, hyp)
@@ -317,12 +314,12 @@ def test_read_only(spe, model, hyp):
     e, twin = fresh(), fresh()
     before = snapshot(e)
     dry = run(e, ids, zs, c.Q, c.mount, pts, hyp, commit=False)
-    assert same_snap(before, snapshot(e)) and same_snap(before, snapshot(twin))
+    assert same_snapshot(before, snapshot(e)) and same_snapshot(before, snapshot(twin))
     wet = run(twin, ids, zs, c.Q, c.mount, pts, hyp)
-    assert same(dry, wet, keys=FLOATS + INTS) and np.array_equal(dry["mu"], c.mu) and np.array_equal(dry["cov"], c.cov)
+    assert same_candidates(dry, wet, keys=FLOATS + INTS) and np.array_equal(dry["mu"], c.mu) and np.array_equal(dry["cov"], c.cov)
     assert not np.array_equal(wet["mu"], c.mu)
     again = run(e, ids, zs, c.Q, c.mount, pts, hyp)   # commit = 0, then commit = 1: the numbers of commit = 1 alone
-    assert same(again, wet)
+    assert same_candidates(again, wet)
     e.close(); twin.close()
     # per-filter Q repeated against ONE 3x3; a device id array filled with one id; the host form
     mid = sr.POSE_POINT if model == "pose" else sr.ORIENT_NAV_VECTOR
@@ -331,13 +328,13 @@ def test_read_only(spe, model, hyp):
     base = run(e, mid, zs, c.Q, c.mount, pts, hyp)
     e.close()
     e = fresh()
-    assert same(run(e, np.full(n, mid, dtype=np.int32), zs, c.Q[0], c.mount, pts, hyp, q_uniform=True), base)
+    assert same_candidates(run(e, np.full(n, mid, dtype=np.int32), zs, c.Q[0], c.mount, pts, hyp, q_uniform=True), base)
     e.close()
     e = fresh()
     o = e.associate_sensor(mid, zs, c.Q, c.mount, pts, point_per_candidate=hyp)
     o["mu"], o["cov"], _ = e.state()
     e.close()
-    assert same(o, base)
+    assert same_candidates(o, base)
 
 
 @pytest.mark.parametrize("hyp", [False, True], ids=["shared", "per-hypothesis"])
@@ -348,12 +345,12 @@ def test_failures_stay_inside_their_filter(spe, model, hyp):
     run without the bad ones"""
     n, dead, neg, all_nan, one_nan = 64, 22, 34, 13, 41
     man = man_of(model)
-    e = tsm.cycled_engine(spe, model, n, 0, 0, skip_init=(dead,))
+    e = cycled_engine(spe, model, n, 0, 0, skip_init=(dead,))
     mu, cov, init = e.state()
     assert not init[dead] and init.sum() == n - 1
     mu_f = mu.copy()
     mu_f[dead] = mu[0]
-    mount, point, gyro, zt, Q = tsm.make_inputs(model, mu_f, np.float64)
+    mount, point, gyro, zt, Q = smc.make_inputs(model, mu_f, np.float64)
     if model == "orient":
         e.set_orient_inputs(gyro=gyro)
     mid = sr.POSE_POINT if model == "pose" else sr.ORIENT_NAV_VECTOR
@@ -382,14 +379,14 @@ def test_failures_stay_inside_their_filter(spe, model, hyp):
     assert np.isnan(got["maha"][0, one_nan]) and np.isfinite(got["maha"][1:, one_nan]).all() and got["n_gated"][one_nan] == K4 - 1
     assert got["best"][one_nan] == (truth[one_nan] if truth[one_nan] != 0 else int(np.nanargmin(got["maha"][:, one_nan])))
     # everyone else: the bits of a clean committing run on a twin
-    twin = tsm.cycled_engine(spe, model, n, 0, 0, skip_init=(dead,))
+    twin = cycled_engine(spe, model, n, 0, 0, skip_init=(dead,))
     if model == "orient":
         twin.set_orient_inputs(gyro=gyro)
     ok = run(twin, mid, zs, Q, mount, pts, hyp)
     twin.close(); e.close()
-    assert same(ok, clean, keys=FLOATS + INTS)
+    assert same_candidates(ok, clean, keys=FLOATS + INTS)
     healthy = ~failing & (np.arange(n) != one_nan)
-    assert same(got, ok, rows=healthy)
+    assert same_candidates(got, ok, rows=healthy)
     ref = ar.associate_sensor(man, mu_f, cov_bad, mid, zb, Q, mount, pts, gyro, point_per_candidate=hyp, initialised=init)
     assert np.array_equal(ref["status"], expect) and np.array_equal(ref["best"], got["best"]) and np.array_equal(ref["n_gated"], got["n_gated"])
 
@@ -402,7 +399,7 @@ def test_small_batches(spe, model):
     mid = sr.POSE_RANGE if model == "pose" else sr.ORIENT_NAV_VECTOR
     for n in (1, 2, 3, 5):
         for hyp in (False, True):
-            c = tsm.Case()
+            c = smc.Case()
             c.model, c.pname, c.n, c.prec, c.wide, c.tol, c.dtype = model, "f64", n, 0, 0, 1e-9, big.dtype
             c.mu, c.cov, c.mount, c.point, c.gyro, c.Q = big.mu[:n], big.cov[:n], big.mount[:n], big.point[:n], big.gyro[:n], big.Q[:n]
             c.z = {mid: big.z[mid][:n]}
@@ -432,7 +429,7 @@ def test_host_array_form_fp32(spe):
         o = e.associate_sensor(mid, zs, c.Q, mount, pts, point_per_candidate=hyp)
         o["mu"], o["cov"], _ = e.state()
         dev = run(twin, mid, stored(zs, np.float32), c.Q, stored(mount, np.float32), stored(pts, np.float32), hyp)
-        assert same(o, dev) and np.array_equal(e.status(), twin.status()) and (o["status"] == 0).all() and np.array_equal(o["best"], truth)
+        assert same_candidates(o, dev) and np.array_equal(e.status(), twin.status()) and (o["status"] == 0).all() and np.array_equal(o["best"], truth)
         e.close(); twin.close()
 
 
@@ -440,7 +437,7 @@ def test_refused_arguments_write_nothing(spe):
     """a uniform id of the other engine: UKFB_ERR_WRONG_MODEL; 0 and 33 candidates: UKFB_ERR_OUT_OF_RANGE; state and outputs untouched"""
     for model, wrong in (("pose", sr.ORIENT_VELOCITY), ("orient", sr.POSE_POSITION), ("pose", -1), ("orient", 8)):
         c = acase(spe, model, "f64", 255)
-        mid = ids_of(model)[0]
+        mid = sr.ids_of(man_of(model))[0]
         e = engine_of(spe, c)
         with pytest.raises(spe.UkfbError, match="code 5"):
             run(e, wrong, c.z[mid][None], c.Q, c.mount, c.point)

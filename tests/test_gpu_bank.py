@@ -29,7 +29,7 @@ import torch
 import bank_reference as br
 import feature_f32 as ff
 import feature_scaled_parity as fsp
-from test_bank_reference import make_tracks
+from engine_support import dev, new_engine, same_snapshot, scaled, snapshot, stored, tdt, unpack
 
 pytestmark = pytest.mark.gpu
 
@@ -39,23 +39,18 @@ LN2PI = float(np.log(2.0 * np.pi))
 
 
 # ---------------------------------------------------------------------------------------------------------------- helpers
-def new_engine(spe, model, n, prec, wide):
-    cfg = {"wide_arithmetic": 1} if wide else {}
-    if model == "pose":
-        return spe.BatchPoseUKF(n, precision=prec, **cfg)
-    sy = spe.synth
-    e = spe.BatchOrientationUKF(n, sy.ORIENT_TAU, sy.ORIENT_TAU, sy.ORIENT_LATITUDE, precision=prec, **cfg)
-    e.set_process_noise(sy.orient_process_noise())
-    return e
+def snap(e):
+    """the engine's snapshot with the process noise of these filters"""
+    return snapshot(e, (0, 1, e.capacity // 2, e.capacity - 1))
 
 
 def bank_engine(spe, onp, model, T, M, prec, wide, seed=7):
     """an engine of T tracks x M hypotheses built as in the prototype, its state as downloaded, and weights as stored"""
-    man, mu, cov, w = make_tracks(spe, onp, model, T, M, seed=seed)
+    man, mu, cov, w = br.make_tracks(spe, onp, model, T, M, seed=seed)
     e = new_engine(spe, model, T * M, prec, wide)
     e.initialize(mu.reshape(T * M, man.S), cov.reshape(T * M, man.D, man.D))
     latch_inputs(spe, e, model)
-    return e, man, stored(e, w)
+    return e, man, stored(w, e.dtype)
 
 
 def latch_inputs(spe, e, model):
@@ -75,26 +70,6 @@ def latch_inputs(spe, e, model):
 def downloaded(e, man, T, M):
     mu, cov, init = e.state()
     return mu.reshape(T, M, man.S), cov.reshape(T, M, man.D, man.D), init.reshape(T, M)
-
-
-def tdt(e):
-    return torch.float64 if e.dtype == np.float64 else torch.float32
-
-
-def stored(e, x):
-    return np.asarray(x, dtype=e.dtype).astype(np.float64)
-
-
-def dev(e, x):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to("cuda", tdt(e))
-
-
-def unpack(packed, D):
-    C = np.zeros(packed.shape[:-1] + (D, D))
-    r, c = np.tril_indices(D)
-    C[..., r, c] = packed
-    C[..., c, r] = packed
-    return C
 
 
 def combine_dev(e, M, w, want_cov=True):
@@ -123,10 +98,6 @@ def mix_dev(e, M, w, P):
     return wp_t.cpu().numpy().astype(np.float64).reshape(T, M), st_t.cpu().numpy().astype(np.int64)
 
 
-def scaled_err(x, ref):
-    return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref)))) if x.size else 0.0
-
-
 def scaled_combine(name, model, pname, m_g, C_g, m_r, C_r, mu, cov, w, **kw):
     """the scaled check (tests/feature_scaled_parity.py) of combined moments against the reference's, block by block"""
     fsp.judge_state(name, model, pname, m_g, C_g, m_r, C_r, f32=lambda: tuple(ff.mixture(model, mu, cov, w, p, **kw) for p in ("f32", "f64")))
@@ -137,25 +108,6 @@ def scaled_mix(name, model, pname, mu_g, cov_g, mu_r, cov_r, mu, cov, w, Pk, **k
     fsp.judge_state(name, model, pname, mu_g, cov_g, mu_r, cov_r, f32=lambda: tuple(ff.mix(model, mu, cov, w, Pk, p, **kw) for p in ("f32", "f64")))
 
 
-def transition(M, seed=11):
-    rng = np.random.default_rng(seed)
-    P = 0.6 * np.eye(M) + 0.4 * rng.uniform(0.1, 1.0, (M, M))
-    return P / P.sum(axis=1, keepdims=True)
-
-
-def snapshot(e):
-    """everything of the engine that can be downloaded: mean, covariance, initialised flags, status, last measurement times,
-    the process noise, and the latched rotation rate where there is a getter (OrientationState)"""
-    mu, cov, init = e.state()
-    noise = np.array([e.process_noise(i) for i in (0, 1, e.capacity // 2, e.capacity - 1)])
-    latch = e.rotation_rate() if e.model == 1 else np.zeros(0)
-    return mu, cov, init, e.status(), e.last_measurement_time(), noise, latch
-
-
-def same_snapshot(a, b):
-    return all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
-
-
 # ---------------------------------------------------------------------------------------------------------------- parity
 @pytest.mark.parametrize("M", [2, 3, 4, 8])
 @pytest.mark.parametrize("pname,prec,wide,tol", PRECS, ids=[p[0] for p in PRECS])
@@ -164,21 +116,21 @@ def test_combine_and_mix_against_the_reference(spe, onp, model, pname, prec, wid
     T = T_TRACKS
     e, man, w = bank_engine(spe, onp, model, T, M, prec, wide)
     w = w / w.sum(axis=1, keepdims=True)
-    w = stored(e, w)
+    w = stored(w, e.dtype)
     mu, cov, init = downloaded(e, man, T, M)
     assert init.all()
     ro = br.rot_offset(man)
     spread = np.linalg.norm(man.boxminus(mu[:, 1], mu[:, 0])[:, ro:ro + 3], axis=1)
     assert spread.max() >= 0.2, "the tracks must spread their rotations, or the transport is not exercised"
     # ---- combine (read-only)
-    before = snapshot(e)
+    before = snap(e)
     m_g, C_g, st, _ = combine_dev(e, M, w)
-    assert same_snapshot(before, snapshot(e)), "combine changed the engine"
+    assert same_snapshot(before, snap(e)), "combine changed the engine"
     m_r, C_r, conv = br.mixture(man, mu, cov, w)
     assert conv.all() and (st == 0).all()
-    em, ec = scaled_err(m_g, m_r), scaled_err(C_g, C_r)
+    em, ec = scaled(m_g, m_r), scaled(C_g, C_r)
     _, C_0, _ = br.mixture(man, mu, cov, w, transport=False)
-    soft = scaled_err(C_0, C_r)
+    soft = scaled(C_0, C_r)
     print(f"bank parity {model} {pname} M={M} combine: mean {em:.3e} cov {ec:.3e} (no-transport reference: {soft:.3e})")
     assert soft > 1e-9, "the no-transport variant must be outside the fp64 gate, or this test cannot tell them apart"
     assert em <= tol and ec <= tol
@@ -190,13 +142,13 @@ def test_combine_and_mix_against_the_reference(spe, onp, model, pname, prec, wid
     m_h, C_h, st_h = e.bank_combine(M, w.reshape(-1))
     assert np.array_equal(m_h, m_g) and np.array_equal(C_h, C_g) and (st_h == 0).all()
     # ---- mix
-    P = transition(M)
-    Pk = stored(e, P) if (prec == 1 and not wide) else P    # fp32 kernels take the matrix in fp32
+    P = br.transition(M)
+    Pk = stored(P, e.dtype) if (prec == 1 and not wide) else P    # fp32 kernels take the matrix in fp32
     mu_r, cov_r, c_r, conv = br.mix(man, mu, cov, w, Pk)
     wp, st = mix_dev(e, M, w, P)
     assert conv.all() and (st == 0).all()
     mu_g, cov_g, _ = downloaded(e, man, T, M)
-    em, ec, ew = scaled_err(mu_g, mu_r), scaled_err(cov_g, cov_r), scaled_err(wp, c_r)
+    em, ec, ew = scaled(mu_g, mu_r), scaled(cov_g, cov_r), scaled(wp, c_r)
     print(f"bank parity {model} {pname} M={M} mix:     mean {em:.3e} cov {ec:.3e} w_pred {ew:.3e}")
     assert em <= tol and ec <= tol and ew <= tol
     scaled_mix(f"bank/{model}/{pname}/M={M}/mix", model, pname, mu_g, cov_g, mu_r, cov_r, mu, cov, w, Pk)
@@ -217,16 +169,16 @@ def test_combine_is_read_only(spe, onp, model, pname, prec, wide, tol):
     T, M = 514, 4
     e, man, w = bank_engine(spe, onp, model, T, M, prec, wide)
     twin, _, _ = bank_engine(spe, onp, model, T, M, prec, wide)
-    w = stored(e, w / w.sum(axis=1, keepdims=True))
+    w = stored(w / w.sum(axis=1, keepdims=True), e.dtype)
     e.predict(0.01); twin.predict(0.01)          # a status array and a state that a launch has written
-    before = snapshot(e)
-    assert len(np.unique(before[4])) == T * M and same_snapshot(before, snapshot(twin))
+    before = snap(e)
+    assert len(np.unique(before[4])) == T * M and same_snapshot(before, snap(twin))
     _, _, st, _ = combine_dev(e, M, w)
     m_h, C_h, st_h = e.bank_combine(M, w.reshape(-1))
     assert (st == 0).all() and (st_h == 0).all()
-    assert same_snapshot(before, snapshot(e)), "combine changed the engine"
+    assert same_snapshot(before, snap(e)), "combine changed the engine"
     e.predict(0.01); twin.predict(0.01)
-    assert same_snapshot(snapshot(e), snapshot(twin)), "the prediction after combine is not the untouched twin's"
+    assert same_snapshot(snap(e), snap(twin)), "the prediction after combine is not the untouched twin's"
     e.close(); twin.close()
 
 
@@ -238,22 +190,22 @@ def test_mean_iteration_cap_sets_noconv(spe, onp, model, pname, prec, wide, tol,
     T, M = 254, 4
     e, man, w = bank_engine(spe, onp, model, T, M, prec, wide)
     e.configure(mean_max_iter=cap)
-    w = stored(e, w / w.sum(axis=1, keepdims=True))
+    w = stored(w / w.sum(axis=1, keepdims=True), e.dtype)
     mu, cov, _ = downloaded(e, man, T, M)
     m_r, C_r, conv = br.mixture(man, mu, cov, w, max_it=cap)
     assert not conv.any(), "the tracks must not converge within the cap, or the flag is not reached"
     m_g, C_g, st, _ = combine_dev(e, M, w)
     assert np.array_equal(st, np.full(T, spe.ST_WARN_MEAN_NOCONV))
-    assert scaled_err(m_g, m_r) <= tol and scaled_err(C_g, C_r) <= tol
+    assert scaled(m_g, m_r) <= tol and scaled(C_g, C_r) <= tol
     scaled_combine(f"bank/{model}/{pname}/cap={cap}/combine", model, pname, m_g, C_g, m_r, C_r, mu, cov, w, max_it=cap)
-    P = transition(M)
-    Pk = stored(e, P) if (prec == 1 and not wide) else P
+    P = br.transition(M)
+    Pk = stored(P, e.dtype) if (prec == 1 and not wide) else P
     mu_r, cov_r, c_r, conv = br.mix(man, mu, cov, w, Pk, max_it=cap)
     assert not conv.any()
     wp, st = mix_dev(e, M, w, P)
     mu_g, cov_g, _ = downloaded(e, man, T, M)
     assert np.array_equal(st, np.full(T, spe.ST_WARN_MEAN_NOCONV))
-    assert scaled_err(mu_g, mu_r) <= tol and scaled_err(cov_g, cov_r) <= tol and scaled_err(wp, c_r) <= tol
+    assert scaled(mu_g, mu_r) <= tol and scaled(cov_g, cov_r) <= tol and scaled(wp, c_r) <= tol
     scaled_mix(f"bank/{model}/{pname}/cap={cap}/mix", model, pname, mu_g, cov_g, mu_r, cov_r, mu, cov, w, Pk, max_it=cap)
     e.close()
 
@@ -262,11 +214,11 @@ def test_mean_iteration_cap_sets_noconv(spe, onp, model, pname, prec, wide, tol,
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_host_mix_equals_device_mix(spe, onp, model, pname, prec, wide, tol):
     T, M = 257, 3
-    P = transition(M)
+    P = br.transition(M)
     out = []
     for host in (False, True):
         e, man, w = bank_engine(spe, onp, model, T, M, prec, wide)
-        w = stored(e, w / w.sum(axis=1, keepdims=True))
+        w = stored(w / w.sum(axis=1, keepdims=True), e.dtype)
         if host:
             wp, st = e.bank_mix(M, w.reshape(-1), P)
             wp = wp.reshape(T, M)
@@ -287,7 +239,7 @@ def opposed_tracks(spe, onp, model, T, M, even, lattice, seed=23):
     alike.  About a random axis the scalar part is rounding noise of either sign, the logarithm +-pi axis, and the mixture
     mean -- which has two equally good values there -- a coin toss between two correct programs: such tracks (lattice = False)
     can be held to finite results and status, not to parity."""
-    man, mu, cov, _ = make_tracks(spe, onp, model, T, M, seed=seed)
+    man, mu, cov, _ = br.make_tracks(spe, onp, model, T, M, seed=seed)
     so = [s_ for kind, s_, _, _ in man.fields if kind == "so3"][0]
     rng = np.random.default_rng(seed + M)
     w = np.zeros((T, M))
@@ -321,7 +273,7 @@ def test_hypothesis_opposite_the_heaviest_one(spe, onp, model, pname, prec, wide
     moments published under WARN_MEAN_NOCONV are those of the reference stopped at the same cap.
     (The sharp test of Jr^-1 towards pi is tests/test_gpu_jacobian_primitives.py.)"""
     T = 7
-    P = transition(M)
+    P = br.transition(M)
     for even in (False, True):
         kw = dict(max_it=1) if even else {}
         man, mu0, cov0, w0, so = opposed_tracks(spe, onp, model, T, M, even, lattice=True)
@@ -330,7 +282,7 @@ def test_hypothesis_opposite_the_heaviest_one(spe, onp, model, pname, prec, wide
         latch_inputs(spe, e, model)
         if even:
             e.configure(mean_max_iter=1)
-        w = stored(e, w0)
+        w = stored(w0, e.dtype)
         mu, cov, init = downloaded(e, man, T, M)
         tr = np.arange(T)
         for j in (tr % M, (tr + 1) % M):
@@ -344,19 +296,19 @@ def test_hypothesis_opposite_the_heaviest_one(spe, onp, model, pname, prec, wide
         assert (conv == (not even)).all()
         m_g, C_g, st, _ = combine_dev(e, M, w)
         assert np.isfinite(m_g).all() and np.isfinite(C_g).all() and np.array_equal(st, want)
-        em, ec = scaled_err(m_g, m_r), scaled_err(C_g, C_r)
+        em, ec = scaled(m_g, m_r), scaled(C_g, C_r)
         print(f"bank parity {model} {pname} M={M} opposed {'0.5/0.5 cap=1' if even else 'tiny weight'} combine: mean {em:.3e} cov {ec:.3e}")
         assert em <= tol and ec <= tol
         name = f"bank/{model}/{pname}/M={M}/opposed{'-cap=1' if even else ''}"
         scaled_combine(name + "/combine", model, pname, m_g, C_g, m_r, C_r, mu, cov, w, **kw)
         # ---- mix
-        Pk = stored(e, P) if (prec == 1 and not wide) else P
+        Pk = stored(P, e.dtype) if (prec == 1 and not wide) else P
         mu_r, cov_r, c_r, conv = br.mix(man, mu, cov, w, Pk, **kw)
         assert (conv == (not even)).all()
         wp, st = mix_dev(e, M, w, P)
         mu_g, cov_g, _ = downloaded(e, man, T, M)
         assert np.isfinite(mu_g).all() and np.isfinite(cov_g).all() and np.array_equal(st, want)
-        em, ec, ew = scaled_err(mu_g, mu_r), scaled_err(cov_g, cov_r), scaled_err(wp, c_r)
+        em, ec, ew = scaled(mu_g, mu_r), scaled(cov_g, cov_r), scaled(wp, c_r)
         print(f"bank parity {model} {pname} M={M} opposed {'0.5/0.5 cap=1' if even else 'tiny weight'} mix:     mean {em:.3e} cov {ec:.3e}")
         assert em <= tol and ec <= tol and ew <= tol
         scaled_mix(name + "/mix", model, pname, mu_g, cov_g, mu_r, cov_r, mu, cov, w, Pk, **kw)
@@ -365,7 +317,7 @@ def test_hypothesis_opposite_the_heaviest_one(spe, onp, model, pname, prec, wide
     man, mu0, cov0, w0, so = opposed_tracks(spe, onp, model, T, M, even=False, lattice=False)
     e = new_engine(spe, model, T * M, prec, wide)
     e.initialize(mu0.reshape(T * M, man.S), cov0.reshape(T * M, man.D, man.D))
-    w = stored(e, w0)
+    w = stored(w0, e.dtype)
     m_g, C_g, st, _ = combine_dev(e, M, w)
     assert np.isfinite(m_g).all() and np.isfinite(C_g).all() and (st == 0).all()
     wp, st = mix_dev(e, M, w, P)
@@ -387,11 +339,11 @@ def test_one_hot_weights_and_identity_transition_keep_the_bits(spe, onp, model, 
     assert (st == 0).all()
     assert np.array_equal(m_g, mu[np.arange(T), pick]) and np.array_equal(C_g, cov[np.arange(T), pick])
     # Pi = I: w_{j|i} is the one-hot on i, every hypothesis is written back with its own bits
-    w = stored(e, w / w.sum(axis=1, keepdims=True))
-    before = snapshot(e)
+    w = stored(w / w.sum(axis=1, keepdims=True), e.dtype)
+    before = snap(e)
     wp, st = mix_dev(e, M, w, np.eye(M))
-    assert (st == 0).all() and same_snapshot(before, snapshot(e))
-    assert scaled_err(wp, w) <= tol
+    assert (st == 0).all() and same_snapshot(before, snap(e))
+    assert scaled(wp, w) <= tol
     e.close()
 
 
@@ -401,10 +353,10 @@ def test_zero_weight_hypothesis_never_reaches_the_result(spe, onp, model, pname,
     """hypothesis 1 of every track has weight exactly 0 and holds 1e300 / NaN / -1e300 in turn: the results are those of the
     track whose hypothesis 1 holds an ordinary state, bit for bit, and those of the reference without it"""
     T, M = 258, 3
-    man, mu, cov, w = make_tracks(spe, onp, model, T, M)
+    man, mu, cov, w = br.make_tracks(spe, onp, model, T, M)
     w[:, 1] = 0.0
     w /= w.sum(axis=1, keepdims=True)
-    P = transition(M)
+    P = br.transition(M)
     res = []
     for poisoned in (False, True):
         mu_p, cov_p = mu.copy(), cov.copy()
@@ -414,7 +366,7 @@ def test_zero_weight_hypothesis_never_reaches_the_result(spe, onp, model, pname,
             cov_p[:, 1] = bad[:, None, None]
         e = new_engine(spe, model, T * M, prec, wide)
         e.initialize(mu_p.reshape(T * M, -1), cov_p.reshape(T * M, man.D, man.D))
-        ws = stored(e, w)
+        ws = stored(w, e.dtype)
         m_g, C_g, st, _ = combine_dev(e, M, ws)
         assert (st == 0).all()
         wp, st = mix_dev(e, M, ws, P)
@@ -423,9 +375,9 @@ def test_zero_weight_hypothesis_never_reaches_the_result(spe, onp, model, pname,
         res.append((m_g, C_g, wp, mu_g[:, [0, 2]], cov_g[:, [0, 2]]))
         if not poisoned:
             keep = [0, 2]
-            mu_d, cov_d = stored(e, mu), stored(e, cov)
+            mu_d, cov_d = stored(mu, e.dtype), stored(cov, e.dtype)
             m_r, C_r, _ = br.mixture(man, mu_d[:, keep], cov_d[:, keep], ws[:, keep])
-            assert scaled_err(m_g, m_r) <= tol and scaled_err(C_g, C_r) <= tol
+            assert scaled(m_g, m_r) <= tol and scaled(C_g, C_r) <= tol
             scaled_combine(f"bank/{model}/{pname}/zero-weight/combine", model, pname, m_g, C_g, m_r, C_r, mu_d[:, keep], cov_d[:, keep],
                            ws[:, keep])
         e.close()
@@ -438,8 +390,8 @@ def test_zero_weight_hypothesis_never_reaches_the_result(spe, onp, model, pname,
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_per_track_failures_stay_on_their_track(spe, onp, model, pname, prec, wide, tol):
     T, M = 64, 4
-    man, mu, cov, w = make_tracks(spe, onp, model, T, M)
-    P = transition(M)
+    man, mu, cov, w = br.make_tracks(spe, onp, model, T, M)
+    P = br.transition(M)
     UNINIT, NEG, NAN, SUM = 5, 18, 35, 50     # tracks 4 ... 7, 16 ... 19, 32 ... 35, 48 ... 51 share a wavefront with one each
     runs = []
     for broken in (False, True):
@@ -451,7 +403,7 @@ def test_per_track_failures_stay_on_their_track(spe, onp, model, pname, prec, wi
             e.initialize(flat_mu[k + 1:], flat_cov[k + 1:], first=k + 1)
         else:
             e.initialize(flat_mu, flat_cov)
-        ws = stored(e, w)
+        ws = stored(w, e.dtype)
         if broken:
             ws[NEG, 1] = -ws[NEG, 1]
             ws[NAN, 3] = np.nan
@@ -500,12 +452,12 @@ def test_weights_against_the_reference(spe, onp, pname, prec, wide, tol):
     T, M = 1001, 4
     e, man, w = bank_engine(spe, onp, "pose", T, M, prec, wide)
     rng = np.random.default_rng(5)
-    lw = stored(e, np.log(w / w.sum(axis=1, keepdims=True)))
+    lw = stored(np.log(w / w.sum(axis=1, keepdims=True)), e.dtype)
     ll = rng.uniform(-30.0, 5.0, (T, M))
     ll[::7] -= 690.0                       # log-likelihoods down to -720
     ll[3::11, 2] = np.nan                  # a dead hypothesis
     ll[5::50] = np.nan                     # every hypothesis of the track dead
-    ll = stored(e, ll)
+    ll = stored(ll, e.dtype)
     t = tdt(e)
 
     def run(lw_in, ll_in, want_w=True):
@@ -526,7 +478,7 @@ def test_weights_against_the_reference(spe, onp, pname, prec, wide, tol):
         assert np.array_equal(st, np.where(dead, spe.ST_ERR_WEIGHTS, 0))
         assert np.array_equal(np.isneginf(lo), np.isneginf(lo_r)) and np.array_equal(wo == 0, wo_r == 0)
         fin = np.isfinite(lo_r)
-        el, ew = scaled_err(lo[fin], lo_r[fin]), scaled_err(wo, wo_r)
+        el, ew = scaled(lo[fin], lo_r[fin]), scaled(wo, wo_r)
         print(f"bank parity weights {pname} prior={'yes' if lw_in is not None else 'no'} loglik={'yes' if ll_in is not None else 'no'}: "
               f"logw {el:.3e} w {ew:.3e} max|sum w - 1| {np.abs(wo.sum(axis=1) - 1).max():.3e}")
         assert el <= tol and ew <= tol
@@ -590,12 +542,12 @@ def test_imm_run_end_to_end(spe, onp, pname, prec, wide, tol):
     e.set_process_noise(R)
     # the reference starts from the state, noise and samples as the engine's arrays hold them
     mu_s, cov_s, _ = e.state()
-    z_s, Q_s, R_s = stored(e, z), stored(e, Q), stored(e, R)
+    z_s, Q_s, R_s = stored(z, e.dtype), stored(Q, e.dtype), stored(R, e.dtype)
     ref = imm_reference(onp, mu_s, cov_s, z_s, Q_s, R_s, P, cycles, dt)
     # How many cycles the storage format itself holds the gate: the same chain, float64 arithmetic, every launch's results
     # rounded to the engine's storage format, against the reference proper.  The engine is held to the gate for these cycles.
     ref_st = imm_reference(onp, mu_s, cov_s, z_s, Q_s, R_s, P, cycles, dt, store=e.dtype)
-    fmt = [max(scaled_err(a[0], b[0]), scaled_err(a[1], b[1]), scaled_err(a[2], b[2])) for a, b in zip(ref_st, ref)]
+    fmt = [max(scaled(a[0], b[0]), scaled(a[1], b[1]), scaled(a[2], b[2])) for a, b in zip(ref_st, ref)]
     held = next((c for c, v in enumerate(fmt) if v > tol), cycles)
     print(f"bank parity imm {pname}: the reference with {np.dtype(e.dtype).name} storage holds {tol:.3e} for {held} of {cycles} cycles "
           f"(its own error per cycle: {' '.join(f'{v:.2e}' for v in fmt)})")
@@ -623,9 +575,9 @@ def test_imm_run_end_to_end(spe, onp, pname, prec, wide, tol):
         e.sync()
         assert e.status_summary() == 0 and (st.cpu().numpy() == 0).all()
         m_r, C_r, w_r = ref[c]
-        errs = (scaled_err(mu_o.cpu().numpy().astype(np.float64), m_r),
-                scaled_err(unpack(cov_o.cpu().numpy().astype(np.float64), 12), C_r),
-                scaled_err(w.cpu().numpy().astype(np.float64).reshape(T, 2), w_r))
+        errs = (scaled(mu_o.cpu().numpy().astype(np.float64), m_r),
+                scaled(unpack(cov_o.cpu().numpy().astype(np.float64), 12), C_r),
+                scaled(w.cpu().numpy().astype(np.float64).reshape(T, 2), w_r))
         worst = [max(a, b) for a, b in zip(worst, errs)]
         print(f"bank parity imm {pname} cycle {c:2d}: mean {errs[0]:.3e} cov {errs[1]:.3e} weights {errs[2]:.3e}")
         if pname == "f64" and c in (0, cycles - 1):   # a chain of launches: the fp64 bound needs no count of roundings

@@ -27,13 +27,13 @@ import torch
 import bearing_f32 as bf
 import bearing_reference as br
 import feature_scaled_parity as fsp
+from engine_support import ACC_COV, Case, engine_of, man_of, new_engine, same, same_snapshot, scaled, snapshot, tdt
 from oracle import ukf_numpy as on
 
 pytestmark = pytest.mark.gpu
 
 N = 1022   # not a multiple of four: the last workgroup holds two filters
 PRECS = [("f64", 0, 0, 1e-9), ("f32", 1, 0, 1e-4), ("f32w", 1, 1, 1e-9 + 2.0 ** -23)]
-ACC_COV = 0.01 * np.eye(3)
 ST_NONFINITE, ST_CHOLESKY, ST_NOCONV, ST_UNINIT, ST_INACTIVE, ST_REJECTED = 1 << 4, 1 << 5, 1 << 6, 1 << 7, 1 << 8, 1 << 9
 OUT_KEYS = ("z_pred", "S", "innov", "maha", "loglik")
 ALL_KEYS = ("mu", "cov") + OUT_KEYS + ("status",)
@@ -42,32 +42,12 @@ BATCHES = {"ordinary": (True, 1.0, 15.0, 80.0), "tight": (True, 1e-8, 15.0, 80.0
 WIDE_SCALE = {"pose": 4.0, "orient": 100.0}
 
 
-def tdt(e):
-    return torch.float64 if e.dtype == np.float64 else torch.float32
-
-
-def man_of(model):
-    return on.POSE if model == "pose" else on.ORIENT
-
-
 def ids_of(model):
     return br.POSE_IDS if model == "pose" else br.ORIENT_IDS
 
 
 def main_id(model):
     return br.POSE_POINT if model == "pose" else br.ORIENT_NAV_DIRECTION
-
-
-def new_engine(spe, model, n, prec, wide, **kw):
-    cfg = dict(kw)
-    if wide:
-        cfg["wide_arithmetic"] = 1
-    if model == "pose":
-        return spe.BatchPoseUKF(n, precision=prec, **cfg)
-    sy = spe.synth
-    e = spe.BatchOrientationUKF(n, sy.ORIENT_TAU, sy.ORIENT_TAU, sy.ORIENT_LATITUDE, precision=prec, **cfg)
-    e.set_process_noise(sy.orient_process_noise())
-    return e
 
 
 def downloaded_state(spe, model, n, prec, wide, cycles, scale):
@@ -94,10 +74,6 @@ def downloaded_state(spe, model, n, prec, wide, cycles, scale):
     dtype = e.dtype
     e.close()
     return mu, cov, dtype
-
-
-class Case:
-    """a state as downloaded and inputs as stored; fresh engines are initialised from it"""
 
 
 _CACHE = {}
@@ -127,14 +103,6 @@ def sub_case(big, n):
     c.z = {k: v[:n] for k, v in big.z.items()}
     c.refs = {}
     return c
-
-
-def engine_of(spe, c, **kw):
-    e = new_engine(spe, c.model, c.n, c.prec, c.wide, **kw)
-    e.initialize(c.mu, c.cov)
-    m, C, _ = e.state()
-    assert np.array_equal(m, c.mu) and np.array_equal(C, c.cov)   # the downloaded state goes back in bit for bit
-    return e
 
 
 def run(e, ids, z, Q, mount, point, commit=True, q_uniform=False):
@@ -186,10 +154,6 @@ def reference(c, ids, gate=-1.0, max_it=on.MEAN_MAX_IT):
     if key is not None:
         c.refs[key] = ref
     return ref
-
-
-def scaled(x, ref):
-    return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref)))) if x.size else 0.0
 
 
 def meas_distances(o, ref):
@@ -256,11 +220,6 @@ def check_parity(name, c, got, ref, ids, rows=None):
         judge_meas("bearing/" + name, c.pname, got, ref, scored, f32=lambda: (f32()["f32"], f32()["f64"]))
 
 
-def same(a, b, keys=ALL_KEYS, rows=None):
-    rows = slice(None) if rows is None else rows
-    return all(np.array_equal(a[k][rows], b[k][rows], equal_nan=True) for k in keys)
-
-
 def cycling_ids(model, n):
     """every model of the engine, -1, an id of the other engine and one beyond 2, so that four wave-mates always differ"""
     table = list(ids_of(model)) + [-1, br.ORIENT_NAV_DIRECTION if model == "pose" else br.POSE_POINT, 3, main_id(model), 7]
@@ -305,7 +264,7 @@ def test_parity(spe, model, pname, batch):
     assert np.array_equal(got["mu"][idle], c.mu[idle]) and np.array_equal(got["cov"][idle], c.cov[idle])
     assert all(np.isnan(got[k][idle]).all() for k in OUT_KEYS)
     for mid in ids_of(model):
-        assert same(got, uniform[mid], rows=per == mid), mid
+        assert same(got, uniform[mid], ALL_KEYS, rows=per == mid), mid
     check_parity(f"{model}/{pname}/{batch}/per-filter-ids", c, got, reference(c, per), per)
 
 
@@ -356,18 +315,6 @@ def test_mean_cap(spe, model):
 
 
 # ------------------------------------------------------------------------------------------------------- bit-level properties
-def snapshot(e):
-    """everything of the engine that can be downloaded"""
-    mu, cov, init = e.state()
-    noise = np.array([e.process_noise(i) for i in range(e.capacity)])
-    latch = e.rotation_rate() if e.model == 1 else np.zeros(0)
-    return mu, cov, init, e.status(), e.last_measurement_time(), noise, latch
-
-
-def same_snap(a, b):
-    return all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
-
-
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_bit_level_properties(spe, model):
     n = 255
@@ -391,32 +338,32 @@ def test_bit_level_properties(spe, model):
     # per-filter mount / point arrays that repeat the uniform ones; a device array filled with the id; per-filter Q repeated
     # against ONE 3x3
     e = fresh()
-    assert same(run(e, np.full(n, mid, dtype=np.int32), c.z[mid], c.Q, np.tile(mount1, (n, 1)), np.tile(point1, (n, 1))), base)
+    assert same(run(e, np.full(n, mid, dtype=np.int32), c.z[mid], c.Q, np.tile(mount1, (n, 1)), np.tile(point1, (n, 1))), base, ALL_KEYS)
     e.close()
     e, e2 = fresh(), fresh()
     assert same(run(e, mid, c.z[mid], c.Q[0], mount1, point1, q_uniform=True),
-                run(e2, mid, c.z[mid], np.tile(c.Q[0], (n, 1, 1)), mount1, point1))
+                run(e2, mid, c.z[mid], np.tile(c.Q[0], (n, 1, 1)), mount1, point1), ALL_KEYS)
     e.close(); e2.close()
     # only the lower triangle of Q is read
     e = fresh()
     Qu = c.Q.copy()
     Qu[:, 0, 1], Qu[:, 0, 2], Qu[:, 1, 2] = 5.0, -3.0, 1e6
-    assert same(run(e, mid, c.z[mid], Qu, mount1, point1), base)
+    assert same(run(e, mid, c.z[mid], Qu, mount1, point1), base, ALL_KEYS)
     e.close()
     # a gate nothing reaches = no gate
     e = fresh(gate_chi2=1e300)
-    assert same(run(e, mid, c.z[mid], c.Q, mount1, point1), base)
+    assert same(run(e, mid, c.z[mid], c.Q, mount1, point1), base, ALL_KEYS)
     e.close()
     # the host form = the device form (per-filter ids, mounts and points too)
     e = fresh()
     o = e.update_bearing(mid, c.z[mid], c.Q, mount1, point1)
     o["mu"], o["cov"], _ = e.state()
-    assert same(o, base)
+    assert same(o, base, ALL_KEYS)
     e.close()
     e, e2 = fresh(), fresh()
     o = e.update_bearing(per, mixed_z(c, per), c.Q, c.mount, c.point)
     o["mu"], o["cov"], _ = e.state()
-    assert same(o, run_case(e2, c, per))
+    assert same(o, run_case(e2, c, per), ALL_KEYS)
     e.close(); e2.close()
     # commit = 0: the whole downloadable engine keeps its bits, the outputs are the committing call's, and the next
     # prediction is an untouched twin's
@@ -424,16 +371,16 @@ def test_bit_level_properties(spe, model):
     before = snapshot(e)
     dry = run(e, mid, c.z[mid], c.Q, mount1, point1, commit=False)
     dry_per = run_case(e, c, per, commit=False)
-    assert same_snap(before, snapshot(e)) and same_snap(before, snapshot(twin))
-    assert same(dry, base, keys=OUT_KEYS + ("status",)) and np.array_equal(dry["mu"], c.mu) and np.array_equal(dry["cov"], c.cov)
+    assert same_snapshot(before, snapshot(e)) and same_snapshot(before, snapshot(twin))
+    assert same(dry, base, OUT_KEYS + ("status",)) and np.array_equal(dry["mu"], c.mu) and np.array_equal(dry["cov"], c.cov)
     assert np.array_equal(dry_per["status"], np.where(np.isin(per, ids_of(model)), 0, ST_INACTIVE))
     e.predict(0.013); twin.predict(0.013)
-    assert same_snap(snapshot(e), snapshot(twin))
+    assert same_snapshot(snapshot(e), snapshot(twin))
     e.close(); twin.close()
     # commit = 0, then commit = 1: the same numbers as commit = 1 alone
     e = fresh()
     run(e, mid, c.z[mid], c.Q, mount1, point1, commit=False)
-    assert same(run(e, mid, c.z[mid], c.Q, mount1, point1), base)
+    assert same(run(e, mid, c.z[mid], c.Q, mount1, point1), base, ALL_KEYS)
     e.close()
 
 
@@ -470,7 +417,7 @@ def test_host_array_form_fp32(spe, pname):
         o = e.update_bearing(mid, z, c.Q, mt, pt)
         o["mu"], o["cov"], _ = e.state()
         dev = run(twin, mid, f32(z), c.Q, f32(mt), f32(pt))
-        assert same(o, dev) and np.array_equal(e.status(), twin.status()) and (o["status"] == 0).all()
+        assert same(o, dev, ALL_KEYS) and np.array_equal(e.status(), twin.status()) and (o["status"] == 0).all()
         e.close(); twin.close()
 
 
@@ -532,8 +479,8 @@ def test_failures_stay_inside_their_filter(spe, model):
     twin = build()
     ok = run(twin, ids, z, Q, mount, point)
     twin.close(); e.close()
-    assert same(ok, clean, keys=OUT_KEYS + ("status",))
-    assert same(got, ok, rows=~failing)
+    assert same(ok, clean, OUT_KEYS + ("status",))
+    assert same(got, ok, ALL_KEYS, rows=~failing)
     for i in (at_sensor - 1, at_sensor + 1, unused):
         assert not np.array_equal(got["mu"][i], mu[i])
     ref = br.update_bearing(man, mu_f, cov_bad, ids, zb, Q, mb, pb, initialised=init)

@@ -57,8 +57,6 @@ primitive errors are drawn up to the pinned bounds, reaches 0.5 - 0.8 of B.)
 """
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -66,9 +64,8 @@ import pytest
 pytest.importorskip("mpmath")
 
 import chol_reference as R  # noqa: E402
+from probe_support import load  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "cpp", "build", "libchol_probe.so")
 IN, OK, RS, LC, COL, OUT = 176, 0, 1, 17, 225, 481     # doubles per record and offsets (tests/cpp/chol_probe.hip CHP_*)
 PACKED, ROWS = 0, 1
 F64, F32 = R.F64, R.F32
@@ -87,16 +84,10 @@ SHORT_IDS = [i for c, i in zip(CASES, IDS) if c in SHORT_CASES]
 
 
 # ------------------------------------------------------------------------------------------------------------ the device
-@functools.lru_cache(maxsize=None)
 def _lib():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), "build/libchol_probe.so"])
-    lib = C.CDLL(LIB)
-    lib.chol_probe.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    lib.chol_probe.restype = C.c_int
-    lib.chol_probe_variant.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
-    lib.chol_probe_variant.restype = C.c_int
-    return lib
+    return load("libchol_probe",
+                chol_probe=(C.c_int, (C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double))),
+                chol_probe_variant=(C.c_int, (C.c_int, C.c_int, C.POINTER(C.c_int))))
 
 
 @functools.lru_cache(maxsize=None)
@@ -165,7 +156,7 @@ def records(prec, D):
 
 
 def placements(prec, D, FPW, tail):
-    """Record order of one launch, as indices into records() -- the idea of placements() in test_gpu_so3_primitives.py:
+    """Record order of one launch, as indices into records() -- the idea of placements() in probe_support.py:
     every record at row 0 among copies of one benign matrix (its base result), then a subset of targets at each of the FPW
     row positions with a NaN, an indefinite, an Inf matrix and a matrix of another family in the other rows, then `tail`
     records that leave the last wavefront ragged (rows past the end re-evaluate the last record)."""
@@ -267,7 +258,7 @@ def test_forward_error(prec, D, KS, PUB, G):
     worst, covered = 0.0, 0
     for i in range(span["cond"].start, span["cond"].stop):
         d = 1.0 / np.sqrt(np.diag(A[i]))
-        lam = np.linalg.eigvalsh(R.scaled(A[i]))
+        lam = np.linalg.eigvalsh(R.unit_diagonal(A[i]))
         lmin = R.lambda_min_H(A[i], prec)
         bound = R.forward_bound(prec, D, lam[-1] / lmin)
         covered += np.isfinite(bound)

@@ -1,6 +1,6 @@
 """Covariance conditioning on the device (ukfb_condition_dev and its host form, include/ukf_batch.h).
 
-States: those of tests/test_gpu_sensor_meas.py (synth.pose_initial / orient_initial after two real cycles, downloaded; its `case`
+States: those of tests/sensor_meas_cases.py (synth.pose_initial / orient_initial after two real cycles, downloaded; its `case`
 cache is shared).  Every filter's covariance is replaced on the host through its correlation eigen-decomposition
 (tests/condition_reference.make_batch, rounded to the engine's storage) and uploaded with initialize, which stores any matrix.
 Four quarters: (a) untouched, (b) lambda_min = -1e-3, (c) two eigenvalues at -0.3 and -0.05, (d) lambda_min = eps / 8 with one
@@ -17,40 +17,22 @@ import pytest
 import torch
 
 import condition_reference as cr
-import test_gpu_sensor_meas as tsm
+import sensor_meas_cases as smc
+from engine_support import ACC_COV, dev, host, man_of, new_engine, same, same_snapshot, scaled, snapshot, stored, tdt, unpack
+from probe_support import LDS_PATTERNS, lds_poison
 
 pytestmark = pytest.mark.gpu
 
-N = tsm.N   # 1022: not a multiple of four
-PRECS = tsm.PRECS
+N = smc.N   # 1022: not a multiple of four
+PRECS = smc.PRECS
 EPS = {"f64": 1e-10, "f32": 1e-4, "f32w": 1e-4}
 ST_NONFINITE, ST_CHOLESKY, ST_UNINIT, ST_INACTIVE, ST_REPAIRED = 1 << 4, 1 << 5, 1 << 7, 1 << 8, 1 << 11
 OUT_KEYS = ("eig_min", "eig_max", "out_mu", "out_cov", "status")
 ALL_KEYS = ("mu", "cov") + OUT_KEYS
-ACC_COV = tsm.ACC_COV
-stored = tsm.stored
-man_of = tsm.man_of
-
-
-def dev(e, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", tsm.tdt(e))
-
-
-def host(t):
-    return t.double().cpu().numpy()
-
-
-def unpack(p, D):
-    """[n, PK] packed lower triangle (row r: r (r + 1) / 2 ... + r) -> [n, D, D] symmetric"""
-    r, c = np.tril_indices(D)
-    full = np.empty((p.shape[0], D, D))
-    full[:, r, c] = p
-    full[:, c, r] = p
-    return full
 
 
 class Batch:
-    """a case of test_gpu_sensor_meas with its covariances replaced: mu, cov as the engine stores them, the floor, the quarters"""
+    """a case of sensor_meas_cases with its covariances replaced: mu, cov as the engine stores them, the floor, the quarters"""
 
 
 _BATCHES = {}
@@ -59,7 +41,7 @@ _BATCHES = {}
 def batch(spe, model, pname, n=N):
     key = (model, pname, n)
     if key not in _BATCHES:
-        c = tsm.case(spe, model, pname, n)
+        c = smc.case(spe, model, pname, n)
         b = Batch()
         b.c, b.model, b.pname, b.n, b.tol, b.wide, b.dtype, b.eps = c, model, pname, n, c.tol, c.wide, c.dtype, EPS[pname]
         b.man = man_of(model)
@@ -74,7 +56,7 @@ def engine_of(spe, b, mu=None, cov=None, skip=(), **kw):
     """a fresh engine holding (mu, cov) of the batch bit for bit; filters in `skip` stay uninitialised"""
     c = b.c
     mu, cov = b.mu if mu is None else mu, b.cov if cov is None else cov
-    e = tsm.new_engine(spe, c.model, mu.shape[0], c.prec, c.wide, **kw)
+    e = new_engine(spe, c.model, mu.shape[0], c.prec, c.wide, **kw)
     if skip:
         for i in range(mu.shape[0]):
             if i not in skip:
@@ -91,7 +73,7 @@ def engine_of(spe, b, mu=None, cov=None, skip=(), **kw):
 
 def run(e, v, eps, select=None, renorm=False, commit=True, outs=True):
     """-> dict(mu, cov: the engine's state after the call; eig_min, eig_max, out_mu, out_cov, status: the call's outputs)"""
-    n, dt, D = e.capacity, tsm.tdt(e), e.D
+    n, dt, D = e.capacity, tdt(e), e.D
     vd = dev(e, v)
     sd = None if select is None else torch.from_numpy(np.asarray(select, dtype=np.uint8)).to("cuda")
     o = {}
@@ -116,11 +98,6 @@ def reference(b, mu=None, cov=None, **kw):
     return cr.condition(b.man, b.mu if mu is None else mu, b.cov if cov is None else cov, b.v, b.eps, u_storage=b.u_storage, **kw)
 
 
-def same(a, b, keys=ALL_KEYS, rows=None):
-    rows = slice(None) if rows is None else rows
-    return all(np.array_equal(a[k][rows], b[k][rows], equal_nan=True) for k in keys)
-
-
 def check_parity(name, b, got, ref, cov_in=None, rows=None):
     """the file's bound on eig_min, eig_max, the covariance output and the engine's covariance, correlation-scaled"""
     cov_in = b.cov if cov_in is None else cov_in
@@ -130,8 +107,8 @@ def check_parity(name, b, got, ref, cov_in=None, rows=None):
     r = {k: np.asarray(ref[k], dtype=np.float64)[rows] for k in ("eig_min", "eig_max", "cov")}
     if b.wide:   # the engine stores fp32
         r = {k: v.astype(np.float32).astype(np.float64) for k, v in r.items()}
-    err = {"eig_min": tsm.scaled(got["eig_min"][rows], r["eig_min"]), "eig_max": tsm.scaled(got["eig_max"][rows], r["eig_max"]),
-           "out_cov": tsm.scaled(got["out_cov"][rows] / scale, r["cov"] / scale), "cov": tsm.scaled(got["cov"][rows] / scale, r["cov"] / scale)}
+    err = {"eig_min": scaled(got["eig_min"][rows], r["eig_min"]), "eig_max": scaled(got["eig_max"][rows], r["eig_max"]),
+           "out_cov": scaled(got["out_cov"][rows] / scale, r["cov"] / scale), "cov": scaled(got["cov"][rows] / scale, r["cov"] / scale)}
     print(f"PARITY condition {name} n={int(rows.sum())} " + " ".join(f"max_scaled_d{k}={v:.3e}" for k, v in err.items()) + f" tol={b.tol:.3e}")
     assert all(v <= b.tol for v in err.values()), (name, err, b.tol)
 
@@ -243,19 +220,19 @@ def test_read_only_mode(spe, model):
     stamps = np.arange(1, b.n + 1, dtype=np.int64) * 1000 + 7
     e = engine_of(spe, b)
     e.set_last_measurement_time(stamps)
-    before = tsm.snapshot(e)
+    before = snapshot(e)
     dry = run(e, b.v, b.eps, commit=False)
-    assert tsm.same_snap(before, tsm.snapshot(e))
-    assert same(dry, base, keys=OUT_KEYS) and np.array_equal(dry["mu"], b.mu) and np.array_equal(dry["cov"], b.cov)
+    assert same_snapshot(before, snapshot(e))
+    assert same(dry, base, OUT_KEYS) and np.array_equal(dry["mu"], b.mu) and np.array_equal(dry["cov"], b.cov)
     alone = run(e, b.v, b.eps, outs=False)
-    assert same(alone, base, keys=("mu", "cov")) and np.array_equal(e.status(), base["status"])
-    after = tsm.snapshot(e)
+    assert same(alone, base, ("mu", "cov")) and np.array_equal(e.status(), base["status"])
+    after = snapshot(e)
     assert np.array_equal(e.last_measurement_time(), stamps)
     assert all(np.array_equal(x, y, equal_nan=True) for x, y in zip(before[4:], after[4:]))
     e.close()
     # select = NULL equals all ones
     e = engine_of(spe, b)
-    assert same(run(e, b.v, b.eps, select=np.ones(b.n, dtype=np.uint8)), base)
+    assert same(run(e, b.v, b.eps, select=np.ones(b.n, dtype=np.uint8)), base, ALL_KEYS)
     e.close()
 
 
@@ -291,7 +268,7 @@ def test_failures_stay_inside_their_filter(spe, model):
         assert np.array_equal(got["cov"][failing], cov_b[failing], equal_nan=True)
         for k in ("eig_min", "eig_max", "out_mu", "out_cov"):
             assert np.isnan(got[k][failing]).all(), k
-        assert same(got, clean, rows=~failing)
+        assert same(got, clean, ALL_KEYS, rows=~failing)
         cov_r = cov.copy()
         cov_r[upper, 0, D - 1] = np.inf   # never read
         ref = cr.condition(b.man, b.mu, cov_r, b.v, b.eps, select=sel, initialised=init)
@@ -364,7 +341,7 @@ def test_quaternion_renormalisation(spe, model, pname):
     assert np.array_equal(got["mu"][:, others], mu[:, others])
     qn = got["mu"][odd, Q:Q + 4]
     norm_err, dir_err = np.abs(np.sum(qn * qn, axis=1) - 1.0).max(), np.abs(qn - unit[odd]).max()
-    ref_err = tsm.scaled(got["mu"], stored(ref["mu"], b.dtype) if b.wide else ref["mu"])
+    ref_err = scaled(got["mu"], stored(ref["mu"], b.dtype) if b.wide else ref["mu"])
     print(f"PARITY condition renormalise {model}/{pname} n={n} | |q|^2 - 1 |={norm_err:.3e} direction={dir_err:.3e} rule={8 * u:.3e} "
           f"max_scaled_dmu={ref_err:.3e} tol={b.tol:.3e}")
     assert norm_err <= 8 * u and dir_err <= 4 * u and ref_err <= b.tol
@@ -529,15 +506,14 @@ def test_no_dependence_on_leftover_lds(spe):
     """the LDS of every compute unit filled with NaN, Inf and zero patterns (tests/cpp/lds_poison.hip, as
     tests/test_gpu_lds_leftovers.py does for the cycle kernels) in front of the call: the same bits -- every LDS scalar the kernel
     reads is one it wrote, the rows that never publish included (wavefronts with failing and unselected rows are in the batch)"""
-    import test_gpu_lds_leftovers as tl
-    poison = tl._poison()
+    poison = lds_poison()
     for model, pname in (("pose", "f64"), ("orient", "f32")):
         b = batch(spe, model, pname, 255)
         sel = (np.arange(b.n) % 7 != 3).astype(np.uint8)
         cov = b.cov.copy()
         cov[21, 2, 1] = cov[21, 1, 2] = np.nan
         runs = []
-        for pat in (None,) + tl.PATTERNS:
+        for pat in (None,) + LDS_PATTERNS:
             e = engine_of(spe, b, cov=cov)
             if pat is not None:
                 torch.cuda.synchronize()
@@ -547,4 +523,4 @@ def test_no_dependence_on_leftover_lds(spe):
         assert (runs[0]["status"][sel == 0] == ST_INACTIVE).all() and runs[0]["status"][21] == ST_CHOLESKY
         assert (runs[0]["status"] == ST_REPAIRED).sum() > b.n // 2
         for r in runs[1:]:
-            assert same(r, runs[0]), (model, pname)
+            assert same(r, runs[0], ALL_KEYS), (model, pname)

@@ -17,6 +17,7 @@ import torch
 import delayed_reference as dr
 import feature_scaled_parity as fsp
 import smoother_reference as sr
+from engine_support import dev, host, new_engine, same_snapshot, scaled_ignoring_nan, snapshot, stored, tdt, unpack
 
 pytestmark = pytest.mark.gpu
 
@@ -29,24 +30,9 @@ ST_UNINITIALISED, ST_INACTIVE, ST_REJECTED_GATE = 1 << 7, 1 << 8, 1 << 9
 UKFB_ERR_OUT_OF_RANGE = 4
 
 
-def tdt(e):
-    return torch.float64 if e.dtype == np.float64 else torch.float32
-
-
-def dev(e, x, dtype=None):
-    return torch.from_numpy(np.ascontiguousarray(x)).to("cuda", dtype or tdt(e))
-
-
-def new_engine(spe, model, n, prec, wide, **kw):
-    cfg = dict(kw)
-    if wide:
-        cfg["wide_arithmetic"] = 1
-    if model == "pose":
-        return spe.BatchPoseUKF(n, precision=prec, **cfg)
-    sy = spe.synth
-    e = spe.BatchOrientationUKF(n, sy.ORIENT_TAU, sy.ORIENT_TAU, sy.ORIENT_LATITUDE, precision=prec, **cfg)
-    e.set_process_noise(sy.orient_process_noise())
-    return e
+def snap(e):
+    """the engine's snapshot with the process noise of these filters"""
+    return snapshot(e, range(min(e.capacity, 8)))
 
 
 class Recording:
@@ -102,17 +88,6 @@ def record(spe, model, n, prec, wide, steps=STEPS, slots=SLOTS, first=FIRST, ski
     return r
 
 
-def unpack(cov_packed, D):
-    c = cov_packed.double().cpu().numpy()
-    out = np.zeros(c.shape[:-1] + (D, D))
-    k = 0
-    for i in range(D):
-        for j in range(i + 1):
-            out[..., i, j] = out[..., j, i] = c[..., k]
-            k += 1
-    return out
-
-
 def params(spe, r):
     e, sy = r.e, spe.synth
     R = np.array([e.process_noise(i) for i in range(r.n)]) if r.per_filter_noise else e.process_noise()
@@ -125,15 +100,11 @@ def params(spe, r):
     return sr.Params("orient", R, tau_g=sy.ORIENT_TAU, tau_a=sy.ORIENT_TAU, earth=on.earth_rotation(sy.ORIENT_LATITUDE), **kw)
 
 
-def stored(e, x):
-    return np.asarray(x, dtype=np.float64).astype(e.dtype).astype(np.float64)
-
-
 def reference(spe, r, lag, models, z, Q, dt=None, rings=True, mu_hist=None, cov_hist=None, gate_chi2=-1.0):
     """-> (result dict of delayed_reference.update_delayed, the call's arguments for the fp32 evaluation)"""
     e = r.e
     mu = sr.window_order((r.mu_hist if mu_hist is None else mu_hist).double().cpu().numpy(), r.first, r.steps)
-    cov = sr.window_order(unpack(r.cov_hist if cov_hist is None else cov_hist, e.D), r.first, r.steps)
+    cov = sr.window_order(unpack(host(r.cov_hist if cov_hist is None else cov_hist), e.D), r.first, r.steps)
     a = sr.window_order(r.in_a.double().cpu().numpy(), r.first, r.steps)
     b = sr.window_order(r.in_b.double().cpu().numpy(), r.first, r.steps)
     if not rings:
@@ -143,7 +114,7 @@ def reference(spe, r, lag, models, z, Q, dt=None, rings=True, mu_hist=None, cov_
     mu_n, cov_n, _ = e.state()
     p = params(spe, r)
     dt = (r.dt if dt is None else dt)[:r.steps - 1]
-    call = (p, mu, cov, mu_n, cov_n, dt, lag, models, stored(e, z), stored(e, Q))
+    call = (p, mu, cov, mu_n, cov_n, dt, lag, models, stored(z, e.dtype), stored(Q, e.dtype))
     return dr.update_delayed(*call, in_a=a, in_b=b, initialised=r.live, gate_chi2=gate_chi2), call + (a, b)
 
 
@@ -168,15 +139,10 @@ def run(r, lag, models, z, Q, commit=False, dt=None, rings=True, mu_hist=None, c
     out = {k: v.double().cpu().numpy() for k, v in o.items() if k not in ("status", "cov_out")}
     if outputs:
         out["status"] = o["status"].cpu().numpy().astype(np.uint32)
-        out["cov_out"] = unpack(o["cov_out"], e.D)
+        out["cov_out"] = unpack(host(o["cov_out"]), e.D)
         out["S"] = out["S"].reshape(n, 3, 3)
     out["raw"] = o
     return out
-
-
-def scaled(x, ref):
-    with np.errstate(invalid="ignore"):
-        return float(np.nanmax(np.abs(x - ref) / (1.0 + np.abs(ref)))) if np.size(x) else 0.0
 
 
 def same_nan(x, ref):
@@ -192,7 +158,7 @@ def check_parity(name, r, got, ref, call, tol, pname, rows=None):
     figs = {}
     for k in ("mu_out", "cov_out", "z_pred", "S", "innov", "maha", "loglik"):
         assert same_nan(got[k], res[k]), (name, k)
-        figs[k] = scaled(got[k], rnd(res[k]))
+        figs[k] = scaled_ignoring_nan(got[k], rnd(res[k]))
     print(f"PARITY delayed/{name} n={r.n} " + " ".join(f"{k}={v:.3e}" for k, v in figs.items()) + f" tol={tol:.3e}")
     for k, v in figs.items():
         assert v <= tol, (name, k, v, tol)
@@ -236,17 +202,6 @@ def recorded(spe, model, pname):
     return _CACHE[key]
 
 
-def snapshot(e):
-    mu, cov, init = e.state()
-    noise = np.array([e.process_noise(i) for i in range(min(e.capacity, 8))])
-    latch = e.rotation_rate() if e.model == 1 else np.zeros(0)
-    return mu, cov, init, e.status(), e.last_measurement_time(), noise, latch
-
-
-def same_snapshot(a, b):
-    return all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
-
-
 MIXED = np.arange(N) % STEPS   # lags 0 ... 5: the four rows of a wavefront differ
 
 
@@ -261,12 +216,12 @@ def test_parity_commit_modes_and_outputs(spe, model, pname, prec, wide, tol):
     models, z, Q = sample(spe, r, MIXED)
     ref, call = reference(spe, r, MIXED, models, z, Q)
     assert (ref["status"] == 0).all() and ref["committed"].all()
-    before = snapshot(r.e)
+    before = snap(r.e)
     got = run(r, MIXED, models, z, Q, commit=False)
-    assert same_snapshot(before, snapshot(r.e)), "commit = 0 changed the engine"
+    assert same_snapshot(before, snap(r.e)), "commit = 0 changed the engine"
     check_parity(f"{model}/{pname}", r, got, ref, call, tol, pname)
     run(r, MIXED, models, z, Q, commit=True, outputs=False)
-    after = snapshot(r.e)
+    after = snap(r.e)
     assert np.array_equal(after[0], got["mu_out"]) and np.array_equal(after[1], got["cov_out"])
     assert (after[3] == 0).all() and all(np.array_equal(x, y) for x, y in zip(before[4:6], after[4:6]))   # times and noise stay
     r.e.close()
@@ -298,7 +253,7 @@ def test_lag_zero_is_the_ordinary_update(spe, model, pname, prec, wide, tol):
     e.update_dev(0, dev(e, z), dev(e, np.broadcast_to(Q.reshape(1, 9), (254, 9))), meas_model_dev=dev(e, models, torch.int32))
     mu_t, cov_t, _ = e.state()
     assert (got["status"] == 0).all() and (e.status() == 0).all()
-    em, ec = scaled(got["mu_out"], mu_t), scaled(got["cov_out"], cov_t)
+    em, ec = scaled_ignoring_nan(got["mu_out"], mu_t), scaled_ignoring_nan(got["cov_out"], cov_t)
     print(f"PARITY delayed/{model}/{pname}/lag-0 against update_dev: mu {em:.3e} cov {ec:.3e} tol={tol:.3e}")
     assert em <= tol and ec <= tol
     r.e.close(); twin.e.close()
@@ -332,7 +287,7 @@ def test_filters_that_commit_nothing_keep_every_bit(spe, model):
     mh[(FIRST + 2) % SLOTS, 14, 1] = float("nan")
     ch[(FIRST + 1) % SLOTS, 15] = ind
     ref, _ = reference(spe, r, lag2, models2, z2, Q, mu_hist=mh, cov_hist=ch)
-    before = snapshot(r.e)
+    before = snap(r.e)
     got = run(r, lag2, models2, z2, Q, mu_hist=mh, cov_hist=ch)
     st = got["status"]
     assert np.array_equal(st, ref["status"]), (st, ref["status"])
@@ -348,10 +303,10 @@ def test_filters_that_commit_nothing_keep_every_bit(spe, model):
     same[15] = False
     for k in ("mu_out", "cov_out", "z_pred", "S", "innov", "maha", "loglik", "status"):
         assert np.array_equal(got[k][same], clean[k][same]), k
-    assert scaled(got["mu_out"][15], ref["mu_out"][15]) <= 1e-9
+    assert scaled_ignoring_nan(got["mu_out"][15], ref["mu_out"][15]) <= 1e-9
     # committing: the quiet filters keep every bit of the engine, the others store mu_out
     run(r, lag2, models2, z2, Q, mu_hist=mh, cov_hist=ch, commit=True, outputs=False)
-    after = snapshot(r.e)
+    after = snap(r.e)
     assert np.array_equal(after[0][quiet], before[0][quiet], equal_nan=True) and np.array_equal(after[1][quiet], before[1][quiet], equal_nan=True)
     keep = np.ones(n, bool)
     keep[quiet] = False
@@ -368,15 +323,15 @@ def test_gate_rejects_with_outputs_written(spe, model):
     z = z.copy()
     z[::2] += 50.0 if model == "orient" else np.where(models[::2, None] == 3, 1.5, 50.0)
     ref, _ = reference(spe, r, 2, models, z, Q, gate_chi2=9.0)
-    before = snapshot(r.e)
+    before = snap(r.e)
     got = run(r, 2, models, z, Q, commit=True)
     assert np.array_equal(got["status"], ref["status"])
     rej = got["status"] == ST_REJECTED_GATE
     assert rej[::2].all() and (got["status"][~rej] == 0).all() and (~rej).sum() >= n // 4   # (a few of the others are 3 sigma off too)
     assert np.isnan(got["mu_out"][rej]).all() and np.isfinite(got["maha"]).all() and np.isfinite(got["S"]).all()
     for k in ("z_pred", "S", "innov", "maha", "loglik"):
-        assert scaled(got[k], ref[k]) <= 1e-9, k
-    after = snapshot(r.e)
+        assert scaled_ignoring_nan(got[k], ref[k]) <= 1e-9, k
+    after = snap(r.e)
     assert np.array_equal(after[0][rej], before[0][rej]) and np.array_equal(after[1][rej], before[1][rej])
     assert np.array_equal(after[0][~rej], got["mu_out"][~rej]) and np.array_equal(after[3], got["status"])
     r.e.close()
@@ -414,7 +369,7 @@ def test_largest_window_and_one_step_more(spe):
     ref, call = reference(spe, r, lag, models, z, Q)
     got = run(r, lag, models, z, Q)
     check_parity("pose/f64/33-steps", r, got, ref, call, 1e-9, "f64")
-    before = snapshot(r.e)
+    before = snap(r.e)
     out = torch.full((n, r.e.S), float("nan"), dtype=torch.float64, device="cuda")
     st = torch.full((n,), -1, dtype=torch.int32, device="cuda")
     with pytest.raises(spe.engine.UkfbError) as err:
@@ -422,7 +377,7 @@ def test_largest_window_and_one_step_more(spe):
                                q_is_uniform=True, commit=True, mu_out=out, status=st)
     assert f"code {UKFB_ERR_OUT_OF_RANGE}" in str(err.value), str(err.value)
     torch.cuda.synchronize()
-    assert torch.isnan(out).all() and (st == -1).all() and same_snapshot(before, snapshot(r.e))
+    assert torch.isnan(out).all() and (st == -1).all() and same_snapshot(before, snap(r.e))
     r.e.close()
 
 
@@ -462,9 +417,9 @@ def in_order_reference(spe, on, model, rb, late, late_at):
     the engine stores them, the state rounded to the engine's storage after every call as the engine rounds it"""
     e, n = rb.e, rb.n
     p = params(spe, rb)
-    rnd = lambda x: stored(e, x)   # noqa: E731
+    rnd = lambda x: stored(x, e.dtype)   # noqa: E731
     mu = sr.window_order(rb.mu_hist.double().cpu().numpy(), rb.first, rb.steps)[late_at]
-    cov = sr.window_order(unpack(rb.cov_hist, e.D), rb.first, rb.steps)[late_at]
+    cov = sr.window_order(unpack(host(rb.cov_hist), e.D), rb.first, rb.steps)[late_at]
     models, zl, Ql = late
     QQ = rnd(np.broadcast_to(Ql, (n, 3, 3)))
     mu, cov, st = on.pose_update_mixed(mu, cov, models, rnd(zl), QQ) if model == "pose" else on.orient_update(mu, cov, rnd(zl), QQ)
@@ -511,7 +466,7 @@ def test_host_array_form(spe, pname, prec, wide, tol):
     models, z, Q = sample(spe, r, MIXED)
     devf = run(r, MIXED, models, z, Q)
     mu = sr.window_order(r.mu_hist.double().cpu().numpy(), FIRST, STEPS)
-    cov = sr.window_order(unpack(r.cov_hist, r.e.D), FIRST, STEPS)
+    cov = sr.window_order(unpack(host(r.cov_hist), r.e.D), FIRST, STEPS)
     a = sr.window_order(r.in_a.double().cpu().numpy(), FIRST, STEPS)
     o = r.e.update_delayed(r.dt, mu, cov, MIXED, models, z, np.broadcast_to(Q, (N, 3, 3)), in_a=a, commit=False)
     assert (o["status"] == 0).all()

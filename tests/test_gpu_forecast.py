@@ -23,7 +23,7 @@ import torch
 import feature_scaled_parity as fsp
 import forecast_reference as fr
 import smoother_reference as sr
-from test_gpu_smooth import new_engine, same_snapshot, snapshot, tdt, unpack
+from engine_support import host, new_engine, same_snapshot, scaled, snapshot, tdt, unpack
 
 pytestmark = pytest.mark.gpu
 
@@ -120,7 +120,7 @@ def reference(spe, s, start=None, dt=None, ts_us=None, steps=None, first=None, r
     if start is None:
         mu, cov, _ = e.state()
     else:
-        mu, cov = start[0].double().cpu().numpy(), unpack(start[1], e.D)
+        mu, cov = start[0].double().cpu().numpy(), unpack(host(start[1]), e.D)
     a = sr.window_order(s.in_a.double().cpu().numpy(), first, steps)
     b = sr.window_order(s.in_b.double().cpu().numpy(), first, steps)
     if not rings:
@@ -154,7 +154,7 @@ def run(s, dt=None, ts_us=None, steps=None, first=None, start=None, cov=True, ri
                    in_b_dev=s.in_b if rings else None, **kw)
     torch.cuda.synchronize()
     mu_f = sr.window_order(mo.double().cpu().numpy(), first, steps)
-    cov_f = sr.window_order(unpack(co, e.D), first, steps) if co is not None else None
+    cov_f = sr.window_order(unpack(host(co), e.D), first, steps) if co is not None else None
     return mu_f, cov_f, st.cpu().numpy().astype(np.uint32), (mo, co)
 
 
@@ -167,11 +167,7 @@ def run_chained(s, chunk):
         st |= part[2]
         prev = (s.first + c0 + chunk - 1) % s.slots
         start = (out[0][prev], out[1][prev])
-    return (sr.window_order(out[0].double().cpu().numpy(), s.first, s.steps), sr.window_order(unpack(out[1], s.e.D), s.first, s.steps), st)
-
-
-def scaled(x, ref):
-    return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref))))
+    return (sr.window_order(out[0].double().cpu().numpy(), s.first, s.steps), sr.window_order(unpack(host(out[1]), s.e.D), s.first, s.steps), st)
 
 
 def check_parity(name, s, got, ref, tol, wide, rows=slice(None)):
@@ -322,7 +318,7 @@ def test_twin_makes_the_same_predictions(spe, model, pname, prec, wide, tol):
         st |= t.e.status()
         t.e.history_push_dev(SLOTS, (FIRST + c) % SLOTS, mh, ch)
     t.e.sync()
-    twin_mu, twin_cov = sr.window_order(mh.double().cpu().numpy(), FIRST, STEPS), sr.window_order(unpack(ch, t.e.D), FIRST, STEPS)
+    twin_mu, twin_cov = sr.window_order(mh.double().cpu().numpy(), FIRST, STEPS), sr.window_order(unpack(host(ch), t.e.D), FIRST, STEPS)
     if wide:
         print(f"TWIN {model}/{pname}/dt one call (chain in fp64, not asserted): max_scaled_dmu={scaled(one_call[0], twin_mu):.3e} "
               f"max_scaled_dcov={scaled(one_call[1], twin_cov):.3e}")
@@ -367,7 +363,7 @@ def test_twin_timestamps(spe, model, pname, prec, wide, tol):
         t.e.history_push_dev(SLOTS, (FIRST + c) % SLOTS, mh, ch)
     t.e.sync()
     report_twin(f"{model}/{pname}/ts", got, sr.window_order(mh.double().cpu().numpy(), FIRST, STEPS),
-                sr.window_order(unpack(ch, t.e.D), FIRST, STEPS), tol)
+                sr.window_order(unpack(host(ch), t.e.D), FIRST, STEPS), tol)
     assert np.array_equal(got[2], st)
     assert np.array_equal(t.e.last_measurement_time()[:6], [1_104_000] * 6)   # (the twin's times moved; the forecast's engine kept its own)
     s.e.close(); t.e.close()

@@ -19,7 +19,7 @@ Each form runs twice, for either model and either precision.
   full  every optional input is given per filter and every output is requested, through the Python wrapper.  The optional
         per-filter inputs repeat what the second run's defaults and uniform values say (ids, mount, point, lag, activity,
         latched inputs, the engine's own state), the required ones come from the features' input families
-        (test_gpu_sensor_meas / bearing_reference / sampled_reference / predict_sampled_reference / test_gpu_state_meas
+        (sensor_meas_cases / bearing_reference / sampled_reference / predict_sampled_reference / state_meas_reference
         make_inputs, synth's cycle inputs).
   bare  every optional per-filter input and every optional output is NULL (the C function through ctypes, with nulls), the
         device form likewise.  Outputs a form refuses to go without stay (innovation: maha; combine, smooth, forecast: mu;
@@ -34,10 +34,10 @@ import torch
 import bearing_reference as br
 import predict_sampled_reference as pr
 import sampled_reference as sm
+import sensor_meas_cases as smc
 import sensor_meas_reference as sr
-import test_gpu_sensor_meas as tsm
-import test_gpu_state_meas as tst
-from oracle import ukf_numpy as on
+import state_meas_reference as smr
+from engine_support import ACC_COV, man_of, new_engine, pack
 
 pytestmark = pytest.mark.gpu
 
@@ -51,17 +51,12 @@ M = 2          # sampled measurement dimension
 # multiple of four: the last wavefront is a partial group.
 N_BIG = 1822
 ITEMS = np.array([4, DEAD, 0], dtype=np.int32)   # gather / scatter: 3 of 5, the uninitialised filter among them
-ACC_COV = 0.01 * np.eye(3)
 ST_UNINIT = 1 << 7
 
 
 # ------------------------------------------------------------------------------------------------------------------ helpers
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def pack(Mx):
-    return tst.pack(np.asarray(Mx))
 
 
 def assert_same(name, host, devt, cov=False):
@@ -99,7 +94,7 @@ class Ctx:
     def __init__(self, spe, model, prec, n):
         sy = spe.synth
         self.spe, self.model, self.prec, self.n = spe, model, prec, n
-        self.man = on.POSE if model == "pose" else on.ORIENT
+        self.man = man_of(model)
         self.S, self.D = (13, 12) if model == "pose" else (14, 13)
         self.PK = self.D * (self.D + 1) // 2
         self.dtype = np.float64 if prec == spe.F64 else np.float32
@@ -122,7 +117,7 @@ class Ctx:
 
     def engine(self):
         spe, n = self.spe, self.n
-        e = tsm.new_engine(spe, self.model, n, self.prec, 0)
+        e = new_engine(spe, self.model, n, self.prec, 0)
         for lo, hi in ((0, DEAD), (DEAD + 1, n)):   # every filter but DEAD
             e.initialize(self.mu0[lo:hi], self.cov0[lo:hi], first=lo)
         if self.model == "pose":
@@ -334,7 +329,7 @@ def form_compact(c, eh, ed, full):
 def form_update_state(c, eh, ed, full):
     n = c.n
     if not hasattr(c, "state_meas"):
-        c.state_meas = tst.make_inputs(c.model, c.mu_f, c.cov_f, c.dtype)
+        c.state_meas = smr.make_inputs(c.man, c.mu_f, c.cov_f, c.dtype)
     z, Qz = c.state_meas
     mask = c.spe.BLOCK_POSE_ALL if c.model == "pose" else c.spe.BLOCK_ORIENT_ALL
     if full:
@@ -359,7 +354,7 @@ def sensor_inputs(c, bearing):
             mount, point, z, Q = br.make_inputs(c.man, c.mu_f, 15.0, 80.0, c.dtype)
         else:
             mid = sr.POSE_POINT if c.model == "pose" else sr.ORIENT_NAV_VECTOR
-            mount, point, _, z, Q = tsm.make_inputs(c.model, c.mu_f, c.dtype)
+            mount, point, _, z, Q = smc.make_inputs(c.model, c.mu_f, c.dtype)
         setattr(c, key, (mid, z[mid], Q, mount[0].copy(), point[0].copy()))
     return getattr(c, key)
 

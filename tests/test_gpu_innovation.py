@@ -23,14 +23,13 @@ import torch
 
 import feature_f32 as ff
 import feature_scaled_parity as fsp
+from engine_support import scaled, stored, tdt
+from innovation_reference import K, POSE_MODELS, clutter, reference, reference_scores
 
 pytestmark = pytest.mark.gpu
 
 N = 4096
-K = 4
-LN2PI = float(np.log(2.0 * np.pi))
 PRECS = [("f64", 0, 0, 1e-9), ("f32", 1, 0, 1e-4), ("f32w", 1, 1, 1e-9 + 2.0 ** -23)]
-POSE_MODELS = list(range(9))
 
 
 # ---------------------------------------------------------------------------------------------------------------- helpers
@@ -61,15 +60,6 @@ def make_engine(spe, kind, n, prec, wide, **cfg):
     return e, Q
 
 
-def tdt(e):
-    return torch.float64 if e.dtype == np.float64 else torch.float32
-
-
-def stored(e, x):
-    """x as the engine's device arrays hold it (fp32 engines round their inputs), in double"""
-    return np.asarray(x, dtype=e.dtype).astype(np.float64)
-
-
 def run_innovation(e, model, z, Q, uniform_q=False, want=("z_pred", "S", "innov", "maha", "loglik", "best", "status")):
     """model: an id or an int32 array of per-filter ids; z [K, n, 3]; Q [n, 3, 3] or [3, 3] (uniform_q)"""
     n, k = e.capacity, z.shape[0]
@@ -93,60 +83,8 @@ def run_innovation(e, model, z, Q, uniform_q=False, want=("z_pred", "S", "innov"
     return out
 
 
-def reference(onp, kind, mid, mu, cov, Q):
-    """(m, manz, mz [n, S_z], S [n, m, m], ok, conv) of ukfom's update up to S"""
-    if kind == "orient":
-        man, manz, m = onp.ORIENT, onp.VECT(3), 3
-        h = lambda X: onp.quat_rotate(onp.quat_inverse(X[..., 0:4]), X[..., 4:7])
-    elif mid == 3:
-        man, manz, m = onp.POSE, onp.SO3, 3
-        h = lambda X: X[..., 3:7]
-    else:
-        idx = onp._POSE_SELECT[mid]
-        man, manz, m = onp.POSE, onp.VECT(len(idx)), len(idx)
-        h = lambda X: X[..., idx]
-    X, ok = onp.sigma_points(man, mu, cov)
-    Z = h(X)
-    mz, conv = onp.mean_sigma_points(manz, Z)
-    S = onp.cov_sigma_points(manz, mz, Z) + Q[:, :m, :m]
-    return m, manz, mz, S, ok, conv
-
-
-def reference_scores(onp, mid_is_so3, m, manz, mz, S, z):
-    """nu [K, n, m], d2 [K, n], loglik [K, n] of candidates z [K, n, 3]"""
-    Si = np.linalg.inv(S)
-    logdet = np.log(np.linalg.det(S))
-    nu, d2 = [], []
-    for k in range(z.shape[0]):
-        zk = onp.so3_exp(z[k], 1.0) if mid_is_so3 else z[k][:, :m]
-        v = manz.boxminus(zk, mz)
-        nu.append(v)
-        d2.append(np.einsum("bi,bij,bj->b", v, Si, v))
-    nu, d2 = np.array(nu), np.array(d2)
-    return nu, d2, -0.5 * (d2 + logdet[None] + m * LN2PI)
-
-
-def h_of_mean(onp, spe, kind, mid, mu, n):
-    if kind == "orient":
-        return onp.quat_rotate(onp.quat_inverse(mu[:, 0:4]), mu[:, 4:7])
-    return spe.synth.pose_measurement_for_model(mu, np.full(n, mid, dtype=np.int32), np.zeros((n, 3)))
-
-
-def clutter(onp, spe, kind, mid, mu, seed=0):
-    """z_k = h(mu) + s (0.3 + k) U(-1, 1)^m, k = 0 ... 3; s = 0.15 (vector models), 0.08 rad (SO(3) axis-angle)"""
-    n = mu.shape[0]
-    s = 0.08 if (kind == "pose" and mid == 3) else 0.15
-    hm = h_of_mean(onp, spe, kind, mid, mu, n)
-    u = spe.synth.uniform(spe.synth.SEED_BASE + 21 + seed, np.arange(n), np.arange(3 * K), -1.0, 1.0).reshape(n, K, 3)
-    return np.array([hm + s * (0.3 + k) * u[:, k] for k in range(K)])
-
-
-def scaled_err(x, ref):
-    return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref)))) if x.size else 0.0
-
-
-def compare(onp, kind, mid, out, sel, mu, cov, Q, z, scaled):
-    """scaled errors of the five float outputs for the filters `sel` (one model id), and the reference d2; scaled = (name,
+def compare(onp, kind, mid, out, sel, mu, cov, Q, z, judged):
+    """scaled errors of the five float outputs for the filters `sel` (one model id), and the reference d2; judged = (name,
     precision name): z-bar, S and nu are also held to the scale of S (tests/feature_scaled_parity.py), before this returns"""
     m, manz, mz, S, ok, conv = reference(onp, kind, mid, mu[sel], cov[sel], Q[sel])
     assert ok.all() and conv.all()
@@ -155,13 +93,13 @@ def compare(onp, kind, mid, out, sel, mu, cov, Q, z, scaled):
     zp = out["z_pred"][sel]
     if so3:   # a quaternion and its negative are the same rotation
         sign = np.sign(np.sum(zp * mz, axis=-1, keepdims=True))
-        err_z = scaled_err(zp * sign, mz)
+        err_z = scaled(zp * sign, mz)
     else:
-        err_z = max(scaled_err(zp[:, :m], mz), float(np.abs(zp[:, m:]).max()))
+        err_z = max(scaled(zp[:, :m], mz), float(np.abs(zp[:, m:]).max()))
     Sp = np.zeros((len(S), 3, 3)); Sp[:, :m, :m] = S
-    errs = {"z_pred": err_z, "S": scaled_err(out["S"][sel], Sp), "innov": scaled_err(out["innov"][:, sel, :m], nu),
-            "maha": scaled_err(out["maha"][:, sel], d2), "loglik": scaled_err(out["loglik"][:, sel], ll)}
-    fsp.judge_meas(scaled[0], scaled[1], zp if so3 else zp[:, :m], out["S"][sel][:, :m, :m], out["innov"][:, sel, :m], mz, S, nu, so3,
+    errs = {"z_pred": err_z, "S": scaled(out["S"][sel], Sp), "innov": scaled(out["innov"][:, sel, :m], nu),
+            "maha": scaled(out["maha"][:, sel], d2), "loglik": scaled(out["loglik"][:, sel], ll)}
+    fsp.judge_meas(judged[0], judged[1], zp if so3 else zp[:, :m], out["S"][sel][:, :m, :m], out["innov"][:, sel, :m], mz, S, nu, so3,
                    f32=lambda: tuple(ff.innovation_stats(kind, mid, mu[sel], cov[sel], Q[sel], z[:, sel], p) for p in ("f32", "f64")))
     return errs, d2
 
@@ -200,7 +138,7 @@ def test_parity_every_model_and_clutter_association(spe, onp, kind, name, prec, 
             Qh = np.broadcast_to(Q[0], Q.shape).copy() if uniform_q else Q
             out = run_innovation(e, mid, z, Q[0] if uniform_q else Q, uniform_q=uniform_q)
             assert (out["status"] == 0).all()
-            errs, d2 = compare(onp, kind, mid, out, np.arange(N), mu, cov, stored(e, Qh), stored(e, z),
+            errs, d2 = compare(onp, kind, mid, out, np.arange(N), mu, cov, stored(Qh, e.dtype), stored(z, e.dtype),
                                    (f"innovation/{kind}/{name}/model={mid}/uniform_q={int(uniform_q)}", name))
             left_out = check_best(out["best"], d2, float(np.float32(gate)) if prec == 1 else gate)
             print(f"innovation parity {kind} {name} model={mid} uniform_q={int(uniform_q)} "
@@ -232,7 +170,7 @@ def test_parity_per_filter_model_ids(spe, onp, name, prec, wide, tol):
     worst = {}
     for mid in POSE_MODELS:
         sel = np.nonzero(models == mid)[0]
-        errs, _ = compare(onp, "pose", mid, out, sel, mu, cov, stored(e, Q), stored(e, z), (f"innovation/pose/{name}/mixed-ids/model={mid}", name))
+        errs, _ = compare(onp, "pose", mid, out, sel, mu, cov, stored(Q, e.dtype), stored(z, e.dtype), (f"innovation/pose/{name}/mixed-ids/model={mid}", name))
         print(f"innovation parity pose-mixed {name} model={mid} " + " ".join(f"{k}={v:.3e}" for k, v in errs.items()))
         for k, v in errs.items():
             worst[(mid, k)] = v
@@ -252,7 +190,7 @@ def test_constructed_candidates_select_and_update(spe, oracle, onp, kind, mid, n
     n = N
     e, Q = make_engine(spe, kind, n, prec, wide, gate_chi2=6.0)
     mu, cov, _ = e.state()
-    Qs = stored(e, Q)
+    Qs = stored(Q, e.dtype)
     m, manz, mz, S, ok, conv = reference(onp, kind, mid, mu, cov, Qs)
     assert ok.all() and conv.all() and m == 3
     L = np.linalg.cholesky(S)
@@ -266,7 +204,7 @@ def test_constructed_candidates_select_and_update(spe, oracle, onp, kind, mid, n
         d = np.einsum("bij,bj->bi", L, u[:, k]) * ck[:, None]
         zk = manz.boxplus(mz, d)
         z[k] = onp.so3_log(zk) if so3 else zk
-    zs = stored(e, z)
+    zs = stored(z, e.dtype)
     nu, d2, _ = reference_scores(onp, so3, m, manz, mz, S, zs)
     ref_best = np.where(d2.min(axis=0) <= 6.0, np.argmin(d2, axis=0), -1)
     assert (ref_best[7::8] == -1).all() and (ref_best[np.arange(n) % 8 != 7] >= 0).all()
@@ -419,9 +357,9 @@ def test_host_array_form_fp32(spe, onp, kind, mid, name, prec, wide, tol):
     e, Q = make_engine(spe, kind, n, prec, wide, gate_chi2=7.81)
     mu, _, _ = e.state()
     z = clutter(onp, spe, kind, mid, mu)[:2]
-    assert not np.array_equal(z, stored(e, z)) and not np.array_equal(Q, stored(e, Q))   # doubles that are NOT fp32 values
+    assert not np.array_equal(z, stored(z, e.dtype)) and not np.array_equal(Q, stored(Q, e.dtype))   # doubles that are NOT fp32 values
     ho = e.innovation(mid, z, Q)
-    out = run_innovation(e, mid, stored(e, z), stored(e, Q))
+    out = run_innovation(e, mid, stored(z, e.dtype), stored(Q, e.dtype))
     assert (ho["status"] == 0).all() and np.isfinite(ho["maha"]).all()
     for key in ("z_pred", "S", "innov", "maha", "loglik", "best", "status"):
         assert np.array_equal(ho[key], out[key]), key
@@ -439,7 +377,7 @@ def test_thirty_two_candidates_and_ties(spe, onp):
     out = run_innovation(e, 0, z, Q)
     m, manz, mz, S, ok, conv = reference(onp, "pose", 0, mu, cov, Q)
     _, d2, _ = reference_scores(onp, False, m, manz, mz, S, z)
-    assert scaled_err(out["maha"], d2) <= 1e-9
+    assert scaled(out["maha"], d2) <= 1e-9
     assert np.array_equal(out["maha"][3], out["maha"][9]) and np.array_equal(out["maha"][3], out["maha"][20])
     expect = np.argmin(out["maha"], axis=0)           # (NumPy's argmin returns the first minimum)
     assert (out["best"] == expect).all() and (out["best"] != 9).all() and (out["best"] != 20).all()
@@ -453,7 +391,7 @@ def test_nis_mean(spe, onp, kind, mid, prec):
     n = 65536
     e, Q = make_engine(spe, kind, n, prec, 0)
     mu, cov, _ = e.state()
-    m, manz, mz, S, ok, conv = reference(onp, kind, mid, mu, cov, stored(e, Q))
+    m, manz, mz, S, ok, conv = reference(onp, kind, mid, mu, cov, stored(Q, e.dtype))
     rng = np.random.default_rng(20240607)
     d = np.einsum("bij,bj->bi", np.linalg.cholesky(S), rng.standard_normal((n, m)))
     zk = manz.boxplus(mz, d)

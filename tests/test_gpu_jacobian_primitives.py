@@ -33,18 +33,14 @@ the 16-lane row and half-wave boundaries 0, 15, 16, 31, 32, 47, 48, 63, and alte
 must be those of the all-own-side wave."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 mp = pytest.importorskip("mpmath")
 
-from test_gpu_so3_primitives import DT, EPS, F32, F64, _axes, _m, _ulps, placements   # the record plumbing of the SO(3) probe
+from probe_support import DT, EPS, F32, F64, _axes, _m, _ulps, load, placements  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "cpp", "build", "libjac_probe.so")
 IN, OUT = 3, 9                       # doubles per record (tests/cpp/jac_probe.hip JACP_IN / JACP_OUT)
 PRIM = dict(jrinv_coeff=0, jr_coeffs=1, jrinv_matrix=2, jr_matrix=3)
 NOUT = dict(jrinv_coeff=1, jr_coeffs=2, jrinv_matrix=9, jr_matrix=9)
@@ -170,14 +166,8 @@ def _theta2(prim, X):
 
 
 # ------------------------------------------------------------------------------------------------ the device
-@functools.lru_cache(maxsize=None)
 def _lib():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp")])
-    lib = C.CDLL(LIB)
-    lib.jac_probe.argtypes = [C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    lib.jac_probe.restype = C.c_int
-    return lib
+    return load("libjac_probe", jac_probe=(C.c_int, (C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double))))
 
 
 def device(prim, prec, X):

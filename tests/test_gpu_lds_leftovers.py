@@ -6,25 +6,12 @@ indirect kernel) and must give the SAME BITS
 after a NaN pattern, an Inf pattern and zeros.  Found in round 3 by tests/fuzz_parity.py as a box-dependent Cholesky failure:
 an alignment pad between two LDS regions was read as "leftover times the table's exact-zero row" -- NaN whenever the leftover
 of an earlier kernel happened to be NaN or Inf (Layout16::LAF_PAD in ukf_kernel16.hpp)."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+from probe_support import LDS_PATTERNS, lds_poison
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "cpp", "build", "liblds_poison.so")
-PATTERNS = (0x7FC00000, 0x7F800000, 0xFFFFFFFF, 0x00000000)     # float NaN, float +Inf, a NaN in both precisions, zero
-
-
-def _poison():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp")])
-    lib = C.CDLL(LIB)
-    lib.lds_poison.argtypes = [C.c_uint32]
-    return lib.lds_poison
 
 
 def _run(spe, model, prec, G, n=4099):
@@ -84,9 +71,9 @@ def _run(spe, model, prec, G, n=4099):
 @pytest.mark.parametrize("prec", [0, 1])
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_results_do_not_depend_on_lds_leftovers(spe, model, prec, G):
-    poison = _poison()
+    poison = lds_poison()
     ref = None
-    for pat in PATTERNS:
+    for pat in LDS_PATTERNS:
         assert poison(pat) == 0
         got = _run(spe, model, prec, G)
         m, c, st, m2, c2, _ = got

@@ -23,7 +23,7 @@ import pytest
 import torch
 
 import lifecycle_reference as lr
-from test_gpu_smooth import new_engine, same_snapshot, snapshot, tdt
+from engine_support import ACC_COV, new_engine, same_snapshot, snapshot, tdt
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +31,6 @@ N = 1022   # not a multiple of four: the last workgroup holds two filters
 PRECS = [("f64", 0), ("f32", 1)]
 IDS = [p[0] for p in PRECS]
 MODELS = ["pose", "orient"]
-ACC_COV = 0.01 * np.eye(3)
 ST_UNINITIALISED, ST_INACTIVE = 1 << 7, 1 << 8
 _HIP = None
 
@@ -46,11 +45,13 @@ def raw(ptr, shape, dtype):
     return out
 
 
-def dev(x, dtype=None):
+def to_dev(x, dtype=None):
+    """x on the device in its own dtype (integer indices and masks stay integers), or in `dtype`"""
     return torch.from_numpy(np.ascontiguousarray(x)).to("cuda", dtype) if dtype is not None else torch.from_numpy(np.ascontiguousarray(x)).to("cuda")
 
 
-def host(t):
+def to_host(t):
+    """a device tensor on the host in its own dtype"""
     return t.cpu().numpy()
 
 
@@ -127,7 +128,7 @@ def full_gather(r, fields=("in_a", "in_b", "noise")):
            "noise": torch.empty((n, e.D, e.D), dtype=t, device="cuda")}
     e.gather_filters_dev(None, **{k: out[k] for k in fields})
     e.sync()
-    return {k: host(out[k]) for k in fields}
+    return {k: to_host(out[k]) for k in fields}
 
 
 def download(r):
@@ -182,11 +183,11 @@ def test_gather(spe, model, pname, prec, variant):
     bound_a = bound_b = None
     if variant == "bound":
         rng = np.random.default_rng(3)
-        bound_a = dev(rng.normal(size=(N, 3)), tdt(e))
+        bound_a = to_dev(rng.normal(size=(N, 3)), tdt(e))
         if model == "pose":
             e.bind_acceleration_dev(bound_a)
         else:
-            bound_b = dev(rng.normal(size=(N, 3)), tdt(e))
+            bound_b = to_dev(rng.normal(size=(N, 3)), tdt(e))
             e.bind_orient_inputs_dev(bound_b, bound_a)
     before = snapshot(e)
     mu_p, cov_p, _ = e.device_views()
@@ -196,20 +197,20 @@ def test_gather(spe, model, pname, prec, variant):
     assert len(set(known["last_ts"].tolist())) > N // 2 and not known["init"][500:503].any() and known["init"].sum() == N - 3
     idx = item_list(257, N, seed=11)
     out = record_buffers(e, idx.size)
-    e.gather_filters_dev(dev(idx), **out)
+    e.gather_filters_dev(to_dev(idx), **out)
     e.sync()
-    ref = lr.gather(known, idx, in_a_read=host(bound_a) if bound_a is not None else None,
-                    in_b_read=host(bound_b) if bound_b is not None else None)
+    ref = lr.gather(known, idx, in_a_read=to_host(bound_a) if bound_a is not None else None,
+                    in_b_read=to_host(bound_b) if bound_b is not None else None)
     for field, key in NAMES.items():
-        assert np.array_equal(host(out[field]), ref[key], equal_nan=True), field
-    assert np.array_equal(host(out["status"]).astype(np.uint32), ref["status"])
-    assert (ref["status"] == ST_INACTIVE).sum() == 7 and not host(out["mu"])[ref["status"] != 0].any()
+        assert np.array_equal(to_host(out[field]), ref[key], equal_nan=True), field
+    assert np.array_equal(to_host(out["status"]).astype(np.uint32), ref["status"])
+    assert (ref["status"] == ST_INACTIVE).sum() == 7 and not to_host(out["mu"])[ref["status"] != 0].any()
     # NULL fields are skipped; a NULL index means item k is filter k
     only = record_buffers(e, N)
     e.gather_filters_dev(None, mu=only["mu"], initialised=only["initialised"])
     e.sync()
-    assert np.array_equal(host(only["mu"]), known["mu"]) and np.array_equal(host(only["initialised"]), known["init"])
-    assert (host(only["cov_packed"]) == 7).all() and (host(only["status"]) == 7).all()
+    assert np.array_equal(to_host(only["mu"]), known["mu"]) and np.array_equal(to_host(only["initialised"]), known["init"])
+    assert (to_host(only["cov_packed"]) == 7).all() and (to_host(only["status"]) == 7).all()
     assert same_snapshot(before, snapshot(e))
     e.close()
 
@@ -218,9 +219,9 @@ def records_from(spe, model, prec, n_items, seed):
     """n_items records of the storage type of `prec`, gathered from a cycled engine that holds other filters than the targets"""
     src = make(spe, model, N, prec, per_filter_noise=True, first=4096)
     out = record_buffers(src.e, n_items)
-    src.e.gather_filters_dev(dev(np.random.default_rng(seed).choice(N, size=n_items, replace=False).astype(np.int32)), **out)
+    src.e.gather_filters_dev(to_dev(np.random.default_rng(seed).choice(N, size=n_items, replace=False).astype(np.int32)), **out)
     src.e.sync()
-    assert not host(out["status"]).any() and host(out["initialised"]).all()
+    assert not to_host(out["status"]).any() and to_host(out["initialised"]).all()
     out["initialised"][::5] = 0   # every fifth record retires its filter
     out["initialised"][1::5] = 3  # any non-zero byte is "initialised"
     src.e.close()
@@ -228,7 +229,7 @@ def records_from(spe, model, prec, n_items, seed):
 
 
 def numpy_records(out, with_noise=True):
-    rec = {key: host(out[field]) for field, key in NAMES.items()}
+    rec = {key: to_host(out[field]) for field, key in NAMES.items()}
     if not with_noise:
         rec["noise"] = None
     return rec
@@ -243,27 +244,27 @@ def test_scatter(spe, model, pname, prec):
     rec = records_from(spe, model, prec, idx.size, seed=13)
     before = download(r)
     views = e.device_views()
-    e.scatter_filters_dev(dev(idx), **rec)
+    e.scatter_filters_dev(to_dev(idx), **rec)
     after = download(r)
     ref, status = lr.scatter(before, idx, numpy_records(rec))
     same_state(after, ref)
-    assert np.array_equal(host(rec["status"]).astype(np.uint32), status)
+    assert np.array_equal(to_host(rec["status"]).astype(np.uint32), status)
     valid = idx[(idx >= 0) & (idx < N)]
     assert (status == ST_INACTIVE).sum() == idx.size - np.unique(valid).size >= 58 and e.device_views() == views
     # lowest item wins: mean and covariance of a thrice-named filter are those of its first item
     f = int(np.bincount(valid).argmax())
     k = int(np.nonzero(idx == f)[0][0])
-    assert (idx == f).sum() >= 3 and np.array_equal(after["mu"][f], host(rec["mu"])[k]) and np.array_equal(after["cov"][f], host(rec["cov_packed"])[k])
+    assert (idx == f).sum() >= 3 and np.array_equal(after["mu"][f], to_host(rec["mu"])[k]) and np.array_equal(after["cov"][f], to_host(rec["cov_packed"])[k])
     # a record with initialised == 0 retired its filter; its time is zero whatever the record says
     retired = [int(idx[k]) for k in range(idx.size) if status[k] == 0 and k % 5 == 0]
-    assert retired and not after["init"][retired].any() and not after["last_ts"][retired].any() and host(rec["last_ts_us"])[::5].all()
+    assert retired and not after["init"][retired].any() and not after["last_ts"][retired].any() and to_host(rec["last_ts_us"])[::5].all()
     # the owner workspace is released: the same call again decides the same way
-    e.scatter_filters_dev(dev(idx), **rec)
+    e.scatter_filters_dev(to_dev(idx), **rec)
     same_state(download(r), ref)
-    assert np.array_equal(host(rec["status"]).astype(np.uint32), status)
+    assert np.array_equal(to_host(rec["status"]).astype(np.uint32), status)
     # without the optional fields: flag 1, time 0, latches and noise untouched
-    e.scatter_filters_dev(dev(idx), mu=rec["mu"], cov_packed=rec["cov_packed"])
-    ref2, _ = lr.scatter(ref, idx, {"mu": host(rec["mu"]), "cov": host(rec["cov_packed"])})
+    e.scatter_filters_dev(to_dev(idx), mu=rec["mu"], cov_packed=rec["cov_packed"])
+    ref2, _ = lr.scatter(ref, idx, {"mu": to_host(rec["mu"]), "cov": to_host(rec["cov_packed"])})
     same_state(download(r), ref2)
     e.close()
 
@@ -275,13 +276,13 @@ def test_scatter_refusals(spe, model):
     rec = records_from(spe, model, 0, 16, seed=14)
     before = download(r)
     with pytest.raises(spe.UkfbError) as err:
-        e.scatter_filters_dev(dev(np.arange(16, dtype=np.int32)), **rec)
+        e.scatter_filters_dev(to_dev(np.arange(16, dtype=np.int32)), **rec)
     assert "code 1" in str(err.value) and "ukfb_set_process_noise_per_filter" in str(err.value)
     for missing in ("mu", "cov_packed"):
         args = {k: v for k, v in rec.items() if k not in ("noise", missing)}
         args.setdefault("mu", None); args.setdefault("cov_packed", None)
         with pytest.raises(spe.UkfbError) as err:
-            e.scatter_filters_dev(dev(np.arange(16, dtype=np.int32)), **args)
+            e.scatter_filters_dev(to_dev(np.arange(16, dtype=np.int32)), **args)
         assert "code 1" in str(err.value)
     with pytest.raises(spe.UkfbError) as err:
         e.scatter_filters_dev(None, rec["mu"], rec["cov_packed"], n=-1)
@@ -289,7 +290,7 @@ def test_scatter_refusals(spe, model):
     e.scatter_filters_dev(None, rec["mu"], rec["cov_packed"], n=0)   # nothing to do
     same_state(download(r), before)   # the storage has not been switched either
     # ... and without the noise the same records are taken
-    e.scatter_filters_dev(dev(np.arange(16, dtype=np.int32)), **{k: v for k, v in rec.items() if k != "noise"})
+    e.scatter_filters_dev(to_dev(np.arange(16, dtype=np.int32)), **{k: v for k, v in rec.items() if k != "noise"})
     ref, _ = lr.scatter(before, np.arange(16), numpy_records(rec, with_noise=False))
     same_state(download(r), ref)
     e.close()
@@ -308,7 +309,7 @@ def test_round_trip_is_complete(spe, model, pname, prec):
     b.e.set_process_noise(np.repeat(3.0 * b.e.process_noise()[None], N, axis=0))
     b.per_filter_noise = True
     b.e.scatter_filters_dev(None, **rec)
-    assert not host(rec["status"]).any()
+    assert not to_host(rec["status"]).any()
     sa, sb = download(a), download(b)
     same_state(sa, sb, keys=("mu", "cov", "init", "last_ts", "in_a", "in_b", "noise"))
     mu_now = a.e.state(with_cov=False)[0]
@@ -328,7 +329,7 @@ def test_retire(spe, model, pname, prec):
     mask = (np.arange(N) % 3 == 0).astype(np.uint8)
     before = download(r)
     assert before["last_ts"][mask != 0].all()
-    r.e.retire_dev(dev(mask))
+    r.e.retire_dev(to_dev(mask))
     after = download(r)
     same_state(after, lr.retire(before, mask))
     assert not after["init"][mask != 0].any() and not after["last_ts"][mask != 0].any() and after["init"][mask == 0].all()
@@ -340,7 +341,7 @@ def test_retire(spe, model, pname, prec):
 def kill(r, dead_filters):
     mask = np.zeros(r.n, dtype=np.uint8)
     mask[dead_filters] = 1
-    r.e.retire_dev(dev(mask))
+    r.e.retire_dev(to_dev(mask))
 
 
 def compact_case(spe, model, prec, case):
@@ -381,7 +382,7 @@ def test_compact(spe, model, pname, prec, case):
     after = download(r)
     ref, ref_new, ref_old, ref_live = lr.compact(before, group)
     same_state(after, ref)
-    assert np.array_equal(host(new_index), ref_new) and np.array_equal(host(old_index), ref_old) and int(live.item()) == ref_live
+    assert np.array_equal(to_host(new_index), ref_new) and np.array_equal(to_host(old_index), ref_old) and int(live.item()) == ref_live
     assert e.device_views() == views
     moved = int((ref_new[ref_new >= 0] != np.nonzero(ref_new >= 0)[0]).sum())
     expect = {"all-live": (N, 0), "all-dead": (0, 0), "one-hole": (2, 1), "live-prefix": (700, 0)}
@@ -425,7 +426,7 @@ def test_compact_then_run(spe):
     old_index = torch.empty((n,), dtype=torch.int32, device="cuda")
     live = torch.empty((1,), dtype=torch.int64, device="cuda")
     b.e.compact_dev(1, new_index, old_index, live)
-    new, old, L = host(new_index), host(old_index), int(live.item())
+    new, old, L = to_host(new_index), to_host(old_index), int(live.item())
     assert L == n - dead.size and (new >= 0).sum() == L and (new[new >= 0] != np.nonzero(new >= 0)[0]).sum() > n // 8
     src = np.where(old >= 0, old, 0)   # the dead slots of B read some filter's inputs: nothing is done with them
     for c in (3, 4):
@@ -467,10 +468,10 @@ def test_birth_without_the_host(spe, model, pname, prec):
     after = download(r)
     L = N - 40
     assert int(live.item()) == L and before["init"][:L].all() and not before["init"][L:].any()
-    ref, st = lr.scatter(before, np.arange(L, L + 64), {"mu": host(mu_t)[:64], "cov": host(cov_t)[:64]})
+    ref, st = lr.scatter(before, np.arange(L, L + 64), {"mu": to_host(mu_t)[:64], "cov": to_host(cov_t)[:64]})
     same_state(after, ref)
-    assert np.array_equal(host(status).astype(np.uint32), st) and (st[:40] == 0).all() and (st[40:] == ST_INACTIVE).all()
-    assert after["init"].all() and not after["last_ts"][L:].any() and np.array_equal(after["mu"][L:], host(mu_t)[:40])
+    assert np.array_equal(to_host(status).astype(np.uint32), st) and (st[:40] == 0).all() and (st[40:] == ST_INACTIVE).all()
+    assert after["init"].all() and not after["last_ts"][L:].any() and np.array_equal(after["mu"][L:], to_host(mu_t)[:40])
     cycle(spe, r, 3, stamped=False)   # the newborn run
     assert not (e.status() & ST_UNINITIALISED).any()
     e.close(); bank.e.close()

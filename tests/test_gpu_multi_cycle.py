@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import max_abs
+from engine_support import dev_state
 
 pytestmark = pytest.mark.gpu
 TOL = {0: 1e-9, 1: 1e-4}
@@ -306,7 +307,6 @@ def test_full_size_multi_cycle_equals_single_launches(spe, prec):
     """The metric's 1 048 576 PoseWithVelocity filters: one launch of 6 cycles (ring of 4 input sets, starting at slot 3) and
     the same 6 cycles as single launches leave the SAME bits in HBM -- compared on the device, every filter."""
     import torch
-    from test_gpu_parity_configs import _dev_state
     s = spe.synth
     n, CH, slots, cycles, first = 1_048_576, 131_072, 4, 6, 3
     tdt = _tdt(prec)
@@ -324,7 +324,7 @@ def test_full_size_multi_cycle_equals_single_launches(spe, prec):
             Q_r[k, lo:lo + CH] = torch.from_numpy(Q.reshape(-1, 9)).to("cuda", tdt)
     eng.set_acceleration(None, 0.01 * np.eye(3))
     torch.cuda.synchronize()       # the rings were filled on torch's stream, the engine launches on its own
-    mu_v, cov_v = _dev_state(eng)
+    mu_v, cov_v = dev_state(eng)
     mu0, cov0 = mu_v.clone(), cov_v.clone()
     torch.cuda.synchronize()
     for c in range(cycles):

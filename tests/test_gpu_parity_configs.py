@@ -11,27 +11,11 @@ import numpy as np
 import pytest
 
 from conftest import max_abs
+from engine_support import dev_state
 
 pytestmark = pytest.mark.gpu
 TOL = {0: 1e-9, 1: 1e-4}
 N_SMALL = 203   # not a multiple of 4: the last wavefront carries a ragged tail
-
-
-class _DevArray:
-    """Zero-copy torch view of engine-owned device memory (CUDA array interface)."""
-
-    def __init__(self, ptr, shape, typestr):
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
-
-
-def _dev_state(eng):
-    """(mean, packed covariance) of an engine as torch tensors over its own HBM buffers."""
-    import torch
-    eng.sync()
-    mu_p, cov_p, _ = eng.device_views()
-    ts = "<f8" if eng.precision == 0 else "<f4"
-    return (torch.as_tensor(_DevArray(mu_p, (eng.capacity, eng.S), ts), device="cuda"),
-            torch.as_tensor(_DevArray(cov_p, (eng.capacity, eng.PK), ts), device="cuda"))
 
 
 def _orient_engine(spe, n, prec, G):
@@ -207,9 +191,9 @@ def test_full_size_config4_orient_fp32(spe, oracle):
         assert eng.status_summary() == 0
         assert eng.last_launch_info()["kernel"] == "ukf_kernel16<f32,orient,cycle-plain>"   # (one dt and one model for the launch, accept-any gate)
     # whole batch == its halves, bit for bit (compared in HBM: 4 M x 105 floats)
-    mu_f, cov_f = _dev_state(full)
+    mu_f, cov_f = dev_state(full)
     for eng, lo, hi in halves:
-        mu_h, cov_h = _dev_state(eng)
+        mu_h, cov_h = dev_state(eng)
         assert torch.equal(mu_f[lo:hi], mu_h) and torch.equal(cov_f[lo:hi], cov_h)
     assert bool(torch.isfinite(mu_f).all()) and bool(torch.isfinite(cov_f).all())
     assert float((torch.linalg.vector_norm(mu_f[:, :4], dim=1) - 1).abs().max()) < 1e-5

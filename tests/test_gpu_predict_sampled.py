@@ -1,6 +1,6 @@
 """User-defined process models on the device (ukfb_predict_sampled_dev and its host form, include/ukf_batch.h).
 
-States: those of tests/test_gpu_sensor_meas.py (synth.pose_initial / orient_initial after two real cycles, downloaded and
+States: those of tests/sensor_meas_cases.py (synth.pose_initial / orient_initial after two real cycles, downloaded and
 re-uploaded bit for bit; its `case` cache is shared).  Inputs: tests/predict_sampled_reference.make_inputs (seed 17), rounded to
 the engine's storage before the reference sees them.  The propagated points XX are computed BY THE TEST from the exported X with
 a torch expression on the device (tests/predict_sampled_reference.user_f) in the engine's storage type, and the reference takes
@@ -19,32 +19,22 @@ import feature_scaled_parity as fsp
 import predict_sampled_f32 as pf
 import predict_sampled_reference as pr
 import sampled_reference as sm
-import test_gpu_sensor_meas as tsm
+import sensor_meas_cases as smc
+from engine_support import (ACC_COV, cycled_engine, dev, host, man_of, same, same_snapshot, scaled, snapshot, stored, tdt,
+                            unpack)
 from oracle import ukf_numpy as on
 
 pytestmark = pytest.mark.gpu
 
-N = tsm.N   # 1022: not a multiple of four
-PRECS = tsm.PRECS
+N = smc.N   # 1022: not a multiple of four
+PRECS = smc.PRECS
 ST_NONFINITE, ST_CHOLESKY, ST_NOCONV, ST_UNINIT, ST_INACTIVE = 1 << 4, 1 << 5, 1 << 6, 1 << 7, 1 << 8
 ALL_KEYS = ("mu", "cov", "out_mu", "out_cov", "status")
-ACC_COV = tsm.ACC_COV
-stored = tsm.stored
-man_of = tsm.man_of
-scaled = tsm.scaled
-
-
-def dev(e, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", tsm.tdt(e))
-
-
-def host(t):
-    return t.double().cpu().numpy()
 
 
 def export(e):
     """-> (X: a device tensor in engine precision, status uint32 [n]) after sigma_points_dev"""
-    X = torch.full((e.capacity, 2 * e.D + 1, e.S), -7.0, dtype=tsm.tdt(e), device="cuda")
+    X = torch.full((e.capacity, 2 * e.D + 1, e.S), -7.0, dtype=tdt(e), device="cuda")
     st = torch.full((e.capacity,), -1, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     e.sigma_points_dev(X, None, st)
@@ -53,19 +43,10 @@ def export(e):
     return X, st.cpu().numpy().astype(np.uint32)
 
 
-def unpack(p, D):
-    """[n, PK] packed lower triangle (row r: r (r + 1) / 2 ... + r) -> [n, D, D] symmetric"""
-    r, c = np.tril_indices(D)
-    full = np.empty((p.shape[0], D, D))
-    full[:, r, c] = p
-    full[:, c, r] = p
-    return full
-
-
 def run(e, XX, R, active=None, commit=True, r_uniform=False, outs=True):
     """-> dict(mu, cov: the engine's state after the call; out_mu, out_cov, status: the call's outputs) after
     predict_sampled_dev; XX a device tensor or an array"""
-    n, dt, D = e.capacity, tsm.tdt(e), e.D
+    n, dt, D = e.capacity, tdt(e), e.D
     Xd = XX if torch.is_tensor(XX) else dev(e, XX)
     Rd = dev(e, np.asarray(R).reshape(D, D) if r_uniform else np.asarray(R).reshape(n, D, D))
     ad = None if active is None else torch.from_numpy(np.asarray(active, dtype=np.uint8)).to("cuda")
@@ -102,7 +83,7 @@ def samples(spe, c, name):
         c.psamples = {}
     if name not in c.psamples:
         par, R = user(c)
-        e = tsm.engine_of(spe, c)
+        e = smc.engine_of(spe, c)
         X, st = export(e)
         assert (st == 0).all()
         if name == "wide":
@@ -141,11 +122,6 @@ def check_parity(name, c, got, ref, XX, R, rows=None):
                     f32=lambda: tuple((f32()[p]["mu"][rows], f32()[p]["cov"][rows]) for p in ("f32", "f64")))
 
 
-def same(a, b, keys=ALL_KEYS, rows=None):
-    rows = slice(None) if rows is None else rows
-    return all(np.array_equal(a[k][rows], b[k][rows], equal_nan=True) for k in keys)
-
-
 _RUNS = {}
 
 
@@ -154,7 +130,7 @@ def committed(spe, c, name):
     key = (c.model, c.pname, c.n, name)
     if key not in _RUNS:
         XX, R = samples(spe, c, name)
-        e = tsm.engine_of(spe, c)
+        e = smc.engine_of(spe, c)
         _RUNS[key] = run(e, XX, R)
         assert np.array_equal(e.status(), _RUNS[key]["status"])   # commit = 1 writes the engine's own status array too
         e.close()
@@ -165,7 +141,7 @@ def committed(spe, c, name):
 @pytest.mark.parametrize("model", ["pose", "orient"])
 @pytest.mark.parametrize("pname", [p[0] for p in PRECS])
 def test_parity(spe, model, pname):
-    c = tsm.case(spe, model, pname)
+    c = smc.case(spe, model, pname)
     for name in pr.USER_MODELS[model]:
         XX, R = samples(spe, c, name)
         got, ref = committed(spe, c, name), reference(c, XX, R)
@@ -183,9 +159,9 @@ def test_user_model_reproduces_builtin(spe):
     sigma points they hold in fp64 registers, a user model sees X rounded to fp32 -- an input perturbation, not a kernel error."""
     sy, dt = spe.synth, 0.01
     for model, with_acc in (("pose", True), ("pose", False), ("orient", True)):
-        c = tsm.case(spe, model, "f64")
+        c = smc.case(spe, model, "f64")
         n = c.n
-        e, twin = tsm.engine_of(spe, c), tsm.engine_of(spe, c)
+        e, twin = smc.engine_of(spe, c), smc.engine_of(spe, c)
         X, st = export(e)
         assert (st == 0).all()
         if model == "pose":
@@ -229,9 +205,9 @@ def test_user_model_reproduces_builtin(spe):
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_small_batches(spe, model):
     """1, 2, 3 and 5 filters: one partly filled wavefront, and a full one with a one-row tail"""
-    big = tsm.case(spe, model, "f64", 255)
+    big = smc.case(spe, model, "f64", 255)
     for n in (1, 2, 3, 5):
-        c = tsm.Case()
+        c = smc.Case()
         c.model, c.pname, c.n, c.prec, c.wide, c.tol, c.dtype = model, "f64", n, 0, 0, 1e-9, big.dtype
         c.mu, c.cov, c.gyro = big.mu[:n], big.cov[:n], big.gyro[:n]
         name = pr.USER_MODELS[model][-1]
@@ -246,7 +222,7 @@ def test_small_batches(spe, model):
 def test_several_mean_iterations(spe, pname):
     """a coordinated turn whose rate x dt spreads the propagated orientations by radians (predict_sampled_reference.wide_turn
     says why ~ 1 rad is not enough): the reference needs more than two trips for most filters"""
-    c = tsm.case(spe, "pose", pname)
+    c = smc.case(spe, "pose", pname)
     XX, R = samples(spe, c, "wide")
     trips = pr.mean_trips(on.POSE, XX)   # on the CPU, before the GPU is asked
     spread = np.linalg.norm(on.POSE.boxminus(XX, XX[:, 0:1])[..., 3:6], axis=-1).max(axis=1)
@@ -259,7 +235,7 @@ def test_several_mean_iterations(spe, pname):
         return
     # mean_max_iter = 1: the filters that still move after their first trip, every one of them
     capped = reference(c, XX, R, max_it=1)
-    e = tsm.engine_of(spe, c, mean_max_iter=1)
+    e = smc.engine_of(spe, c, mean_max_iter=1)
     one = run(e, XX, R)
     e.close()
     assert set(np.unique(capped["status"])) <= {0, ST_NOCONV} and (capped["status"] == ST_NOCONV).sum() > c.n // 2
@@ -270,7 +246,7 @@ def test_several_mean_iterations(spe, pname):
 # ------------------------------------------------------------------------------------------------- 5. bit-level properties
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_bit_level_properties(spe, model):
-    c = tsm.case(spe, model, "f64")
+    c = smc.case(spe, model, "f64")
     n, name = c.n, pr.USER_MODELS[model][0]
     XX, R = samples(spe, c, name)
     base = committed(spe, c, name)
@@ -278,42 +254,42 @@ def test_bit_level_properties(spe, model):
     stamps = np.arange(1, n + 1, dtype=np.int64) * 1000 + 7
 
     def fresh(**kw):
-        e = tsm.engine_of(spe, c, **kw)
+        e = smc.engine_of(spe, c, **kw)
         e.set_last_measurement_time(stamps)
         return e
     # commit = 0: the whole downloadable engine keeps its bits, the outputs are the committing call's; then commit = 1 without
     # `out`: the numbers of commit = 1 with it; the stamps set before the calls are the stamps after them
     e = fresh()
-    before = tsm.snapshot(e)
+    before = snapshot(e)
     dry = run(e, XX, R, commit=False)
-    assert tsm.same_snap(before, tsm.snapshot(e))
-    assert same(dry, base, keys=("out_mu", "out_cov", "status")) and np.array_equal(dry["mu"], c.mu) and np.array_equal(dry["cov"], c.cov)
+    assert same_snapshot(before, snapshot(e))
+    assert same(dry, base, ("out_mu", "out_cov", "status")) and np.array_equal(dry["mu"], c.mu) and np.array_equal(dry["cov"], c.cov)
     alone = run(e, XX, R, outs=False)
-    assert same(alone, base, keys=("mu", "cov")) and np.array_equal(e.status(), base["status"])
+    assert same(alone, base, ("mu", "cov")) and np.array_equal(e.status(), base["status"])
     assert np.array_equal(e.last_measurement_time(), stamps)
-    after = tsm.snapshot(e)
+    after = snapshot(e)
     # times and noise tables (the rotation rate of the snapshot is a function of the committed bias: it may move)
     assert all(np.array_equal(x, y, equal_nan=True) for x, y in zip(before[4:6], after[4:6]))
     e.close()
     # active = NULL equals all ones
     e = fresh()
-    assert same(run(e, XX, R, active=np.ones(n, dtype=np.uint8)), base)
+    assert same(run(e, XX, R, active=np.ones(n, dtype=np.uint8)), base, ALL_KEYS)
     e.close()
     # ONE D x D with r_is_uniform equals the repeated R
     Ru = np.broadcast_to(R[5], R.shape).copy()
     e, e2 = fresh(), fresh()
-    assert same(run(e, XX, Ru[0], r_uniform=True), run(e2, XX, Ru))
+    assert same(run(e, XX, Ru[0], r_uniform=True), run(e2, XX, Ru), ALL_KEYS)
     e.close(); e2.close()
     # a filter's bits are the same in the batch of 1022, alone, and at another index (row 2 of a second wavefront)
     i = 7
     for nn, at in ((1, 0), (7, 6)):
-        s = tsm.Case()
+        s = smc.Case()
         s.__dict__.update(c.__dict__)
         s.n = nn
         pick = np.arange(nn) + 40   # the other rows: other filters' states
         pick[at] = i
         s.mu, s.cov, s.gyro = c.mu[pick], c.cov[pick], c.gyro[pick]
-        e = tsm.engine_of(spe, s)
+        e = smc.engine_of(spe, s)
         one = run(e, XX[pick], R[pick])
         e.close()
         assert all(np.array_equal(one[k][at], base[k][i], equal_nan=True) for k in ALL_KEYS), (nn, at)
@@ -331,7 +307,7 @@ def test_bit_level_properties(spe, model):
     e, e2 = fresh(), fresh()
     a, b = run(e, XXg, R), run(e2, XXt, R)
     e.close(); e2.close()
-    assert (a["status"] == 0).all() and same(a, b, keys=("cov", "out_cov", "status"))
+    assert (a["status"] == 0).all() and same(a, b, ("cov", "out_cov", "status"))
     assert np.array_equal(a["mu"][:, others], b["mu"][:, others])
     d = np.abs(b["mu"][:, sl] - (a["mu"][:, sl] + t)).max()
     print(f"PARITY predict_sampled translation {model} n={n} max |mean moved - translation| = {d:.3e} bound={1e-12 * 1000.0:.3e}")
@@ -350,7 +326,7 @@ def test_failures_stay_inside_their_filter(spe, model):
     name = pr.USER_MODELS[model][0]
 
     def make():
-        e = tsm.cycled_engine(spe, model, n, 0, 0, skip_init=(dead,))
+        e = cycled_engine(spe, model, n, 0, 0, skip_init=(dead,))
         mu, cov, init = e.state()
         mu_f = mu.copy()
         mu_f[dead] = mu[0]
@@ -391,7 +367,7 @@ def test_failures_stay_inside_their_filter(spe, model):
     failing = expect != 0
     assert np.array_equal(got["mu"][failing], mu_b[failing], equal_nan=True) and np.array_equal(got["cov"][failing], cov_b[failing], equal_nan=True)
     assert np.isnan(got["out_mu"][failing]).all() and np.isnan(got["out_cov"][failing]).all()
-    assert same(got, clean, rows=~failing)
+    assert same(got, clean, ALL_KEYS, rows=~failing)
     assert not np.array_equal(got["mu"][upper], mu[upper])
     ref = pr.predict_sampled(man, mu_b, cov_b, XX, Rb, active=act, initialised=init)
     assert np.array_equal(ref["status"], expect)
@@ -399,8 +375,8 @@ def test_failures_stay_inside_their_filter(spe, model):
 
 # ------------------------------------------------------------------------------------------------------------- 7. refusals
 def test_refusals(spe):
-    c = tsm.case(spe, "pose", "f64", 255)
-    e = tsm.engine_of(spe, c)
+    c = smc.case(spe, "pose", "f64", 255)
+    e = smc.engine_of(spe, c)
     n, pts = c.n, 2 * e.D + 1
     lib = spe.load_library()
     buf = torch.zeros(n * pts * e.S, dtype=torch.float64, device="cuda")
@@ -432,9 +408,9 @@ def test_host_array_form_fp32(spe, pname):
     """fp32 engines: the host form narrows / widens the host doubles itself; its outputs and the committed state are the bits
     of the device form fed the same values rounded to float32.  Five filters."""
     n = 5
-    c = tsm.case(spe, "pose", pname, n)
+    c = smc.case(spe, "pose", pname, n)
     par, R = user(c)
-    e, twin = tsm.engine_of(spe, c), tsm.engine_of(spe, c)
+    e, twin = smc.engine_of(spe, c), smc.engine_of(spe, c)
     X, _, st = e.sigma_points()
     assert (st == 0).all()
     rng = np.random.default_rng(9)
@@ -456,13 +432,13 @@ def test_predict_and_update_compose(spe, model):
     """three cycles of export -> user f -> predict_sampled_dev -> export -> user h (m = 3) -> update_sampled_dev against the same
     three cycles of the two references on the CPU, each fed the samples the device chain produced"""
     n, m = 64, 3
-    c = tsm.case(spe, model, "f64", n)
+    c = smc.case(spe, model, "f64", n)
     man = man_of(model)
     par, R = user(c)
     b, r, noise, Q = sm.make_inputs(model, c.mu, c.dtype)
     z = sm.user_h(model, m, c.mu, b, r) + noise[m]
     name = pr.USER_MODELS[model][-1]
-    e = tsm.engine_of(spe, c)
+    e = smc.engine_of(spe, c)
     zd, qd = dev(e, z), dev(e, Q[m])
     mu_r, cov_r = c.mu.copy(), c.cov.copy()
     for cyc in range(3):
@@ -496,7 +472,7 @@ def test_recorded_in_a_graph(spe):
     replayed twice: the state of two direct rounds on a twin, bit for bit.  (The prediction alone does not read the state; with
     the export and f in front of it the second replay starts from what the first one committed.)"""
     n, model, name = 64, "pose", "drag"
-    c = tsm.case(spe, model, "f64", n)
+    c = smc.case(spe, model, "f64", n)
     par, R = user(c)
     side = torch.cuda.Stream()
     torch.cuda.synchronize()

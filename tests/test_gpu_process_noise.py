@@ -13,15 +13,12 @@ import numpy as np
 import pytest
 
 from conftest import max_abs
+from engine_support import f32r
 
 pytestmark = pytest.mark.gpu
 
 TOL = {0: 1e-9, 1: 1e-4}  # F64, F32
 THREADS = 8               # oracle threads (a GPU box command has 16 CPUs)
-
-
-def f32r(x):
-    return np.asarray(x).astype(np.float32).astype(np.float64)
 
 
 def _dev(x, prec):

@@ -1,7 +1,7 @@
 """User-defined measurement models on the device (ukfb_sigma_points_dev / ukfb_update_sampled_dev and their host forms,
 include/ukf_batch.h).
 
-States: those of tests/test_gpu_sensor_meas.py (synth.pose_initial / orient_initial after two real cycles, downloaded and
+States: those of tests/sensor_meas_cases.py (synth.pose_initial / orient_initial after two real cycles, downloaded and
 re-uploaded bit for bit; its `case` cache is shared).  Inputs: tests/sampled_reference.make_inputs (seed 11), rounded to the
 engine's storage before the reference sees them.  The samples Z are computed BY THE TEST from the exported X with a torch
 expression on the device (tests/sampled_reference.user_h) in the engine's storage type, and the reference takes them as stored.
@@ -19,28 +19,23 @@ import torch
 import feature_scaled_parity as fsp
 import sampled_f32 as sf
 import sampled_reference as sm
+import sensor_meas_cases as smc
 import sensor_meas_reference as sr
-import test_gpu_sensor_meas as tsm
+from engine_support import cycled_engine, dev, host, man_of, same, same_snapshot, scaled, snapshot, stored, tdt
 from oracle import ukf_numpy as on
 
 pytestmark = pytest.mark.gpu
 
-N = tsm.N   # 1022: not a multiple of four
-PRECS = tsm.PRECS
+N = smc.N   # 1022: not a multiple of four
+PRECS = smc.PRECS
 ST_NONFINITE, ST_CHOLESKY, ST_UNINIT, ST_INACTIVE, ST_REJECTED = 1 << 4, 1 << 5, 1 << 7, 1 << 8, 1 << 9
 OUT_KEYS = ("z_pred", "S", "innov", "maha", "loglik")
 ALL_KEYS = ("mu", "cov") + OUT_KEYS + ("status",)
-stored = tsm.stored
-man_of = tsm.man_of
-
-
-def dev(e, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", tsm.tdt(e))
 
 
 def export(e, want_X=True, want_delta=True):
     """-> (X, delta: device tensors in engine precision or None, status uint32 [n]) after sigma_points_dev"""
-    n, dt, pts = e.capacity, tsm.tdt(e), 2 * e.D + 1
+    n, dt, pts = e.capacity, tdt(e), 2 * e.D + 1
     X = torch.full((n, pts, e.S), -7.0, dtype=dt, device="cuda") if want_X else None
     dl = torch.full((n, pts, e.D), -7.0, dtype=dt, device="cuda") if want_delta else None
     st = torch.full((n,), -1, dtype=torch.int32, device="cuda")
@@ -51,13 +46,9 @@ def export(e, want_X=True, want_delta=True):
     return X, dl, st.cpu().numpy().astype(np.uint32)
 
 
-def host(t):
-    return t.double().cpu().numpy()
-
-
 def run(e, Z, z, Q, active=None, commit=True, q_uniform=False):
     """-> dict(mu, cov, z_pred, S, innov, maha, loglik, status) after update_sampled_dev; Z a device tensor or an array"""
-    n, dt = e.capacity, tsm.tdt(e)
+    n, dt = e.capacity, tdt(e)
     Zd = Z if torch.is_tensor(Z) else dev(e, Z)
     m = int(Zd.shape[2])
     zd, qd = dev(e, z), dev(e, np.asarray(Q).reshape(m, m) if q_uniform else np.asarray(Q).reshape(n, m, m))
@@ -89,7 +80,7 @@ def samples(spe, c, m):
         c.samples = {}
     if m not in c.samples:
         b, r, noise, Q = user(c)
-        e = tsm.engine_of(spe, c)
+        e = smc.engine_of(spe, c)
         X, _, st = export(e, want_delta=False)
         assert (st == 0).all()
         Z = host(sm.user_h(c.model, m, X, dev(e, b)[:, None, :], dev(e, r)[:, None, :]))
@@ -101,10 +92,6 @@ def samples(spe, c, m):
 
 def reference(c, m, Z, z, Q, gate=-1.0, **kw):
     return sm.update_sampled(man_of(c.model), c.mu, c.cov, Z, z, Q, gate_chi2=gate, **kw)
-
-
-def scaled(x, ref):
-    return tsm.scaled(x, ref)
 
 
 def check_parity(name, c, got, ref, Z, z, Q, rows=None):
@@ -134,20 +121,15 @@ def check_parity(name, c, got, ref, Z, z, Q, rows=None):
         fsp.judge_meas("sampled/" + name, c.pname, *pick(got), *pick(ref), f32=lambda: tuple(pick(f32()[p]) for p in ("f32", "f64")))
 
 
-def same(a, b, keys=ALL_KEYS, rows=None):
-    rows = slice(None) if rows is None else rows
-    return all(np.array_equal(a[k][rows], b[k][rows], equal_nan=True) for k in keys)
-
-
 # ------------------------------------------------------------------------------------------------------------------ export
 @pytest.mark.parametrize("model", ["pose", "orient"])
 @pytest.mark.parametrize("pname", [p[0] for p in PRECS])
 def test_export(spe, model, pname):
-    c = tsm.case(spe, model, pname)
-    e = tsm.engine_of(spe, c)
-    before = tsm.snapshot(e)
+    c = smc.case(spe, model, pname)
+    e = smc.engine_of(spe, c)
+    before = snapshot(e)
     X, dl, st = export(e)
-    assert tsm.same_snap(before, tsm.snapshot(e))   # read-only on the engine
+    assert same_snapshot(before, snapshot(e))   # read-only on the engine
     Xo, _, st_x = export(e, want_delta=False)
     _, do, st_d = export(e, want_X=False)
     e.close()
@@ -171,7 +153,7 @@ def test_export_failures_stay_inside_their_filter(spe, model):
     the bits of a run without the broken covariance"""
     n, dead, neg = 64, 22, 34
     man = man_of(model)
-    e = tsm.cycled_engine(spe, model, n, 0, 0, skip_init=(dead,))
+    e = cycled_engine(spe, model, n, 0, 0, skip_init=(dead,))
     mu, cov, init = e.state()
     assert not init[dead]
     Xc, dc, stc = export(e)
@@ -200,7 +182,7 @@ def committed(spe, c, m):
     key = (c.model, c.pname, c.n, m)
     if key not in _RUNS:
         Z, z, Q = samples(spe, c, m)
-        e = tsm.engine_of(spe, c)
+        e = smc.engine_of(spe, c)
         _RUNS[key] = run(e, Z, z, Q)
         assert np.array_equal(e.status(), _RUNS[key]["status"])   # commit = 1 writes the engine's own status array too
         e.close()
@@ -210,7 +192,7 @@ def committed(spe, c, m):
 @pytest.mark.parametrize("model", ["pose", "orient"])
 @pytest.mark.parametrize("pname", [p[0] for p in PRECS])
 def test_parity(spe, model, pname):
-    c = tsm.case(spe, model, pname)
+    c = smc.case(spe, model, pname)
     for m in sm.USER_DIMS:
         Z, z, Q = samples(spe, c, m)
         got, ref = committed(spe, c, m), reference(c, m, Z, z, Q)
@@ -223,9 +205,9 @@ def test_parity(spe, model, pname):
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_small_batches(spe, model):
     """1, 2, 3 and 5 filters: one partly filled wavefront, and a full one with a one-row tail"""
-    big = tsm.case(spe, model, "f64", 255)
+    big = smc.case(spe, model, "f64", 255)
     for n in (1, 2, 3, 5):
-        c = tsm.Case()
+        c = smc.Case()
         c.model, c.pname, c.n, c.prec, c.wide, c.tol, c.dtype = model, "f64", n, 0, 0, 1e-9, big.dtype
         c.mu, c.cov, c.gyro = big.mu[:n], big.cov[:n], big.gyro[:n]
         for m in (1, 6):
@@ -242,9 +224,9 @@ def test_user_model_reproduces_builtin(spe):
     evaluate h on sigma points they hold in fp64 registers, a user model sees X rounded to fp32 -- an input perturbation, not a
     kernel error."""
     for model, mid in (("pose", sr.POSE_RANGE), ("pose", sr.POSE_POINT), ("orient", sr.ORIENT_NAV_VECTOR)):
-        c = tsm.case(spe, model, "f64")
+        c = smc.case(spe, model, "f64")
         m = sr.meas_dim(mid)
-        e, twin = tsm.engine_of(spe, c), tsm.engine_of(spe, c)
+        e, twin = smc.engine_of(spe, c), smc.engine_of(spe, c)
         X, _, _ = export(e)
         r, qs, b = dev(e, c.mount[:, None, 0:3]), dev(e, c.mount[:, None, 3:7]), dev(e, c.point[:, None, :])
         if mid == sr.POSE_RANGE:
@@ -254,9 +236,9 @@ def test_user_model_reproduces_builtin(spe):
         else:
             Zt = sm.rot_t(qs, sm.rot_t(X[..., 0:4], b + 0.0 * X[..., 4:7]))
         got = run(e, Zt, c.z[mid][:, :m], c.Q[:, :m, :m])
-        built = tsm.run_case(twin, c, mid)
+        built = smc.run_case(twin, c, mid)
         e.close(); twin.close()
-        ref = tsm.reference(c, mid)
+        ref = smc.reference(c, mid)
         assert (got["status"] == 0).all() and (built["status"] == 0).all() and (ref["status"] == 0).all()
         cut = {"z_pred": ref["z_pred"][:, :m], "S": ref["S"][:, :m, :m], "innov": ref["innov"][:, :m]}
         err = {k: scaled(got[k], cut.get(k, ref[k])) for k in ALL_KEYS[:-1]}
@@ -265,9 +247,9 @@ def test_user_model_reproduces_builtin(spe):
               f" built-in worst={max(err_b.values()):.3e} tol={c.tol:.3e}")
         assert all(v <= c.tol for v in err.values()) and all(v <= c.tol for v in err_b.values()), (mid, err, err_b)
     # the position selection against ukfb_update_dev(UKFB_MEAS_POS3)
-    c = tsm.case(spe, "pose", "f64")
+    c = smc.case(spe, "pose", "f64")
     z = stored(c.mu[:, 0:3] + 0.05 * np.random.default_rng(29).standard_normal((c.n, 3)), c.dtype)
-    e, twin = tsm.engine_of(spe, c), tsm.engine_of(spe, c)
+    e, twin = smc.engine_of(spe, c), smc.engine_of(spe, c)
     X, _, _ = export(e)
     got = run(e, X[..., 0:3], z, c.Q)
     twin.update(spe.MEAS_POS3, z, c.Q)
@@ -284,44 +266,44 @@ def test_user_model_reproduces_builtin(spe):
 # ------------------------------------------------------------------------------------------------------- bit-level properties
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_bit_level_properties(spe, model):
-    c = tsm.case(spe, model, "f64")
+    c = smc.case(spe, model, "f64")
     n, m = c.n, 4
     Z, z, Q = samples(spe, c, m)
     base = committed(spe, c, m)
     assert (base["status"] == 0).all()
 
     def fresh(**kw):
-        e = tsm.engine_of(spe, c, **kw)
+        e = smc.engine_of(spe, c, **kw)
         e.set_last_measurement_time(np.arange(1, n + 1, dtype=np.int64) * 1000 + 7)
         return e
     # commit = 0: the whole downloadable engine keeps its bits, the outputs are the committing call's; then commit = 1: the
     # numbers of commit = 1 alone
     e = fresh()
-    before = tsm.snapshot(e)
+    before = snapshot(e)
     dry = run(e, Z, z, Q, commit=False)
-    assert tsm.same_snap(before, tsm.snapshot(e))
-    assert same(dry, base, keys=OUT_KEYS + ("status",)) and np.array_equal(dry["mu"], c.mu) and np.array_equal(dry["cov"], c.cov)
-    assert same(run(e, Z, z, Q), base)
+    assert same_snapshot(before, snapshot(e))
+    assert same(dry, base, OUT_KEYS + ("status",)) and np.array_equal(dry["mu"], c.mu) and np.array_equal(dry["cov"], c.cov)
+    assert same(run(e, Z, z, Q), base, ALL_KEYS)
     e.close()
     # active = NULL equals all ones; a gate nothing reaches = no gate
     e = fresh(gate_chi2=1e300)
-    assert same(run(e, Z, z, Q, active=np.ones(n, dtype=np.uint8)), base)
+    assert same(run(e, Z, z, Q, active=np.ones(n, dtype=np.uint8)), base, ALL_KEYS)
     e.close()
     # ONE m x m with q_is_uniform equals the repeated Q
     Qu = np.broadcast_to(Q[5], Q.shape).copy()
     e, e2 = fresh(), fresh()
-    assert same(run(e, Z, z, Qu[0], q_uniform=True), run(e2, Z, z, Qu))
+    assert same(run(e, Z, z, Qu[0], q_uniform=True), run(e2, Z, z, Qu), ALL_KEYS)
     e.close(); e2.close()
     # a filter's bits are the same in the batch of 1022, alone, and at another index (row 2 of a second wavefront)
     i = 7
     for nn, at in ((1, 0), (7, 6)):
-        s = tsm.Case()
+        s = smc.Case()
         s.__dict__.update(c.__dict__)
         s.n = nn
         pick = np.arange(nn) + 40   # the other rows: other filters' states
         pick[at] = i
         s.mu, s.cov, s.gyro = c.mu[pick], c.cov[pick], c.gyro[pick]
-        e = tsm.engine_of(spe, s)
+        e = smc.engine_of(spe, s)
         one = run(e, Z[pick], z[pick], Q[pick])
         e.close()
         assert all(np.array_equal(one[k][at], base[k][i], equal_nan=True) for k in ALL_KEYS), (nn, at)
@@ -334,7 +316,7 @@ def test_bit_level_properties(spe, model):
     e, e2 = fresh(), fresh()
     a, b = run(e, Zg, zg, Q), run(e2, Zg + t[:, None, :], zg + t, Q)
     e.close(); e2.close()
-    assert (a["status"] == 0).all() and same(a, b, keys=("mu", "cov", "S", "innov", "maha", "loglik", "status"))
+    assert (a["status"] == 0).all() and same(a, b, ("mu", "cov", "S", "innov", "maha", "loglik", "status"))
     assert np.abs(b["z_pred"] - (a["z_pred"] + t)).max() <= 1e-12 * 1000.0
 
 
@@ -343,14 +325,14 @@ def test_bit_level_properties(spe, model):
 def test_gate(spe, model, pname):
     """gate_chi2 = the median of the reference's d^2: accepted and REJECTED_GATE split as the reference's; filters within the
     margin of tests/test_gpu_sensor_meas.py::test_gate of the gate are left out, under its cap"""
-    c = tsm.case(spe, model, pname)
+    c = smc.case(spe, model, pname)
     m = 3
     Z, z, Q = samples(spe, c, m)
     free = reference(c, m, Z, z, Q)
     gate = float(np.median(free["maha"]))
     assert free["maha"].min() < gate < free["maha"].max()
     ref = reference(c, m, Z, z, Q, gate=gate)
-    e = tsm.engine_of(spe, c, gate_chi2=gate)
+    e = smc.engine_of(spe, c, gate_chi2=gate)
     got = run(e, Z, z, Q)
     e.close()
     near = np.abs(free["maha"] - gate) <= c.tol * (1.0 + free["maha"])
@@ -371,7 +353,7 @@ def test_failures_stay_inside_their_filter(spe, model):
     n, m, dead = 64, 6, 22
     nan_s, nan_z, neg_q, idle, upper = 13, 17, 25, 38, 41   # every one in another wavefront
     man = man_of(model)
-    e = tsm.cycled_engine(spe, model, n, 0, 0, skip_init=(dead,))
+    e = cycled_engine(spe, model, n, 0, 0, skip_init=(dead,))
     mu, cov, init = e.state()
     assert not init[dead] and init.sum() == n - 1
     mu_f = mu.copy()
@@ -400,11 +382,11 @@ def test_failures_stay_inside_their_filter(spe, model):
     failing = expect != 0
     assert np.array_equal(got["mu"][failing], mu[failing], equal_nan=True) and np.array_equal(got["cov"][failing], cov[failing], equal_nan=True)
     assert all(np.isnan(got[k][failing]).all() for k in OUT_KEYS)
-    twin = tsm.cycled_engine(spe, model, n, 0, 0, skip_init=(dead,))
+    twin = cycled_engine(spe, model, n, 0, 0, skip_init=(dead,))
     ok = run(twin, Z, z, Q)
     twin.close()
-    assert same(ok, clean, keys=OUT_KEYS + ("status",))
-    assert same(got, ok, rows=~failing)
+    assert same(ok, clean, OUT_KEYS + ("status",))
+    assert same(got, ok, ALL_KEYS, rows=~failing)
     assert not np.array_equal(got["mu"][upper], mu[upper])
     ref = sm.update_sampled(man, mu_f, cov, Zb, zb, Qb, active=act, initialised=init)
     assert np.array_equal(ref["status"], expect)
@@ -412,8 +394,8 @@ def test_failures_stay_inside_their_filter(spe, model):
 
 # ------------------------------------------------------------------------------------------------------------------ refusals
 def test_refusals(spe):
-    c = tsm.case(spe, "pose", "f64", 255)
-    e = tsm.engine_of(spe, c)
+    c = smc.case(spe, "pose", "f64", 255)
+    e = smc.engine_of(spe, c)
     n, pts = c.n, 2 * e.D + 1
     for m in (0, 7):   # code 4 = UKFB_ERR_OUT_OF_RANGE; nothing is written
         Zd = torch.zeros((n, pts, max(m, 1)), dtype=torch.float64, device="cuda")
@@ -448,9 +430,9 @@ def test_host_array_form_fp32(spe, pname):
     """fp32 engines: the host forms narrow / widen the host doubles themselves; their outputs and the committed state are the
     bits of the device forms fed the same values rounded to float32.  Five filters."""
     n, m = 5, 3
-    c = tsm.case(spe, "pose", pname, n)
+    c = smc.case(spe, "pose", pname, n)
     b, r, noise, Qs = user(c)
-    e, twin = tsm.engine_of(spe, c), tsm.engine_of(spe, c)
+    e, twin = smc.engine_of(spe, c), smc.engine_of(spe, c)
     X, dl, st = e.sigma_points()
     Xd, dd, std = export(twin)
     assert np.array_equal(X, host(Xd)) and np.array_equal(dl, host(dd)) and np.array_equal(st, std) and (st == 0).all()
@@ -461,5 +443,5 @@ def test_host_array_form_fp32(spe, pname):
     o = e.update_sampled(Z, z, Qs[m])
     o["mu"], o["cov"], _ = e.state()
     d = run(twin, stored(Z, np.float32), stored(z, np.float32), Qs[m])
-    assert same(o, d) and np.array_equal(e.status(), twin.status()) and (o["status"] == 0).all()
+    assert same(o, d, ALL_KEYS) and np.array_equal(e.status(), twin.status()) and (o["status"] == 0).all()
     e.close(); twin.close()

@@ -24,186 +24,20 @@ import subprocess
 
 import numpy as np
 import pytest
-import torch
 
 import feature_f32 as ff
 import feature_scaled_parity as fsp
 import sensor_meas_reference as sr
-from oracle import ukf_numpy as on
+from engine_support import cycled_engine, man_of, same, same_snapshot, scaled, snapshot, stored
+from sensor_meas_cases import (PRECS, Case, case, cycling_ids, engine_of, make_inputs, mixed_z, reference, run, run_case,
+                               spe_identity)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N = 1022   # not a multiple of four: the last workgroup holds two filters
-PRECS = [("f64", 0, 0, 1e-9), ("f32", 1, 0, 1e-4), ("f32w", 1, 1, 1e-9 + 2.0 ** -23)]
-ACC_COV = 0.01 * np.eye(3)
 ST_NONFINITE, ST_CHOLESKY, ST_UNINIT, ST_INACTIVE, ST_REJECTED = 1 << 4, 1 << 5, 1 << 7, 1 << 8, 1 << 9
 OUT_KEYS = ("z_pred", "S", "innov", "maha", "loglik")
 ALL_KEYS = ("mu", "cov") + OUT_KEYS + ("status",)
-
-
-def tdt(e):
-    return torch.float64 if e.dtype == np.float64 else torch.float32
-
-
-def man_of(model):
-    return on.POSE if model == "pose" else on.ORIENT
-
-
-def ids_of(model):
-    return sr.POSE_IDS if model == "pose" else sr.ORIENT_IDS
-
-
-def new_engine(spe, model, n, prec, wide, **kw):
-    cfg = dict(kw)
-    if wide:
-        cfg["wide_arithmetic"] = 1
-    if model == "pose":
-        return spe.BatchPoseUKF(n, precision=prec, **cfg)
-    sy = spe.synth
-    e = spe.BatchOrientationUKF(n, sy.ORIENT_TAU, sy.ORIENT_TAU, sy.ORIENT_LATITUDE, precision=prec, **cfg)
-    e.set_process_noise(sy.orient_process_noise())
-    return e
-
-
-def cycled_engine(spe, model, n, prec, wide, skip_init=(), **kw):
-    """an engine after two real cycles (Pose: acceleration branch, POS3; OrientationState: its body-velocity update)"""
-    sy = spe.synth
-    e = new_engine(spe, model, n, prec, wide, **kw)
-    mu0, cov0 = sy.pose_initial(n) if model == "pose" else sy.orient_initial(n)
-    if skip_init:
-        for i in range(n):
-            if i not in skip_init:
-                e.initialize(mu0[i:i + 1], cov0[i:i + 1], first=i)
-    else:
-        e.initialize(mu0, cov0)
-    for c in range(2):
-        mu_now = e.state(with_cov=False)[0]
-        if model == "pose":
-            acc, z, Q = sy.pose_cycle_inputs(n, c, mu_now[:, :3])
-            e.set_acceleration(acc, ACC_COV)
-            e.cycle(0.01, spe.MEAS_POS3, z, Q)
-        else:
-            gyro, acc, z, Q = sy.orient_cycle_inputs(n, c, mu_now[:, 0:4])
-            e.set_orient_inputs(gyro, acc)
-            e.cycle(0.01, spe.MEAS_ORIENT_BODYVEL3, z, Q)
-    return e
-
-
-def stored(x, dtype):
-    return np.asarray(x, dtype=np.float64).astype(dtype).astype(np.float64)
-
-
-def make_inputs(model, mu, dtype, seed=5):
-    """-> (mount [n, 7], point [n, 3], gyro [n, 3], {id: z [n, 3]}, Q [n, 3, 3]) as the engine stores them"""
-    n = mu.shape[0]
-    rng = np.random.default_rng(seed)
-    mount = np.concatenate([rng.uniform(-1.0, 1.0, (n, 3)), on.so3_exp(rng.uniform(-1.0, 1.0, (n, 3)))], axis=1)
-    d = rng.standard_normal((n, 3))
-    away = d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(15.0, 80.0, (n, 1))
-    point = (mu[:, 0:3] + away) if model == "pose" else away
-    gyro = 0.1 * rng.standard_normal((n, 3))
-    mount, point, gyro = stored(mount, dtype), stored(point, dtype), stored(gyro, dtype)
-    z = {}
-    for mid in ids_of(model):
-        zz = np.zeros((n, 3))
-        zz[:, :sr.meas_dim(mid)] = sr.h(mid, mu, mount, point, gyro) + 0.05 * rng.standard_normal((n, sr.meas_dim(mid)))
-        z[mid] = stored(zz, dtype)
-    Q = stored(np.broadcast_to(0.05 ** 2 * np.eye(3), (n, 3, 3)), dtype)
-    return mount, point, gyro, z, Q
-
-
-class Case:
-    """the state of a cycled engine as downloaded, and inputs as stored; fresh engines are initialised from it"""
-
-
-_CACHE = {}
-
-
-def case(spe, model, pname, n=N):
-    key = (model, pname, n)
-    if key not in _CACHE:
-        _, prec, wide, tol = [p for p in PRECS if p[0] == pname][0]
-        e = cycled_engine(spe, model, n, prec, wide)
-        c = Case()
-        c.model, c.pname, c.n, c.prec, c.wide, c.tol = model, pname, n, prec, wide, tol
-        c.mu, c.cov, _ = e.state()
-        c.dtype = e.dtype
-        e.close()
-        c.mount, c.point, c.gyro, c.z, c.Q = make_inputs(model, c.mu, c.dtype)
-        if model == "pose":
-            dist = np.linalg.norm(c.point - c.mu[:, 0:3], axis=1)
-            assert 14.9 < dist.min() and dist.max() < 80.1
-        c.refs = {}
-        _CACHE[key] = c
-    return _CACHE[key]
-
-
-def engine_of(spe, c, **kw):
-    e = new_engine(spe, c.model, c.n, c.prec, c.wide, **kw)
-    e.initialize(c.mu, c.cov)
-    if c.model == "orient":
-        e.set_orient_inputs(gyro=c.gyro)
-    m, C, _ = e.state()
-    assert np.array_equal(m, c.mu) and np.array_equal(C, c.cov)   # the downloaded state goes back in bit for bit
-    return e
-
-
-def run(e, ids, z, Q, mount, point, commit=True, q_uniform=False):
-    """-> dict(mu, cov, z_pred, S, innov, maha, loglik, status) after update_sensor_dev; mount [7] / point [3]: uniform"""
-    n, dt = e.capacity, tdt(e)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dt)
-    zd = dev(z)
-    qd = dev(np.asarray(Q).reshape(9) if q_uniform else np.asarray(Q).reshape(n, 9))
-    idd = None if np.isscalar(ids) else torch.from_numpy(np.asarray(ids, dtype=np.int32)).to("cuda")
-    mount, point = np.asarray(mount), np.asarray(point)
-    md = dev(mount) if mount.ndim == 2 else None
-    pd = dev(point) if point.ndim == 2 else None
-    o = {"z_pred": torch.full((n, 3), -7.0, dtype=dt, device="cuda"), "S": torch.full((n, 9), -7.0, dtype=dt, device="cuda"),
-         "innov": torch.full((n, 3), -7.0, dtype=dt, device="cuda"), "maha": torch.full((n,), -7.0, dtype=dt, device="cuda"),
-         "loglik": torch.full((n,), -7.0, dtype=dt, device="cuda"), "status": torch.full((n,), -1, dtype=torch.int32, device="cuda")}
-    torch.cuda.synchronize()
-    e.update_sensor_dev(int(ids) if idd is None else 0, zd, qd, q_is_uniform=q_uniform, model_dev=idd, mount_dev=md,
-                        mount=mount if md is None else spe_identity(), point_dev=pd, point=point if pd is None else (0.0, 0.0, 0.0),
-                        commit=commit, **o)
-    e.sync()
-    torch.cuda.synchronize()
-    r = {k: v.double().cpu().numpy() for k, v in o.items() if k != "status"}
-    r["S"] = r["S"].reshape(n, 3, 3)
-    r["status"] = o["status"].cpu().numpy().astype(np.uint32)
-    r["mu"], r["cov"], _ = e.state()
-    return r
-
-
-def spe_identity():
-    return (0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0)
-
-
-def run_case(e, c, ids, **kw):
-    z = c.z[int(ids)] if np.isscalar(ids) else mixed_z(c, ids)
-    return run(e, ids, z, c.Q, c.mount, c.point, **kw)
-
-
-def mixed_z(c, ids):
-    z = np.zeros((c.n, 3))
-    for mid in ids_of(c.model):
-        z[ids == mid] = c.z[mid][ids == mid]
-    return z
-
-
-def reference(c, ids, gate=-1.0):
-    key = (int(ids), gate) if np.isscalar(ids) else None
-    if key is not None and key in c.refs:
-        return c.refs[key]
-    z = c.z[int(ids)] if np.isscalar(ids) else mixed_z(c, ids)
-    ref = sr.update_sensor(man_of(c.model), c.mu, c.cov, ids, z, c.Q, c.mount, c.point, c.gyro, gate_chi2=gate)
-    if key is not None:
-        c.refs[key] = ref
-    return ref
-
-
-def scaled(x, ref):
-    return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref)))) if x.size else 0.0
 
 
 def check_parity(name, c, got, ref, tol=None, rows=None, ids=None):
@@ -232,23 +66,12 @@ def check_parity(name, c, got, ref, tol=None, rows=None, ids=None):
         return evals
     fsp.judge_state("sensor_meas/" + name, c.model, c.pname, got["mu"][rows], got["cov"][rows], ref["mu"][rows], ref["cov"][rows],
                     f32=lambda: tuple((f32()[p]["mu"][rows], f32()[p]["cov"][rows]) for p in ("f32", "f64")))
-    dims = np.array([sr.meas_dim(int(i)) if i in ids_of(c.model) else 0 for i in idv])
+    dims = np.array([sr.meas_dim(int(i)) if i in sr.ids_of(man_of(c.model)) else 0 for i in idv])
     for m in (1, 3):
         sel = scored & (dims == m)
         if sel.any():
             pick = lambda o: (o["z_pred"][sel][:, :m], o["S"][sel][:, :m, :m], o["innov"][sel][:, :m])   # noqa: E731
             fsp.judge_meas(f"sensor_meas/{name}/m={m}", c.pname, *pick(got), *pick(ref), f32=lambda: tuple(pick(f32()[p]) for p in ("f32", "f64")))
-
-
-def same(a, b, keys=ALL_KEYS, rows=None):
-    rows = slice(None) if rows is None else rows
-    return all(np.array_equal(a[k][rows], b[k][rows], equal_nan=True) for k in keys)
-
-
-def cycling_ids(model, n):
-    """every model of the engine, -1 and one id of the other engine, so that four wave-mates always differ"""
-    table = list(ids_of(model)) + [-1, sr.ORIENT_VELOCITY if model == "pose" else sr.POSE_POSITION]
-    return np.array(table, dtype=np.int32)[np.arange(n) % len(table)]
 
 
 # ------------------------------------------------------------------------------------------------------------------ parity
@@ -257,7 +80,7 @@ def cycling_ids(model, n):
 def test_parity(spe, model, pname):
     c = case(spe, model, pname)
     uniform = {}
-    for mid in ids_of(model):
+    for mid in sr.ids_of(man_of(model)):
         e = engine_of(spe, c)
         got, ref = run_case(e, c, mid), reference(c, mid)
         e.close()
@@ -275,13 +98,13 @@ def test_parity(spe, model, pname):
     got = run_case(e, c, per)
     assert np.array_equal(e.status(), got["status"])   # commit = 1 writes the engine's own status array too
     e.close()
-    idle = ~np.isin(per, ids_of(model))
+    idle = ~np.isin(per, sr.ids_of(man_of(model)))
     assert idle.sum() >= c.n // 7
     assert np.array_equal(got["status"], np.where(idle, ST_INACTIVE, 0))
     assert np.array_equal(got["mu"][idle], c.mu[idle]) and np.array_equal(got["cov"][idle], c.cov[idle])
     assert all(np.isnan(got[k][idle]).all() for k in OUT_KEYS)
-    for mid in ids_of(model):
-        assert same(got, uniform[mid], rows=per == mid), mid
+    for mid in sr.ids_of(man_of(model)):
+        assert same(got, uniform[mid], ALL_KEYS, rows=per == mid), mid
     check_parity(f"{model}/{pname}/per-filter-ids", c, got, reference(c, per), ids=per)
 
 
@@ -290,7 +113,7 @@ def test_parity(spe, model, pname):
 def test_gate(spe, model, pname):
     """a gate between the batch's smallest and largest d^2: accepted and REJECTED_GATE split as the reference's"""
     c = case(spe, model, pname)
-    mid = ids_of(model)[0]
+    mid = sr.ids_of(man_of(model))[0]
     free = reference(c, mid)
     gate = float(np.median(free["maha"]))
     assert free["maha"].min() < gate < free["maha"].max()
@@ -310,24 +133,12 @@ def test_gate(spe, model, pname):
 
 
 # ------------------------------------------------------------------------------------------------------- bit-level properties
-def snapshot(e):
-    """everything of the engine that can be downloaded"""
-    mu, cov, init = e.state()
-    noise = np.array([e.process_noise(i) for i in range(e.capacity)])
-    latch = e.rotation_rate() if e.model == 1 else np.zeros(0)
-    return mu, cov, init, e.status(), e.last_measurement_time(), noise, latch
-
-
-def same_snap(a, b):
-    return all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
-
-
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_bit_level_properties(spe, model, tmp_path):
     n = 255
     c = case(spe, model, "f64", n)
     per = cycling_ids(model, n)
-    mid = ids_of(model)[0] + 2 if model == "pose" else sr.ORIENT_VELOCITY   # POSE_POINT / ORIENT_VELOCITY: read mount (and point)
+    mid = sr.ids_of(man_of(model))[0] + 2 if model == "pose" else sr.ORIENT_VELOCITY   # POSE_POINT / ORIENT_VELOCITY: read mount (and point)
     mount1, point1 = c.mount[7], c.point[7]
 
     def fresh(**kw):
@@ -342,25 +153,25 @@ def test_bit_level_properties(spe, model, tmp_path):
     # per-filter mount / point arrays that repeat the uniform ones; a device array filled with the id; per-filter Q repeated
     # against ONE 3x3
     e = fresh()
-    assert same(run(e, np.full(n, mid, dtype=np.int32), c.z[mid], c.Q, np.tile(mount1, (n, 1)), np.tile(point1, (n, 1))), base)
+    assert same(run(e, np.full(n, mid, dtype=np.int32), c.z[mid], c.Q, np.tile(mount1, (n, 1)), np.tile(point1, (n, 1))), base, ALL_KEYS)
     e.close()
     e = fresh()
-    assert same(run(e, mid, c.z[mid], c.Q[0], mount1, point1, q_uniform=True), base)
+    assert same(run(e, mid, c.z[mid], c.Q[0], mount1, point1, q_uniform=True), base, ALL_KEYS)
     e.close()
     # a gate nothing reaches = no gate
     e = fresh(gate_chi2=1e300)
-    assert same(run(e, mid, c.z[mid], c.Q, mount1, point1), base)
+    assert same(run(e, mid, c.z[mid], c.Q, mount1, point1), base, ALL_KEYS)
     e.close()
     # the host form = the device form (per-filter ids, mounts and points too)
     e = fresh()
     o = e.update_sensor(mid, c.z[mid], c.Q, mount1, point1)
     o["mu"], o["cov"], _ = e.state()
-    assert same(o, base)
+    assert same(o, base, ALL_KEYS)
     e.close()
     e, e2 = fresh(), fresh()
     o = e.update_sensor(per, mixed_z(c, per), c.Q, c.mount, c.point)
     o["mu"], o["cov"], _ = e.state()
-    assert same(o, run_case(e2, c, per))
+    assert same(o, run_case(e2, c, per), ALL_KEYS)
     e.close(); e2.close()
     # commit = 0: the whole downloadable engine keeps its bits, the outputs are the committing call's, and the next
     # prediction is an untouched twin's
@@ -368,16 +179,16 @@ def test_bit_level_properties(spe, model, tmp_path):
     before = snapshot(e)
     dry = run(e, mid, c.z[mid], c.Q, mount1, point1, commit=False)
     dry_per = run_case(e, c, per, commit=False)
-    assert same_snap(before, snapshot(e)) and same_snap(before, snapshot(twin))
-    assert same(dry, base, keys=OUT_KEYS + ("status",)) and np.array_equal(dry["mu"], c.mu) and np.array_equal(dry["cov"], c.cov)
-    assert np.array_equal(dry_per["status"], np.where(np.isin(per, ids_of(model)), 0, ST_INACTIVE))
+    assert same_snapshot(before, snapshot(e)) and same_snapshot(before, snapshot(twin))
+    assert same(dry, base, OUT_KEYS + ("status",)) and np.array_equal(dry["mu"], c.mu) and np.array_equal(dry["cov"], c.cov)
+    assert np.array_equal(dry_per["status"], np.where(np.isin(per, sr.ids_of(man_of(model))), 0, ST_INACTIVE))
     e.predict(0.013); twin.predict(0.013)
-    assert same_snap(snapshot(e), snapshot(twin))
+    assert same_snapshot(snapshot(e), snapshot(twin))
     e.close(); twin.close()
     # commit = 0, then commit = 1: the same numbers as commit = 1 alone
     e = fresh()
     run(e, mid, c.z[mid], c.Q, mount1, point1, commit=False)
-    assert same(run(e, mid, c.z[mid], c.Q, mount1, point1), base)
+    assert same(run(e, mid, c.z[mid], c.Q, mount1, point1), base, ALL_KEYS)
     e.close()
     # integrateSensorMeasurement of include/pose_estimation/Batch.hpp from a C++ host: the same bits
     gxx = shutil.which("g++")
@@ -406,7 +217,7 @@ def test_bit_level_properties(spe, model, tmp_path):
         at += cnt
     assert at == raw.size
     o["status"] = o["status"].astype(np.uint32)
-    assert same(o, base)
+    assert same(o, base, ALL_KEYS)
 
 
 @pytest.mark.parametrize("model", ["pose", "orient"])
@@ -414,7 +225,7 @@ def test_small_batches(spe, model):
     """1, 2, 3 and 5 filters: one partly filled wavefront, and a full one with a one-row tail"""
     big = case(spe, model, "f64", 255)
     for n in (1, 2, 3, 5):
-        for mid in ids_of(model):
+        for mid in sr.ids_of(man_of(model)):
             c = Case()
             c.model, c.pname, c.n, c.prec, c.wide, c.tol, c.dtype = model, "f64", n, 0, 0, 1e-9, big.dtype
             c.mu, c.cov, c.mount, c.point, c.gyro, c.Q = big.mu[:n], big.cov[:n], big.mount[:n], big.point[:n], big.gyro[:n], big.Q[:n]
@@ -444,7 +255,7 @@ def test_host_array_form_fp32(spe, pname):
         o = e.update_sensor(mid, z, c.Q, mt, pt)
         o["mu"], o["cov"], _ = e.state()
         dev = run(twin, mid, stored(z, np.float32), c.Q, stored(mt, np.float32), stored(pt, np.float32))
-        assert same(o, dev) and np.array_equal(e.status(), twin.status()) and (o["status"] == 0).all()
+        assert same(o, dev, ALL_KEYS) and np.array_equal(e.status(), twin.status()) and (o["status"] == 0).all()
         e.close(); twin.close()
 
 
@@ -470,7 +281,7 @@ def test_failures_stay_inside_their_filter(spe, model):
     rng_id = sr.POSE_RANGE if model == "pose" else sr.ORIENT_SPECIFIC_FORCE
     ids[list(unused)] = [rng_id, sr.POSE_VELOCITY if model == "pose" else sr.ORIENT_VELOCITY, sr.POSE_NAV_VELOCITY if model == "pose" else sr.ORIENT_SPECIFIC_FORCE]
     z = np.zeros((n, 3))
-    for mid in ids_of(model):
+    for mid in sr.ids_of(man_of(model)):
         z[ids == mid] = zs[mid][ids == mid]
     snap = e.state()
     clean = run(e, ids, z, Q, mount, point, commit=False)
@@ -514,8 +325,8 @@ def test_failures_stay_inside_their_filter(spe, model):
         twin.set_orient_inputs(gyro=gyro)
     ok = run(twin, ids, z, Q, mount, point)
     twin.close(); e.close()
-    assert same(ok, clean, keys=OUT_KEYS + ("status",))
-    assert same(got, ok, rows=~failing)
+    assert same(ok, clean, OUT_KEYS + ("status",))
+    assert same(got, ok, ALL_KEYS, rows=~failing)
     for i in unused:
         assert not np.array_equal(got["mu"][i], mu[i])
     ref = sr.update_sensor(man, mu_f, cov_bad, ib, zb, Qb, mb, pb, gyro, initialised=init)
@@ -556,6 +367,6 @@ def test_uniform_id_of_the_other_engine_is_refused(spe):
         c = case(spe, model, "f64", 255)
         e = engine_of(spe, c)
         with pytest.raises(spe.UkfbError, match="code 5"):
-            run(e, wrong, c.z[ids_of(model)[0]], c.Q, c.mount, c.point)
+            run(e, wrong, c.z[sr.ids_of(man_of(model))[0]], c.Q, c.mount, c.point)
         assert np.array_equal(e.state()[0], c.mu)
         e.close()

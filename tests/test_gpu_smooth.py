@@ -25,6 +25,7 @@ import torch
 import feature_f32 as ff
 import feature_scaled_parity as fsp
 import smoother_reference as sr
+from engine_support import host, new_engine, same_snapshot, scaled, snapshot, tdt, unpack
 
 pytestmark = pytest.mark.gpu
 
@@ -33,22 +34,6 @@ STEPS, SLOTS, FIRST = 6, 8, 5
 PRECS = [("f64", 0, 0, 1e-9), ("f32", 1, 0, 1e-4), ("f32w", 1, 1, 1e-9 + 2.0 ** -23)]
 ACC_COV = 0.01 * np.eye(3)
 ST_SKIPPED_SMALL_DT, ST_ERR_CHOLESKY, ST_UNINITIALISED = 1 << 1, 1 << 5, 1 << 7
-
-
-def tdt(e):
-    return torch.float64 if e.dtype == np.float64 else torch.float32
-
-
-def new_engine(spe, model, n, prec, wide, **kw):
-    cfg = dict(kw)
-    if wide:
-        cfg["wide_arithmetic"] = 1
-    if model == "pose":
-        return spe.BatchPoseUKF(n, precision=prec, **cfg)
-    sy = spe.synth
-    e = spe.BatchOrientationUKF(n, sy.ORIENT_TAU, sy.ORIENT_TAU, sy.ORIENT_LATITUDE, precision=prec, **cfg)
-    e.set_process_noise(sy.orient_process_noise())
-    return e
 
 
 class Recording:
@@ -106,23 +91,12 @@ def record(spe, model, n, prec, wide, steps=STEPS, slots=SLOTS, first=FIRST, ski
     return r
 
 
-def unpack(cov_packed, D):
-    c = cov_packed.double().cpu().numpy()
-    out = np.zeros(c.shape[:-1] + (D, D))
-    k = 0
-    for i in range(D):
-        for j in range(i + 1):
-            out[..., i, j] = out[..., j, i] = c[..., k]
-            k += 1
-    return out
-
-
 def reference(spe, r, mu_hist=None, cov_hist=None, dt=None, steps=None, first=None, rings=True):
     e, sy = r.e, spe.synth
     steps = r.steps if steps is None else steps
     first = r.first if first is None else first
     mu = sr.window_order((r.mu_hist if mu_hist is None else mu_hist).double().cpu().numpy(), first, steps)
-    cov = sr.window_order(unpack(r.cov_hist if cov_hist is None else cov_hist, e.D), first, steps)
+    cov = sr.window_order(unpack(host(r.cov_hist if cov_hist is None else cov_hist), e.D), first, steps)
     a = sr.window_order(r.in_a.double().cpu().numpy(), first, steps)
     b = sr.window_order(r.in_b.double().cpu().numpy(), first, steps)
     if not rings:   # the engine's latched inputs serve every step
@@ -165,12 +139,8 @@ def run(r, dt=None, steps=None, first=None, mu_hist=None, cov_hist=None, in_plac
                  in_a_dev=r.in_a if rings else None, in_b_dev=r.in_b if rings else None)
     torch.cuda.synchronize()
     mu_s = sr.window_order(mo.double().cpu().numpy(), first, steps)
-    cov_s = sr.window_order(unpack(co, e.D), first, steps) if co is not False else None
+    cov_s = sr.window_order(unpack(host(co), e.D), first, steps) if co is not False else None
     return mu_s, cov_s, st.cpu().numpy().astype(np.uint32), (mo, co)
-
-
-def scaled(x, ref):
-    return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref))))
 
 
 def check_parity(name, r, got, ref, tol, wide, rows=slice(None), unscaled=()):
@@ -243,7 +213,7 @@ def test_parity_twelve_steps(spe, model, pname, prec, wide, tol):
 def test_history_push_is_the_state_bit_for_bit(spe, model):
     r = record(spe, model, 255, 0, 0, keep_states=True)
     mu = sr.window_order(r.mu_hist.cpu().numpy(), FIRST, STEPS)
-    cov = sr.window_order(unpack(r.cov_hist, r.e.D), FIRST, STEPS)
+    cov = sr.window_order(unpack(host(r.cov_hist), r.e.D), FIRST, STEPS)
     for c, (m, C, _) in enumerate(r.states):
         assert np.array_equal(mu[c], m) and np.array_equal(cov[c], C), c
 
@@ -271,21 +241,8 @@ def test_history_push_follows_a_split_launch_without_sync(spe):
     assert e.stream_kind == "private" and e.config().split_streams == 1 and e.config().lanes_per_filter in (0, 16)
     assert "ukf_kernel16" in e.last_launch_info()["kernel"] and e.last_launch_info()["grid"] == n // 4
     assert not os.environ.get("UKFB_SPLIT_MAX")
-    assert np.array_equal(mh[0].double().cpu().numpy(), m) and np.array_equal(unpack(ch[0], e.D), C)
+    assert np.array_equal(mh[0].double().cpu().numpy(), m) and np.array_equal(unpack(host(ch[0]), e.D), C)
     assert not np.array_equal(mh[1].double().cpu().numpy(), m)
-
-
-def snapshot(e):
-    """everything of the engine that can be downloaded: mean, covariance, initialised flags, status, last measurement times, the
-    process noise of EVERY filter, and the latched rotation rate where there is a getter (OrientationState)"""
-    mu, cov, init = e.state()
-    noise = np.array([e.process_noise(i) for i in range(e.capacity)])
-    latch = e.rotation_rate() if e.model == 1 else np.zeros(0)
-    return mu, cov, init, e.status(), e.last_measurement_time(), noise, latch
-
-
-def same_snapshot(a, b):
-    return all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
 
 
 @pytest.mark.parametrize("model", ["pose", "orient"])
@@ -306,14 +263,14 @@ def test_read_only_in_place_and_no_covariance(spe, model):
     noc = run(r, cov=False)
     lat = run(r, rings=False)
     mu = sr.window_order(r.mu_hist.cpu().numpy(), FIRST, STEPS)
-    host = r.e.smooth(r.dt, mu, sr.window_order(unpack(r.cov_hist, r.e.D), FIRST, STEPS),
-                      in_a=sr.window_order(r.in_a.cpu().numpy(), FIRST, STEPS), in_b=sr.window_order(r.in_b.cpu().numpy(), FIRST, STEPS))
+    host_form = r.e.smooth(r.dt, mu, sr.window_order(unpack(host(r.cov_hist), r.e.D), FIRST, STEPS),
+                           in_a=sr.window_order(r.in_a.cpu().numpy(), FIRST, STEPS), in_b=sr.window_order(r.in_b.cpu().numpy(), FIRST, STEPS))
     assert same_snapshot(before, snapshot(r.e)), "a smoother call changed the engine"
     r.e.predict(0.013); twin.e.predict(0.013)
     assert same_snapshot(snapshot(r.e), snapshot(twin.e)), "the prediction after smoothing is not the untouched twin's"
     assert np.array_equal(out[0], inp[0]) and np.array_equal(out[1], inp[1]) and np.array_equal(out[2], inp[2])
     assert np.array_equal(out[0], noc[0]) and noc[1] is None
-    assert np.array_equal(out[0], host[0]) and np.array_equal(out[1], host[1])
+    assert np.array_equal(out[0], host_form[0]) and np.array_equal(out[1], host_form[1])
     assert (lat[2] == 0).all() and not np.array_equal(lat[0], out[0])
     r.e.close(); twin.e.close()
 
@@ -342,7 +299,7 @@ def test_chain_residency_one_call_equals_chained_calls(spe, model):
         assert int(st.abs().max()) == 0
     torch.cuda.synchronize()
     assert np.array_equal(sr.window_order(mh.cpu().numpy(), FIRST, STEPS), one[0])
-    assert np.array_equal(sr.window_order(unpack(ch, r.e.D), FIRST, STEPS), one[1])
+    assert np.array_equal(sr.window_order(unpack(host(ch), r.e.D), FIRST, STEPS), one[1])
 
 
 def test_chunking_two_launches(spe):
@@ -359,7 +316,7 @@ def test_chunking_two_launches(spe):
     r.e.smooth_dev(r.dt[0:31], slots, first, mh, ch, in_a_dev=r.in_a, in_b_dev=r.in_b)
     torch.cuda.synchronize()
     assert np.array_equal(sr.window_order(mh.cpu().numpy(), first, steps), whole[0])
-    assert np.array_equal(sr.window_order(unpack(ch, r.e.D), first, steps), whole[1])
+    assert np.array_equal(sr.window_order(unpack(host(ch), r.e.D), first, steps), whole[1])
     # no covariance output: the chain's covariance crosses the launch boundary through the engine's workspace -- the same means
     noc = run(r, cov=False)
     assert np.array_equal(noc[0], whole[0]) and noc[1] is None and (noc[2] == 0).all()
@@ -410,7 +367,7 @@ def test_host_array_form(spe, pname, prec, wide, tol):
     r, _ = recorded(spe, "pose", pname)
     dev = run(r)
     mu = sr.window_order(r.mu_hist.double().cpu().numpy(), FIRST, STEPS)
-    cov = sr.window_order(unpack(r.cov_hist, r.e.D), FIRST, STEPS)
+    cov = sr.window_order(unpack(host(r.cov_hist), r.e.D), FIRST, STEPS)
     a = sr.window_order(r.in_a.double().cpu().numpy(), FIRST, STEPS)
     mu_s, cov_s, st = r.e.smooth(r.dt, mu, cov, in_a=a)
     assert (st == 0).all()

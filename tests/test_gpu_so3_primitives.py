@@ -21,25 +21,19 @@ must be those of the all-own-regime wave."""
 import ctypes as C
 import functools
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 mp = pytest.importorskip("mpmath")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "tests", "cpp", "build", "libso3_probe.so")
+from probe_support import DT, EPS, F32, F64, _axes, _m, _ulps, load, placements  # noqa: E402
+
 IN, OUT = 12, 8                      # doubles per record (tests/cpp/so3_probe.hip SO3P_IN / SO3P_OUT)
 PRIM = dict(rcp=0, rsqrt=1, cos_sinc=2, exp_fast=3, exp=4, log=5, log_fast=6, log_fast_n=7, log_fast_n2=8, rebase=9,
             quat_mul=10, quat_rotate=11)
 NOUT = dict(rcp=1, rsqrt=1, cos_sinc=2, exp_fast=4, exp=4, log=3, log_fast=3, log_fast_n=3, log_fast_n2=6, rebase=3,
             quat_mul=4, quat_rotate=3)
-POS = (0, 15, 16, 31, 32, 47, 48, 63)   # 16-lane DPP rows and half-waves of a 64-lane wavefront
-F64, F32 = 0, 1
-DT = {F64: np.float64, F32: np.float32}
-EPS = {F64: 2.0 ** -52, F32: 2.0 ** -23}
 Y_SMALL = {F64: np.float64(0.62), F32: np.float32(0.62)}
 U_SMALL = {F64: np.float64(0.07), F32: np.float32(0.07)}
 TAYLOR_N = {F64: np.float64(0.0001220703125), F32: np.float32(0.018581361)}   # Num<T>::taylor_n_bound
@@ -62,11 +56,6 @@ def _bounds(table):
 
 
 # ------------------------------------------------------------------------------------------------ 40-digit references
-def _m(x):
-    """exact: a double (or a numpy scalar) as it is, an mpf unrounded"""
-    return x if isinstance(x, mp.mpf) else mp.mpf(float(x))
-
-
 def ref_exp(v, scale):
     """MTK SO3::exp(v, scale): (sinc(a) (scale/2) v, cos a), a = |v| |scale| / 2 (storage x y z w)"""
     v = [_m(c) for c in v]
@@ -149,22 +138,6 @@ def reference(prim, prec, X):
 
 
 # ------------------------------------------------------------------------------------------------ inputs at the edges
-def _ulps(x, k, T):
-    """x moved by -k..k ulp of T"""
-    x = T(x)
-    out = [x]
-    up = dn = x
-    for _ in range(k):
-        up, dn = np.nextafter(up, T(np.inf)), np.nextafter(dn, T(-np.inf))
-        out += [up, dn]
-    return out
-
-
-def _axes(rng, m):
-    a = rng.normal(size=(m, 3))
-    return a / np.linalg.norm(a, axis=1, keepdims=True)
-
-
 def _rec(rows):
     X = np.zeros((len(rows), IN))
     for i, r in enumerate(rows):
@@ -319,14 +292,8 @@ def _scale(prim, X):
 
 
 # ------------------------------------------------------------------------------------------------ the device
-@functools.lru_cache(maxsize=None)
 def _lib():
-    if not os.path.exists(LIB):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp")])
-    lib = C.CDLL(LIB)
-    lib.so3_probe.argtypes = [C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    lib.so3_probe.restype = C.c_int
-    return lib
+    return load("libso3_probe", so3_probe=(C.c_int, (C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double))))
 
 
 def device(prim, prec, X):
@@ -336,33 +303,6 @@ def device(prim, prec, X):
                           Y.ctypes.data_as(C.POINTER(C.c_double)))
     assert rc == 0, rc
     return Y
-
-
-def placements(cls):
-    """Record order of one launch: every regime in waves of its own (the base position of each record), then each regime's
-    records in waves with one lane of another regime or a NaN record (index -1) at each of POS, then regimes alternating."""
-    regimes = sorted(set(cls.tolist()))
-    ids = {c: np.nonzero(cls == c)[0] for c in regimes}
-    src, base, n0 = [], np.empty(len(cls), dtype=np.int64), 0
-    for c in regimes:
-        base[ids[c]] = n0 + np.arange(len(ids[c]))
-        src.append(np.resize(ids[c], -(-len(ids[c]) // 64) * 64))
-        n0 += src[-1].size
-    for a in regimes:
-        nw = -(-len(ids[a]) // 63)
-        fill = np.resize(ids[a], nw * 63).reshape(nw, 63)
-        for b in [r for r in regimes if r != a] + [None]:
-            foreign = np.full(nw, -1) if b is None else np.resize(ids[b], nw)
-            for p in POS:
-                src.append(np.insert(fill, p, foreign, axis=1).ravel())
-    for i, a in enumerate(regimes):
-        for b in regimes[i + 1:]:
-            k = max(len(ids[a]), len(ids[b]))
-            alt = np.stack([np.resize(ids[a], k), np.resize(ids[b], k)], axis=1).ravel()
-            src.append(np.resize(alt, -(-alt.size // 64) * 64))
-    src = np.concatenate(src)
-    assert src.size % 64 == 0 and n0 % 64 == 0
-    return src, base
 
 
 @functools.lru_cache(maxsize=None)

@@ -22,85 +22,14 @@ import torch
 import feature_f32 as ff
 import feature_scaled_parity as fsp
 import state_meas_reference as smr
+from engine_support import Case, cycled_engine, engine_of, man_of, pack, same_snapshot, scaled, snapshot, tdt
 from oracle import ukf_numpy as on
 
 pytestmark = pytest.mark.gpu
 
 N = 1022   # not a multiple of four: the last workgroup holds two filters
 PRECS = [("f64", 0, 0, 1e-9), ("f32", 1, 0, 1e-4), ("f32w", 1, 1, 1e-9 + 2.0 ** -23)]
-ACC_COV = 0.01 * np.eye(3)
 ST_NONFINITE, ST_CHOLESKY, ST_UNINIT, ST_INACTIVE, ST_REJECTED = 1 << 4, 1 << 5, 1 << 7, 1 << 8, 1 << 9
-
-
-def tdt(e):
-    return torch.float64 if e.dtype == np.float64 else torch.float32
-
-
-def man_of(model):
-    return on.POSE if model == "pose" else on.ORIENT
-
-
-def full_mask(model):
-    return 15 if model == "pose" else 31
-
-
-def new_engine(spe, model, n, prec, wide, **kw):
-    cfg = dict(kw)
-    if wide:
-        cfg["wide_arithmetic"] = 1
-    if model == "pose":
-        return spe.BatchPoseUKF(n, precision=prec, **cfg)
-    sy = spe.synth
-    e = spe.BatchOrientationUKF(n, sy.ORIENT_TAU, sy.ORIENT_TAU, sy.ORIENT_LATITUDE, precision=prec, **cfg)
-    e.set_process_noise(sy.orient_process_noise())
-    return e
-
-
-def cycled_engine(spe, model, n, prec, wide, skip_init=(), **kw):
-    """an engine after two real cycles (Pose: acceleration branch, POS3; OrientationState: its body-velocity update)"""
-    sy = spe.synth
-    e = new_engine(spe, model, n, prec, wide, **kw)
-    mu0, cov0 = sy.pose_initial(n) if model == "pose" else sy.orient_initial(n)
-    if skip_init:
-        for i in range(n):
-            if i not in skip_init:
-                e.initialize(mu0[i:i + 1], cov0[i:i + 1], first=i)
-    else:
-        e.initialize(mu0, cov0)
-    for c in range(2):
-        mu_now = e.state(with_cov=False)[0]
-        if model == "pose":
-            acc, z, Q = sy.pose_cycle_inputs(n, c, mu_now[:, :3])
-            e.set_acceleration(acc, ACC_COV)
-            e.cycle(0.01, spe.MEAS_POS3, z, Q)
-        else:
-            gyro, acc, z, Q = sy.orient_cycle_inputs(n, c, mu_now[:, 0:4])
-            e.set_orient_inputs(gyro, acc)
-            e.cycle(0.01, spe.MEAS_ORIENT_BODYVEL3, z, Q)
-    return e
-
-
-def make_inputs(model, mu, cov, dtype, seed=11):
-    """z = mu (+) L xi, Qz = Sigma + (L A)(L A)^T, as the engine stores them"""
-    man = man_of(model)
-    n = mu.shape[0]
-    rng = np.random.default_rng(seed)
-    L = np.linalg.cholesky(cov)
-    z = man.boxplus(mu, np.einsum("bij,bj->bi", L, rng.standard_normal((n, man.D))))
-    LA = L @ (0.3 * rng.standard_normal((n, man.D, man.D)))
-    Qz = cov + LA @ np.swapaxes(LA, 1, 2)
-    Qz = 0.5 * (Qz + np.swapaxes(Qz, 1, 2))
-    return z.astype(dtype).astype(np.float64), Qz.astype(dtype).astype(np.float64)
-
-
-def pack(M):
-    D = M.shape[-1]
-    r, c = np.tril_indices(D)
-    return np.ascontiguousarray(M[..., r, c])
-
-
-class Case:
-    """the state of a cycled engine as downloaded, and inputs as stored; fresh engines are initialised from it"""
 
 
 _CACHE = {}
@@ -115,19 +44,11 @@ def case(spe, model, pname, n=N):
         c.model, c.pname, c.n, c.prec, c.wide, c.tol = model, pname, n, prec, wide, tol
         c.mu, c.cov, _ = e.state()
         c.dtype = e.dtype
-        c.z, c.Qz = make_inputs(model, c.mu, c.cov, e.dtype)
+        c.z, c.Qz = smr.make_inputs(man_of(model), c.mu, c.cov, e.dtype)
         e.close()
         c.refs = {}
         _CACHE[key] = c
     return _CACHE[key]
-
-
-def engine_of(spe, c, **kw):
-    e = new_engine(spe, c.model, c.n, c.prec, c.wide, **kw)
-    e.initialize(c.mu, c.cov)
-    m, C, _ = e.state()
-    assert np.array_equal(m, c.mu) and np.array_equal(C, c.cov)   # the downloaded state goes back in bit for bit
-    return e
 
 
 def run(e, masks, z, Qz, a=1.0, b=1.0, commit=True):
@@ -161,10 +82,6 @@ def reference(c, masks, z=None, Qz=None, a=1.0, b=1.0, gate=-1.0, initialised=No
     return ref
 
 
-def scaled(x, ref):
-    return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref)))) if x.size else 0.0
-
-
 def check_parity(name, c, got, ref, tol=None, rows=None, masks=None, z=None, Qz=None, a=1.0, b=1.0):
     """the file's bound on mean, covariance, d^2 and log-likelihood, then the scaled check of the updated state
     (tests/feature_scaled_parity.py); masks, z, Qz, a, b: the call, for the fp32 evaluation behind a plain fp32 engine's bound"""
@@ -190,18 +107,13 @@ def check_parity(name, c, got, ref, tol=None, rows=None, masks=None, z=None, Qz=
     fsp.judge_state("state_meas/" + name, c.model, c.pname, got[0][rows], got[1][rows], ref[0][rows], ref[1][rows], f32=f32)
 
 
-def cycling_masks(model, n):
-    """every mask of the model, 0 included, so that four wave-mates always differ"""
-    return (np.arange(n) % (full_mask(model) + 1)).astype(np.int32)
-
-
 # ------------------------------------------------------------------------------------------------------------------ parity
 @pytest.mark.parametrize("model", ["pose", "orient"])
 @pytest.mark.parametrize("pname", [p[0] for p in PRECS])
 def test_parity(spe, model, pname):
     c = case(spe, model, pname)
     nb = len(man_of(model).fields)
-    masks = [full_mask(model)] + ([3] if model == "pose" else []) + [1 << b for b in range(nb)]
+    masks = [smr.full_mask(model)] + ([3] if model == "pose" else []) + [1 << b for b in range(nb)]
     for m in masks:
         e = engine_of(spe, c)
         got, ref = run(e, m, c.z, c.Qz), reference(c, m)
@@ -209,7 +121,7 @@ def test_parity(spe, model, pname):
         assert (ref[4] == 0).all(), (m, np.unique(ref[4]))
         assert (got[4] == 0).all(), (m, np.unique(got[4]))
         check_parity(f"{model}/{pname}/mask={m}", c, got, ref, masks=m)
-    per = cycling_masks(model, c.n)
+    per = smr.cycling_masks(model, c.n)
     e = engine_of(spe, c)
     got, ref = run(e, per, c.z, c.Qz), reference(c, per)
     assert np.array_equal(e.status(), got[4])   # commit = 1 writes the engine's own status array too
@@ -227,20 +139,20 @@ def test_covariance_intersection(spe, model, pname):
     w = 0.3
     c = case(spe, model, pname)
     e = engine_of(spe, c)
-    got = run(e, full_mask(model), c.z, c.Qz, a=1.0 / w, b=1.0 / (1.0 - w))
+    got = run(e, smr.full_mask(model), c.z, c.Qz, a=1.0 / w, b=1.0 / (1.0 - w))
     e.close()
-    ref = reference(c, full_mask(model), a=1.0 / w, b=1.0 / (1.0 - w))
+    ref = reference(c, smr.full_mask(model), a=1.0 / w, b=1.0 / (1.0 - w))
     assert (ref[4] == 0).all() and (got[4] == 0).all()
-    check_parity(f"{model}/{pname}/covariance-intersection", c, got, ref, masks=full_mask(model), a=1.0 / w, b=1.0 / (1.0 - w))
+    check_parity(f"{model}/{pname}/covariance-intersection", c, got, ref, masks=smr.full_mask(model), a=1.0 / w, b=1.0 / (1.0 - w))
     assert np.linalg.eigvalsh(got[1]).min() > 0.0
-    assert not np.array_equal(got[1], reference(c, full_mask(model))[1])
+    assert not np.array_equal(got[1], reference(c, smr.full_mask(model))[1])
 
 
 @pytest.mark.parametrize("model", ["pose", "orient"])
 @pytest.mark.parametrize("pname", ["f64", "f32"])
 def test_gate(spe, model, pname):
     c = case(spe, model, pname)
-    m = full_mask(model)
+    m = smr.full_mask(model)
     free = reference(c, m)
     gate = float(np.median(free[2]))
     ref = reference(c, m, gate=gate)
@@ -259,24 +171,12 @@ def test_gate(spe, model, pname):
 
 
 # ------------------------------------------------------------------------------------------------------- bit-level properties
-def snapshot(e):
-    """everything of the engine that can be downloaded"""
-    mu, cov, init = e.state()
-    noise = np.array([e.process_noise(i) for i in range(e.capacity)])
-    latch = e.rotation_rate() if e.model == 1 else np.zeros(0)
-    return mu, cov, init, e.status(), e.last_measurement_time(), noise, latch
-
-
-def same(a, b):
-    return all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
-
-
 @pytest.mark.parametrize("model", ["pose", "orient"])
 def test_bit_level_properties(spe, model):
     n = 255
     c = case(spe, model, "f64", n)
     m = 0b0110
-    per = cycling_masks(model, n)
+    per = smr.cycling_masks(model, n)
 
     def fresh(**kw):
         e = engine_of(spe, c, **kw)
@@ -288,22 +188,22 @@ def test_bit_level_properties(spe, model):
     e.close()
     # a device array filled with m = the uniform mask m
     e = fresh()
-    assert same(run(e, np.full(n, m, dtype=np.int32), c.z, c.Qz), base)
+    assert same_snapshot(run(e, np.full(n, m, dtype=np.int32), c.z, c.Qz), base)
     e.close()
     # the host form = the device form (per-filter masks too)
     e = fresh()
     d2, ll, st = e.update_state(m, c.z, c.Qz)
     mu, cov, _ = e.state()
-    assert same((mu, cov, d2, ll, st), base)
+    assert same_snapshot((mu, cov, d2, ll, st), base)
     e.close()
     e, e2 = fresh(), fresh()
     d2, ll, st = e.update_state(per, c.z, c.Qz)
     mu, cov, _ = e.state()
-    assert same((mu, cov, d2, ll, st), run(e2, per, c.z, c.Qz))
+    assert same_snapshot((mu, cov, d2, ll, st), run(e2, per, c.z, c.Qz))
     e.close(); e2.close()
     # inflation 1, 1 under a gate nothing reaches = no gate
     e = fresh(gate_chi2=1e300)
-    assert same(run(e, m, c.z, c.Qz), base)
+    assert same_snapshot(run(e, m, c.z, c.Qz), base)
     e.close()
     # commit = 0: the whole downloadable engine keeps its bits, the outputs are the committing call's, and the next
     # prediction is an untouched twin's
@@ -311,16 +211,16 @@ def test_bit_level_properties(spe, model):
     before = snapshot(e)
     dry = run(e, m, c.z, c.Qz, commit=False)
     dry_per = run(e, per, c.z, c.Qz, commit=False)
-    assert same(before, snapshot(e)) and same(before, snapshot(twin))
-    assert same(dry[2:], base[2:]) and np.array_equal(dry[0], c.mu) and np.array_equal(dry[1], c.cov)
+    assert same_snapshot(before, snapshot(e)) and same_snapshot(before, snapshot(twin))
+    assert same_snapshot(dry[2:], base[2:]) and np.array_equal(dry[0], c.mu) and np.array_equal(dry[1], c.cov)
     assert np.array_equal(dry_per[4], np.where(per == 0, ST_INACTIVE, 0))
     e.predict(0.013); twin.predict(0.013)
-    assert same(snapshot(e), snapshot(twin))
+    assert same_snapshot(snapshot(e), snapshot(twin))
     e.close(); twin.close()
     # commit = 0, then commit = 1: the same d^2 as commit = 1 alone
     e = fresh()
     run(e, m, c.z, c.Qz, commit=False)
-    assert same(run(e, m, c.z, c.Qz), base)
+    assert same_snapshot(run(e, m, c.z, c.Qz), base)
     e.close()
 
 
@@ -331,10 +231,10 @@ def test_host_array_form_fp32(spe, model, pname):
     bits of the device form fed the same values rounded to float32.  Five filters: one full wavefront and a one-row tail."""
     n = 5
     c = case(spe, model, pname, n)
-    z, Qz = make_inputs(model, c.mu, c.cov, np.float64)   # doubles that are NOT fp32 values
+    z, Qz = smr.make_inputs(man_of(model), c.mu, c.cov, np.float64)   # doubles that are NOT fp32 values
     z32, Qz32 = z.astype(np.float32).astype(np.float64), Qz.astype(np.float32).astype(np.float64)
     assert not np.array_equal(z, z32) and not np.array_equal(Qz, Qz32)
-    full = full_mask(model)
+    full = smr.full_mask(model)
     per = np.array([full, 0, 1, 0b0110, 0b0101], dtype=np.int32)
     for masks in (0b0110, per):
         e, twin = engine_of(spe, c), engine_of(spe, c)
@@ -363,7 +263,7 @@ def test_failures_stay_inside_their_filter(spe, model):
     live = init.copy()
     mu_f, cov_f = mu.copy(), cov.copy()   # (the dead filter's inputs are made from a neighbour's state: they are never used)
     mu_f[dead], cov_f[dead] = mu[0], cov[0]
-    z, Qz = make_inputs(model, mu_f, cov_f, np.float64, seed=5)
+    z, Qz = smr.make_inputs(man_of(model), mu_f, cov_f, np.float64, seed=5)
     masks = np.full(n, m, dtype=np.int32)
     clean = run(e, masks, z, Qz, commit=False)
     zb, Qb, mb = z.copy(), Qz.copy(), masks.copy()
@@ -383,7 +283,7 @@ def test_failures_stay_inside_their_filter(spe, model):
     twin = cycled_engine(spe, model, n, 0, 0, skip_init=(dead,))
     ok = run(twin, masks, z, Qz)
     twin.close(); e.close()
-    assert same(ok[2:], clean[2:])
+    assert same_snapshot(ok[2:], clean[2:])
     assert np.array_equal(got[0][~failing], ok[0][~failing]) and np.array_equal(got[1][~failing], ok[1][~failing])
     assert np.array_equal(got[2][~failing], ok[2][~failing]) and np.array_equal(got[3][~failing], ok[3][~failing])
     assert not np.array_equal(got[1][nan_unsel], cov[nan_unsel])
@@ -448,7 +348,7 @@ def test_body_state_records(spe):
         e, twin = engine_of(spe, c), engine_of(spe, c)
         e.update_body_states(mask, rec, active)
         _, _, st = twin.update_state(np.where(active != 0, mask, 0).astype(np.int32), z, Qz)
-        assert same(snapshot(e), snapshot(twin)) and np.array_equal(e.status(), st)
+        assert same_snapshot(snapshot(e), snapshot(twin)) and np.array_equal(e.status(), st)
         assert np.array_equal(st, np.where(active != 0, 0, ST_INACTIVE))
         assert not np.array_equal(e.state()[0], c.mu)
         e.close(); twin.close()

@@ -21,12 +21,9 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import drift_f32  # noqa: E402
+from engine_support import f32r  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def f32r(x):
-    return np.asarray(x).astype(np.float32).astype(np.float64)
 
 
 def rel_err(a, b):

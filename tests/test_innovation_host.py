@@ -2,11 +2,8 @@
 ctypes can bind, the argument checks of ukf_host.hpp (check_innovation_args, check_select_args) hold under ASan / UBSan
 (tests/cpp/innovation_host.cpp, compiled here), and a NULL engine is refused before anything touches a device."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_support import run_sanitized
 
 
 def test_symbols_and_signatures(spe):
@@ -29,14 +26,4 @@ def test_null_engine_is_refused(spe):
 
 
 def test_argument_checks_under_sanitizers(tmp_path):
-    gxx = shutil.which("g++")
-    assert gxx, "g++ is needed for the host-side checks"
-    exe = tmp_path / "innovation_host_asan"
-    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "innovation_host.cpp"), "-o", str(exe)], check=True, timeout=300)
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "OK: 0 failure(s)" in out.stdout
-    for marker in ("AddressSanitizer", "LeakSanitizer", "runtime error", "UndefinedBehaviorSanitizer"):
-        assert marker not in out.stderr + out.stdout, out.stderr
+    run_sanitized("innovation_host.cpp", tmp_path)

@@ -4,10 +4,9 @@ host decisions of ukf_host.hpp (check_lifecycle_args, check_compact_args, lifecy
 device."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import lifecycle_reference as lr
+from host_support import header_text, run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("ukfb_gather_filters_dev", "ukfb_scatter_filters_dev", "ukfb_retire_dev", "ukfb_compact_dev", "ukfb_gather_filters",
@@ -16,7 +15,7 @@ NAMES = ("ukfb_gather_filters_dev", "ukfb_scatter_filters_dev", "ukfb_retire_dev
 
 def test_symbols_and_bindings(spe):
     lib = spe.load_library()
-    header = open(os.path.join(ROOT, "include", "ukf_batch.h")).read()
+    header = header_text()
     for name in NAMES:
         assert name in spe.engine.EXPORTS and hasattr(lib, name) and ("int " + name + "(") in header
     for method in ("gather_filters_dev", "scatter_filters_dev", "retire_dev", "compact_dev", "gather_filters", "scatter_filters",
@@ -54,15 +53,5 @@ def test_null_engine_is_refused(spe):
 
 
 def test_host_decisions_under_sanitizers(tmp_path):
-    gxx = shutil.which("g++")
-    assert gxx, "g++ is needed for the host-side checks"
-    exe = tmp_path / "lifecycle_host_asan"
-    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "lifecycle_host.cpp"), "-o", str(exe)], check=True, timeout=300)
     # the capacity of the GPU compact test: the program asserts that it spans three count blocks with a ragged last one
-    out = subprocess.run([str(exe), str(lr.COMPACT_N)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "OK: 0 failure(s)" in out.stdout
-    for marker in ("AddressSanitizer", "LeakSanitizer", "runtime error", "UndefinedBehaviorSanitizer"):
-        assert marker not in out.stderr + out.stdout, out.stderr
+    run_sanitized("lifecycle_host.cpp", tmp_path, args=(lr.COMPACT_N,))

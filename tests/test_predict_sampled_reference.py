@@ -9,16 +9,13 @@ import pytest
 import predict_sampled_f32 as pf
 import predict_sampled_reference as pr
 import slam_pose_estimation_amd as spe
+from engine_support import man_of
 from oracle import ukf_numpy as on
-from test_sensor_meas_reference import states
+from sensor_meas_cases import states
 
 N = 1022
 ACC_COV = 0.01 * np.eye(3)
 sy = spe.synth
-
-
-def man_of(model):
-    return on.POSE if model == "pose" else on.ORIENT
 
 
 def builtin(model, with_acc=True, n=N):

@@ -7,14 +7,11 @@ import pytest
 
 import sampled_reference as sm
 import sensor_meas_reference as sr
+from engine_support import man_of
 from oracle import ukf_numpy as on
-from test_sensor_meas_reference import mounts, states
+from sensor_meas_cases import mounts, states
 
 N = 1022
-
-
-def man_of(model):
-    return on.POSE if model == "pose" else on.ORIENT
 
 
 # ------------------------------------------------------------------------------------------------------------------ export

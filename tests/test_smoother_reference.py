@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import smoother_reference as sr
+from engine_support import scaled
 
 ACC_COV = 0.01 * np.eye(3)
 
@@ -74,10 +75,6 @@ def textbook_rts(mu, P6, dt, acc, pv):
         xs[c] = x[c] + np.einsum("bij,bj->bi", Gn, xs[c + 1] - xp)
         Ps[c] = P6[c] + Gn @ (Ps[c + 1] - Pp) @ np.swapaxes(Gn, -1, -2)
     return xs, Ps
-
-
-def scaled(x, ref):
-    return float(np.max(np.abs(x - ref) / (1.0 + np.abs(ref))))
 
 
 def linear_errors(rot_var):

@@ -3,17 +3,15 @@ decisions of ukf_host.hpp (check_state_meas_args, the masks per model, state_mea
 under ASan / UBSan (tests/cpp/state_meas_host.cpp, compiled here), and a NULL engine is refused before anything touches a
 device."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_support import header_text, run_sanitized
+
 NAMES = ("ukfb_update_state_dev", "ukfb_update_state", "ukfb_pose_update_body_states")
 
 
 def test_symbols_and_bindings(spe):
     lib = spe.load_library()
-    header = open(os.path.join(ROOT, "include", "ukf_batch.h")).read()
+    header = header_text()
     for name in NAMES:
         assert name in spe.engine.EXPORTS and hasattr(lib, name) and ("int " + name + "(") in header
     for method in ("update_state_dev", "update_state", "update_body_states"):
@@ -36,14 +34,4 @@ def test_null_engine_is_refused(spe):
 
 
 def test_host_decisions_under_sanitizers(tmp_path):
-    gxx = shutil.which("g++")
-    assert gxx, "g++ is needed for the host-side checks"
-    exe = tmp_path / "state_meas_host_asan"
-    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "cpp", "state_meas_host.cpp"), "-o", str(exe)], check=True, timeout=300)
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "OK: 0 failure(s)" in out.stdout
-    for marker in ("AddressSanitizer", "LeakSanitizer", "runtime error", "UndefinedBehaviorSanitizer"):
-        assert marker not in out.stderr + out.stdout, out.stderr
+    run_sanitized("state_meas_host.cpp", tmp_path)
