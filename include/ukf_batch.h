@@ -903,8 +903,10 @@ int ukfb_update_sensor(ukfb_engine* e, int model, const int32_t* model_per_filte
  *   innov   [capacity][3]  nu = log_z-bar(z^), nu perpendicular to z-bar
  *   maha    d^2 = nu^T S3^-1 nu;  loglik = -0.5 (d^2 + ln det S3 + 2 ln 2 pi)
  * Sphere maps, for unit u, v and w perpendicular to u:
- *   log_u(v) = theta t / |t|, t = v - (u.v) u, theta = atan2(|u x v|, u.v); 0 when t = 0 and u.v > 0.  At the exact antipode
- *              (t = 0, u.v < 0) any tangent vector of length pi: the direction is unspecified, the result finite.
+ *   log_u(v) = theta t / |t|, t = v - (u.v) u, theta = atan2(|u x v|, u.v); exact zeros at v = u.  The result is tangent at u
+ *              over the whole range, the neighbourhood of the antipode included: |u . log_u(v)| <= 8 eps |log_u(v)|, eps = 2^-52.
+ *              Where the tangent part of v is not resolved (u.v < 0 and |t| <= 4 eps: theta within 4 eps of pi, the exact
+ *              antipode included) a tangent vector of length pi: the direction is unspecified, the result finite.
  *   exp_u(w) = cos|w| u + sinc|w| w, renormalised.
  * Per filter the steps are those of ukf::update with the measurement manifold S^2:
  *   1. L = chol(Sigma), sigma points X_i, Z_i = h(X_i);

@@ -57,24 +57,43 @@ template <class M> UKFB_DEV bool bearing_h(const double (&x)[M::S], bool to_poin
     return pos_finite(n2);
 }
 
-// log_u(v) for unit u, v: theta t / |t|, t = v - (u.v) u, theta = atan2(|u x v|, u.v); 0 at t = 0, u.v > 0; at the exact
-// antipode a tangent vector of length pi (which one is unspecified).  NaN in, NaN out.
+// log_u(v) for unit u, v: theta t / |t|, t = v - (u.v) u, theta = atan2(|u x v|, u.v); exact zeros at v = u.  The result is
+// tangent over the whole range, |u.w| <= 8 eps |w|.
+//  * t is the tangent part of v - u (for unit u the same vector: u has none), projected against u twice.  v - u is zero to the
+//    bit at v = u, and for directions a milliradian apart it is small and nearly exact, where v - fl(u.v) u is not: fl(u.v)
+//    (and |u|^2 - 1) is off by an eps whatever |t| is, which stays in t as a RADIAL part.  One projection leaves such a part
+//    towards the antipode as well, where |v - u| is 2 and u.(v - u) rounds at 3 eps: formed once, t gave w a radial share of
+//    2e-4 at theta = 1e-12, 5e-8 at pi - 1e-8 and all of w at v = -u (fl(u.u) != 1: t = (fl(u.u) - 1) u != 0, the result
+//    +-pi u).  The second projection takes it out to 2 eps of what it is given.
+//  * Where |t| <= 4 eps is left with u.v < 0 the tangent part is not resolved: it is below the half ulp that each entry of v
+//    carries, and the radial part the first projection left (<= 3 eps) is no longer small against it -- from 4 eps on the second
+//    projection is given at most 1.75 |t| and leaves 3.5 eps |t|, inside the 8 eps above.  There, the exact antipode included, the
+//    result is a tangent vector of length pi whose direction is unspecified (theta is within 4 eps of pi).
+//  * theta = atan2(|t|, u.v): |u x v| = |t| for unit u (for |u|^2 = 1 + delta they differ by delta / 2, relative); |t| from the
+//    reciprocal root k needs anyway and one Heron step, an ulp.  No cross product, no sqrt.
+// NaN in, NaN out.
 UKFB_DEV void s2_log(const double (&u)[3], const double (&v)[3], double (&w)[3]) {
+    constexpr double UNRESOLVED2 = 0x1p-100;   // (4 eps)^2
     const double c = fma(u[0], v[0], fma(u[1], v[1], u[2] * v[2]));
-    const double t[3] = {fma(-c, u[0], v[0]), fma(-c, u[1], v[1]), fma(-c, u[2], v[2])};
-    const double x0 = u[1] * v[2] - u[2] * v[1], x1 = u[2] * v[0] - u[0] * v[2], x2 = u[0] * v[1] - u[1] * v[0];
-    const double s = m_sqrt(fma(x0, x0, fma(x1, x1, x2 * x2)));
-    const double th = atan2(s, c);
+    const double dv[3] = {v[0] - u[0], v[1] - u[1], v[2] - u[2]};
+    const double e = fma(u[0], dv[0], fma(u[1], dv[1], u[2] * dv[2]));
+    const double t0[3] = {fma(-e, u[0], dv[0]), fma(-e, u[1], dv[1]), fma(-e, u[2], dv[2])};
+    const double d = fma(u[0], t0[0], fma(u[1], t0[1], u[2] * t0[2]));
+    const double t[3] = {fma(-d, u[0], t0[0]), fma(-d, u[1], t0[1]), fma(-d, u[2], t0[2])};
     const double t2 = fma(t[0], t[0], fma(t[1], t[1], t[2] * t[2]));
-    const double k = (t2 > 0.0) ? th * fast_rsqrt(t2) : 0.0;
+    const double rt = fast_rsqrt(t2);
+    const double s0 = t2 * rt;
+    const double s = (t2 > 0.0) ? fma(0.5 * rt, fma(-s0, s0, t2), s0) : 0.0;   // |t|
+    const double th = atan2(s, c);
+    const double k = (t2 > 0.0) ? th * rt : 0.0;
 #pragma unroll
     for (int i = 0; i < 3; ++i) w[i] = k * t[i];   // (t = 0: zeros; t NaN: NaN)
-    if (wave_any(t2 == 0.0 && c < 0.0)) {
+    if (wave_any(t2 <= UNRESOLVED2 && c < 0.0)) {
         // e x u for the axis e in {e0, e1} farther from u: its norm is at least 0.6
         const bool first = m_abs(u[0]) < 0.6;
         const double p[3] = {first ? 0.0 : u[2], first ? -u[2] : 0.0, first ? u[1] : -u[0]};
         const double kp = 3.14159265358979323846 * fast_rsqrt(fma(p[0], p[0], fma(p[1], p[1], p[2] * p[2])));
-        const bool anti = t2 == 0.0 && c < 0.0;
+        const bool anti = t2 <= UNRESOLVED2 && c < 0.0;
 #pragma unroll
         for (int i = 0; i < 3; ++i) w[i] = anti ? kp * p[i] : w[i];
     }

@@ -31,15 +31,31 @@ def unit(v):
 
 
 # ------------------------------------------------------------------------------------------------ the sphere
+S2_UNRESOLVED2 = 2.0 ** -100   # (4 eps)^2: below it, with u.v < 0, the tangent part of v is not resolved (ukf_bearing.hpp)
+
+
 def s2_log(u, v):
-    """log_u(v) [..., 3] for unit u, v: theta t / |t|, t = v - (u.v) u, theta = atan2(|u x v|, u.v); 0 where t = 0"""
+    """log_u(v) [..., 3] for unit u, v: theta t / |t|, t = v - (u.v) u, theta = atan2(|u x v|, u.v); 0 where t = 0.  The
+    kernel's definition (ukf_bearing.hpp s2_log): t is the tangent part of v - u, projected against u twice, so that the result
+    is tangent over the whole range and zero to the bit at v = u; theta = atan2(|t|, u.v) (|u x v| = |t| for unit u); where
+    |t| <= 4 eps is left with u.v < 0, the exact antipode included, a tangent vector of length pi (pi e x u / |e x u| for the
+    axis e of e0, e1 farther from u).  NaN in, NaN out."""
     u, v = np.broadcast_arrays(np.asarray(u, dtype=np.float64), np.asarray(v, dtype=np.float64))
     c = np.sum(u * v, axis=-1, keepdims=True)
-    t = v - c * u
-    s = np.linalg.norm(np.cross(u, v), axis=-1, keepdims=True)
-    th = np.arctan2(s, c)
-    nt = np.linalg.norm(t, axis=-1, keepdims=True)
-    return np.where(nt > 0, th * t / np.where(nt > 0, nt, 1.0), 0.0)
+    t = v - u
+    t = t - np.sum(u * t, axis=-1, keepdims=True) * u
+    t = t - np.sum(u * t, axis=-1, keepdims=True) * u
+    nt2 = np.sum(t * t, axis=-1, keepdims=True)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        nt = np.sqrt(nt2)
+        w = np.where(nt2 > 0, np.arctan2(nt, c) * t / np.where(nt2 > 0, nt, 1.0), 0.0 * t)   # (t NaN: NaN)
+    anti = (nt2 <= S2_UNRESOLVED2) & (c < 0)
+    if anti.any():
+        first = np.abs(u[..., 0:1]) < 0.6
+        z = np.zeros_like(u[..., 0])
+        p = np.where(first, np.stack([z, -u[..., 2], u[..., 1]], axis=-1), np.stack([u[..., 2], z, -u[..., 0]], axis=-1))
+        w = np.where(anti, np.pi * p / np.linalg.norm(p, axis=-1, keepdims=True), w)
+    return w
 
 
 def s2_exp(u, w):
