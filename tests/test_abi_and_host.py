@@ -165,12 +165,12 @@ def test_new_entry_points_reject_a_null_engine(spe):
     d9 = (C.c_double * 9)()
     i1 = (C.c_int32 * 1)()
     assert lib.ukfb_cycle_multi_dev(null, 1, C.c_double(0.01), 0, 1, 0, null, null, null, null) != 0
-    assert lib.ukfb_cycle_multi(null, 1, C.c_double(0.01), 0, null, null, d9, d9) != 0
-    assert lib.ukfb_cycle_multi_mixed_dev(null, 1, C.c_double(0.01), 1, 0, null, null, null, null, null) != 0
+    assert lib.ukfb_cycle_multi(null, 1, C.c_double(0.01), 0, None, None, d9, d9) != 0
+    assert lib.ukfb_cycle_multi_mixed_dev(null, 1, C.c_double(0.01), 1, 0, null, null, None, null, null) != 0
     assert lib.ukfb_cycle_schedule_dev(null, 1, d9, i1, 1, 0, null, null, null, null) != 0
     assert lib.ukfb_cycle_uniform_q(null, C.c_double(0.01), 0, d9, d9) != 0
     assert lib.ukfb_cycle_uniform_q_dev(null, C.c_double(0.01), 0, null, null) != 0
-    assert lib.ukfb_update_uniform_q(null, 0, d9, d9, null) != 0
+    assert lib.ukfb_update_uniform_q(null, 0, d9, d9, None) != 0
 
 
 def test_group_entry_points_without_a_gpu(spe):
@@ -188,11 +188,11 @@ def test_group_entry_points_without_a_gpu(spe):
     assert lib.ukfb_group_shard_range(C.c_int64(8), 2, 2, None, None) != 0
     null = C.c_void_p(None)
     assert lib.ukfb_group_size(null) == -1
-    assert lib.ukfb_group_sync(null) != 0 and lib.ukfb_group_cycle_dev(null, C.c_double(0.01), 0, null, null) != 0
-    assert lib.ukfb_group_gather_means(null, null) != 0 and lib.ukfb_group_destroy(null) == 0
-    assert lib.ukfb_group_cycle_mixed_dev(null, C.c_double(0.01), null, null, null) != 0
-    assert lib.ukfb_group_cycle_timestamps(null, null, null, null, null) != 0
-    assert lib.ukfb_group_process_events(null, C.c_int64(0), null, null, null, null, null, null, null) != 0
+    assert lib.ukfb_group_sync(null) != 0 and lib.ukfb_group_cycle_dev(null, C.c_double(0.01), 0, None, None) != 0
+    assert lib.ukfb_group_gather_means(null, None) != 0 and lib.ukfb_group_destroy(null) == 0
+    assert lib.ukfb_group_cycle_mixed_dev(null, C.c_double(0.01), None, None, None) != 0
+    assert lib.ukfb_group_cycle_timestamps(null, None, None, None, None) != 0
+    assert lib.ukfb_group_process_events(null, C.c_int64(0), None, None, None, None, None, None, None) != 0
     if not torch.cuda.is_available():
         with pytest.raises(spe.UkfbError) as ei:
             spe.UKFGroup(spe.MODEL_POSE, spe.F64, 64, [0, 0])

@@ -249,7 +249,8 @@ def test_thirty_three_steps_are_out_of_range_and_write_nothing(spe):
     st = torch.full((64,), -1, dtype=torch.int32, device="cuda")
     dt = (C.c_double * 33)(*([0.01] * 33))
     ptr = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-    args = (C.c_int(40), C.c_int(0), None, None, None, None, ptr(mo), ptr(co), ptr(st))
+    stp = C.cast(st.data_ptr(), C.POINTER(C.c_uint32))   # the header's uint32_t* status_dev
+    args = (C.c_int(40), C.c_int(0), None, None, None, None, ptr(mo), ptr(co), stp)
     assert e._lib.ukfb_forecast_dev(e._h, C.c_int(33), dt, None, *args) == 4   # UKFB_ERR_OUT_OF_RANGE
     with pytest.raises(spe.engine.UkfbError):
         e.forecast_dev(40, 0, mo, co, st, dt=np.full(33, 0.01))
@@ -260,7 +261,7 @@ def test_thirty_three_steps_are_out_of_range_and_write_nothing(spe):
     assert torch.isfinite(mo[:32]).all() and torch.isnan(mo[32:]).all() and (st == 0).all()
     # exactly one start pointer is an invalid argument
     assert e._lib.ukfb_forecast_dev(e._h, C.c_int(2), dt, None, C.c_int(40), C.c_int(0), ptr(mo), None, None, None, ptr(mo), ptr(co),
-                                    ptr(st)) == 1
+                                    stp) == 1
     e.close()
 
 

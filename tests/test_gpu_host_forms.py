@@ -243,7 +243,7 @@ def form_bank_mix(c, eh, ed, full):
         ok(eh, eh._lib.ukfb_bank_mix(eh._h, C.c_int(HYP), pd(f64(w)), pd(P), pd(host["w_pred"]), None), "ukfb_bank_mix")
     wt, st = c.fl(w), dev["status"]   # (the wrapper always makes a status buffer: the C function, so that it can go without)
     ok(ed, ed._lib.ukfb_bank_mix_dev(ed._h, C.c_int(HYP), C.c_void_p(wt.data_ptr()), pd(P), C.c_void_p(dev["w_pred"].data_ptr()),
-                                     None if st is None else C.c_void_p(st.data_ptr())), "ukfb_bank_mix_dev")
+                                     None if st is None else C.cast(st.data_ptr(), C.POINTER(C.c_uint32))), "ukfb_bank_mix_dev")
     compare("bank_mix", host, dev)
 
 
