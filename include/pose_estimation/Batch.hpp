@@ -6,6 +6,7 @@
 #define _POSE_ESTIMATION_BATCH_HPP
 
 #include <ukf_batch.h>
+#include <ukf_batch_relative.h>
 
 #include <stdexcept>
 #include <string>
@@ -340,6 +341,28 @@ public:
         std::vector<uint32_t> st(static_cast<size_t>(cap));
         check(ukfb_update_delayed(engine, steps, dt, mu_hist, cov_hist, in_a, in_b, lag_uniform, lag, model, model_per_filter, z, Q,
                                   commit ? 1 : 0, NULL, NULL, NULL, maha, loglik, st.data(), mu_out, cov_out));
+        return st;
+    }
+    /** Relative measurements (ukf_batch_relative.h): an odometry or scan-match increment "since step n - lag you
+     *  moved by dp and turned by dq" corrects the CURRENT state -- the update on the pair (present, clone of that step), the
+     *  clone recovered from the history ring.  Pose filters only; the window is updateDelayedDev's; commit = false is read-only.
+     *  Stream-ordered. */
+    void integrateRelativeMeasurementDev(const ukfb_relative_in& in, bool commit = true, const ukfb_relative_out* out = NULL)
+    {
+        check(ukfb_update_relative_dev(engine, &in, commit ? 1 : 0, out));
+    }
+    /** host arrays in window order, as updateDelayed: lag / model_per_filter [N] or NULL (lag_uniform / model, a
+     *  ukfb_relative_model); z [N][7] (dp, then dq as x y z w), Q [N][6][6] in the tangent order (dp, dtheta); mu_out [N][S] /
+     *  cov_out [N][D][D] or NULL: the corrected present state.  Returns the status. */
+    std::vector<uint32_t> integrateRelativeMeasurement(int steps, const double* dt, const double* mu_hist, const double* cov_hist,
+                                                       int lag_uniform, int model, const double* z, const double* Q, bool commit = true,
+                                                       const int32_t* lag = NULL, const int32_t* model_per_filter = NULL,
+                                                       const double* in_a = NULL, const double* in_b = NULL, double* mu_out = NULL,
+                                                       double* cov_out = NULL, double* maha = NULL, double* loglik = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_update_relative(engine, steps, dt, mu_hist, cov_hist, in_a, in_b, lag_uniform, lag, model, model_per_filter, z, Q,
+                                   commit ? 1 : 0, NULL, NULL, NULL, maha, loglik, st.data(), mu_out, cov_out));
         return st;
     }
     /** host arrays in window order, smoothed in place: mu [steps][N][S], cov [steps][N][D][D]; returns the per-filter status */

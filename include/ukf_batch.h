@@ -584,6 +584,9 @@ int ukfb_update_delayed(ukfb_engine* e, int steps, const double* dt, const doubl
  * window.  The residual offset inside a step interval is ignored.  Stream-ordered. */
 int ukfb_delayed_lag_dev(ukfb_engine* e, int steps, const int64_t* step_ts_us, const int64_t* sample_ts_us_dev, int32_t* lag_out_dev);
 
+/* ---- relative measurements (odometry and scan-match increments between a step of this ring and the present, on the same
+ * window and lags): ukf_batch_relative.h, a header of its own beside this one. */
+
 /* ---- forecast: read-only multi-step prediction into a ring ------------------------------------------------------------------ */
 /* Where every filter will be after the next 1 ... steps predictions, with covariance, WITHOUT committing them (collision
  * checks, gating a scan that has not arrived yet, latency-compensated output at one common time for filters whose last samples

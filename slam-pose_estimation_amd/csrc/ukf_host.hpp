@@ -1,6 +1,6 @@
 // ukf_host.hpp -- the engine's host decisions as pure functions of plain values: configuration checks, process-noise
 // classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, packed covariances, workspace sizing, the filter lifecycle's checks and geometry, the delayed-measurement
-// update's checks, geometry and lag rule, and the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
+// update's checks, geometry and lag rule, the relative-measurement update's checks, models and map, and the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
 #pragma once
 
 #include <stddef.h>
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/ukf_batch.h"
+#include "../../include/ukf_batch_relative.h"
 
 #if defined(__HIP__)
 #define UKFB_HD __host__ __device__ __forceinline__
@@ -770,6 +771,55 @@ constexpr DelayedMap delayed_map(int S, int D) {
 }
 constexpr int delayed_filter_scalars(int S, int D) { return S > 16 ? -1 : delayed_map(S, D).PF; }
 inline RowGeometry delayed_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(delayed_filter_scalars(S, D), capacity, compute_size); }
+
+// ---- relative measurements (ukfb_update_relative_dev) -------------------------------------------------------------------------
+// An increment between step n - lag of the delayed update's window and the present, Pose engines only (UKFB_RELATIVE_*).  The
+// record of one filter's sample: z = dp (3) then dq (4), Q 6 x 6 row-major in the tangent order (dp, dtheta).
+constexpr int RELATIVE_MODELS = 3, RELATIVE_Z = 7, RELATIVE_M = 6;
+UKFB_HD bool relative_model_ok(int64_t id) { return id >= UKFB_RELATIVE_POSE && id <= UKFB_RELATIVE_ROTATION; }
+constexpr int relative_meas_dim(int64_t id) { return (id < 0 || id >= RELATIVE_MODELS) ? 0 : (id == UKFB_RELATIVE_POSE ? 6 : 3); }
+// tangent row / column t of the sample (0 ... 5) is read by model id
+constexpr bool relative_reads(int64_t id, int t) {
+    return t >= 0 && t < RELATIVE_M && (id == UKFB_RELATIVE_POSE || (id == UKFB_RELATIVE_POSITION && t < 3) || (id == UKFB_RELATIVE_ROTATION && t >= 3));
+}
+// the clauses of check_delayed_args in their order, with the engine's model judged first: the feature has no kernel for
+// OrientationState engines (include/ukf_batch.h says why)
+inline Verdict check_relative_args(int engine_model, const ukfb_relative_in* in, int commit, const ukfb_relative_out* out) {
+    if (engine_model != UKFB_MODEL_POSE) return {UKFB_ERR_WRONG_MODEL, "relative measurements serve Pose engines only"};
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    if (in->slots < 1 || in->steps < 1) return {UKFB_ERR_INVALID_ARG, "steps >= 1, slots >= 1"};
+    if (in->first_slot < 0 || in->first_slot >= in->slots) return {UKFB_ERR_INVALID_ARG, "0 <= first_slot < slots"};
+    if (in->steps > 1 && !in->dt) return {UKFB_ERR_INVALID_ARG, "dt must not be NULL for a window of more than one step"};
+    if (!in->mu_hist_dev || !in->cov_hist_dev) return {UKFB_ERR_INVALID_ARG, "mu_hist_dev and cov_hist_dev must not be NULL"};
+    if (!in->z_dev || !in->Q_dev) return {UKFB_ERR_INVALID_ARG, "z_dev and Q_dev must not be NULL"};
+    if (!zero_or_one(in->q_is_uniform)) return {UKFB_ERR_INVALID_ARG, "q_is_uniform must be 0 or 1"};
+    if (!zero_or_one(commit)) return {UKFB_ERR_INVALID_ARG, "commit must be 0 or 1"};
+    if (const Verdict v = nothing_to_compute(commit, out && (out->z_pred || out->S || out->innov || out->maha || out->loglik || out->status ||
+                                                             out->mu_out || out->cov_out));
+        v.rc != UKFB_OK)
+        return v;
+    if (in->steps > std::min(in->slots, DELAYED_MAX_STEPS))
+        return {UKFB_ERR_OUT_OF_RANGE, "steps <= min(slots, 33): an increment that starts before that is out of the window"};
+    return {};
+}
+// The delayed update's slice, not one scalar wider: what the update on the pair adds lives in regions the chain leaves dead.
+struct RelativeMap : DelayedMap {
+    int NR, LE, PRK;   // (ZS, WT, YN: the delayed map's names, with six columns here; YM is not used)
+};
+// the scores parked across the commit, every filter's own: S packed (21), nu (6), z-bar (7), d^2, ln det S
+constexpr int RELATIVE_PARK_S = 0, RELATIVE_PARK_NU = 21, RELATIVE_PARK_ZBAR = 27, RELATIVE_PARK_D2 = 34, RELATIVE_PARK_LNDET = 35;
+constexpr int RELATIVE_PARK_SCALARS = 36;
+constexpr RelativeMap relative_map(int S, int D) {
+    RelativeMap m{delayed_map(S, D), 0, 0, 0};
+    m.ZS = RELATIVE_M;   // row stride of the D x 6 matrices W and Y_n in the dead delta table
+    m.NR = m.TAB;        // the rows of N = Sigma_n M^T (D * LS), dead before W is written
+    m.WT = m.TAB; m.YM = m.TAB; m.YN = m.TAB + D * m.ZS;
+    m.LE = m.SMR;        // the columns of L_e (D * LS) in the parked rows of Sigma^-
+    m.PRK = m.SMR;       // ... and, once L_e is dead, the scores (RELATIVE_PARK_SCALARS <= D * LS)
+    return m;
+}
+constexpr int relative_filter_scalars(int S, int D) { return S > 16 ? -1 : relative_map(S, D).PF; }
+inline RowGeometry relative_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(relative_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- bounded waits ----------------------------------------------------------------------------------------------------------
 // Waiting by polling: hipEventSynchronize / hipStreamSynchronize sleep on an interrupt and were measured to

@@ -16,6 +16,8 @@ import numpy as np
 
 from . import abi
 from .abi import *  # noqa: F401,F403  (the constants, the structures, SIGNATURES and EXPORTS stay reachable as engine.X)
+from . import abi_relative
+from .abi_relative import RELATIVE_NONE, RELATIVE_POSE, RELATIVE_POSITION, RELATIVE_ROTATION, RelativeIn, RelativeOut  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UKFB_LIB", os.path.join(_HERE, "lib", "libukf_batch.so"))  # UKFB_LIB: debug builds only
@@ -37,6 +39,7 @@ def load_library():
                             f"(make -C slam-pose_estimation_amd/csrc); there is no CPU fallback")
         lib = C.CDLL(LIB_PATH)
         abi.declare(lib)
+        abi_relative.declare(lib)   # (include/ukf_batch_relative.h)
         _lib = lib
     return _lib
 
@@ -816,6 +819,44 @@ class BatchUKF:
         len(step_ts_us) (out of the window) for one older than the first step by more than half a step.  Stream-ordered."""
         ts = _i64(step_ts_us)
         self._call("ukfb_delayed_lag_dev", ts.size, _pi64(ts), _dev_i64(sample_ts_us_dev), _dev_i32(lag_out_dev))
+
+    # ---- relative measurements: an increment between a step of the delayed update's window and the present (Pose engines)
+    def update_relative_dev(self, dt, slots: int, first_slot: int, mu_hist, cov_hist, lag, model, z_dev, Q_dev,
+                            q_is_uniform: bool = False, in_a_dev=None, in_b_dev=None, commit: bool = True, z_pred=None, S=None,
+                            innov=None, maha=None, loglik=None, status=None, mu_out=None, cov_out=None):
+        """An increment "since step n - lag you moved by dp and turned by dq" corrects the current state through the history
+        ring (include/ukf_batch_relative.h): the update on the pair (present, clone of that step).  The window
+        is update_delayed_dev's.  lag / model (RELATIVE_POSE / RELATIVE_POSITION / RELATIVE_ROTATION): an int for the whole batch
+        or an int32 device array [capacity]; a lag <= 0 is INACTIVE.  z_dev [capacity, 7] (dp, then dq as x y z w), Q_dev
+        [capacity, 36] (36 scalars with q_is_uniform), tangent order (dp, dtheta).  commit=False is read-only: only the keyword
+        outputs (z_pred [capacity, 7], S [capacity, 36], innov [capacity, 6], maha, loglik, status, mu_out [capacity, S],
+        cov_out [capacity, PK]) are written.  Stream-ordered, nothing is allocated."""
+        d = _f64(dt, -1)
+        per = lambda x: (0, _dev(x)) if hasattr(x, "data_ptr") else (int(x), None)
+        (lag_u, lag_p), (mod_u, mod_p) = per(lag), per(model)
+        rin = RelativeIn(d.size + 1, _pd(d) if d.size else None, int(slots), int(first_slot), _dev(mu_hist), _dev(cov_hist),
+                         _dev(in_a_dev), _dev(in_b_dev), lag_u, lag_p, mod_u, mod_p, _dev(z_dev), _dev(Q_dev), q_is_uniform)
+        out = RelativeOut(_dev(z_pred), _dev(S), _dev(innov), _dev(maha), _dev(loglik), _dev(status), _dev(mu_out), _dev(cov_out))
+        self._call("ukfb_update_relative_dev", C.byref(rin), commit, C.byref(out))
+
+    def update_relative(self, dt, mu_hist, cov_hist, lag, model, z, Q, in_a=None, in_b=None, commit: bool = True):
+        """Host arrays in window order, as update_delayed: mu_hist [steps, capacity, S], cov_hist [steps, capacity, D, D] (the
+        last step is not read), dt [steps - 1], in_a / in_b [steps, capacity, 3] or None; lag / model an int or an int32 array
+        [capacity]; z [capacity, 7], Q [capacity, 6, 6].  Returns a dict of NumPy arrays: z_pred [n, 7], S [n, 6, 6], innov
+        [n, 6], maha, loglik, status [n], mu_out [n, S], cov_out [n, D, D]; synchronises"""
+        d = _f64(dt, -1)
+        steps, n = d.size + 1, self.capacity
+        mu_hist = _f64(mu_hist, (steps, n, self.S)); cov_hist = _f64(cov_hist, (steps, n, self.D, self.D))
+        a, b = _f64(in_a, (steps, n, 3)), _f64(in_b, (steps, n, 3))
+        z = _f64(z, (n, 7)); Q = _f64(Q, (n, 6, 6))
+        (lag_u, lag_p), (mod_u, mod_p) = _int_or_i32(lag, n), _int_or_i32(model, n)
+        o = {"z_pred": np.empty((n, 7)), "S": np.empty((n, 6, 6)), "innov": np.empty((n, 6)), "maha": np.empty(n),
+             "loglik": np.empty(n), "status": np.empty(n, dtype=np.uint32), "mu_out": np.empty((n, self.S)),
+             "cov_out": np.empty((n, self.D, self.D))}
+        self._call("ukfb_update_relative", steps, _pd(d) if d.size else None, _pd(mu_hist), _pd(cov_hist), _pd(a), _pd(b), lag_u,
+                   _pi32(lag_p), mod_u, _pi32(mod_p), _pd(z), _pd(Q), commit, _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]),
+                   _pd(o["maha"]), _pd(o["loglik"]), _pu32(o["status"]), _pd(o["mu_out"]), _pd(o["cov_out"]))
+        return o
 
     # ---- fused cycle
     def cycle(self, dt: float, meas_model: int, z, Q):
