@@ -1,7 +1,8 @@
 """NumPy float64 statement of the bearing measurements of include/ukf_batch.h ("bearing measurements"): the three direction
 models, the sphere S^2 as a measurement manifold for the oracle's own pieces (on.sigma_points, on.mean_sigma_points,
-on.cov_sigma_points, on.ukf_update, which are duck-typed on the manifold), and the status rules of the header.
-A helper, not collected; tests/test_bearing_reference.py pins it.
+on.cov_sigma_points, on.ukf_update, which are duck-typed on the manifold), and on it the scored update of
+tests/update_reference.py with the status rules of the header.  A helper, not collected; tests/test_bearing_reference.py pins
+it.
 
 The update is stated in the 2 x 2 BASIS FORM: S2 carries an explicit orthonormal tangent basis B(u) [3, 2]; boxminus returns
 B(u)^T log_u(v), boxplus is exp_u(B(u) d), the noise is Q2 = B^T Q B at the predicted direction.  S and nu are lifted to the
@@ -13,6 +14,7 @@ import numpy as np
 
 import sensor_meas_reference as sr
 from oracle import ukf_numpy as on
+from update_reference import mean_iteration, nan_outputs, scored_update
 
 LN_2PI = float(np.log(2.0 * np.pi))
 
@@ -117,21 +119,7 @@ def used_inputs(mid):
     return mm, np.ones(3, bool)
 
 
-def mean_steps(manz, Z, tol=on.MEAN_TOL, max_it=on.MEAN_MAX_IT):
-    """the iteration of on.mean_sigma_points once more, for what it does not return -> (trips [B]: steps whose norm exceeded
-    tol, norms [B, trips.max() + 1]: the norm of every step a filter made, NaN beyond its last)"""
-    B = Z.shape[0]
-    ref = Z[:, 0].copy()
-    active, it, norms = np.ones(B, bool), np.zeros(B, np.int64), []
-    while active.any():
-        md = manz.boxminus(Z, ref[:, None, :]).mean(axis=1)
-        nrm = np.sqrt(np.sum(md * md, axis=-1))
-        norms.append(np.where(active, nrm, np.nan))
-        ref = np.where(active[:, None], manz.boxplus(ref, md), ref)
-        big = nrm > tol
-        it = np.where(active & big, it + 1, it)
-        active = active & big & (it < max_it)
-    return it, np.stack(norms, axis=1)
+mean_steps = mean_iteration   # (trips [B], norms [B, trips.max() + 1]) of the mean on the sphere
 
 
 def update_bearing(man, mu, cov, models, z, Q, mount, point, gate_chi2=-1.0, initialised=None, tol=on.MEAN_TOL,
@@ -148,10 +136,8 @@ def update_bearing(man, mu, cov, models, z, Q, mount, point, gate_chi2=-1.0, ini
     point = np.broadcast_to(np.asarray(point, dtype=np.float64), (B, 3))
     init = np.ones(B, bool) if initialised is None else np.asarray(initialised, dtype=bool)
     manz = S2(basis)
-    o = {"mu": mu.copy(), "cov": cov.copy(), "z_pred": np.full((B, 3), np.nan), "S": np.full((B, 3, 3), np.nan),
-         "innov": np.full((B, 3), np.nan), "maha": np.full(B, np.nan), "loglik": np.full(B, np.nan),
-         "status": np.zeros(B, dtype=np.uint32), "trips": np.zeros(B, np.int64), "spread": np.full(B, np.nan),
-         "logdet": np.full(B, np.nan), "tol_margin": np.full(B, np.nan)}
+    o = dict(nan_outputs(mu, cov, 3, 3), trips=np.zeros(B, np.int64), spread=np.full(B, np.nan), logdet=np.full(B, np.nan),
+             tol_margin=np.full(B, np.nan))
     valid = np.isin(models, ids_of(man))
     o["status"][~init] = on.ST_UNINITIALISED
     o["status"][init & ~valid] = on.ST_INACTIVE
@@ -173,8 +159,9 @@ def update_bearing(man, mu, cov, models, z, Q, mount, point, gate_chi2=-1.0, ini
         # entries the model does not read never meet arithmetic
         mt = np.where(um, mount[idx], sr.IDENTITY_MOUNT)[:, None, :]
         pt = point[idx][:, None, :]
-        X, ok = on.sigma_points(man, mu[idx], np.where(_pd(cov[idx])[:, None, None], cov[idx], np.eye(man.D)))
         ok = _pd(cov[idx])
+        sig = np.where(ok[:, None, None], cov[idx], np.eye(man.D))
+        X, _ = on.sigma_points(man, mu[idx], sig)
         d = direction(mid, X, mt, pt)
         with np.errstate(over="ignore", invalid="ignore"):
             d2n = np.sum(d * d, axis=-1)
@@ -185,37 +172,29 @@ def update_bearing(man, mu, cov, models, z, Q, mount, point, gate_chi2=-1.0, ini
             dd = direction(mid, Xs, mt if Xs.ndim == 3 else mt[:, 0], pt if Xs.ndim == 3 else pt[:, 0])
             sel = degen[:, None, None] if Xs.ndim == 3 else degen[:, None]
             return unit(np.where(sel, safe, dd))
-        Z = hh(X)
-        mz, _ = on.mean_sigma_points(manz, Z, tol, max_it)
-        trips, steps = mean_steps(manz, Z, tol, max_it)
-        Bz = basis(mz)
-        Q2 = np.swapaxes(Bz, 1, 2) @ Q3 @ Bz
-        S = on.cov_sigma_points(manz, mz, Z) + Q2
-        _, ok_s = on.cholesky_lower(S)
-        ok_s &= ok & ~degen
-        eye = np.eye(2)
-        S_safe = np.where(ok_s[:, None, None], S, eye)
-        innov = manz.boxminus(zhat, mz)
-        d2 = np.einsum("bi,bij,bj->b", innov, np.linalg.inv(S_safe), innov)
-        logdet = np.linalg.slogdet(S_safe)[1]
-        # (a filter whose Sigma or S is not positive definite gets the identity: its result is discarded below)
-        m2, C2, s = on.ukf_update(man, manz, mu[idx], np.where(ok[:, None, None], cov[idx], np.eye(man.D)), zhat, hh,
-                                  np.where(ok_s[:, None, None], Q2, eye), tol, max_it, gate_chi2)
-        s = np.where(ok_s, s, s | on.ST_ERR_CHOLESKY).astype(np.uint32)
-        s = np.where((s & on.ST_ERR_CHOLESKY) != 0, s & ~np.uint32(on.ST_REJECTED_GATE), s).astype(np.uint32)
-        s = np.where(ok, s, s & ~np.uint32(on.ST_WARN_MEAN_NOCONV)).astype(np.uint32)   # no sigma points, no mean
-        commit = (s & (on.ST_ERR_CHOLESKY | on.ST_REJECTED_GATE)) == 0
-        scored = (s & on.ST_ERR_CHOLESKY) == 0
-        o["mu"][idx[commit]], o["cov"][idx[commit]] = m2[commit], C2[commit]
+
+        def Q2(mz, Q3=Q3):
+            Bz = basis(mz)
+            return np.swapaxes(Bz, 1, 2) @ Q3 @ Bz
+        # Sigma is judged here, on the matrix as given; a failed one goes in as the identity and fails through extra_fail
+        u = scored_update(man, manz, mu[idx], sig, zhat, hh, Q2, tol, max_it, gate_chi2, extra_fail=degen | ~ok)
+        # No sigma points, no mean: the kernels set the bit only where Sigma factorised (do_u && ok1 && !conv).  Stated here
+        # and not in the core, which returns what the other three references have always returned: on S^2 the identity that
+        # stands in for a failed Sigma spreads the points by a radian and the mean really iterates; no test of the others pairs
+        # a failed Sigma with a capped mean.
+        s = np.where(ok, u.status, u.status & ~np.uint32(on.ST_WARN_MEAN_NOCONV)).astype(np.uint32)
+        trips, steps = mean_steps(manz, u.Z, tol, max_it)
+        Bz, scored = basis(u.mz), u.scored
+        o["mu"][idx[u.commit]], o["cov"][idx[u.commit]] = u.mu2[u.commit], u.cov2[u.commit]
         sc = idx[scored]
-        o["z_pred"][sc] = mz[scored]
-        o["S"][sc] = (Bz @ S @ np.swapaxes(Bz, 1, 2))[scored]
-        o["innov"][sc] = np.einsum("bij,bj->bi", Bz, innov)[scored]
-        o["maha"][sc] = d2[scored]
-        o["logdet"][sc] = logdet[scored]
-        o["loglik"][sc] = -0.5 * (d2[scored] + logdet[scored] + 2.0 * LN_2PI)
+        o["z_pred"][sc] = u.mz[scored]
+        o["S"][sc] = (Bz @ u.S @ np.swapaxes(Bz, 1, 2))[scored]
+        o["innov"][sc] = np.einsum("bij,bj->bi", Bz, u.innov)[scored]
+        o["maha"][sc] = u.d2[scored]
+        o["logdet"][sc] = u.logdet[scored]
+        o["loglik"][sc] = -0.5 * (u.d2[scored] + u.logdet[scored] + 2.0 * LN_2PI)
         o["trips"][sc] = trips[scored]
-        o["spread"][sc] = np.max(np.linalg.norm(s2_log(mz[:, None, :], Z), axis=-1), axis=1)[scored]
+        o["spread"][sc] = np.max(np.linalg.norm(s2_log(u.mz[:, None, :], u.Z), axis=-1), axis=1)[scored]
         o["tol_margin"][sc] = np.nanmin(np.abs(steps - tol) / tol, axis=1)[scored]
         o["status"][idx] = s
     return o

@@ -12,6 +12,7 @@ import numpy as np
 from oracle import ukf_numpy as on
 from bank_reference import jr_inv, rot_offset, hat
 import smoother_reference as sr
+from update_reference import commit_through_history
 
 LN_2PI = 1.8378770664093454835606594728112
 JR_SMALL_T = 0.25   # theta^2 up to which the second coefficient of Jr comes from its series (as Jr^-1's, ukf_bank.hpp)
@@ -193,23 +194,9 @@ def update_delayed(p, mu, cov, mu_n, cov_n, dt, lag, models, z, Q, in_a=None, in
                 okc = good[k] & ok & ok_s & np.isfinite(sig2).all(axis=(1, 2))
                 sig2s = np.where((okc & accept)[:, None, None], sig2, np.eye(D)[None])
                 m2, C2, ok2 = on.apply_delta(man, mu_n[i], sig2s, np.einsum("bij,bj->bi", K, nu))
-            okc = okc & (ok2 | ~accept)
-            commit = okc & accept
-            st[i] |= np.where(okc, 0, on.ST_ERR_CHOLESKY).astype(np.uint32)
-            st[i] |= np.where(good[k] & ok & ~conv, on.ST_WARN_MEAN_NOCONV, 0).astype(np.uint32)
-            st[i] |= np.where(okc & ~accept, on.ST_REJECTED_GATE, 0).astype(np.uint32)
-            s_ = i[okc]
-            zp = np.zeros((len(k), 4))
-            zp[:, :mz.shape[1]] = mz
-            S3, nu3 = np.zeros((len(k), 3, 3)), np.zeros((len(k), 3))
-            S3[:, :m, :m], nu3[:, :m] = S, nu
-            o["z_pred"][s_], o["S"][s_], o["innov"][s_] = zp[okc], S3[okc], nu3[okc]
-            o["maha"][s_] = maha[okc]
-            o["loglik"][s_] = -0.5 * (maha[okc] + lndet[okc] + m * LN_2PI)
-            c_ = i[commit]
-            o["mu"][c_], o["cov"][c_] = m2[commit], C2[commit]
-            o["mu_out"][c_], o["cov_out"][c_] = m2[commit], C2[commit]
-            o["committed"][c_] = True
+                loglik = -0.5 * (maha + lndet + m * LN_2PI)
+            commit_through_history(o, st, i, okc, ok2, accept, good[k] & ok & ~conv, mz, S, nu, maha, loglik,
+                                   np.arange(mz.shape[1]), np.arange(m), m2, C2)
     o["status"] = st.astype(np.uint32)
     return o
 

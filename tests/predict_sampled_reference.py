@@ -6,6 +6,7 @@ collected; tests/test_predict_sampled_reference.py pins it."""
 import numpy as np
 
 from oracle import ukf_numpy as on
+from update_reference import mean_iteration
 
 
 def predict_sampled(man, mu, cov, XX, R, active=None, initialised=None, tol=on.MEAN_TOL, max_it=on.MEAN_MAX_IT):
@@ -34,20 +35,8 @@ def predict_sampled(man, mu, cov, XX, R, active=None, initialised=None, tol=on.M
 
 
 def mean_trips(man, XX, tol=on.MEAN_TOL):
-    """-> [B] the moves above the tolerance on.mean_sigma_points makes per filter (its `it`), recounted alone"""
-    B = XX.shape[0]
-    ref, active, it = XX[:, 0].copy(), np.ones(B, bool), np.zeros(B, dtype=np.int64)
-    while active.any():
-        md = man.boxminus(XX, ref[:, None, :])
-        s = np.zeros((B, man.D))
-        for i in range(XX.shape[1]):
-            s = s + md[:, i]
-        s = s / float(XX.shape[1])
-        ref = np.where(active[:, None], man.boxplus(ref, s), ref)
-        big = np.sqrt(np.sum(s * s, axis=-1)) > tol
-        it = np.where(active & big, it + 1, it)
-        active = active & big
-    return it
+    """-> [B] the moves above the tolerance on.mean_sigma_points makes per filter (its `it`, under its default cap)"""
+    return mean_iteration(man, XX, tol)[0]
 
 
 # ------------------------------------------------------------------------------------------------ a family of user process models

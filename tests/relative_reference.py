@@ -13,6 +13,7 @@ import numpy as np
 from oracle import ukf_numpy as on
 import delayed_reference as dr
 import smoother_reference as sr
+from update_reference import commit_through_history
 
 LN_2PI = dr.LN_2PI
 TAU = 64.0 * np.finfo(np.float64).eps          # the clamp of the factorisation of Sigma_e, in units of its diagonal
@@ -167,23 +168,10 @@ def update_relative(p, mu, cov, mu_n, cov_n, dt, lag, models, z, Q, in_a=None, i
                 okc = good[k] & ok_n & ok_e & ok_s & np.isfinite(sig2).all(axis=(1, 2))
                 sig2s = np.where((okc & accept)[:, None, None], sig2, np.eye(D)[None])
                 m2, C2, ok2 = on.apply_delta(man, mu_n[i], sig2s, np.einsum("bim,bm->bi", Yn, y))
-            okc = okc & (ok2 | ~accept)
-            commit = okc & accept
-            st[i] |= np.where(okc, 0, on.ST_ERR_CHOLESKY).astype(np.uint32)
-            st[i] |= np.where(good[k] & ok_n & ok_e & ~conv, on.ST_WARN_MEAN_NOCONV, 0).astype(np.uint32)
-            st[i] |= np.where(okc & ~accept, on.ST_REJECTED_GATE, 0).astype(np.uint32)
-            s_ = i[okc]
-            zp, S6, nu6 = np.zeros((len(k), 7)), np.zeros((len(k), 6, 6)), np.zeros((len(k), 6))
-            zp[:, si], nu6[:, ti] = mz, nu
-            S6[:, ti[:, None], ti[None, :]] = S
-            o["z_pred"][s_], o["S"][s_], o["innov"][s_] = zp[okc], S6[okc], nu6[okc]
-            o["maha"][s_] = maha[okc]
-            o["loglik"][s_] = -0.5 * (maha[okc] + lndet[okc] + m * LN_2PI)
+                loglik = -0.5 * (maha + lndet + m * LN_2PI)
+            commit_through_history(o, st, i, okc, ok2, accept, good[k] & ok_n & ok_e & ~conv, mz, S, nu, maha, loglik, si, ti,
+                                   m2, C2)
             o["clamped"][i] = clamped.sum(axis=1)
-            c_ = i[commit]
-            o["mu"][c_], o["cov"][c_] = m2[commit], C2[commit]
-            o["mu_out"][c_], o["cov_out"][c_] = m2[commit], C2[commit]
-            o["committed"][c_] = True
     o["status"] = st.astype(np.uint32)
     return o
 

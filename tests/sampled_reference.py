@@ -1,11 +1,12 @@
 """NumPy float64 statement of the user-defined measurement models of include/ukf_batch.h ("user-defined measurement models"):
-the sigma-point export in its filter-major layout, and oracle.ukf_numpy.ukf_update(POSE | ORIENT, VECT(m), ..., h = the
-caller's samples, ...) plus what the oracle's update does not return (z-bar, S, the innovation, the squared Mahalanobis
-distance, the log-likelihood) and the status rules of the header.  A helper, not collected; tests/test_sampled_reference.py
-pins it."""
+the sigma-point export in its filter-major layout, and the scored update of tests/update_reference.py on (POSE | ORIENT,
+VECT(m)) with h = the caller's samples: oracle.ukf_numpy.ukf_update, what it does not return (z-bar, S, the innovation, the
+squared Mahalanobis distance, the log-likelihood) and the status rules of the header.  A helper, not collected;
+tests/test_sampled_reference.py pins it."""
 import numpy as np
 
 from oracle import ukf_numpy as on
+from update_reference import nan_outputs, scored_update
 
 LN_2PI = float(np.log(2.0 * np.pi))
 MAX_M = 6
@@ -33,16 +34,14 @@ def sigma_points(man, mu, cov, initialised=None):
 
 def update_sampled(man, mu, cov, Z, z, Q, active=None, gate_chi2=-1.0, initialised=None, tol=on.MEAN_TOL, max_it=on.MEAN_MAX_IT):
     """mu [B, S], cov [B, D, D], Z [B, 2 D + 1, m], z [B, m], Q [B, m, m] (or [m, m]), active [B] or None -> dict(mu, cov,
-    z_pred [B, m], S [B, m, m], innov [B, m], maha [B], loglik [B], status [B]): one call of on.ukf_update over the filters
-    that take part"""
+    z_pred [B, m], S [B, m, m], innov [B, m], maha [B], loglik [B], status [B]): one scored update over the filters that take
+    part"""
     B, m = mu.shape[0], Z.shape[2]
     assert 1 <= m <= MAX_M and Z.shape == (B, 2 * man.D + 1, m) and z.shape == (B, m)
     Q = np.broadcast_to(np.asarray(Q, dtype=np.float64), (B, m, m))
     init = np.ones(B, bool) if initialised is None else np.asarray(initialised, dtype=bool)
     act = np.ones(B, bool) if active is None else np.asarray(active) != 0
-    o = {"mu": mu.copy(), "cov": cov.copy(), "z_pred": np.full((B, m), np.nan), "S": np.full((B, m, m), np.nan),
-         "innov": np.full((B, m), np.nan), "maha": np.full(B, np.nan), "loglik": np.full(B, np.nan),
-         "status": np.zeros(B, dtype=np.uint32)}
+    o = nan_outputs(mu, cov, m, m)
     o["status"][~init] = on.ST_UNINITIALISED
     o["status"][init & ~act] = on.ST_INACTIVE
     lower = np.tril(np.ones((m, m), bool))
@@ -53,31 +52,13 @@ def update_sampled(man, mu, cov, Z, z, Q, active=None, gate_chi2=-1.0, initialis
         return o
     zz, ZZ = z[idx], Z[idx]
     QQ = np.where(lower, Q[idx], np.swapaxes(Q[idx], 1, 2))   # the lower triangle is what is read
-    manz = on.VECT(m)
-    # the statistics of the update, from the oracle's own pieces in the oracle's own order
-    _, ok = on.sigma_points(man, mu[idx], cov[idx])
-    mz, _ = on.mean_sigma_points(manz, ZZ, tol, max_it)
-    S = on.cov_sigma_points(manz, mz, ZZ) + QQ
-    _, ok_s = on.cholesky_lower(S)
-    ok_s &= ok
-    eye = np.eye(m)
-    S_safe = np.where(ok_s[:, None, None], S, eye)
-    innov = manz.boxminus(zz, mz)
-    d2 = np.einsum("bi,bij,bj->b", innov, np.linalg.inv(S_safe), innov)
-    logdet = np.linalg.slogdet(S_safe)[1]
-    # (a filter whose Sigma or S is not positive definite gets the identity: its result is discarded below)
-    m2, C2, s = on.ukf_update(man, manz, mu[idx], np.where(ok[:, None, None], cov[idx], np.eye(man.D)), zz, lambda X: ZZ,
-                              np.where(ok_s[:, None, None], QQ, eye), tol, max_it, gate_chi2)
-    s = np.where(ok_s, s, s | on.ST_ERR_CHOLESKY).astype(np.uint32)
-    s = np.where((s & on.ST_ERR_CHOLESKY) != 0, s & ~np.uint32(on.ST_REJECTED_GATE), s).astype(np.uint32)
-    commit = (s & (on.ST_ERR_CHOLESKY | on.ST_REJECTED_GATE)) == 0
-    scored = (s & on.ST_ERR_CHOLESKY) == 0
-    o["mu"][idx[commit]], o["cov"][idx[commit]] = m2[commit], C2[commit]
-    sc = idx[scored]
-    o["z_pred"][sc], o["S"][sc], o["innov"][sc] = mz[scored], S[scored], innov[scored]
-    o["maha"][sc] = d2[scored]
-    o["loglik"][sc] = -0.5 * (d2[scored] + logdet[scored] + m * LN_2PI)
-    o["status"][idx] = s
+    u = scored_update(man, on.VECT(m), mu[idx], cov[idx], zz, lambda X: ZZ, QQ, tol, max_it, gate_chi2)
+    o["mu"][idx[u.commit]], o["cov"][idx[u.commit]] = u.mu2[u.commit], u.cov2[u.commit]
+    sc = idx[u.scored]
+    o["z_pred"][sc], o["S"][sc], o["innov"][sc] = u.mz[u.scored], u.S[u.scored], u.innov[u.scored]
+    o["maha"][sc] = u.d2[u.scored]
+    o["loglik"][sc] = -0.5 * (u.d2[u.scored] + u.logdet[u.scored] + m * LN_2PI)
+    o["status"][idx] = u.status
     return o
 
 

@@ -1,13 +1,14 @@
 """NumPy float64 statement of the sensor-frame measurements of include/ukf_batch.h ("sensor-frame measurements"): the eight
-h functions, and oracle.ukf_numpy.ukf_update(POSE | ORIENT, VECT(m), ...) per model id, plus what the oracle's update does not
-return (z-bar, S, the innovation, the squared Mahalanobis distance, the log-likelihood) and the status rules of the header.
-A helper, not collected; tests/test_sensor_meas_reference.py pins it.
+h functions, and per model id the scored update of tests/update_reference.py on (POSE | ORIENT, VECT(m)):
+oracle.ukf_numpy.ukf_update, what it does not return (z-bar, S, the innovation, the squared Mahalanobis distance, the
+log-likelihood) and the status rules of the header.  A helper, not collected; tests/test_sensor_meas_reference.py pins it.
 
 Conventions: R(q) x = on.quat_rotate(q, x); R(q)^T x = on.quat_rotate(on.quat_inverse(q), x) (what the reference library's
 q.inverse() * x is); mount = r[3] then qs[4] (x, y, z, w); point = b[3]."""
 import numpy as np
 
 from oracle import ukf_numpy as on
+from update_reference import nan_outputs, scored_update
 
 LN_2PI = float(np.log(2.0 * np.pi))
 
@@ -74,7 +75,7 @@ def update_sensor(man, mu, cov, models, z, Q, mount, point, gyro=None, gate_chi2
                   max_it=on.MEAN_MAX_IT):
     """mu [B, S], cov [B, D, D], models an int or [B], z [B, 3], Q [B, 3, 3] (or [3, 3]), mount [B, 7] (or [7]), point [B, 3]
     (or [3]), gyro [B, 3] (OrientationState) -> dict(mu, cov, z_pred [B, 3], S [B, 3, 3], innov [B, 3], maha [B], loglik [B],
-    status [B]).  Filters are grouped by model id; every group is one call of on.ukf_update."""
+    status [B]).  Filters are grouped by model id; every group is one scored update."""
     B = mu.shape[0]
     models = np.broadcast_to(np.asarray(models, dtype=np.int64), (B,))
     Q = np.broadcast_to(np.asarray(Q, dtype=np.float64), (B, 3, 3))
@@ -82,9 +83,7 @@ def update_sensor(man, mu, cov, models, z, Q, mount, point, gyro=None, gate_chi2
     point = np.broadcast_to(np.asarray(point, dtype=np.float64), (B, 3))
     gyro = np.zeros((B, 3)) if gyro is None else np.asarray(gyro, dtype=np.float64)
     init = np.ones(B, bool) if initialised is None else np.asarray(initialised, dtype=bool)
-    o = {"mu": mu.copy(), "cov": cov.copy(), "z_pred": np.full((B, 3), np.nan), "S": np.full((B, 3, 3), np.nan),
-         "innov": np.full((B, 3), np.nan), "maha": np.full(B, np.nan), "loglik": np.full(B, np.nan),
-         "status": np.zeros(B, dtype=np.uint32)}
+    o = nan_outputs(mu, cov, 3, 3)
     valid = np.isin(models, ids_of(man))
     o["status"][~init] = on.ST_UNINITIALISED
     o["status"][init & ~valid] = on.ST_INACTIVE
@@ -106,34 +105,15 @@ def update_sensor(man, mu, cov, models, z, Q, mount, point, gyro=None, gate_chi2
         pt = np.where(up, point[idx], 0.0)[:, None, :]
         gy = gyro[idx][:, None, :]
         hh = lambda X: h(mid, X, mt, pt, gy)
-        manz = on.VECT(m)
-        # the statistics of the update, from the oracle's own pieces in the oracle's own order
-        X, ok = on.sigma_points(man, mu[idx], cov[idx])
-        Z = hh(X)
-        mz, _ = on.mean_sigma_points(manz, Z, tol, max_it)
-        S = on.cov_sigma_points(manz, mz, Z) + QQ
-        _, ok_s = on.cholesky_lower(S)
-        ok_s &= ok
-        eye = np.eye(m)
-        S_safe = np.where(ok_s[:, None, None], S, eye)
-        innov = manz.boxminus(zz, mz)
-        d2 = np.einsum("bi,bij,bj->b", innov, np.linalg.inv(S_safe), innov)
-        logdet = np.linalg.slogdet(S_safe)[1]
-        # (a filter whose Sigma or S is not positive definite gets the identity: its result is discarded below)
-        m2, C2, s = on.ukf_update(man, manz, mu[idx], np.where(ok[:, None, None], cov[idx], np.eye(man.D)), zz, hh,
-                                  np.where(ok_s[:, None, None], QQ, eye), tol, max_it, gate_chi2)
-        s = np.where(ok_s, s, s | on.ST_ERR_CHOLESKY).astype(np.uint32)
-        s = np.where((s & on.ST_ERR_CHOLESKY) != 0, s & ~np.uint32(on.ST_REJECTED_GATE), s).astype(np.uint32)
-        commit = (s & (on.ST_ERR_CHOLESKY | on.ST_REJECTED_GATE)) == 0
-        scored = (s & on.ST_ERR_CHOLESKY) == 0
-        o["mu"][idx[commit]], o["cov"][idx[commit]] = m2[commit], C2[commit]
-        sc = idx[scored]
+        u = scored_update(man, on.VECT(m), mu[idx], cov[idx], zz, hh, QQ, tol, max_it, gate_chi2)
+        o["mu"][idx[u.commit]], o["cov"][idx[u.commit]] = u.mu2[u.commit], u.cov2[u.commit]
+        sc = idx[u.scored]
         o["z_pred"][sc] = 0.0
-        o["z_pred"][sc, :m] = mz[scored]
+        o["z_pred"][sc, :m] = u.mz[u.scored]
         o["S"][sc] = 0.0
-        o["S"][sc[:, None, None], np.arange(m)[None, :, None], np.arange(m)[None, None, :]] = S[scored]
-        o["innov"][sc, :m] = innov[scored]
-        o["maha"][sc] = d2[scored]
-        o["loglik"][sc] = -0.5 * (d2[scored] + logdet[scored] + m * LN_2PI)
-        o["status"][idx] = s
+        o["S"][sc[:, None, None], np.arange(m)[None, :, None], np.arange(m)[None, None, :]] = u.S[u.scored]
+        o["innov"][sc, :m] = u.innov[u.scored]
+        o["maha"][sc] = u.d2[u.scored]
+        o["loglik"][sc] = -0.5 * (u.d2[u.scored] + u.logdet[u.scored] + m * LN_2PI)
+        o["status"][idx] = u.status
     return o

@@ -1,10 +1,11 @@
 """NumPy float64 statement of the joint state-block measurement of include/ukf_batch.h ("joint state-block measurements"):
-oracle.ukf_numpy.ukf_update with the measurement manifold the compound of the selected state blocks and h their selection,
-plus what the oracle's update does not return (the squared Mahalanobis distance, the log-likelihood) and the status rules of
-the header.  A helper, not collected; tests/test_state_meas_reference.py pins it."""
+the scored update of tests/update_reference.py (oracle.ukf_numpy.ukf_update, what it does not return, the status rules of the
+header) with the measurement manifold the compound of the selected state blocks and h their selection.  A helper, not
+collected; tests/test_state_meas_reference.py pins it."""
 import numpy as np
 
 from oracle import ukf_numpy as on
+from update_reference import scored_update
 
 LN_2PI = float(np.log(2.0 * np.pi))
 
@@ -30,7 +31,7 @@ def mask_valid(man, masks):
 def update_state(man, mu, cov, masks, z, Qz, a=1.0, b=1.0, gate_chi2=-1.0, initialised=None, tol=on.MEAN_TOL,
                  max_it=on.MEAN_MAX_IT):
     """mu [B, S], cov [B, D, D], masks an int or [B], z [B, S], Qz [B, D, D] -> (mu, cov, maha [B], loglik [B], status [B]).
-    Filters are grouped by mask; every group is one call of on.ukf_update on a * cov and b * Qz[sel][sel]."""
+    Filters are grouped by mask; every group is one scored update on a * cov and b * Qz[sel][sel]."""
     B = mu.shape[0]
     masks = np.broadcast_to(np.asarray(masks, dtype=np.int64), (B,))
     init = np.ones(B, bool) if initialised is None else np.asarray(initialised, dtype=bool)
@@ -49,31 +50,11 @@ def update_state(man, mu, cov, masks, z, Qz, a=1.0, b=1.0, gate_chi2=-1.0, initi
         idx, zz, QQ = idx[fin], zz[fin], b * QQ[fin]
         if idx.size == 0:
             continue
-        sig = a * cov[idx]
-        h = lambda X: X[..., si]
-        # the statistics of the update, from the oracle's own pieces in the oracle's own order
-        X, ok = on.sigma_points(man, mu[idx], sig)
-        Z = h(X)
-        mz, _ = on.mean_sigma_points(manz, Z, tol, max_it)
-        S = on.cov_sigma_points(manz, mz, Z) + QQ
-        _, ok_s = on.cholesky_lower(S)
-        ok_s &= ok
-        eye = np.eye(manz.D)
-        S_safe = np.where(ok_s[:, None, None], S, eye)
-        innov = manz.boxminus(zz, mz)
-        d2 = np.einsum("bi,bij,bj->b", innov, np.linalg.inv(S_safe), innov)
-        logdet = np.linalg.slogdet(S_safe)[1]
-        # (a filter whose S is not positive definite gets the identity for Q: its result is discarded below)
-        m2, C2, s = on.ukf_update(man, manz, mu[idx], np.where(ok[:, None, None], sig, np.eye(man.D)), zz, h,
-                                  np.where(ok_s[:, None, None], QQ, eye), tol, max_it, gate_chi2)
-        s = np.where(ok_s, s, s | on.ST_ERR_CHOLESKY).astype(np.uint32)
-        s = np.where((s & on.ST_ERR_CHOLESKY) != 0, s & ~np.uint32(on.ST_REJECTED_GATE), s).astype(np.uint32)
-        commit = (s & (on.ST_ERR_CHOLESKY | on.ST_REJECTED_GATE)) == 0
-        scored = (s & on.ST_ERR_CHOLESKY) == 0
-        mu_o[idx[commit]], cov_o[idx[commit]] = m2[commit], C2[commit]
-        maha[idx] = np.where(scored, d2, np.nan)
-        ll[idx] = np.where(scored, -0.5 * (d2 + logdet + manz.D * LN_2PI), np.nan)
-        st[idx] = s
+        u = scored_update(man, manz, mu[idx], a * cov[idx], zz, lambda X: X[..., si], QQ, tol, max_it, gate_chi2)
+        mu_o[idx[u.commit]], cov_o[idx[u.commit]] = u.mu2[u.commit], u.cov2[u.commit]
+        maha[idx] = np.where(u.scored, u.d2, np.nan)
+        ll[idx] = np.where(u.scored, -0.5 * (u.d2 + u.logdet + manz.D * LN_2PI), np.nan)
+        st[idx] = u.status
     return mu_o, cov_o, maha, ll, st
 
 

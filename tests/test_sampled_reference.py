@@ -1,7 +1,8 @@
 """Pins for tests/sampled_reference.py, the NumPy statement of the user-defined measurement models (include/ukf_batch.h) the GPU
-tests compare with: fed the samples of a built-in sensor model it returns what tests/sensor_meas_reference.py returns, a linear
-h gives the closed-form Kalman update, a translation of z and Z moves z-bar and nothing else, the status rules hold one by one,
-and the GPU file's input family gives status 0 for every filter not deliberately broken."""
+tests compare with: fed the samples of a built-in sensor model it returns what tests/sensor_meas_reference.py returns, a
+translation of z and Z moves z-bar and nothing else, the status rules hold one by one, and the GPU file's input family gives
+status 0 for every filter not deliberately broken.  (That a linear h gives the closed-form Kalman update is pinned where the
+arithmetic lives, in tests/test_update_reference.py.)"""
 import numpy as np
 import pytest
 
@@ -74,42 +75,6 @@ def test_samples_of_a_sensor_model_give_the_sensor_reference(mid):
         assert np.array_equal(got[k], ref[k]), k
     assert np.array_equal(got["z_pred"], ref["z_pred"][:, :m]) and np.array_equal(got["innov"], ref["innov"][:, :m])
     assert np.array_equal(got["S"], ref["S"][:, :m, :m])
-
-
-# ------------------------------------------------------------------------------------------------------- a linear h: Kalman
-def test_linear_h_is_the_kalman_update():
-    """m = 6: position and velocity.  For a linear h the unscented statistics are exact: z-bar = H mu, S = H Sigma H^T + Q,
-    C = Sigma H^T, so that K, nu, d^2 and the log-likelihood are the Kalman filter's, and the committed state is ukfom's commit
-    of the Kalman result, applyDelta(mu, Sigma - K S K^T, K nu) (the mean is mu (+) K nu; on SO(3) re-sampling about the moved
-    mean changes the rotation block of Sigma - K S K^T in second order, 2e-8 here, which is the update's and not an error): all
-    to rounding, 1e-10."""
-    mu, cov, _ = states("pose")
-    rng = np.random.default_rng(7)
-    X, _, st = sm.sigma_points(on.POSE, mu, cov)
-    assert (st == 0).all()
-    sel = [0, 1, 2, 7, 8, 9]
-    tsel = [0, 1, 2, 6, 7, 8]
-    Z = X[..., sel]
-    z = mu[:, sel] + 0.05 * rng.standard_normal((N, 6))
-    G = rng.standard_normal((N, 6, 6))
-    Q = 0.05 ** 2 * (np.eye(6) + G @ np.swapaxes(G, 1, 2) / 24.0)
-    got = sm.update_sampled(on.POSE, mu, cov, Z, z, Q)
-    assert (got["status"] == 0).all()
-    H = np.zeros((6, 12))
-    H[np.arange(6), tsel] = 1.0
-    S = H @ cov @ H.T + Q
-    K = cov @ H.T @ np.linalg.inv(S)
-    nu = z - mu[:, sel]
-    mu_k, cov_k, ok = on.apply_delta(on.POSE, mu, cov - K @ S @ np.swapaxes(K, 1, 2), np.einsum("bij,bj->bi", K, nu))
-    assert ok.all() and np.abs(mu_k - on.POSE.boxplus(mu, np.einsum("bij,bj->bi", K, nu))).max() <= 1e-14
-    d2 = np.einsum("bi,bij,bj->b", nu, np.linalg.inv(S), nu)
-    ll = -0.5 * (d2 + np.linalg.slogdet(S)[1] + 6 * sm.LN_2PI)
-    err = {"mu": np.abs(got["mu"] - mu_k).max(), "cov": np.abs(got["cov"] - cov_k).max(), "S": np.abs(got["S"] - S).max(),
-           "z_pred": np.abs(got["z_pred"] - mu[:, sel]).max(), "innov": np.abs(got["innov"] - nu).max(),
-           "maha": (np.abs(got["maha"] - d2) / (1.0 + d2)).max(), "loglik": (np.abs(got["loglik"] - ll) / (1.0 + np.abs(ll))).max()}
-    print("linear h against the Kalman update: " + " ".join(f"{k}={v:.3e}" for k, v in err.items()))
-    assert all(v <= 1e-10 for v in err.values()), err
-    assert np.abs(got["mu"] - mu).max() > 1e-4
 
 
 # ------------------------------------------------------------------------------------------------------- the user family
