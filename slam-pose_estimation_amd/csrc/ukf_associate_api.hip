@@ -1,7 +1,7 @@
 // ukf_associate_api.hip -- C-ABI of the sensor-frame association (include/ukf_batch.h, "sensor-frame association"): argument
 // checks (ukf_host.hpp), the device form and the host-array form.
 #include "ukf_api_common.hpp"
-#include "ukf_associate_req.hpp"
+#include "ukf_feature_req.hpp"
 
 extern "C" {
 
@@ -14,7 +14,7 @@ int ukfb_associate_sensor_dev(ukfb_engine* e, int model_uniform, const ukfb_asso
     r.in = *in;
     r.commit = commit != 0;
     if (out) r.out = *out;
-    return e->model == UKFB_MODEL_POSE ? ukfb::launch_associate_pose(e, r) : ukfb::launch_associate_orient(e, r);
+    return ukfb::launch_for_model(e, r);
 }
 
 int ukfb_associate_sensor(ukfb_engine* e, int model, const int32_t* model_per_filter, int candidates, const double* z, const double* Q,

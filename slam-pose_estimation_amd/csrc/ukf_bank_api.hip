@@ -1,7 +1,7 @@
 // ukf_bank_api.hip -- C-ABI of the filter banks (include/ukf_batch.h, "filter banks"): argument checks (ukf_host.hpp), the
 // launch requests, and the host-array forms.
 #include "ukf_api_common.hpp"
-#include "ukf_bank_req.hpp"
+#include "ukf_feature_req.hpp"
 
 namespace {
 
@@ -9,10 +9,6 @@ int entry(ukfb_engine* e, int hypotheses) {
     if (!e) return UKFB_ERR_INVALID_ARG;
     if (const int rc = ukfb::fail(ukfb::check_bank_args(hypotheses, e->cap))) return rc;
     return ukfb::refuse_poisoned(e);
-}
-
-int launch(ukfb_engine* e, const ukfb::BankReq& r) {
-    return e->model == UKFB_MODEL_POSE ? ukfb::launch_bank_pose(e, r) : ukfb::launch_bank_orient(e, r);
 }
 
 }  // namespace
@@ -45,7 +41,7 @@ int ukfb_bank_combine_dev(ukfb_engine* e, int hypotheses, const void* w_dev, voi
     r.mu_out_dev = mu_out_dev;
     r.cov_out_dev = cov_packed_out_dev;
     r.status_dev = status_dev;
-    return launch(e, r);
+    return ukfb::launch_for_model(e, r);
 }
 
 int ukfb_bank_mix_dev(ukfb_engine* e, int hypotheses, const void* w_dev, const double* transition, void* w_pred_out_dev,
@@ -61,7 +57,7 @@ int ukfb_bank_mix_dev(ukfb_engine* e, int hypotheses, const void* w_dev, const d
     r.w_pred_dev = w_pred_out_dev;
     r.transition = transition;   // copied into the kernel arguments: nothing of the caller's is read after the call returns
     r.status_dev = status_dev;
-    return launch(e, r);
+    return ukfb::launch_for_model(e, r);
 }
 
 int ukfb_bank_combine(ukfb_engine* e, int hypotheses, const double* w, double* mu, double* cov, uint32_t* status) {

@@ -1,55 +1,18 @@
-// ukf_bearing_api.hip -- C-ABI of the bearing measurements (include/ukf_batch.h, "bearing measurements"):
-// argument checks (ukf_host.hpp), the device form and the host-array form.
-#include "ukf_api_common.hpp"
-#include "ukf_bearing_req.hpp"
+// ukf_bearing_api.hip -- C-ABI of the bearing measurements (include/ukf_batch.h, "bearing measurements"): the device form and
+// the host-array form, over the body they share with the sensor-frame measurements.
+#include "ukf_sensor_frame_api.hpp"
 
 extern "C" {
 
 int ukfb_update_bearing_dev(ukfb_engine* e, int model_uniform, const ukfb_sensor_in* in, int commit, const ukfb_sensor_out* out) {
-    if (const int rc = ukfb::entry(e)) return rc;
-    if (const int rc = ukfb::fail(ukfb::check_bearing_args(e->model, in && in->model_dev, model_uniform, in, commit, out))) return rc;
-    ON_DEVICE(e->device);
-    ukfb::BearingReq r;
-    r.model_uniform = model_uniform;
-    r.in = *in;
-    r.commit = commit != 0;
-    if (out) r.out = *out;
-    return e->model == UKFB_MODEL_POSE ? ukfb::launch_bearing_pose(e, r) : ukfb::launch_bearing_orient(e, r);
+    return ukfb::update_sensor_frame_dev<ukfb::BearingReq>(e, ukfb::check_bearing_args, model_uniform, in, commit, out);
 }
 
-// (ukfb_update_sensor is this function with check_sensor_args and ukfb_update_sensor_dev)
 int ukfb_update_bearing(ukfb_engine* e, int model, const int32_t* model_per_filter, const double* z, const double* Q, const double* mount,
                         const double* mount_uniform, const double* point, const double* point_uniform, int commit, double* z_pred,
                         double* S, double* innov, double* maha, double* loglik, uint32_t* status) {
-    if (const int rc = ukfb::entry(e)) return rc;
-    // (what the device call will see: a buffer for each input given and each output wanted)
-    ukfb_sensor_in in{};
-    in.model_dev = model_per_filter;
-    in.z_dev = z;
-    in.Q_dev = Q;
-    in.mount_dev = mount;
-    in.point_dev = point;
-    ukfb::set_mount_point_uniform(&in, mount_uniform, point_uniform);
-    const ukfb_sensor_out wanted{z_pred, S, innov, maha, loglik, status};
-    if (const int rc = ukfb::fail(ukfb::check_bearing_args(e->model, model_per_filter != nullptr, model, &in, commit, &wanted))) return rc;
-    ON_DEVICE(e->device);
-    const size_t n = size_t(e->cap);
-    ukfb::HostStage stage(e);
-    in.model_dev = stage.raw_in(model_per_filter, n);
-    in.z_dev = stage.in(z, n * 3);
-    in.Q_dev = stage.in(Q, n * 9);
-    in.mount_dev = stage.in(mount, n * 7);
-    in.point_dev = stage.in(point, n * 3);
-    ukfb_sensor_out out{};
-    out.z_pred = stage.out(z_pred, n * 3);
-    out.S = stage.out(S, n * 9);
-    out.innov = stage.out(innov, n * 3);
-    out.maha = stage.out(maha, n);
-    out.loglik = stage.out(loglik, n);
-    out.status = stage.raw_out(status, n);
-    if (const int rc = stage.rc()) return rc;
-    if (const int rc = ukfb_update_bearing_dev(e, model, &in, commit, &out)) return rc;
-    return stage.finish();
+    return ukfb::update_sensor_frame(e, ukfb::check_bearing_args, ukfb_update_bearing_dev, model, model_per_filter, z, Q, mount,
+                                     mount_uniform, point, point_uniform, commit, z_pred, S, innov, maha, loglik, status);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // ukf_condition_api.hip -- C-ABI of the covariance conditioning (include/ukf_batch.h, "covariance conditioning"): argument checks
 // (ukf_host.hpp), the device form and the host-array form.
 #include "ukf_api_common.hpp"
-#include "ukf_condition_req.hpp"
+#include "ukf_feature_req.hpp"
 
 extern "C" {
 
@@ -13,7 +13,7 @@ int ukfb_condition_dev(ukfb_engine* e, const ukfb_condition_in* in, int commit, 
     r.in = *in;
     r.commit = commit != 0;
     if (out) r.out = *out;
-    return e->model == UKFB_MODEL_POSE ? ukfb::launch_condition_pose(e, r) : ukfb::launch_condition_orient(e, r);
+    return ukfb::launch_for_model(e, r);
 }
 
 int ukfb_condition(ukfb_engine* e, const double* var_floor, double eig_floor, const uint8_t* select, int renormalize_quaternion,

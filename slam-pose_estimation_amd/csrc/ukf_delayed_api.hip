@@ -1,7 +1,7 @@
 // ukf_delayed_api.hip -- C-ABI of the delayed-measurement update (include/ukf_batch.h, "late samples"): argument checks
 // (ukf_host.hpp), the device form, the lag helper and the host-array form.
 #include "ukf_api_common.hpp"
-#include "ukf_delayed_req.hpp"
+#include "ukf_feature_req.hpp"
 
 namespace ukfb {
 
@@ -31,7 +31,7 @@ int ukfb_update_delayed_dev(ukfb_engine* e, const ukfb_delayed_in* in, int commi
     r.in = *in;   // (in->dt is copied into the kernel arguments: nothing of the caller's is read after the call returns)
     r.commit = commit != 0;
     if (out) r.out = *out;
-    return e->model == UKFB_MODEL_POSE ? ukfb::launch_delayed_pose(e, r) : ukfb::launch_delayed_orient(e, r);
+    return ukfb::launch_for_model(e, r);
 }
 
 int ukfb_delayed_lag_dev(ukfb_engine* e, int steps, const int64_t* step_ts_us, const int64_t* sample_ts_us_dev, int32_t* lag_out_dev) {

@@ -1,7 +1,7 @@
 // ukf_forecast_api.hip -- C-ABI of the forecast (include/ukf_batch.h, "forecast"): argument checks (ukf_host.hpp), the one
 // launch of a call, and the host-array form.
 #include "ukf_api_common.hpp"
-#include "ukf_forecast_req.hpp"
+#include "ukf_feature_req.hpp"
 
 extern "C" {
 
@@ -26,7 +26,7 @@ int ukfb_forecast_dev(ukfb_engine* e, int steps, const double* dt, const int64_t
     r.mu_out_dev = mu_out_dev;
     r.cov_out_dev = cov_out_dev;
     r.status_dev = status_dev;
-    return e->model == UKFB_MODEL_POSE ? ukfb::launch_forecast_pose(e, r) : ukfb::launch_forecast_orient(e, r);
+    return ukfb::launch_for_model(e, r);
 }
 
 int ukfb_forecast(ukfb_engine* e, int steps, const double* dt, const int64_t* ts_us, const double* start_mu,

@@ -2,7 +2,7 @@
 // measurement association"): argument checks (ukf_host.hpp), the launch requests, and the host-array form.
 #include "ukf_api_common.hpp"
 #include "ukf_innovation.hpp"
-#include "ukf_innovation_req.hpp"
+#include "ukf_feature_req.hpp"
 
 extern "C" {
 
@@ -22,7 +22,7 @@ int ukfb_innovation_dev(ukfb_engine* e, int meas_model_uniform, const int32_t* m
     r.Q_dev = Q_dev;
     r.q_uniform = q_is_uniform != 0;
     r.out = *out;
-    return e->model == UKFB_MODEL_POSE ? ukfb::launch_innovation_pose(e, r) : ukfb::launch_innovation_orient(e, r);
+    return ukfb::launch_for_model(e, r);
 }
 
 int ukfb_select_candidates_dev(ukfb_engine* e, int candidates, const int32_t* best_dev, int meas_model_uniform,

@@ -1,7 +1,7 @@
 // ukf_predict_sampled_api.hip -- C-ABI of the user-defined process models (include/ukf_batch.h, "user-defined process models"):
 // argument checks (ukf_host.hpp), the device form and the host-array form.
 #include "ukf_api_common.hpp"
-#include "ukf_predict_sampled_req.hpp"
+#include "ukf_feature_req.hpp"
 
 extern "C" {
 
@@ -13,7 +13,7 @@ int ukfb_predict_sampled_dev(ukfb_engine* e, const ukfb_predict_sampled_in* in, 
     r.in = *in;
     r.commit = commit != 0;
     if (out) r.out = *out;
-    return e->model == UKFB_MODEL_POSE ? ukfb::launch_predict_sampled_pose(e, r) : ukfb::launch_predict_sampled_orient(e, r);
+    return ukfb::launch_for_model(e, r);
 }
 
 int ukfb_predict_sampled(ukfb_engine* e, const double* XX, const double* R, int r_is_uniform, const uint8_t* active, int commit,

@@ -1,7 +1,7 @@
 // ukf_relative_api.hip -- C-ABI of the relative-measurement update (include/ukf_batch_relative.h): argument
 // checks (ukf_host.hpp), the device form and the host-array form.
 #include "ukf_api_common.hpp"
-#include "ukf_relative_req.hpp"
+#include "ukf_feature_req.hpp"
 
 extern "C" {
 
@@ -13,7 +13,7 @@ int ukfb_update_relative_dev(ukfb_engine* e, const ukfb_relative_in* in, int com
     r.in = *in;   // (in->dt is copied into the kernel arguments: nothing of the caller's is read after the call returns)
     r.commit = commit != 0;
     if (out) r.out = *out;
-    return ukfb::launch_relative_pose(e, r);
+    return ukfb::launch_for_model(e, r);
 }
 
 int ukfb_update_relative(ukfb_engine* e, int steps, const double* dt, const double* mu_hist, const double* cov_hist, const double* in_a,

@@ -1,7 +1,7 @@
 // ukf_sampled_api.hip -- C-ABI of the user-defined measurement models (include/ukf_batch.h, "user-defined measurement models"):
 // argument checks (ukf_host.hpp), the device forms and the host-array forms.
 #include "ukf_api_common.hpp"
-#include "ukf_sampled_req.hpp"
+#include "ukf_feature_req.hpp"
 
 extern "C" {
 
@@ -13,7 +13,7 @@ int ukfb_sigma_points_dev(ukfb_engine* e, void* X_out_dev, void* delta_out_dev, 
     r.X = X_out_dev;
     r.delta = delta_out_dev;
     r.status = status_dev;
-    return e->model == UKFB_MODEL_POSE ? ukfb::launch_sigma_points_pose(e, r) : ukfb::launch_sigma_points_orient(e, r);
+    return ukfb::launch_for_model(e, r);
 }
 
 int ukfb_update_sampled_dev(ukfb_engine* e, const ukfb_sampled_in* in, int commit, const ukfb_sampled_out* out) {
@@ -24,7 +24,7 @@ int ukfb_update_sampled_dev(ukfb_engine* e, const ukfb_sampled_in* in, int commi
     r.in = *in;
     r.commit = commit != 0;
     if (out) r.out = *out;
-    return e->model == UKFB_MODEL_POSE ? ukfb::launch_sampled_pose(e, r) : ukfb::launch_sampled_orient(e, r);
+    return ukfb::launch_for_model(e, r);
 }
 
 int ukfb_sigma_points(ukfb_engine* e, double* X, double* delta, uint32_t* status) {

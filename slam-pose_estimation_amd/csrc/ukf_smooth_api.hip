@@ -1,7 +1,7 @@
 // ukf_smooth_api.hip -- C-ABI of the fixed-interval smoother (include/ukf_batch.h, "fixed-interval smoothing"): argument
 // checks and the chunking of a window into launches (ukf_host.hpp), the history push, and the host-array form.
 #include "ukf_api_common.hpp"
-#include "ukf_smooth_req.hpp"
+#include "ukf_feature_req.hpp"
 
 namespace {
 
@@ -60,7 +60,7 @@ int ukfb_smooth_dev(ukfb_engine* e, int steps, const double* dt, int slots, int 
         r.start_cov_dev = cov_out_dev ? static_cast<const void*>(static_cast<char*>(cov_out_dev) + size_t(r.part.top_slot) * cov_rec)
                                       : static_cast<const void*>(e->smooth_chain);
         r.end_cov_dev = (!cov_out_dev && k + 1 < plan.launches()) ? e->smooth_chain : nullptr;
-        const int rc = e->model == UKFB_MODEL_POSE ? ukfb::launch_smooth_pose(e, r) : ukfb::launch_smooth_orient(e, r);
+        const int rc = ukfb::launch_for_model(e, r);
         if (rc != UKFB_OK) return rc;
     }
     return UKFB_OK;

@@ -3,7 +3,7 @@
 #include <vector>
 
 #include "ukf_api_common.hpp"
-#include "ukf_state_meas_req.hpp"
+#include "ukf_feature_req.hpp"
 
 extern "C" {
 
@@ -24,7 +24,7 @@ int ukfb_update_state_dev(ukfb_engine* e, uint32_t block_mask_uniform, const int
     r.meas_inflation = meas_inflation;
     r.commit = commit != 0;
     if (out) r.out = *out;
-    return e->model == UKFB_MODEL_POSE ? ukfb::launch_state_meas_pose(e, r) : ukfb::launch_state_meas_orient(e, r);
+    return ukfb::launch_for_model(e, r);
 }
 
 int ukfb_update_state(ukfb_engine* e, uint32_t block_mask, const int32_t* block_mask_per_filter, const double* z, const double* Qz,

@@ -23,14 +23,15 @@ def assert_clean_run(out):
         assert marker not in out.stderr + out.stdout, out.stderr
 
 
-def build_sanitized(source_name, tmp_path):
-    """Compile tests/cpp/<source_name> (or an absolute path) with g++ under ASan / UBSan into tmp_path; the program's path."""
+def build_sanitized(source_name, tmp_path, extra_flags=()):
+    """Compile tests/cpp/<source_name> (or an absolute path) with g++ under ASan / UBSan into tmp_path; the program's path.
+    extra_flags: further compiler arguments, for a program that needs more than the project's own headers."""
     gxx = shutil.which("g++")
     assert gxx, "g++ is needed for the host-side checks"
     exe = tmp_path / (os.path.splitext(os.path.basename(source_name))[0] + "_asan")
     subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-static-libasan", "-static-libubsan", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(CPP, source_name), "-o", str(exe)], check=True, timeout=300)
+                    *extra_flags, os.path.join(CPP, source_name), "-o", str(exe)], check=True, timeout=300)
     return exe
 
 
@@ -38,8 +39,8 @@ def run_built(exe, args=()):
     return subprocess.run([str(exe), *map(str, args)], capture_output=True, text=True, timeout=120)
 
 
-def run_sanitized(source_name, tmp_path, args=()):
+def run_sanitized(source_name, tmp_path, args=(), extra_flags=()):
     """Build tests/cpp/<source_name> under the sanitizers, run it with `args` and hold the run to assert_clean_run."""
-    out = run_built(build_sanitized(source_name, tmp_path), args)
+    out = run_built(build_sanitized(source_name, tmp_path, extra_flags), args)
     assert_clean_run(out)
     return out
