@@ -7,6 +7,7 @@
 
 #include <ukf_batch.h>
 #include <ukf_batch_relative.h>
+#include <ukf_batch_robust.h>
 
 #include <stdexcept>
 #include <string>
@@ -198,6 +199,29 @@ public:
         std::vector<uint32_t> st(static_cast<size_t>(cap));
         check(ukfb_update_sensor(engine, model, model_per_filter, z, Q, mount, mount_uniform, point, point_uniform, commit ? 1 : 0,
                                  z_pred, S, innov, maha, loglik, st.data()));
+        return st;
+    }
+    /** The robust form of the sensor-frame measurements (ukf_batch_robust.h): a sample whose raw Mahalanobis distance exceeds
+     *  the rule's threshold is not rejected but updates with lambda Q, lambda >= 1 by the rule's mode; the filters' own gate
+     *  acts on the raw distance.  Device form: the arrays of ukfb_sensor_in; commit = false is read-only.  Stream-ordered. */
+    void integrateRobustSensorMeasurementDev(int model_uniform, const ukfb_sensor_in& in, const ukfb_robust_rule& rule, bool commit = true,
+                                             const ukfb_robust_out* out = NULL)
+    {
+        check(ukfb_update_robust_dev(engine, model_uniform, &in, &rule, commit ? 1 : 0, out));
+    }
+    /** host arrays, shaped as for integrateSensorMeasurement; maha0 [N] the raw distance, maha [N] the distance under
+     *  lambda Q, scale [N] = lambda, iterations [N] the Newton steps taken, or NULL; returns the status */
+    std::vector<uint32_t> integrateRobustSensorMeasurement(int model, const double* z, const double* Q, const ukfb_robust_rule& rule,
+                                                           const double* mount_uniform = NULL, const double* point_uniform = NULL,
+                                                           const double* mount = NULL, const double* point = NULL,
+                                                           const int32_t* model_per_filter = NULL, bool commit = true,
+                                                           double* z_pred = NULL, double* S = NULL, double* innov = NULL,
+                                                           double* maha0 = NULL, double* maha = NULL, double* loglik = NULL,
+                                                           double* scale = NULL, int32_t* iterations = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_update_robust(engine, model, model_per_filter, z, Q, mount, mount_uniform, point, point_uniform, &rule, commit ? 1 : 0,
+                                 z_pred, S, innov, maha0, maha, loglik, scale, iterations, st.data()));
         return st;
     }
     /** Bearing measurements (ukf_batch.h, "bearing measurements"): ukf->update(z, h, Q) with a direction on the sphere S^2 --

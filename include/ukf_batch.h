@@ -882,6 +882,7 @@ int ukfb_update_sensor(ukfb_engine* e, int model, const int32_t* model_per_filte
                        const double* mount /* or NULL */, const double* mount_uniform /* or NULL */,
                        const double* point /* or NULL */, const double* point_uniform /* or NULL */, int commit,
                        double* z_pred, double* S, double* innov, double* maha, double* loglik, uint32_t* status);
+/* ---- the robust form (an outlier is down-weighted by an inflated Q, not rejected): ukf_batch_robust.h, a header of its own. */
 
 /* ---- bearing measurements: directions on the sphere S^2 ------------------------------------------------------------------ */
 /* ukf->update(z, h, Q) for sensors that measure a DIRECTION: a camera pixel of a known landmark, a USBL or sonar bearing, a

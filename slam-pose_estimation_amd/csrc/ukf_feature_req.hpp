@@ -131,4 +131,12 @@ struct RelativeReq {
 };
 template <> inline constexpr bool pose_only<RelativeReq> = true;
 
+struct RobustReq {
+    int model_uniform = -1;
+    ukfb_sensor_in in{};      // device pointers and the by-value mount / point
+    ukfb_robust_rule rule{};  // HOST values, already checked
+    bool commit = false;
+    ukfb_robust_out out{};    // any may be null
+};
+
 }  // namespace ukfb

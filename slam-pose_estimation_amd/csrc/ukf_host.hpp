@@ -1,6 +1,6 @@
 // ukf_host.hpp -- the engine's host decisions as pure functions of plain values: configuration checks, process-noise
 // classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, packed covariances, workspace sizing, the filter lifecycle's checks and geometry, the delayed-measurement
-// update's checks, geometry and lag rule, the relative-measurement update's checks, models and map, and the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
+// update's checks, geometry and lag rule, the relative-measurement update's checks, models and map, the robust update's rule, and the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
 #pragma once
 
 #include <stddef.h>
@@ -15,6 +15,7 @@
 
 #include "../../include/ukf_batch.h"
 #include "../../include/ukf_batch_relative.h"
+#include "../../include/ukf_batch_robust.h"
 
 #if defined(__HIP__)
 #define UKFB_HD __host__ __device__ __forceinline__
@@ -820,6 +821,32 @@ constexpr RelativeMap relative_map(int S, int D) {
 }
 constexpr int relative_filter_scalars(int S, int D) { return S > 16 ? -1 : relative_map(S, D).PF; }
 inline RowGeometry relative_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(relative_filter_scalars(S, D), capacity, compute_size); }
+
+// ---- the robust sensor-frame update (ukfb_update_robust_dev) ----------------------------------------------------------------
+// The sensor-frame update's arguments and the rule (include/ukf_batch_robust.h).  The rule is judged first: it is the part of
+// the call that no other entry point checks.  Models, inputs, LDS map and geometry are the sensor-frame measurements'.
+constexpr int ROBUST_MAX_ITER = 64;
+inline Verdict check_robust_rule(const ukfb_robust_rule* rule) {
+    if (!rule) return {UKFB_ERR_INVALID_ARG, "rule must not be NULL"};
+    if (rule->mode != UKFB_ROBUST_MATCH && rule->mode != UKFB_ROBUST_HUBER)
+        return {UKFB_ERR_INVALID_ARG, "rule.mode must be UKFB_ROBUST_MATCH or UKFB_ROBUST_HUBER"};
+    if (!std::isfinite(rule->chi2_m1) || !(rule->chi2_m1 > 0.0) || !std::isfinite(rule->chi2_m3) || !(rule->chi2_m3 > 0.0))
+        return {UKFB_ERR_INVALID_ARG, "rule.chi2_m1 and rule.chi2_m3 must be finite and > 0"};
+    if (!std::isfinite(rule->scale_max) || !(rule->scale_max >= 1.0)) return {UKFB_ERR_INVALID_ARG, "rule.scale_max must be finite and >= 1"};
+    if (!std::isfinite(rule->tol) || !(rule->tol >= 0.0)) return {UKFB_ERR_INVALID_ARG, "rule.tol must be finite and >= 0"};
+    if (rule->max_iter < 1 || rule->max_iter > ROBUST_MAX_ITER) return {UKFB_ERR_INVALID_ARG, "rule.max_iter must be 1 ... 64"};
+    return {};
+}
+inline bool robust_has_output(const ukfb_robust_out* out) {
+    return out && (out->z_pred || out->S || out->innov || out->maha0 || out->maha || out->loglik || out->scale || out->iterations || out->status);
+}
+inline Verdict check_robust_args(int engine_model, bool per_filter_models, int model_uniform, const ukfb_sensor_in* in,
+                                 const ukfb_robust_rule* rule, int commit, const ukfb_robust_out* out) {
+    if (const Verdict v = check_robust_rule(rule); v.rc != UKFB_OK) return v;
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    return check_sensor_call(sensor_call(in), commit, per_filter_models || sensor_model_ok(engine_model, model_uniform),
+                             "sensor model id not valid for this engine (Pose: 0 ... 4, OrientationState: 5 ... 7)", robust_has_output(out));
+}
 
 // ---- bounded waits ----------------------------------------------------------------------------------------------------------
 // Waiting by polling: hipEventSynchronize / hipStreamSynchronize sleep on an interrupt and were measured to

@@ -18,6 +18,8 @@ from . import abi
 from .abi import *  # noqa: F401,F403  (the constants, the structures, SIGNATURES and EXPORTS stay reachable as engine.X)
 from . import abi_relative
 from .abi_relative import RELATIVE_NONE, RELATIVE_POSE, RELATIVE_POSITION, RELATIVE_ROTATION, RelativeIn, RelativeOut  # noqa: F401
+from . import abi_robust
+from .abi_robust import ROBUST_HUBER, ROBUST_MATCH, RobustOut, RobustRule  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UKFB_LIB", os.path.join(_HERE, "lib", "libukf_batch.so"))  # UKFB_LIB: debug builds only
@@ -40,6 +42,7 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
         abi.declare(lib)
         abi_relative.declare(lib)   # (include/ukf_batch_relative.h)
+        abi_robust.declare(lib)     # (include/ukf_batch_robust.h)
         _lib = lib
     return _lib
 
@@ -627,6 +630,35 @@ class BatchUKF:
         [capacity, 7], point [3] or [capacity, 3].  Returns a dict of NumPy arrays: z_pred [n, 3], S [n, 3, 3], innov [n, 3],
         maha [n], loglik [n], status [n]; synchronises"""
         return self._update_sensor_frame("ukfb_update_sensor", model, z, Q, mount, point, commit)
+
+    # ---- the robust sensor-frame update: update_sensor's arguments and a rule (include/ukf_batch_robust.h)
+    def update_robust_dev(self, model: int, z_dev, Q_dev, rule: RobustRule, q_is_uniform: bool = False, model_dev=None,
+                          mount_dev=None, mount=SENSOR_MOUNT_IDENTITY, point_dev=None, point=(0.0, 0.0, 0.0), commit: bool = True,
+                          z_pred=None, S=None, innov=None, maha0=None, maha=None, loglik=None, scale=None, iterations=None,
+                          status=None):
+        """update_sensor_dev with an outlying sample down-weighted, not rejected: a filter whose raw distance maha0 exceeds the
+        rule's threshold (chi2_m1 / chi2_m3 by the model's m) updates with scale * Q, scale from the rule's mode (ROBUST_MATCH:
+        d^2(scale) = c^2 by Newton, ROBUST_HUBER: sqrt(maha0 / c^2)), clamped to [1, scale_max]; the engine's gate acts on
+        maha0.  Keyword outputs as for update_sensor_dev, and maha0, scale (engine precision), iterations (int32).
+        Stream-ordered."""
+        sin = _sensor_in(SensorIn, model_dev, z_dev, Q_dev, q_is_uniform, mount_dev, mount, point_dev, point)
+        out = RobustOut(*[_dev(x) for x in (z_pred, S, innov, maha0, maha, loglik, scale, iterations, status)])
+        self._call("ukfb_update_robust_dev", int(model), C.byref(sin), C.byref(rule), commit, C.byref(out))
+
+    def update_robust(self, model, z, Q, rule: RobustRule, mount=SENSOR_MOUNT_IDENTITY, point=(0.0, 0.0, 0.0), commit: bool = True):
+        """Host arrays, shaped as for update_sensor.  Returns its dict of NumPy arrays with maha0 [n], scale [n] and iterations
+        [n] (int32) added; synchronises"""
+        n = self.capacity
+        z = _f64(z, (n, 3)); Q = _f64(Q, (n, 3, 3))
+        uniform, per = _int_or_i32(model, n)
+        mp, mu_ = _per_or_uniform(mount, n, 7)
+        pp, pu = _per_or_uniform(point, n, 3)
+        o = {"z_pred": np.empty((n, 3)), "S": np.empty((n, 3, 3)), "innov": np.empty((n, 3)), "maha0": np.empty(n), "maha": np.empty(n),
+             "loglik": np.empty(n), "scale": np.empty(n), "iterations": np.empty(n, dtype=np.int32), "status": np.empty(n, dtype=np.uint32)}
+        self._call("ukfb_update_robust", uniform, _pi32(per), _pd(z), _pd(Q), _pd(mp), _pd(mu_), _pd(pp), _pd(pu), C.byref(rule), commit,
+                   _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha0"]), _pd(o["maha"]), _pd(o["loglik"]), _pd(o["scale"]),
+                   _pi32(o["iterations"]), _pu32(o["status"]))
+        return o
 
     # ---- bearing measurements: z [capacity, 3] a direction, Q [capacity, 9] (or 9 scalars), mount [capacity, 7], point [capacity, 3]
     def update_bearing_dev(self, model: int, z_dev, Q_dev, q_is_uniform: bool = False, model_dev=None, mount_dev=None,
