@@ -225,7 +225,8 @@ inline RowGeometry row_geometry(int filter_scalars, int64_t capacity, size_t com
 }
 // A filter's slice is described once: a *_map(S, D) below lists its regions in their order, as offsets in scalars of the compute
 // type.  The kernel reads the map as a constexpr object, the host sizes the launch from its PF (*_filter_scalars: -1 where a
-// filter does not fit a row).  Every scalar a kernel reads is one it wrote: the pads are never read.
+// filter does not fit a row).  Every scalar a kernel reads is one it wrote: the pads are never read
+// (tests/test_gpu_feature_lds_leftovers.py holds that, family by family, against NaN, Inf and zero leftovers).
 constexpr bool row_fits(int S, int D) { return ROW_LS >= D && S <= 16 && D + 1 <= 16; }   // a filter fits one row: every kernel asserts it
 struct RowSlice {   // bump counter over a slice
     int used = 0;
@@ -279,7 +280,8 @@ inline Verdict check_bank_transition(const double* P, int hypotheses) {
     return {};
 }
 // LDS of one track, in scalars of the compute type: the M records (mean, packed covariance), the M deltas to the mixture's
-// mean with their weights, and one output record.  Every scalar a kernel reads is one it wrote.
+// mean with their weights, and one output record.  Every scalar a kernel reads is one it wrote
+// (tests/test_gpu_feature_lds_leftovers.py::test_bank).
 UKFB_HD int bank_track_scalars(int S, int D, int hypotheses) {
     const int PK = D * (D + 1) / 2;
     return (hypotheses * (S + PK + D + 1) + S + PK + 1) / 2 * 2;

@@ -13,6 +13,41 @@ __global__ void lds_fill_kernel(uint32_t pattern, int dwords, uint32_t* sink) {
     if (threadIdx.x == 0 && lds[(blockIdx.x * 131) % dwords] != pattern) sink[0] = 1u;
 }
 
+// The canary of the instrument: the fill's geometry, no LDS store, every dword of the workgroup's own allocation read and
+// compared with the pattern.  The volatile reads cannot be folded into "uninitialised, any value will do".
+__global__ void lds_seen_kernel(uint32_t pattern, int dwords, unsigned long long* counts) {
+    extern __shared__ uint32_t lds[];
+    const volatile uint32_t* p = lds;
+    unsigned long long matched = 0, read = 0;
+    for (int i = threadIdx.x; i < dwords; i += blockDim.x) {
+        matched += p[i] == pattern ? 1u : 0u;
+        read += 1u;
+    }
+    atomicAdd(&counts[0], matched);
+    atomicAdd(&counts[1], read);
+}
+
+// matched = the dwords that still held `pattern`, read = the dwords looked at (grid x 160 KiB / 4); returns 0
+extern "C" int lds_leftovers_seen(uint32_t pattern, uint64_t* matched, uint64_t* read) {
+    const int bytes = 160 * 1024;
+    if (matched == nullptr || read == nullptr) return 4;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(lds_seen_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
+        return 1;
+    unsigned long long* counts = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&counts), 16) != hipSuccess) return 2;
+    unsigned long long host[2] = {0, 0};
+    hipError_t err = hipMemset(counts, 0, 16);
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(lds_seen_kernel, dim3(256 * 4), dim3(256), bytes, 0, pattern, bytes / 4, counts);
+        err = hipDeviceSynchronize();
+    }
+    if (err == hipSuccess) err = hipMemcpy(host, counts, 16, hipMemcpyDeviceToHost);
+    (void)hipFree(counts);
+    *matched = host[0];
+    *read = host[1];
+    return err == hipSuccess ? 0 : 3;
+}
+
 extern "C" int lds_poison(uint32_t pattern) {
     const int bytes = 160 * 1024;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(lds_fill_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)

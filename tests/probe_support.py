@@ -30,7 +30,25 @@ def load(name, **signatures):
 
 def lds_poison():
     """lds_poison(pattern) of tests/cpp/lds_poison.hip: fills the LDS of every CU with a bit pattern; returns 0"""
-    return load("liblds_poison", lds_poison=(C.c_int, (C.c_uint32,))).lds_poison
+    return _lds_library().lds_poison
+
+
+def _lds_library():
+    return load("liblds_poison", lds_poison=(C.c_int, (C.c_uint32,)),
+                lds_leftovers_seen=(C.c_int, (C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))))
+
+
+def lds_leftovers_seen():
+    """seen(pattern) -> (matched, read) by lds_leftovers_seen of tests/cpp/lds_poison.hip: a kernel of the fill's geometry that
+    writes no LDS counts the dwords of its own allocation that still hold the pattern"""
+    fn = _lds_library().lds_leftovers_seen
+
+    def seen(pattern):
+        matched, read = C.c_uint64(0), C.c_uint64(0)
+        rc = fn(pattern, C.byref(matched), C.byref(read))
+        assert rc == 0, rc
+        return int(matched.value), int(read.value)
+    return seen
 
 
 def _m(x):
