@@ -8,6 +8,7 @@
 #include <ukf_batch.h>
 #include <ukf_batch_relative.h>
 #include <ukf_batch_robust.h>
+#include <ukf_batch_delayed_sensor.h>
 
 #include <stdexcept>
 #include <string>
@@ -387,6 +388,33 @@ public:
         std::vector<uint32_t> st(static_cast<size_t>(cap));
         check(ukfb_update_relative(engine, steps, dt, mu_hist, cov_hist, in_a, in_b, lag_uniform, lag, model, model_per_filter, z, Q,
                                    commit ? 1 : 0, NULL, NULL, NULL, maha, loglik, st.data(), mu_out, cov_out));
+        return st;
+    }
+    /** Late SENSOR-FRAME samples (ukf_batch_delayed_sensor.h): a lever-arm fix, range or landmark sighting (ukfb_sensor_model)
+     *  taken in.lag steps ago corrects the CURRENT state through the history ring -- updateDelayedDev with the h of
+     *  updateSensorDev, evaluated on the smoothed state of the sample's own step.  The window is updateDelayedDev's; model 5
+     *  reads in.rate_dev, else the rotation-rate ring at the sample's step, else the latch; commit = false is read-only.
+     *  Stream-ordered. */
+    void updateDelayedSensorDev(const ukfb_delayed_sensor_in& in, bool commit = true, const ukfb_delayed_out* out = NULL)
+    {
+        check(ukfb_update_delayed_sensor_dev(engine, &in, commit ? 1 : 0, out));
+    }
+    /** host arrays in window order, as updateDelayed: lag / model_per_filter [N] or NULL (lag_uniform / model, a
+     *  ukfb_sensor_model); z [N][3], Q [N][3][3]; mount [N][7] or NULL, then mount_uniform [7] (NULL: r = 0, qs the identity);
+     *  point [N][3] or NULL, then point_uniform [3] (NULL: 0); rate [N][3] or NULL; mu_out [N][S] / cov_out [N][D][D] or NULL:
+     *  the corrected present state.  Returns the status. */
+    std::vector<uint32_t> updateDelayedSensor(int steps, const double* dt, const double* mu_hist, const double* cov_hist, int lag_uniform,
+                                              int model, const double* z, const double* Q, const double* mount_uniform = NULL,
+                                              const double* point_uniform = NULL, bool commit = true, const int32_t* lag = NULL,
+                                              const int32_t* model_per_filter = NULL, const double* mount = NULL,
+                                              const double* point = NULL, const double* rate = NULL, const double* in_a = NULL,
+                                              const double* in_b = NULL, double* mu_out = NULL, double* cov_out = NULL,
+                                              double* maha = NULL, double* loglik = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_update_delayed_sensor(engine, steps, dt, mu_hist, cov_hist, in_a, in_b, lag_uniform, lag, model, model_per_filter, z, Q,
+                                         mount, mount_uniform, point, point_uniform, rate, commit ? 1 : 0, NULL, NULL, NULL, maha, loglik,
+                                         st.data(), mu_out, cov_out));
         return st;
     }
     /** host arrays in window order, smoothed in place: mu [steps][N][S], cov [steps][N][D][D]; returns the per-filter status */

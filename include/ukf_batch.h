@@ -505,7 +505,7 @@ int ukfb_smooth(ukfb_engine* e, int steps, const double* dt, double* mu, double*
  * the filter keeps every bit.
  * SAMPLE: the measurement models of ukfb_update_dev, ids 0 ... 9, uniform or per filter (meas_model_dev; a negative id or one
  * the engine's model does not have: INACTIVE); z_dev [capacity][3] (axis-angle for the SO(3) model, as ukfb_update_dev);
- * Q_dev [capacity][9] or one 3 x 3 with q_is_uniform.  State-block and sensor-frame models are not served.
+ * Q_dev [capacity][9] or one 3 x 3 with q_is_uniform.  State-block models are not served; sensor-frame models: ukf_batch_delayed_sensor.h.
  *
  * Per filter ((+) / (-): the engine's; J(phi): the identity with Jr^-1(phi) on the SO(3) block, the smoother's transport;
  * A(phi): the identity with Jr(phi) = I - (1 - cos t) / t^2 [phi]x + (t - sin t) / t^3 [phi]x^2 there):
@@ -586,6 +586,7 @@ int ukfb_delayed_lag_dev(ukfb_engine* e, int steps, const int64_t* step_ts_us, c
 
 /* ---- relative measurements (odometry and scan-match increments between a step of this ring and the present, on the same
  * window and lags): ukf_batch_relative.h, a header of its own beside this one. */
+/* ---- late SENSOR-FRAME samples (ids 0 ... 7 of enum ukfb_sensor_model through the same ring): ukf_batch_delayed_sensor.h. */
 
 /* ---- forecast: read-only multi-step prediction into a ring ------------------------------------------------------------------ */
 /* Where every filter will be after the next 1 ... steps predictions, with covariance, WITHOUT committing them (collision

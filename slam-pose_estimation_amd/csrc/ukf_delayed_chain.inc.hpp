@@ -1,6 +1,6 @@
 // ukf_delayed_chain.inc.hpp -- steps 1-2 of the delayed update, as statements: the backward chain from the engine's present state
 // down to each row's step, with the operator M carried along it.  Included INSIDE a kernel body (no include guard), by
-// ukf_delayed_kernel and by ukf_relative_kernel: one statement of the chain, and the delayed kernel compiles the token stream it
+// ukf_delayed_kernel, by ukf_relative_kernel and by ukf_delayed_sensor_kernel: one statement of the chain, and the delayed kernel compiles the token stream it
 // always had (as a shared function the same statements moved its register count).  The including body provides
 //   a             the DelayedArgs<T, TS>
 //   delayed_smem  the workgroup's dynamic LDS

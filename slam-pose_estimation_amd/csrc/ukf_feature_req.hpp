@@ -139,4 +139,10 @@ struct RobustReq {
     ukfb_robust_out out{};    // any may be null
 };
 
+struct DelayedSensorReq {
+    ukfb_delayed_sensor_in in{};   // in.dt: HOST [steps - 1], copied into the kernel arguments; the by-value mount / point
+    bool commit = false;
+    ukfb_delayed_out out{};        // all NULL when the caller passed none
+};
+
 }  // namespace ukfb

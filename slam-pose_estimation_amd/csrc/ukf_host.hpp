@@ -1,6 +1,7 @@
 // ukf_host.hpp -- the engine's host decisions as pure functions of plain values: configuration checks, process-noise
 // classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, packed covariances, workspace sizing, the filter lifecycle's checks and geometry, the delayed-measurement
-// update's checks, geometry and lag rule, the relative-measurement update's checks, models and map, the robust update's rule, and the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
+// update's checks, geometry and lag rule, the relative-measurement update's checks, models and map, the robust update's rule, the late
+// sensor-frame sample's checks, input record and map, and the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
 #pragma once
 
 #include <stddef.h>
@@ -16,6 +17,7 @@
 #include "../../include/ukf_batch.h"
 #include "../../include/ukf_batch_relative.h"
 #include "../../include/ukf_batch_robust.h"
+#include "../../include/ukf_batch_delayed_sensor.h"
 
 #if defined(__HIP__)
 #define UKFB_HD __host__ __device__ __forceinline__
@@ -823,6 +825,48 @@ constexpr RelativeMap relative_map(int S, int D) {
 }
 constexpr int relative_filter_scalars(int S, int D) { return S > 16 ? -1 : relative_map(S, D).PF; }
 inline RowGeometry relative_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(relative_filter_scalars(S, D), capacity, compute_size); }
+
+// ---- late sensor-frame samples (ukfb_update_delayed_sensor_dev) -----------------------------------------------------------------
+// The delayed update's window and lag with the sensor-frame measurements' models and inputs (include/ukf_batch_delayed_sensor.h).
+// The record of one filter's inputs as the kernel stages it: the sensor-frame record (SENSOR_INPUT_*), then the rotation rate at
+// the time of the sample (3), which ORIENT_VELOCITY alone reads; its neutral value is 0.
+constexpr int DELAYED_SENSOR_INPUT_RATE = SENSOR_INPUT_SCALARS, DELAYED_SENSOR_INPUT_SCALARS = DELAYED_SENSOR_INPUT_RATE + 3;
+constexpr int DELAYED_SENSOR_INPUT_REGION = 32;   // what the staging writes: lane l takes entries l and l + 16
+constexpr bool delayed_sensor_input_used(int64_t id, int i) {
+    return i < DELAYED_SENSOR_INPUT_RATE ? sensor_input_used(id, i) : (i < DELAYED_SENSOR_INPUT_SCALARS && id == UKFB_SENSOR_ORIENT_VELOCITY);
+}
+// the window and lag fields of a late sensor-frame sample as the delayed update's own structure (the model fields stay unset)
+inline ukfb_delayed_in delayed_window_of(const ukfb_delayed_sensor_in* in) {
+    ukfb_delayed_in d{};
+    d.steps = in->steps; d.dt = in->dt; d.slots = in->slots; d.first_slot = in->first_slot;
+    d.mu_hist_dev = in->mu_hist_dev; d.cov_hist_dev = in->cov_hist_dev; d.in_a_dev = in->in_a_dev; d.in_b_dev = in->in_b_dev;
+    d.lag_uniform = in->lag_uniform; d.lag_dev = in->lag_dev;
+    d.z_dev = in->z_dev; d.Q_dev = in->Q_dev; d.q_is_uniform = in->q_is_uniform;
+    return d;
+}
+// the clauses of check_delayed_args, then the clauses of check_sensor_call, in that order (a per-filter id is the kernel's to
+// judge: INACTIVE)
+inline Verdict check_delayed_sensor_args(int engine_model, const ukfb_delayed_sensor_in* in, int commit, const ukfb_delayed_out* out) {
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    const ukfb_delayed_in win = delayed_window_of(in);
+    if (const Verdict v = check_delayed_args(&win, commit, out); v.rc != UKFB_OK) return v;
+    return check_sensor_call({/*candidates*/ 1, in->z_dev != nullptr, in->Q_dev != nullptr, in->q_is_uniform, /*point_per_candidate*/ 0, /*has_point*/ true},
+                             commit, in->model_dev != nullptr || sensor_model_ok(engine_model, in->model_uniform),
+                             "sensor model id not valid for this engine (Pose: 0 ... 4, OrientationState: 5 ... 7)",
+                             out && (out->z_pred || out->S || out->innov || out->maha || out->loglik || out->status || out->mu_out || out->cov_out));
+}
+// The delayed update's slice, not one scalar wider: the staged input record lives in the parked rows of Sigma^-, which are dead
+// once the chain has ended (the record is written after the loop and read until the statistics are formed).
+struct DelayedSensorMap : DelayedMap {
+    int INP;
+};
+constexpr DelayedSensorMap delayed_sensor_map(int S, int D) {
+    DelayedSensorMap m{delayed_map(S, D), 0};
+    m.INP = m.SMR;   // DELAYED_SENSOR_INPUT_REGION <= D * LS
+    return m;
+}
+constexpr int delayed_sensor_filter_scalars(int S, int D) { return S > 16 ? -1 : delayed_sensor_map(S, D).PF; }
+inline RowGeometry delayed_sensor_geometry(int S, int D, int64_t capacity, size_t compute_size) { return row_geometry(delayed_sensor_filter_scalars(S, D), capacity, compute_size); }
 
 // ---- the robust sensor-frame update (ukfb_update_robust_dev) ----------------------------------------------------------------
 // The sensor-frame update's arguments and the rule (include/ukf_batch_robust.h).  The rule is judged first: it is the part of

@@ -20,6 +20,8 @@ from . import abi_relative
 from .abi_relative import RELATIVE_NONE, RELATIVE_POSE, RELATIVE_POSITION, RELATIVE_ROTATION, RelativeIn, RelativeOut  # noqa: F401
 from . import abi_robust
 from .abi_robust import ROBUST_HUBER, ROBUST_MATCH, RobustOut, RobustRule  # noqa: F401
+from . import abi_delayed_sensor
+from .abi_delayed_sensor import DelayedSensorIn  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UKFB_LIB", os.path.join(_HERE, "lib", "libukf_batch.so"))  # UKFB_LIB: debug builds only
@@ -43,6 +45,7 @@ def load_library():
         abi.declare(lib)
         abi_relative.declare(lib)   # (include/ukf_batch_relative.h)
         abi_robust.declare(lib)     # (include/ukf_batch_robust.h)
+        abi_delayed_sensor.declare(lib)   # (include/ukf_batch_delayed_sensor.h)
         _lib = lib
     return _lib
 
@@ -888,6 +891,53 @@ class BatchUKF:
         self._call("ukfb_update_relative", steps, _pd(d) if d.size else None, _pd(mu_hist), _pd(cov_hist), _pd(a), _pd(b), lag_u,
                    _pi32(lag_p), mod_u, _pi32(mod_p), _pd(z), _pd(Q), commit, _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]),
                    _pd(o["maha"]), _pd(o["loglik"]), _pu32(o["status"]), _pd(o["mu_out"]), _pd(o["cov_out"]))
+        return o
+
+    # ---- late sensor-frame samples: update_delayed's window with update_sensor's models and inputs
+    def update_delayed_sensor_dev(self, dt, slots: int, first_slot: int, mu_hist, cov_hist, lag, model, z_dev, Q_dev,
+                                  q_is_uniform: bool = False, mount_dev=None, mount=SENSOR_MOUNT_IDENTITY, point_dev=None,
+                                  point=(0.0, 0.0, 0.0), rate_dev=None, in_a_dev=None, in_b_dev=None, commit: bool = True,
+                                  z_pred=None, S=None, innov=None, maha=None, loglik=None, status=None, mu_out=None, cov_out=None):
+        """A sensor-frame sample (SENSOR_* constants: a lever-arm fix, range, landmark sighting ...) taken `lag` steps ago corrects
+        the current state through the history ring (include/ukf_batch_delayed_sensor.h): update_delayed_dev with the h of
+        update_sensor_dev, evaluated on the smoothed state of the sample's own step.  The window is update_delayed_dev's.  lag /
+        model: an int for the whole batch or an int32 device array [capacity].  z_dev [capacity, 3], Q_dev [capacity, 9] (9
+        scalars with q_is_uniform); mount = r[3] then qs[4] (x, y, z, w), point = b[3]: host values for the whole batch, or
+        device arrays per filter (mount_dev / point_dev).  rate_dev [capacity, 3]: the rotation rate at the time of the sample
+        (SENSOR_ORIENT_VELOCITY); None: the rotation-rate ring in_b_dev at the sample's step when it is given and lag >= 1, else
+        the engine's latch.  commit=False is read-only: only the keyword outputs (update_delayed_dev's) are written.
+        Stream-ordered, nothing is allocated."""
+        d = _f64(dt, -1)
+        per = lambda x: (0, _dev(x)) if hasattr(x, "data_ptr") else (int(x), None)
+        (lag_u, lag_p), (mod_u, mod_p) = per(lag), per(model)
+        din = DelayedSensorIn(d.size + 1, _pd(d) if d.size else None, int(slots), int(first_slot), _dev(mu_hist), _dev(cov_hist),
+                              _dev(in_a_dev), _dev(in_b_dev), lag_u, lag_p, mod_u, mod_p, _dev(z_dev), _dev(Q_dev), q_is_uniform,
+                              _dev(mount_dev), (C.c_double * 7)(*mount), _dev(point_dev), (C.c_double * 3)(*point), _dev(rate_dev))
+        out = DelayedOut(_dev(z_pred), _dev(S), _dev(innov), _dev(maha), _dev(loglik), _dev(status), _dev(mu_out), _dev(cov_out))
+        self._call("ukfb_update_delayed_sensor_dev", C.byref(din), commit, C.byref(out))
+
+    def update_delayed_sensor(self, dt, mu_hist, cov_hist, lag, model, z, Q, mount=SENSOR_MOUNT_IDENTITY, point=(0.0, 0.0, 0.0),
+                              rate=None, in_a=None, in_b=None, commit: bool = True):
+        """Host arrays in window order, as update_delayed: mu_hist [steps, capacity, S], cov_hist [steps, capacity, D, D] (the
+        last step is not read), dt [steps - 1], in_a / in_b [steps, capacity, 3] or None; lag / model an int or an int32 array
+        [capacity]; z [capacity, 3], Q [capacity, 3, 3]; mount [7] or [capacity, 7], point [3] or [capacity, 3]; rate
+        [capacity, 3] or None.  Returns update_delayed's dict of NumPy arrays; synchronises"""
+        d = _f64(dt, -1)
+        steps, n = d.size + 1, self.capacity
+        mu_hist = _f64(mu_hist, (steps, n, self.S)); cov_hist = _f64(cov_hist, (steps, n, self.D, self.D))
+        a, b = _f64(in_a, (steps, n, 3)), _f64(in_b, (steps, n, 3))
+        z = _f64(z, (n, 3)); Q = _f64(Q, (n, 3, 3))
+        (lag_u, lag_p), (mod_u, mod_p) = _int_or_i32(lag, n), _int_or_i32(model, n)
+        mp, mu_ = _per_or_uniform(mount, n, 7)
+        pp, pu = _per_or_uniform(point, n, 3)
+        w = _f64(rate, (n, 3))
+        o = {"z_pred": np.empty((n, 4)), "S": np.empty((n, 3, 3)), "innov": np.empty((n, 3)), "maha": np.empty(n),
+             "loglik": np.empty(n), "status": np.empty(n, dtype=np.uint32), "mu_out": np.empty((n, self.S)),
+             "cov_out": np.empty((n, self.D, self.D))}
+        self._call("ukfb_update_delayed_sensor", steps, _pd(d) if d.size else None, _pd(mu_hist), _pd(cov_hist), _pd(a), _pd(b),
+                   lag_u, _pi32(lag_p), mod_u, _pi32(mod_p), _pd(z), _pd(Q), _pd(mp), _pd(mu_), _pd(pp), _pd(pu), _pd(w), commit,
+                   _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]), _pu32(o["status"]),
+                   _pd(o["mu_out"]), _pd(o["cov_out"]))
         return o
 
     # ---- fused cycle
