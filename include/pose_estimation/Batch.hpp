@@ -8,6 +8,7 @@
 #include <ukf_batch.h>
 #include <ukf_batch_relative.h>
 #include <ukf_batch_robust.h>
+#include <ukf_batch_pda.h>
 #include <ukf_batch_delayed_sensor.h>
 
 #include <stdexcept>
@@ -270,6 +271,30 @@ public:
         std::vector<uint32_t> st(static_cast<size_t>(cap));
         check(ukfb_associate_sensor(engine, model, model_per_filter, candidates, z, Q, mount, mount_uniform, point, point_uniform,
                                     point_per_candidate ? 1 : 0, commit ? 1 : 0, z_pred, S, innov, maha, loglik, best, n_gated, st.data()));
+        return st;
+    }
+    /** Probabilistic data association (ukf_batch_pda.h): the shared-h association whose update uses EVERY candidate inside the
+     *  gate at its posterior association weight beta_k, weighs the probability beta_0 that none is the target, and widens the
+     *  covariance by the spread of the weighted innovations.  in.point_per_candidate must be 0; rule: P_D, P_G and the clutter
+     *  density for m = 1 / m = 3.  commit = false is read-only (only `out` is written).  Stream-ordered. */
+    void integratePdaSensorMeasurementDev(int model_uniform, const ukfb_associate_in& in, const ukfb_pda_rule& rule, bool commit = true,
+                                          const ukfb_pda_out* out = NULL)
+    {
+        check(ukfb_update_pda_dev(engine, model_uniform, &in, &rule, commit ? 1 : 0, out));
+    }
+    /** host arrays, shaped as for associateSensorMeasurement in shared-h mode; beta [candidates][N] the weights, beta0 [N],
+     *  innov_comb [N][3] = sum beta_k nu_k, best / n_gated [N], or NULL; returns the status */
+    std::vector<uint32_t> integratePdaSensorMeasurement(int model, int candidates, const double* z, const double* Q, const ukfb_pda_rule& rule,
+                                                        const double* mount_uniform = NULL, const double* point_uniform = NULL,
+                                                        const double* mount = NULL, const double* point = NULL,
+                                                        const int32_t* model_per_filter = NULL, bool commit = true,
+                                                        double* z_pred = NULL, double* S = NULL, double* innov = NULL, double* maha = NULL,
+                                                        double* loglik = NULL, double* beta = NULL, double* beta0 = NULL,
+                                                        double* innov_comb = NULL, int32_t* best = NULL, int32_t* n_gated = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_update_pda(engine, model, model_per_filter, candidates, z, Q, mount, mount_uniform, point, point_uniform, &rule,
+                              commit ? 1 : 0, z_pred, S, innov, maha, loglik, beta, beta0, innov_comb, best, n_gated, st.data()));
         return st;
     }
     /** User-defined measurement models (ukf_batch.h, "user-defined measurement models"): ukf->update(z, h, Q) for an h of the

@@ -139,6 +139,14 @@ struct RobustReq {
     ukfb_robust_out out{};    // any may be null
 };
 
+struct PdaReq {
+    int model_uniform = -1;
+    ukfb_associate_in in{};    // device pointers and the by-value mount / point; shared-h mode
+    ukfb_pda_rule rule{};      // HOST values, already checked
+    bool commit = false;
+    ukfb_pda_out out{};        // any may be null
+};
+
 struct DelayedSensorReq {
     ukfb_delayed_sensor_in in{};   // in.dt: HOST [steps - 1], copied into the kernel arguments; the by-value mount / point
     bool commit = false;

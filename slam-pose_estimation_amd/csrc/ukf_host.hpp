@@ -1,7 +1,7 @@
 // ukf_host.hpp -- the engine's host decisions as pure functions of plain values: configuration checks, process-noise
 // classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, packed covariances, workspace sizing, the filter lifecycle's checks and geometry, the delayed-measurement
 // update's checks, geometry and lag rule, the relative-measurement update's checks, models and map, the robust update's rule, the late
-// sensor-frame sample's checks, input record and map, and the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
+// sensor-frame sample's checks, input record and map, the probabilistic data association's rule, and the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
 #pragma once
 
 #include <stddef.h>
@@ -18,6 +18,7 @@
 #include "../../include/ukf_batch_relative.h"
 #include "../../include/ukf_batch_robust.h"
 #include "../../include/ukf_batch_delayed_sensor.h"
+#include "../../include/ukf_batch_pda.h"
 
 #if defined(__HIP__)
 #define UKFB_HD __host__ __device__ __forceinline__
@@ -892,6 +893,45 @@ inline Verdict check_robust_args(int engine_model, bool per_filter_models, int m
     if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
     return check_sensor_call(sensor_call(in), commit, per_filter_models || sensor_model_ok(engine_model, model_uniform),
                              "sensor model id not valid for this engine (Pose: 0 ... 4, OrientationState: 5 ... 7)", robust_has_output(out));
+}
+
+// ---- probabilistic data association (ukfb_update_pda_dev) -------------------------------------------------------------------
+// The shared-h association's arguments and the rule (include/ukf_batch_pda.h).  The rule is judged first, as the robust
+// update's is; then the candidate range (it alone decides UKFB_ERR_OUT_OF_RANGE), then the mode, then the association's clauses.
+// Models, inputs, LDS map and geometry are the sensor-frame measurements'.
+inline Verdict check_pda_rule(const ukfb_pda_rule* rule) {
+    if (!rule) return {UKFB_ERR_INVALID_ARG, "rule must not be NULL"};
+    const auto prob = [](double p) { return std::isfinite(p) && p > 0.0 && p <= 1.0; };
+    if (!prob(rule->p_detect)) return {UKFB_ERR_INVALID_ARG, "rule.p_detect must be in (0, 1]"};
+    if (!prob(rule->p_gate_m1) || !prob(rule->p_gate_m3)) return {UKFB_ERR_INVALID_ARG, "rule.p_gate_m1 and rule.p_gate_m3 must be in (0, 1]"};
+    if (!(rule->p_detect * rule->p_gate_m1 < 1.0) || !(rule->p_detect * rule->p_gate_m3 < 1.0))
+        return {UKFB_ERR_INVALID_ARG, "rule.p_detect * rule.p_gate must be < 1 for m = 1 and m = 3"};
+    if (!std::isfinite(rule->clutter_m1) || !(rule->clutter_m1 > 0.0) || !std::isfinite(rule->clutter_m3) || !(rule->clutter_m3 > 0.0))
+        return {UKFB_ERR_INVALID_ARG, "rule.clutter_m1 and rule.clutter_m3 must be finite and > 0"};
+    return {};
+}
+// what the kernel gets of a checked rule, formed in double: a_0 = ln lambda_m + ln(1 - P_D P_G,m) for m = 1 / m = 3, and ln P_D
+struct PdaLogs {
+    double a0_m1, a0_m3, ln_pd;
+};
+inline PdaLogs pda_logs(const ukfb_pda_rule& r) {
+    return {std::log(r.clutter_m1) + std::log1p(-r.p_detect * r.p_gate_m1), std::log(r.clutter_m3) + std::log1p(-r.p_detect * r.p_gate_m3),
+            std::log(r.p_detect)};
+}
+inline bool pda_has_output(const ukfb_pda_out* out) {
+    return out && (out->z_pred || out->S || out->innov || out->maha || out->loglik || out->beta || out->beta0 || out->innov_comb || out->best ||
+                   out->n_gated || out->status);
+}
+inline Verdict check_pda_args(int engine_model, bool per_filter_models, int model_uniform, const ukfb_associate_in* in, const ukfb_pda_rule* rule,
+                              int commit, const ukfb_pda_out* out) {
+    if (const Verdict v = check_pda_rule(rule); v.rc != UKFB_OK) return v;
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    if (in->candidates < 1 || in->candidates > UKFB_ASSOCIATE_MAX_CANDIDATES) return {UKFB_ERR_OUT_OF_RANGE, "candidates must be 1 ... 32"};
+    if (in->point_per_candidate != 0)
+        return {UKFB_ERR_INVALID_ARG, "point_per_candidate must be 0: per-hypothesis candidates combine into a mixture, not PDA"};
+    return check_sensor_call({in->candidates, in->z_dev != nullptr, in->Q_dev != nullptr, in->q_is_uniform, 0, in->point_dev != nullptr}, commit,
+                             per_filter_models || sensor_model_ok(engine_model, model_uniform),
+                             "sensor model id not valid for this engine (Pose: 0 ... 4, OrientationState: 5 ... 7)", pda_has_output(out));
 }
 
 // ---- bounded waits ----------------------------------------------------------------------------------------------------------

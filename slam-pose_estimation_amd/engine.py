@@ -20,6 +20,8 @@ from . import abi_relative
 from .abi_relative import RELATIVE_NONE, RELATIVE_POSE, RELATIVE_POSITION, RELATIVE_ROTATION, RelativeIn, RelativeOut  # noqa: F401
 from . import abi_robust
 from .abi_robust import ROBUST_HUBER, ROBUST_MATCH, RobustOut, RobustRule  # noqa: F401
+from . import abi_pda
+from .abi_pda import PdaOut, PdaRule  # noqa: F401
 from . import abi_delayed_sensor
 from .abi_delayed_sensor import DelayedSensorIn  # noqa: F401
 
@@ -46,6 +48,7 @@ def load_library():
         abi_relative.declare(lib)   # (include/ukf_batch_relative.h)
         abi_robust.declare(lib)     # (include/ukf_batch_robust.h)
         abi_delayed_sensor.declare(lib)   # (include/ukf_batch_delayed_sensor.h)
+        abi_pda.declare(lib)        # (include/ukf_batch_pda.h)
         _lib = lib
     return _lib
 
@@ -718,6 +721,41 @@ class BatchUKF:
         self._call("ukfb_associate_sensor", uniform, _pi32(per), K, _pd(z), _pd(Q), _pd(mp), _pd(mu_), _pd(pp), _pd(pu),
                    point_per_candidate, commit, _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]),
                    _pi32(o["best"]), _pi32(o["n_gated"]), _pu32(o["status"]))
+        return o
+
+    # ---- probabilistic data association: associate_sensor's shared-h arguments and a rule (include/ukf_batch_pda.h)
+    def update_pda_dev(self, model: int, candidates: int, z_dev, Q_dev, rule: PdaRule, q_is_uniform: bool = False, model_dev=None,
+                       mount_dev=None, mount=SENSOR_MOUNT_IDENTITY, point_dev=None, point=(0.0, 0.0, 0.0), commit: bool = True,
+                       z_pred=None, S=None, innov=None, maha=None, loglik=None, beta=None, beta0=None, innov_comb=None, best=None,
+                       n_gated=None, status=None):
+        """associate_sensor_dev in shared-h mode whose update uses EVERY candidate inside the gate at its posterior association
+        weight (PDAF): beta [candidates, capacity] the weights (0 outside the gate, NaN where not scored), beta0 [capacity] the
+        weight of "none of them", innov_comb [capacity, 3] = sum beta_k nu_k; the covariance is widened by the spread of the
+        weighted innovations.  rule: P_D, P_G and the clutter density for m = 1 / m = 3.  The other keyword outputs as for
+        associate_sensor_dev with H = 1; best is the candidate of the largest weight.  commit=False is read-only.
+        Stream-ordered."""
+        ain = _sensor_in(AssociateIn, model_dev, z_dev, Q_dev, q_is_uniform, mount_dev, mount, point_dev, point,
+                         candidates=int(candidates), point_per_candidate=False)
+        out = PdaOut(*[_dev(x) for x in (z_pred, S, innov, maha, loglik, beta, beta0, innov_comb, best, n_gated, status)])
+        self._call("ukfb_update_pda_dev", int(model), C.byref(ain), C.byref(rule), commit, C.byref(out))
+
+    def update_pda(self, model, z, Q, rule: PdaRule, mount=SENSOR_MOUNT_IDENTITY, point=(0.0, 0.0, 0.0), commit: bool = True):
+        """Host arrays, shaped as for associate_sensor in shared-h mode: z [candidates, capacity, 3], point [3] or [capacity, 3].
+        Returns a dict of NumPy arrays: z_pred [n, 3], S [n, 3, 3], innov [K, n, 3], maha / loglik / beta [K, n], beta0 [n],
+        innov_comb [n, 3], best / n_gated / status [n]; synchronises"""
+        n = self.capacity
+        z = _f64(z)
+        K = int(z.shape[0]) if z.ndim == 3 else 0
+        z = _f64(z, (K, n, 3)); Q = _f64(Q, (n, 3, 3))
+        uniform, per = _int_or_i32(model, n)
+        mp, mu_ = _per_or_uniform(mount, n, 7)
+        pp, pu = _per_or_uniform(point, n, 3)
+        o = {"z_pred": np.empty((n, 3)), "S": np.empty((n, 3, 3)), "innov": np.empty((K, n, 3)), "maha": np.empty((K, n)),
+             "loglik": np.empty((K, n)), "beta": np.empty((K, n)), "beta0": np.empty(n), "innov_comb": np.empty((n, 3)),
+             "best": np.empty(n, dtype=np.int32), "n_gated": np.empty(n, dtype=np.int32), "status": np.empty(n, dtype=np.uint32)}
+        self._call("ukfb_update_pda", uniform, _pi32(per), K, _pd(z), _pd(Q), _pd(mp), _pd(mu_), _pd(pp), _pd(pu), C.byref(rule), commit,
+                   _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]), _pd(o["beta"]), _pd(o["beta0"]),
+                   _pd(o["innov_comb"]), _pi32(o["best"]), _pi32(o["n_gated"]), _pu32(o["status"]))
         return o
 
     # ---- user-defined measurement models: X [capacity, 2 D + 1, S], delta [capacity, 2 D + 1, D], Z [capacity, 2 D + 1, m]
