@@ -38,7 +38,11 @@ extern "C" {
  *      for positive definite Q.  NEWTON on psi(lambda) = 1 / d^2(lambda) - 1 / c^2 from lambda = 1: with x = S(lambda)^-1 nu,
  *      f = nu^T x and g = x^T Q x the step is lambda <- lambda + f (f - c^2) / (c^2 g).  psi is concave and increasing (1 / psi
  *      is a weighted harmonic mean of the shifted generalised eigenvalues of (Sigma_z, Q)), so the iterates rise MONOTONICALLY
- *      towards the root and never pass it; for m = 1, or Sigma_z proportional to Q, one step is exact.  A filter stops on the
+ *      towards the root and never pass it -- in exact arithmetic.  In the engine's precision f carries a relative rounding
+ *      error of a few eps cond(S(lambda)) (S scaled to a unit diagonal), and the returned lambda may lie past the root by
+ *      that much: d^2(lambda) >= c^2 (1 - e), e of that size, is what tests/test_gpu_score_primitives.py holds.  For m = 1, or
+ *      Sigma_z proportional to Q, one step is exact.  With tol below that rounding error a filter ends on the rounded f
+ *      meeting tol or on a step that no longer increases lambda, not on the cap.  A filter stops on the
  *      first of: f - c^2 <= tol c^2; a step that does not increase lambda; g not positive or not finite; a pivot of S(lambda)
  *      that fails; lambda >= scale_max; max_iter steps.  There is no status bit for the cap: iterations == max_iter together
  *      with maha > c^2 (1 + tol) is how a caller sees it;
