@@ -9,6 +9,7 @@
 #include <ukf_batch_relative.h>
 #include <ukf_batch_robust.h>
 #include <ukf_batch_pda.h>
+#include <ukf_batch_assign.h>
 #include <ukf_batch_delayed_sensor.h>
 
 #include <stdexcept>
@@ -295,6 +296,22 @@ public:
         std::vector<uint32_t> st(static_cast<size_t>(cap));
         check(ukfb_update_pda(engine, model, model_per_filter, candidates, z, Q, mount, mount_uniform, point, point_uniform, &rule,
                               commit ? 1 : 0, z_pred, S, innov, maha, loglik, beta, beta0, innov_comb, best, n_gated, st.data()));
+        return st;
+    }
+    /** Global nearest-neighbour assignment (ukf_batch_assign.h): the one-to-one assignment of detections to the filters of
+     *  each scene, a contiguous run of slots that share one detection list; in.cost_dev is the maha or -2 loglik an
+     *  association call wrote.  out.assign is a drop-in for best_dev.  Read-only on the filters.  Stream-ordered. */
+    void assignScenesDev(const ukfb_assign_in& in, const ukfb_assign_out& out) { check(ukfb_assign_scenes_dev(engine, &in, &out)); }
+    /** host arrays: cost [candidates][N], scene_start [scenes + 1] (NULL: uniform scenes of tracks_per_scene slots), miss [N]
+     *  (NULL: miss_uniform); assign [N], owner [scenes][candidates], objective [scenes], or NULL; returns the scenes' status */
+    std::vector<uint32_t> assignScenes(int candidates, const double* cost, int scenes, const int32_t* scene_start, int tracks_per_scene,
+                                       double gate, const double* miss, double miss_uniform, int32_t* assign, int32_t* owner = NULL,
+                                       double* objective = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(scenes > 0 ? scenes : 0));
+        std::vector<uint32_t> none(1);
+        check(ukfb_assign_scenes(engine, candidates, cost, scenes, scene_start, tracks_per_scene, gate, miss, miss_uniform, assign, owner,
+                                 objective, st.empty() ? none.data() : st.data()));
         return st;
     }
     /** User-defined measurement models (ukf_batch.h, "user-defined measurement models"): ukf->update(z, h, Q) for an h of the

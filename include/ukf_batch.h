@@ -973,7 +973,8 @@ int ukfb_update_bearing(ukfb_engine* e, int model, const int32_t* model_per_filt
  * compute in fp32, with wide_arithmetic in fp64 (stored fp32).  A uniform id of the other engine's models is
  * UKFB_ERR_WRONG_MODEL; candidates outside 1 ... 32 is UKFB_ERR_OUT_OF_RANGE and writes nothing.  Bearings on S^2, per-candidate
  * Q or mount and assignment across filters are not served; weighted association (the probabilistic data association update):
- * ukf_batch_pda.h, a header of its own.  Device groups: per shard through ukfb_group_shard. */
+ * ukf_batch_pda.h, a header of its own; the one-to-one assignment across the filters of a scene, from the scores written
+ * here: ukf_batch_assign.h, likewise.  Device groups: per shard through ukfb_group_shard. */
 #define UKFB_ASSOCIATE_MAX_CANDIDATES 32
 typedef struct ukfb_associate_in {   /* device pointers in engine precision; the *_uniform values are host doubles, by value */
     const int32_t* model_dev;        /* [capacity] model id per filter, or NULL: the call's model_uniform serves every filter */

@@ -19,6 +19,7 @@
 #include "../../include/ukf_batch_robust.h"
 #include "../../include/ukf_batch_delayed_sensor.h"
 #include "../../include/ukf_batch_pda.h"
+#include "../../include/ukf_batch_assign.h"
 
 #if defined(__HIP__)
 #define UKFB_HD __host__ __device__ __forceinline__
@@ -932,6 +933,68 @@ inline Verdict check_pda_args(int engine_model, bool per_filter_models, int mode
     return check_sensor_call({in->candidates, in->z_dev != nullptr, in->Q_dev != nullptr, in->q_is_uniform, 0, in->point_dev != nullptr}, commit,
                              per_filter_models || sensor_model_ok(engine_model, model_uniform),
                              "sensor model id not valid for this engine (Pose: 0 ... 4, OrientationState: 5 ... 7)", pda_has_output(out));
+}
+
+// ---- global nearest-neighbour assignment (ukfb_assign_scenes_dev) -------------------------------------------------------------
+// One wavefront per scene, ASSIGN_SCENES_PER_GROUP scenes per workgroup, one lane per column of the T x (K + T) problem.  The
+// LDS map, stated once for host and device: every scene of a workgroup owns one block of doubles, the staged cost
+// cost[i][k] at i * ASSIGN_ROW_STRIDE + k (the odd stride keeps the staging writes, which run along i, off one bank).
+constexpr int ASSIGN_SCENES_PER_GROUP = 4, ASSIGN_THREADS = 64 * ASSIGN_SCENES_PER_GROUP;
+constexpr int ASSIGN_ROW_STRIDE = UKFB_ASSOCIATE_MAX_CANDIDATES + 1;
+struct AssignMap {
+    int scene_scalars = UKFB_ASSIGN_MAX_TRACKS * ASSIGN_ROW_STRIDE;   // doubles of one scene's block
+    constexpr int cost(int scene_in_group, int track, int k) const { return scene_in_group * scene_scalars + track * ASSIGN_ROW_STRIDE + k; }
+    constexpr int scalars() const { return ASSIGN_SCENES_PER_GROUP * scene_scalars; }
+    constexpr int bytes() const { return scalars() * int(sizeof(double)); }
+};
+constexpr AssignMap assign_map() { return {}; }
+static_assert(UKFB_ASSIGN_MAX_TRACKS + UKFB_ASSOCIATE_MAX_CANDIDATES <= 64, "one lane per column");
+static_assert(assign_map().bytes() <= 65536, "a workgroup's cost blocks fit the LDS a workgroup may have");
+// the loops of the solver, bounded by constants: tracks, Dijkstra steps of one sweep (one column is scanned per step), walk back
+constexpr int ASSIGN_MAX_STEPS = UKFB_ASSIGN_MAX_TRACKS + UKFB_ASSOCIATE_MAX_CANDIDATES, ASSIGN_MAX_WALK = UKFB_ASSIGN_MAX_TRACKS;
+struct AssignGeometry {
+    int64_t grid;    // workgroups of ASSIGN_SCENES_PER_GROUP scenes
+    int lds_bytes;   // static LDS of a workgroup
+};
+inline AssignGeometry assign_geometry(int scenes) {
+    return {(int64_t(scenes) + ASSIGN_SCENES_PER_GROUP - 1) / ASSIGN_SCENES_PER_GROUP, assign_map().bytes()};
+}
+// the segment rule: what the kernel asks of offsets it cannot trust, and the host-array form of offsets it can see
+UKFB_HD bool assign_segment_ok(int64_t a, int64_t b, int64_t capacity) {
+    return a >= 0 && b <= capacity && b >= a && b - a <= UKFB_ASSIGN_MAX_TRACKS;
+}
+// scene s of uniform mode
+UKFB_HD void assign_uniform_segment(int64_t s, int tracks_per_scene, int64_t capacity, int64_t* a, int64_t* b) {
+    *a = s * tracks_per_scene;
+    *b = *a + tracks_per_scene < capacity ? *a + tracks_per_scene : capacity;
+}
+// the rules of a pair and of a track
+UKFB_HD bool assign_value_ok(double v) { return v >= -UKFB_ASSIGN_COST_MAX && v <= UKFB_ASSIGN_COST_MAX; }   // (false for NaN and +-Inf)
+UKFB_HD bool assign_pair_allowed(double cost, double gate) { return assign_value_ok(cost) && !(gate >= 0.0 && cost > gate); }
+inline int64_t assign_max_scenes(const ukfb_assign_in* in, int64_t capacity) {
+    if (in->scene_start_dev) return capacity + 1;
+    return (capacity + in->tracks_per_scene - 1) / in->tracks_per_scene;
+}
+inline Verdict check_assign_args(int64_t capacity, const ukfb_assign_in* in, const ukfb_assign_out* out) {
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    if (!in->cost_dev) return {UKFB_ERR_INVALID_ARG, "cost must not be NULL"};
+    if (!out || (!out->assign && !out->owner && !out->objective && !out->scene_status))
+        return {UKFB_ERR_INVALID_ARG, "every output of ukfb_assign_out is NULL: nothing to compute"};
+    if (!in->miss_dev && !std::isfinite(in->miss_uniform)) return {UKFB_ERR_INVALID_ARG, "miss_uniform must be finite when miss is NULL"};
+    if (in->candidates < 1 || in->candidates > UKFB_ASSOCIATE_MAX_CANDIDATES) return {UKFB_ERR_OUT_OF_RANGE, "candidates must be 1 ... 32"};
+    if (!in->scene_start_dev && (in->tracks_per_scene < 1 || in->tracks_per_scene > UKFB_ASSIGN_MAX_TRACKS))
+        return {UKFB_ERR_OUT_OF_RANGE, "tracks_per_scene must be 1 ... 32 in uniform mode"};
+    if (in->scenes < 0) return {UKFB_ERR_OUT_OF_RANGE, "scenes must be >= 0"};
+    if (int64_t(in->scenes) > assign_max_scenes(in, capacity))
+        return {UKFB_ERR_OUT_OF_RANGE, "more scenes than the engine has room for (uniform: ceil(capacity / tracks_per_scene); ragged: capacity + 1)"};
+    return {};
+}
+// the host-array form sees the offsets: every segment must pass the kernel's rule, and the offsets ascend
+inline Verdict check_assign_offsets(int64_t capacity, int scenes, const int32_t* scene_start) {
+    for (int s = 0; s < scenes; ++s)
+        if (!assign_segment_ok(scene_start[s], scene_start[s + 1], capacity))
+            return {UKFB_ERR_OUT_OF_RANGE, "scene_start: a scene must lie inside [0, capacity), end at or after its start and hold at most 32 tracks"};
+    return {};
 }
 
 // ---- bounded waits ----------------------------------------------------------------------------------------------------------

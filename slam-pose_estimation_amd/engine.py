@@ -22,6 +22,8 @@ from . import abi_robust
 from .abi_robust import ROBUST_HUBER, ROBUST_MATCH, RobustOut, RobustRule  # noqa: F401
 from . import abi_pda
 from .abi_pda import PdaOut, PdaRule  # noqa: F401
+from . import abi_assign
+from .abi_assign import ASSIGN_BAD_SCENE, ASSIGN_COST_MAX, ASSIGN_MAX_TRACKS, ASSIGN_OK, AssignIn, AssignOut  # noqa: F401
 from . import abi_delayed_sensor
 from .abi_delayed_sensor import DelayedSensorIn  # noqa: F401
 
@@ -49,6 +51,7 @@ def load_library():
         abi_robust.declare(lib)     # (include/ukf_batch_robust.h)
         abi_delayed_sensor.declare(lib)   # (include/ukf_batch_delayed_sensor.h)
         abi_pda.declare(lib)        # (include/ukf_batch_pda.h)
+        abi_assign.declare(lib)     # (include/ukf_batch_assign.h)
         _lib = lib
     return _lib
 
@@ -756,6 +759,42 @@ class BatchUKF:
         self._call("ukfb_update_pda", uniform, _pi32(per), K, _pd(z), _pd(Q), _pd(mp), _pd(mu_), _pd(pp), _pd(pu), C.byref(rule), commit,
                    _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]), _pd(o["beta"]), _pd(o["beta0"]),
                    _pd(o["innov_comb"]), _pi32(o["best"]), _pi32(o["n_gated"]), _pu32(o["status"]))
+        return o
+
+    # ---- global nearest-neighbour assignment across the filters of a scene (include/ukf_batch_assign.h)
+    def assign_scenes_dev(self, candidates: int, cost_dev, scenes: int, scene_start_dev=None, tracks_per_scene: int = 0,
+                          gate: float = -1.0, miss_dev=None, miss: float = 0.0, assign=None, owner=None, objective=None,
+                          scene_status=None):
+        """The one-to-one assignment of `candidates` detections to the filters of each of `scenes` scenes, contiguous runs of
+        slots that share one detection list: scene_start_dev int32 [scenes + 1], or uniform scenes of tracks_per_scene slots.
+        cost_dev [candidates, capacity] in engine precision (the maha or -2 loglik an association call wrote); pairs with a
+        non-finite cost or, with gate >= 0, a cost above the gate are forbidden; miss_dev [capacity] (or the host value
+        `miss`) is the cost of leaving a track without a detection, a non-finite entry takes the track out.  Keyword outputs
+        (device buffers): assign int32 [capacity] (a drop-in for `best`), owner int32 [scenes, candidates], objective float64
+        [scenes], scene_status uint32 [scenes].  Read-only on the filters.  Stream-ordered."""
+        ain = AssignIn(_dev(cost_dev), int(candidates), int(scenes), _dev(scene_start_dev), int(tracks_per_scene), float(gate),
+                       _dev(miss_dev), float(miss))
+        out = AssignOut(_dev(assign), _dev(owner), _dev(objective), _dev(scene_status))
+        self._call("ukfb_assign_scenes_dev", C.byref(ain), C.byref(out))
+
+    def assign_scenes(self, cost, scene_start=None, tracks_per_scene: int = 0, gate: float = -1.0, miss=0.0, scenes=None):
+        """Host arrays: cost [candidates, capacity]; scene_start int32 [scenes + 1], or uniform scenes of tracks_per_scene
+        slots (`scenes` of them; default: all that fit); miss a float or an array [capacity].  Returns a dict of NumPy arrays:
+        assign [n] (-1 where no scene covers a slot), owner [scenes, K], objective [scenes], scene_status [scenes];
+        synchronises"""
+        n = self.capacity
+        cost = _f64(cost)
+        K = int(cost.shape[0]) if cost.ndim == 2 else 0
+        cost = _f64(cost, (K, n))
+        start = _i32(scene_start)
+        if scenes is None:
+            scenes = len(start) - 1 if start is not None else (-(-n // tracks_per_scene) if tracks_per_scene > 0 else 0)
+        miss_per, miss_uniform = (None, float(miss)) if np.isscalar(miss) else (_f64(miss, n), 0.0)
+        ns = max(int(scenes), 0)
+        o = {"assign": np.empty(n, dtype=np.int32), "owner": np.empty((ns, K), dtype=np.int32), "objective": np.empty(ns),
+             "scene_status": np.empty(ns, dtype=np.uint32)}
+        self._call("ukfb_assign_scenes", K, _pd(cost), int(scenes), _pi32(start), int(tracks_per_scene), float(gate), _pd(miss_per),
+                   miss_uniform, _pi32(o["assign"]), _pi32(o["owner"]), _pd(o["objective"]), _pu32(o["scene_status"]))
         return o
 
     # ---- user-defined measurement models: X [capacity, 2 D + 1, S], delta [capacity, 2 D + 1, D], Z [capacity, 2 D + 1, m]
