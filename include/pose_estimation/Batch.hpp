@@ -10,6 +10,7 @@
 #include <ukf_batch_robust.h>
 #include <ukf_batch_pda.h>
 #include <ukf_batch_assign.h>
+#include <ukf_batch_jpda.h>
 #include <ukf_batch_delayed_sensor.h>
 
 #include <stdexcept>
@@ -312,6 +313,42 @@ public:
         std::vector<uint32_t> none(1);
         check(ukfb_assign_scenes(engine, candidates, cost, scenes, scene_start, tracks_per_scene, gate, miss, miss_uniform, assign, owner,
                                  objective, st.empty() ? none.data() : st.data()));
+        return st;
+    }
+    /** Joint probabilistic data association (ukf_batch_jpda.h): the exact association marginals of each scene (at most six
+     *  tracks), from the loglik / maha integratePdaSensorMeasurementDev(commit = false) wrote.  out.beta / out.beta0 may be the
+     *  arrays that call filled: bad and too-large scenes keep what is there.  Read-only on the filters.  Stream-ordered. */
+    void jpdaScenesDev(const ukfb_jpda_in& in, const ukfb_pda_rule& rule, const ukfb_jpda_out& out) { check(ukfb_jpda_scenes_dev(engine, &in, &rule, &out)); }
+    /** host arrays: loglik, maha (or NULL) [candidates][N], scene_start [scenes + 1] (NULL: uniform scenes of tracks_per_scene
+     *  slots); beta [candidates][N], beta0 [N], free [scenes][candidates], log_z [scenes], or NULL; returns the scenes' status */
+    std::vector<uint32_t> jpdaScenes(int candidates, const double* loglik, const double* maha, int scenes, const int32_t* scene_start,
+                                     int tracks_per_scene, double gate, int model, const int32_t* model_per_filter, const ukfb_pda_rule& rule,
+                                     double* beta, double* beta0 = NULL, double* free_k = NULL, double* log_z = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(scenes > 0 ? scenes : 0));
+        std::vector<uint32_t> none(1);
+        check(ukfb_jpda_scenes(engine, candidates, loglik, maha, scenes, scene_start, tracks_per_scene, gate, model, model_per_filter, &rule,
+                               beta, beta0, free_k, log_z, st.empty() ? none.data() : st.data()));
+        return st;
+    }
+    /** The probabilistic data association update with GIVEN weights (ukf_batch_jpda.h): weight_dev [candidates][N] in engine
+     *  precision, used as w / max(1, sum w); cfg.gate_chi2 plays no part.  commit = false is read-only.  Stream-ordered. */
+    void updateWeightedDev(int model_uniform, const ukfb_associate_in& in, const void* weight_dev, bool commit = true,
+                           const ukfb_weighted_out* out = NULL)
+    {
+        check(ukfb_update_weighted_dev(engine, model_uniform, &in, weight_dev, commit ? 1 : 0, out));
+    }
+    /** host arrays, shaped as for integratePdaSensorMeasurement; weight [candidates][N]; returns the status */
+    std::vector<uint32_t> updateWeighted(int model, int candidates, const double* z, const double* Q, const double* weight,
+                                         const double* mount_uniform = NULL, const double* point_uniform = NULL, const double* mount = NULL,
+                                         const double* point = NULL, const int32_t* model_per_filter = NULL, bool commit = true,
+                                         double* z_pred = NULL, double* S = NULL, double* innov = NULL, double* maha = NULL,
+                                         double* loglik = NULL, double* weight_used = NULL, double* beta0 = NULL, double* innov_comb = NULL,
+                                         int32_t* n_used = NULL)
+    {
+        std::vector<uint32_t> st(static_cast<size_t>(cap));
+        check(ukfb_update_weighted(engine, model, model_per_filter, candidates, z, Q, mount, mount_uniform, point, point_uniform, weight,
+                                   commit ? 1 : 0, z_pred, S, innov, maha, loglik, weight_used, beta0, innov_comb, n_used, st.data()));
         return st;
     }
     /** User-defined measurement models (ukf_batch.h, "user-defined measurement models"): ukf->update(z, h, Q) for an h of the

@@ -12,4 +12,4 @@ from . import synth  # noqa: F401
 from .sharding import gather_means, shard_range  # noqa: F401
 from .build import build_engine  # noqa: F401
 from .engine import *  # noqa: F401,F403
-from .engine import AssignIn, AssignOut, BatchOrientationUKF, BatchPoseUKF, BatchUKF, ConditionIn, ConditionOut, Config, PredictSampledIn, PredictSampledOut, SampledIn, SampledOut, SensorIn, SensorOut, UKFGroup, UkfbError, layout_supported, load_library  # noqa: F401
+from .engine import AssignIn, AssignOut, BatchOrientationUKF, BatchPoseUKF, BatchUKF, ConditionIn, ConditionOut, Config, JpdaIn, JpdaOut, PredictSampledIn, PredictSampledOut, SampledIn, SampledOut, SensorIn, SensorOut, UKFGroup, UkfbError, WeightedOut, layout_supported, load_library  # noqa: F401

@@ -3,7 +3,7 @@
 // temporary device buffer, the bounded waits, the transfers between host doubles and the engine's arrays, and HostStage, the
 // one place where the host-array forms allocate their temporaries and copy to and from the device.  What is only declared
 // here is defined once, in namespace ukfb: the error channel, the waits, the transfers and launch in ukf_runtime.hip,
-// build_model_buckets in ukf_buckets.hip, rebuild_racc in ukf_batch.hip, launch_assign in ukf_assign_launch.hip.
+// build_model_buckets in ukf_buckets.hip, rebuild_racc in ukf_batch.hip, launch_assign in ukf_assign_launch.hip, launch_jpda in ukf_jpda_launch.hip.
 #pragma once
 
 #include <algorithm>
@@ -100,6 +100,7 @@ int launch(ukfb_engine* e, const ukfb::LaunchReq& r);
 int build_model_buckets(ukfb_engine* e, const int32_t* meas_dev, int64_t* items);
 int rebuild_racc(ukfb_engine* e);
 int launch_assign(ukfb_engine* e, const ukfb_assign_in& in, const ukfb_assign_out& out);   // checked arguments (ukf_assign_launch.hip)
+int launch_jpda(ukfb_engine* e, const ukfb_jpda_in& in, const ukfb_pda_rule& rule, const ukfb_jpda_out& out);   // checked arguments (ukf_jpda_launch.hip)
 
 // mount and point of a sensor-frame form (ukfb_sensor_in, ukfb_associate_in): r = 0, qs the identity and b = 0, unless the
 // caller says otherwise

@@ -147,6 +147,14 @@ struct PdaReq {
     ukfb_pda_out out{};        // any may be null
 };
 
+struct WeightedReq {
+    int model_uniform = -1;
+    ukfb_associate_in in{};    // device pointers and the by-value mount / point; shared-h mode
+    const void* weight = nullptr;   // [candidates][capacity], engine precision
+    bool commit = false;
+    ukfb_weighted_out out{};   // any may be null
+};
+
 struct DelayedSensorReq {
     ukfb_delayed_sensor_in in{};   // in.dt: HOST [steps - 1], copied into the kernel arguments; the by-value mount / point
     bool commit = false;

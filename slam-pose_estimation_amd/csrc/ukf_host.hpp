@@ -1,7 +1,7 @@
 // ukf_host.hpp -- the engine's host decisions as pure functions of plain values: configuration checks, process-noise
 // classification, measurement-model checks, shard ranges and the event owner pass, multi-cycle plans, packed covariances, workspace sizing, the filter lifecycle's checks and geometry, the delayed-measurement
 // update's checks, geometry and lag rule, the relative-measurement update's checks, models and map, the robust update's rule, the late
-// sensor-frame sample's checks, input record and map, the probabilistic data association's rule, and the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
+// sensor-frame sample's checks, input record and map, the probabilistic data association's rule, the joint association's checks and segment rule, and the kernel level of a launch.  No HIP dependency: tests/cpp/host_logic.cpp compiles it with g++ under ASan / UBSan.
 #pragma once
 
 #include <stddef.h>
@@ -20,6 +20,7 @@
 #include "../../include/ukf_batch_delayed_sensor.h"
 #include "../../include/ukf_batch_pda.h"
 #include "../../include/ukf_batch_assign.h"
+#include "../../include/ukf_batch_jpda.h"
 
 #if defined(__HIP__)
 #define UKFB_HD __host__ __device__ __forceinline__
@@ -995,6 +996,68 @@ inline Verdict check_assign_offsets(int64_t capacity, int scenes, const int32_t*
         if (!assign_segment_ok(scene_start[s], scene_start[s + 1], capacity))
             return {UKFB_ERR_OUT_OF_RANGE, "scene_start: a scene must lie inside [0, capacity), end at or after its start and hold at most 32 tracks"};
     return {};
+}
+
+// ---- joint probabilistic data association (ukfb_jpda_scenes_dev, ukfb_update_weighted_dev) --------------------------------------
+// One wavefront per scene, JPDA_SCENES_PER_GROUP scenes per workgroup, one lane per SUBSET of the scene's tracks (the lane
+// index is the subset's bitmask, 2^6 = 64).  No LDS: psi is staged in registers (lane k holds psi_ik of every track i) and read
+// with constant lane indices; the table of the backward recurrence lives in 32 fp64 registers.
+constexpr int JPDA_SCENES_PER_GROUP = 4, JPDA_THREADS = 64 * JPDA_SCENES_PER_GROUP;
+static_assert((1 << UKFB_JPDA_MAX_TRACKS) == 64, "one lane per subset of the tracks");
+static_assert(UKFB_JPDA_MAX_TRACKS <= UKFB_ASSIGN_MAX_TRACKS, "a too-large scene is still a well-formed segment");
+struct JpdaGeometry {
+    int64_t grid;    // workgroups of JPDA_SCENES_PER_GROUP scenes
+    int lds_bytes;   // none
+};
+inline JpdaGeometry jpda_geometry(int scenes) { return {(int64_t(scenes) + JPDA_SCENES_PER_GROUP - 1) / JPDA_SCENES_PER_GROUP, 0}; }
+// the segment rule: assign_segment_ok decides BAD_SCENE (offsets the kernel cannot trust), then the limit of six tracks
+UKFB_HD uint32_t jpda_segment_status(int64_t a, int64_t b, int64_t capacity) {
+    return !assign_segment_ok(a, b, capacity) ? uint32_t(UKFB_JPDA_BAD_SCENE)
+                                              : (b - a > UKFB_JPDA_MAX_TRACKS ? uint32_t(UKFB_JPDA_TOO_LARGE) : uint32_t(UKFB_JPDA_OK));
+}
+// the rules of a pair: finite (x - x == 0 is false for NaN and +-Inf, on host and device alike)
+UKFB_HD bool jpda_finite(double v) { return v - v == 0.0; }
+UKFB_HD bool jpda_gate_on(double gate) { return gate >= 0.0; }   // (false for NaN)
+UKFB_HD bool jpda_pair_allowed(double loglik, double maha, double gate) {
+    return jpda_finite(loglik) && (!jpda_gate_on(gate) || (jpda_finite(maha) && maha <= gate));
+}
+// m as the PDA kernel takes it: the model's, 3 for an id this engine does not have
+UKFB_HD int jpda_kernel_dim(int engine_model, int64_t id) { return sensor_model_ok(engine_model, id) ? sensor_meas_dim(id) : 3; }
+inline bool jpda_has_output(const ukfb_jpda_out* out) { return out && (out->beta || out->beta0 || out->free || out->log_z || out->scene_status); }
+inline int64_t jpda_max_scenes(const ukfb_jpda_in* in, int64_t capacity) {
+    if (in->scene_start_dev) return capacity + 1;
+    return (capacity + in->tracks_per_scene - 1) / in->tracks_per_scene;
+}
+// The rule is judged first, as the PDA update's is; then the INVALID_ARG clauses, then the ranges.
+inline Verdict check_jpda_args(int64_t capacity, const ukfb_jpda_in* in, const ukfb_pda_rule* rule, const ukfb_jpda_out* out) {
+    if (const Verdict v = check_pda_rule(rule); v.rc != UKFB_OK) return v;
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    if (!in->loglik_dev) return {UKFB_ERR_INVALID_ARG, "loglik must not be NULL"};
+    if (!jpda_has_output(out)) return {UKFB_ERR_INVALID_ARG, "every output of ukfb_jpda_out is NULL: nothing to compute"};
+    if (!in->maha_dev && jpda_gate_on(in->gate)) return {UKFB_ERR_INVALID_ARG, "a gate >= 0 needs maha"};
+    if (in->candidates < 1 || in->candidates > UKFB_ASSOCIATE_MAX_CANDIDATES) return {UKFB_ERR_OUT_OF_RANGE, "candidates must be 1 ... 32"};
+    if (!in->scene_start_dev && (in->tracks_per_scene < 1 || in->tracks_per_scene > UKFB_JPDA_MAX_TRACKS))
+        return {UKFB_ERR_OUT_OF_RANGE, "tracks_per_scene must be 1 ... 6 in uniform mode"};
+    if (in->scenes < 0) return {UKFB_ERR_OUT_OF_RANGE, "scenes must be >= 0"};
+    if (int64_t(in->scenes) > jpda_max_scenes(in, capacity))
+        return {UKFB_ERR_OUT_OF_RANGE, "more scenes than the engine has room for (uniform: ceil(capacity / tracks_per_scene); ragged: capacity + 1)"};
+    return {};
+}
+// the update with given weights: the shared-h association's arguments and the weights; cfg.gate_chi2 plays no part
+inline bool weighted_has_output(const ukfb_weighted_out* out) {
+    return out && (out->z_pred || out->S || out->innov || out->maha || out->loglik || out->weight_used || out->beta0 || out->innov_comb ||
+                   out->n_used || out->status);
+}
+inline Verdict check_weighted_args(int engine_model, bool per_filter_models, int model_uniform, const ukfb_associate_in* in, const void* weight,
+                                   int commit, const ukfb_weighted_out* out) {
+    if (!in) return {UKFB_ERR_INVALID_ARG, "in must not be NULL"};
+    if (!weight) return {UKFB_ERR_INVALID_ARG, "weight must not be NULL"};
+    if (in->candidates < 1 || in->candidates > UKFB_ASSOCIATE_MAX_CANDIDATES) return {UKFB_ERR_OUT_OF_RANGE, "candidates must be 1 ... 32"};
+    if (in->point_per_candidate != 0)
+        return {UKFB_ERR_INVALID_ARG, "point_per_candidate must be 0: per-hypothesis candidates combine into a mixture, not PDA"};
+    return check_sensor_call({in->candidates, in->z_dev != nullptr, in->Q_dev != nullptr, in->q_is_uniform, 0, in->point_dev != nullptr}, commit,
+                             per_filter_models || sensor_model_ok(engine_model, model_uniform),
+                             "sensor model id not valid for this engine (Pose: 0 ... 4, OrientationState: 5 ... 7)", weighted_has_output(out));
 }
 
 // ---- bounded waits ----------------------------------------------------------------------------------------------------------

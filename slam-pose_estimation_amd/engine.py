@@ -24,6 +24,8 @@ from . import abi_pda
 from .abi_pda import PdaOut, PdaRule  # noqa: F401
 from . import abi_assign
 from .abi_assign import ASSIGN_BAD_SCENE, ASSIGN_COST_MAX, ASSIGN_MAX_TRACKS, ASSIGN_OK, AssignIn, AssignOut  # noqa: F401
+from . import abi_jpda
+from .abi_jpda import JPDA_BAD_SCENE, JPDA_LOG_RATIO_MAX, JPDA_MAX_TRACKS, JPDA_OK, JPDA_TOO_LARGE, JpdaIn, JpdaOut, WeightedOut  # noqa: F401
 from . import abi_delayed_sensor
 from .abi_delayed_sensor import DelayedSensorIn  # noqa: F401
 
@@ -52,6 +54,7 @@ def load_library():
         abi_delayed_sensor.declare(lib)   # (include/ukf_batch_delayed_sensor.h)
         abi_pda.declare(lib)        # (include/ukf_batch_pda.h)
         abi_assign.declare(lib)     # (include/ukf_batch_assign.h)
+        abi_jpda.declare(lib)       # (include/ukf_batch_jpda.h)
         _lib = lib
     return _lib
 
@@ -795,6 +798,77 @@ class BatchUKF:
              "scene_status": np.empty(ns, dtype=np.uint32)}
         self._call("ukfb_assign_scenes", K, _pd(cost), int(scenes), _pi32(start), int(tracks_per_scene), float(gate), _pd(miss_per),
                    miss_uniform, _pi32(o["assign"]), _pi32(o["owner"]), _pd(o["objective"]), _pu32(o["scene_status"]))
+        return o
+
+    # ---- joint probabilistic data association: the marginals of a scene, the update with given weights (include/ukf_batch_jpda.h)
+    def jpda_scenes_dev(self, candidates: int, loglik_dev, rule: PdaRule, scenes: int, scene_start_dev=None, tracks_per_scene: int = 0,
+                        maha_dev=None, gate: float = -1.0, model: int = 0, model_dev=None, beta=None, beta0=None, free=None,
+                        log_z=None, scene_status=None):
+        """The exact joint association marginals of each of `scenes` scenes (at most 6 tracks each), contiguous runs of slots
+        that share one detection list: scene_start_dev int32 [scenes + 1], or uniform scenes of tracks_per_scene slots.
+        loglik_dev (and maha_dev, needed with gate >= 0) [candidates, capacity] in engine precision, as update_pda_dev or an
+        association call wrote them; model / model_dev the sensor model of the tracks.  Keyword outputs (device buffers): beta
+        [candidates, capacity] and beta0 [capacity] in engine precision -- they may be the arrays update_pda_dev filled: bad and
+        too-large scenes and uncovered slots keep what is there --, free float64 [scenes, candidates], log_z float64 [scenes],
+        scene_status uint32 [scenes].  Read-only on the filters.  Stream-ordered."""
+        jin = JpdaIn(_dev(loglik_dev), _dev(maha_dev), int(candidates), int(scenes), _dev(scene_start_dev), int(tracks_per_scene),
+                     float(gate), int(model), _dev(model_dev))
+        out = JpdaOut(_dev(beta), _dev(beta0), _dev(free), _dev(log_z), _dev(scene_status))
+        self._call("ukfb_jpda_scenes_dev", C.byref(jin), C.byref(rule), C.byref(out))
+
+    def jpda_scenes(self, loglik, rule: PdaRule, scene_start=None, tracks_per_scene: int = 0, maha=None, gate: float = -1.0, model=0,
+                    scenes=None):
+        """Host arrays: loglik (and maha) [candidates, capacity]; scene_start int32 [scenes + 1], or uniform scenes of
+        tracks_per_scene slots (`scenes` of them; default: all that fit); model an id or an int32 array [capacity].  Returns a
+        dict of NumPy arrays: beta [K, n] and beta0 [n] (NaN where no good scene covers a slot), free [scenes, K], log_z
+        [scenes], scene_status [scenes]; synchronises"""
+        n = self.capacity
+        loglik = _f64(loglik)
+        K = int(loglik.shape[0]) if loglik.ndim == 2 else 0
+        loglik = _f64(loglik, (K, n))
+        maha = None if maha is None else _f64(maha, (K, n))
+        start = _i32(scene_start)
+        if scenes is None:
+            scenes = len(start) - 1 if start is not None else (-(-n // tracks_per_scene) if tracks_per_scene > 0 else 0)
+        uniform, per = _int_or_i32(model, n)
+        ns = max(int(scenes), 0)
+        o = {"beta": np.empty((K, n)), "beta0": np.empty(n), "free": np.empty((ns, K)), "log_z": np.empty(ns),
+             "scene_status": np.empty(ns, dtype=np.uint32)}
+        self._call("ukfb_jpda_scenes", K, _pd(loglik), _pd(maha), int(scenes), _pi32(start), int(tracks_per_scene), float(gate), uniform,
+                   _pi32(per), C.byref(rule), _pd(o["beta"]), _pd(o["beta0"]), _pd(o["free"]), _pd(o["log_z"]), _pu32(o["scene_status"]))
+        return o
+
+    def update_weighted_dev(self, model: int, candidates: int, z_dev, Q_dev, weight_dev, q_is_uniform: bool = False, model_dev=None,
+                            mount_dev=None, mount=SENSOR_MOUNT_IDENTITY, point_dev=None, point=(0.0, 0.0, 0.0), commit: bool = True,
+                            z_pred=None, S=None, innov=None, maha=None, loglik=None, weight_used=None, beta0=None, innov_comb=None,
+                            n_used=None, status=None):
+        """update_pda_dev whose association weights are READ from weight_dev [candidates, capacity] (engine precision) instead
+        of computed: the joint marginals jpda_scenes_dev wrote, or any weights the caller normalised.  A weight counts where
+        its candidate is scored with a finite d^2 and the weight is finite and > 0; the weights are used as w / max(1, sum w)
+        (weight_used), beta0 = 1 - sum of them; cfg.gate_chi2 plays no part.  The other keyword outputs as for
+        update_pda_dev; n_used int32 [capacity].  commit=False is read-only.  Stream-ordered."""
+        ain = _sensor_in(AssociateIn, model_dev, z_dev, Q_dev, q_is_uniform, mount_dev, mount, point_dev, point,
+                         candidates=int(candidates), point_per_candidate=False)
+        out = WeightedOut(*[_dev(x) for x in (z_pred, S, innov, maha, loglik, weight_used, beta0, innov_comb, n_used, status)])
+        self._call("ukfb_update_weighted_dev", int(model), C.byref(ain), _dev(weight_dev), commit, C.byref(out))
+
+    def update_weighted(self, model, z, Q, weight, mount=SENSOR_MOUNT_IDENTITY, point=(0.0, 0.0, 0.0), commit: bool = True):
+        """Host arrays, shaped as for update_pda: z [candidates, capacity, 3], weight [candidates, capacity].  Returns a dict of
+        NumPy arrays: z_pred [n, 3], S [n, 3, 3], innov [K, n, 3], maha / loglik / weight_used [K, n], beta0 [n], innov_comb
+        [n, 3], n_used / status [n]; synchronises"""
+        n = self.capacity
+        z = _f64(z)
+        K = int(z.shape[0]) if z.ndim == 3 else 0
+        z = _f64(z, (K, n, 3)); Q = _f64(Q, (n, 3, 3)); weight = _f64(weight, (K, n))
+        uniform, per = _int_or_i32(model, n)
+        mp, mu_ = _per_or_uniform(mount, n, 7)
+        pp, pu = _per_or_uniform(point, n, 3)
+        o = {"z_pred": np.empty((n, 3)), "S": np.empty((n, 3, 3)), "innov": np.empty((K, n, 3)), "maha": np.empty((K, n)),
+             "loglik": np.empty((K, n)), "weight_used": np.empty((K, n)), "beta0": np.empty(n), "innov_comb": np.empty((n, 3)),
+             "n_used": np.empty(n, dtype=np.int32), "status": np.empty(n, dtype=np.uint32)}
+        self._call("ukfb_update_weighted", uniform, _pi32(per), K, _pd(z), _pd(Q), _pd(mp), _pd(mu_), _pd(pp), _pd(pu), _pd(weight), commit,
+                   _pd(o["z_pred"]), _pd(o["S"]), _pd(o["innov"]), _pd(o["maha"]), _pd(o["loglik"]), _pd(o["weight_used"]), _pd(o["beta0"]),
+                   _pd(o["innov_comb"]), _pi32(o["n_used"]), _pu32(o["status"]))
         return o
 
     # ---- user-defined measurement models: X [capacity, 2 D + 1, S], delta [capacity, 2 D + 1, D], Z [capacity, 2 D + 1, m]

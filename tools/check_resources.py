@@ -33,7 +33,8 @@ def parse(text):
 GATED = ("ukf_kernel", "ukf_innovation_kernel", "ukf_bank_", "ukf_smooth_kernel", "ukf_forecast_kernel", "ukf_lifecycle_",
          "ukf_state_meas_kernel", "ukf_sensor_meas_kernel", "ukf_sampled_kernel", "ukf_sigma_points_kernel",
          "ukf_predict_sampled_kernel", "ukf_delayed_kernel", "ukf_condition_kernel", "ukf_bearing_kernel", "ukf_associate_kernel",
-         "ukf_relative_kernel", "ukf_robust_kernel", "ukf_delayed_sensor_kernel", "ukf_pda_kernel", "ukf_assign_kernel")
+         "ukf_relative_kernel", "ukf_robust_kernel", "ukf_delayed_sensor_kernel", "ukf_pda_kernel", "ukf_assign_kernel",
+         "ukf_weighted_kernel", "ukf_jpda_kernel")
 
 # (name fragments, fragments that exclude, wavefronts per SIMD the kernel must keep, what the error calls it), checked in this
 # order.  The tuned kernels (the register side; LDS is checked by the layout's static_asserts): ukf_kernel16<double, ...> three
@@ -57,6 +58,7 @@ FLOORS = (
     (("ukf_robust_kernel",), (), 2, "robust sensor-measurement kernels", None),
     (("ukf_delayed_sensor_kernel",), (), 2, "delayed sensor-frame kernels", None),
     (("ukf_pda_kernel",), (), 2, "probabilistic-association kernels", None),
+    (("ukf_weighted_kernel",), (), 2, "weighted-update kernels", None),
 )
 
 
